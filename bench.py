@@ -10,6 +10,15 @@ call (RCCL over xGMI).
   --scaling weak   every GPU holds configs[1]'s shape — 200 keyframes x 10 k points — so the map grows with the GPU count
                    (configs[2], [3]: N x 200 keyframes); value = candidates / s of that N-times-larger problem (NOT multiplied
                    by N: the record says how many keyframes a candidate covered).
+
+A plain run sets up, warms up, times --steps steps and prints the record (metric, value, unit, ms_per_step, config). Everything
+else the benchmark measures — the repeated timed regions, the 512-candidate step, the per-kernel times and the roofline, the
+extras (batch sweeps, wide candidates, shard emulation, plane refit, KITTI-sized scans, calibrations, MADS replay, ORB-only BA,
+sustained regions) and the CPU baseline — runs only with --full (--no-extras / --no-cpu-baseline then trim it as before).
+
+  --dump-outputs DIR  after the timed steps, what the last timed step returned to its caller (the cost tuples and the normal
+                      equations of the B candidates) as DIR/<struct>_<field>.npy, float64, one row per candidate. The scene and
+                      the candidates are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import hashlib
@@ -63,7 +72,10 @@ def build_parser():
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--plane-cache", type=int, default=1, help="1 = memoise the x-independent local-plane fits (default), 0 = refit inside every evaluation")
-    ap.add_argument("--no-extras", action="store_true", help="timed region and roofline only (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: repeated regions, the 512-candidate step, per-kernel times and roofline, "
+                                                         "extras and the CPU baseline (off by default: a plain run times the headline only)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: timed region and roofline only (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float64)")
     ap.add_argument("--launch", choices=("auto", "ranks", "group"), default="auto",
                     help="how N GPUs are driven: ranks = one process per GPU over torch.distributed / RCCL (what the driver's torchrun line gives; "
                          "without WORLD_SIZE in the environment bench.py starts the N ranks itself), group = ONE process, iba_group_* with one issuing "
@@ -79,6 +91,24 @@ def job_value(evals, seconds, n_gpus, scaling):
     return evals / seconds
 
 
+def output_arrays(cost, nrm):
+    """The outputs of one iba_eval_full call as float64 arrays, one row per candidate: cost_<field> from the iba_cost_out
+    structs, normal_<field> from the iba_normal_out structs (H as B x 7 x 7, b as B x 7; the counters are exact in float64).
+    Copies: the step's output structs are reused by the next call."""
+    arrays = {}
+    for prefix, seq in (("cost", cost), ("normal", nrm)):
+        for name, _ in type(seq[0])._fields_:
+            arrays["%s_%s" % (prefix, name)] = np.array([np.array(getattr(s, name)) for s in seq], dtype=np.float64)
+    arrays["normal_H"] = arrays["normal_H"].reshape(-1, 7, 7)
+    return arrays
+
+
+def dump_outputs(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 SUSTAIN_S = 10.0   # seconds per sustained region of extras.sustained
 
 
@@ -89,6 +119,8 @@ def main():
     env_world = os.environ.get("WORLD_SIZE")
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if env_world is not None and int(env_world) != args.gpus and not os.environ.get("IBA_FORCE_DIST"):
         sys.exit("bench.py: --gpus %d disagrees with WORLD_SIZE=%s of the launcher: refusing to report a number for the wrong GPU count" % (args.gpus, env_world))
     if args.launch == "group" and env_world is not None and int(env_world) > 1:
@@ -244,10 +276,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     stage("timed steps done")
+    if args.dump_outputs and rank == 0:   # (before any later call reuses the step's output structs)
+        dump_outputs(args.dump_outputs, output_arrays(*out))
+        stage("outputs of the last timed step written to " + args.dump_outputs)
     # the timed region is ~10 ms at the default 20 steps: four more regions of the same K steps (AFTER the one the record's value
     # comes from) give its spread — a regression of a few per cent is otherwise inside the noise of one region
     region_rates = [B * args.steps / dt]
-    for _ in range(4):
+    for _ in range(4 if args.full else 0):
         sync()
         t0r = time.perf_counter()
         for i in range(args.steps):
@@ -263,9 +298,9 @@ def main():
     # ---- the same step with 512 candidates per call: ONE launch chain (one pair search, one anchor plan, one set of launches), every rank
     #      on its shard, one all-reduce of 512 x 64 doubles. Not the headline (an optimiser's poll is tens of candidates); what the path
     #      gives a caller that has that many — and what keeps a small shard's GPU full in a multi-GPU job. Same bracket as the headline. ----
-    #      (Skipped with --no-extras: a profiling run then sees launches of ONE shape.)
+    #      (--full only; skipped with --no-extras: a profiling run then sees launches of ONE shape.)
     dt_big, n_big = None, max(4, args.steps // 2)
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         xs_big = [np.vstack([xs_all[(k + j) % len(xs_all)] for j in range(BIG // B)]) for k in range(2)]
         for i in range(3):
             step(i, xs_big)
@@ -282,29 +317,30 @@ def main():
         for i in range(2):   # (the record's counts below come from the headline's candidates)
             out = step(i)
 
-    # ---- dominant kernels, timed with HIP events on their launch stream ----
-    L = pkg.load_library()
-    L.iba_last_phase_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    if args.full:
+        # ---- dominant kernels, timed with HIP events on their launch stream ----
+        L = pkg.load_library()
+        L.iba_last_phase_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
 
-    def phases():
-        a, n, r = C.c_float(0), C.c_float(0), C.c_float(0)
-        L.iba_last_phase_ms(h.h, C.byref(a), C.byref(n), C.byref(r))
-        return a.value, n.value, r.value
+        def phases():
+            a, n, r = C.c_float(0), C.c_float(0), C.c_float(0)
+            L.iba_last_phase_ms(h.h, C.byref(a), C.byref(n), C.byref(r))
+            return a.value, n.value, r.value
 
-    xs = xs_all[0]
-    kms = []
-    h.set_timing(True)
-    for _ in range(5):
-        h.eval_full_partial(xs, d_part.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        kms.append(phases())
-    h.set_timing(False)
-    assoc_ms, nn_ms, rest_ms = (float(v) for v in np.median(np.array(kms), axis=0))
-    pair_ms = assoc_ms + nn_ms   # the two kernels that do what the reference's BAError / BuildProblem association does
-    cost0 = pkg.finalize_cost(params, d_part[: B * stride].cpu().numpy())   # this rank's partial: the counts one launch processes
-    n_slots = len(prob.arrays["covis_frame"]) / prob.n_frames
-    per_eval = float(np.mean([algorithmic_bytes(h.n_points, f1 - f0, h.n_keypoints, c.n_corr, c.cnt_3d_3d, n_slots) for c in cost0]))
-    achieved = B * per_eval / (pair_ms * 1e-3) / 1e9
+        xs = xs_all[0]
+        kms = []
+        h.set_timing(True)
+        for _ in range(5):
+            h.eval_full_partial(xs, d_part.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            kms.append(phases())
+        h.set_timing(False)
+        assoc_ms, nn_ms, rest_ms = (float(v) for v in np.median(np.array(kms), axis=0))
+        pair_ms = assoc_ms + nn_ms   # the two kernels that do what the reference's BAError / BuildProblem association does
+        cost0 = pkg.finalize_cost(params, d_part[: B * stride].cpu().numpy())   # this rank's partial: the counts one launch processes
+        n_slots = len(prob.arrays["covis_frame"]) / prob.n_frames
+        per_eval = float(np.mean([algorithmic_bytes(h.n_points, f1 - f0, h.n_keypoints, c.n_corr, c.cnt_3d_3d, n_slots) for c in cost0]))
+        achieved = B * per_eval / (pair_ms * 1e-3) / 1e9
 
     evals = B * args.steps
     units = 1            # one unit = one candidate against every keyframe of the job (never multiplied by the GPU count)
@@ -345,7 +381,9 @@ def main():
                                 "value = candidates/s, not multiplied by the GPU count" % (prob.n_frames, args.frames)) if args.scaling == "weak" else
                                "strong scaling: 1 eval = one candidate x against the whole %d-keyframe / %.1fM-point problem (cost tuple + normal equations), whatever the GPU count" % (args.frames, args.frames * args.pts / 1e6),
         },
-        "roofline": {
+    }
+    if args.full:
+        res["roofline"] = {
             # PHYSICAL figures only (round 3's `frac` was an effective rate against the reference's formulation and exceeded 1):
             #   achieved = HBM bytes the dominant kernels really moved per launch (FETCH_SIZE x2 + WRITE_SIZE, separate --pmc passes,
             #              profiles/pmc_latest.json, stamped with the kernel sources' hash) / their launch time measured HERE with HIP
@@ -363,48 +401,47 @@ def main():
                         "an effective rate against the uncached, unbatched formulation. The kernels do not move those bytes (planes memoised, one pair search per batch, 1-NN memoised around an anchor), "
                         "so it may exceed the HBM peak; like_for_like = the same ratio with the planes fitted inside every evaluation (plane_cache = 0), over the whole step",
                 "algorithmic_bytes_per_eval": per_eval, "effective_GBs": achieved, "ratio_to_hbm_peak": achieved / HBM_PEAK_GBS, "like_for_like": None},
-        },
-    }
-    # measured HBM traffic and VALU issue share of the same launch shape from the committed counter passes (tools/prof_run.sh +
-    # tools/summarize_prof.py stamp them with the kernel sources' hash). Counters taken on OTHER sources of the same shape are
-    # still quoted, flagged pmc_stale (a physical figure of a nearby kernel version beats none); another shape is not quoted.
-    pmc_file = os.path.join(ROOT, "profiles", "pmc_latest.json")
-    if os.path.exists(pmc_file):
-        try:
-            pmc = json.load(open(pmc_file))
-            same_shape = (pmc.get("frames"), pmc.get("pts"), pmc.get("batch")) == (f1 - f0, args.pts, B)
-            if same_shape:
-                rf = res["roofline"]
-                rf["traffic"] = pmc.get("hbm_bytes_per_launch")
-                rf["issue_frac"] = pmc.get("valu_issue_frac")
-                rf["achieved"] = rf["traffic"] / (pair_ms * 1e-3) / 1e9
-                rf["hbm_frac"] = rf["achieved"] / HBM_PEAK_GBS
-                rf["frac"] = rf["issue_frac"]
-                rf["pmc_stale"] = pmc.get("source_stamp") != source_stamp()
-                if pmc.get("hbm_bytes_per_step"):
-                    rf["whole_step"] = {"hbm_bytes": pmc["hbm_bytes_per_step"], "hbm_frac": pmc["hbm_bytes_per_step"] / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
-                                        "issue_frac": pmc.get("valu_issue_frac_step")}
-                rf["pmc_provenance"] = {k: pmc.get(k) for k in ("round", "git_head", "source_stamp", "taken_on", "counters")}
-                # per kernel of one step, from the same counter passes and the committed rocprofv3 summary: duration, share of the HBM peak, VALU-active share
-                pk = pmc.get("per_kernel") or {}
-                step_kernels = {k: v for k, v in pk.items() if not any(t in k for t in ("anchor", "plane_kernel", "verdict"))}
-                if step_kernels:
-                    rf["per_kernel"] = {k: {"avg_us": v.get("avg_us"), "hbm_frac": ((v.get("hbm_read_bytes", 0) + v.get("hbm_write_bytes", 0)) / (v["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS) if v.get("avg_us") else None,
-                                            "valu_active": v.get("valu_active_share"), "wait_any": v.get("wait_any_share"), "l2_requests": v.get("l2_requests")} for k, v in step_kernels.items()}
-                    rf["longest_kernel"] = max(step_kernels, key=lambda k: step_kernels[k].get("avg_us") or 0.0)
-            else:
-                res["roofline"]["pmc_provenance"] = "profiles/pmc_latest.json was taken on another launch shape (%s frames x %s pts x %s candidates): not quoted" % (pmc.get("frames"), pmc.get("pts"), pmc.get("batch"))
-        except Exception:
-            pass
+        }
+        # measured HBM traffic and VALU issue share of the same launch shape from the committed counter passes (tools/prof_run.sh +
+        # tools/summarize_prof.py stamp them with the kernel sources' hash). Counters taken on OTHER sources of the same shape are
+        # still quoted, flagged pmc_stale (a physical figure of a nearby kernel version beats none); another shape is not quoted.
+        pmc_file = os.path.join(ROOT, "profiles", "pmc_latest.json")
+        if os.path.exists(pmc_file):
+            try:
+                pmc = json.load(open(pmc_file))
+                same_shape = (pmc.get("frames"), pmc.get("pts"), pmc.get("batch")) == (f1 - f0, args.pts, B)
+                if same_shape:
+                    rf = res["roofline"]
+                    rf["traffic"] = pmc.get("hbm_bytes_per_launch")
+                    rf["issue_frac"] = pmc.get("valu_issue_frac")
+                    rf["achieved"] = rf["traffic"] / (pair_ms * 1e-3) / 1e9
+                    rf["hbm_frac"] = rf["achieved"] / HBM_PEAK_GBS
+                    rf["frac"] = rf["issue_frac"]
+                    rf["pmc_stale"] = pmc.get("source_stamp") != source_stamp()
+                    if pmc.get("hbm_bytes_per_step"):
+                        rf["whole_step"] = {"hbm_bytes": pmc["hbm_bytes_per_step"], "hbm_frac": pmc["hbm_bytes_per_step"] / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
+                                            "issue_frac": pmc.get("valu_issue_frac_step")}
+                    rf["pmc_provenance"] = {k: pmc.get(k) for k in ("round", "git_head", "source_stamp", "taken_on", "counters")}
+                    # per kernel of one step, from the same counter passes and the committed rocprofv3 summary: duration, share of the HBM peak, VALU-active share
+                    pk = pmc.get("per_kernel") or {}
+                    step_kernels = {k: v for k, v in pk.items() if not any(t in k for t in ("anchor", "plane_kernel", "verdict"))}
+                    if step_kernels:
+                        rf["per_kernel"] = {k: {"avg_us": v.get("avg_us"), "hbm_frac": ((v.get("hbm_read_bytes", 0) + v.get("hbm_write_bytes", 0)) / (v["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS) if v.get("avg_us") else None,
+                                                "valu_active": v.get("valu_active_share"), "wait_any": v.get("wait_any_share"), "l2_requests": v.get("l2_requests")} for k, v in step_kernels.items()}
+                        rf["longest_kernel"] = max(step_kernels, key=lambda k: step_kernels[k].get("avg_us") or 0.0)
+                else:
+                    res["roofline"]["pmc_provenance"] = "profiles/pmc_latest.json was taken on another launch shape (%s frames x %s pts x %s candidates): not quoted" % (pmc.get("frames"), pmc.get("pts"), pmc.get("batch"))
+            except Exception:
+                pass
 
     if dt_big is not None:
         res["large_batch"] = {"candidates_per_step": BIG, "steps": n_big, "ms_per_step": dt_big / n_big * 1e3, "evals_per_s": BIG * n_big / dt_big,
                               "note": "512 candidates per call = one launch chain; same scene, same candidate spread, same bracket (barrier + synchronize on both sides, max over ranks) as the headline, which stays at 64 per step"}
     if group_mode:
         res["config"]["group_issue_us_last_call"] = grp.last_issue_us
-    if not args.no_extras and group_mode:
+    if args.full and not args.no_extras and group_mode:
         stage("extras are measured in the default launch mode: skipped with --launch group")
-    if not args.no_extras and not group_mode:
+    if args.full and not args.no_extras and not group_mode:
         extras = {}
         extras["timed_region_repeats"] = {"regions": len(region_rates), "steps_each": args.steps, "evals_per_s": region_rates, "min": float(np.min(region_rates)), "median": float(np.median(region_rates)),
                                           "max": float(np.max(region_rates)), "note": "region 0 is the record's value; the others follow it back to back"}
@@ -749,7 +786,7 @@ def main():
         res["extras"] = extras
     stage("extras done")
 
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         # ---- CPU baseline: the oracle — a port of the reference algorithm, per-evaluation 2-D tree rebuild included — on
         #      this box's host cores: x0 and 16 seeded perturbations, cost tuple + normal equations each; 1 warm-up, then the
         #      median over the 17 candidates on ONE thread (what the reference's NOMAD loop runs, iba_global.cpp:385) and the

@@ -1,6 +1,8 @@
 """Generates tests/golden/geo_corr_nanoflann_v150.npz: GeoCalib.h:18-33 computeCorrespondence run by the REFERENCE's own nanoflann (compiled where it
 lies by oracle/Makefile into oracle/_ref: KDTreeSingleIndexAdaptor, L2_Simple, max_leaf 15, knnSearch(1), sq_dist <= maxDistance) on seeded clouds.
-Inputs and the reference's outputs only; nothing of the reference is copied. Run in the build container:  python tests/golden/make_geo_golden.py"""
+Inputs and the reference's outputs only; nothing of the reference is copied. Run where oracle/_ref is built:  python tests/golden/make_geo_golden.py
+`python tests/golden/make_geo_golden.py live` writes geo_corr_nanoflann_v150_live.npz instead: the reference's pairs on the seeded clouds of
+tests/test_geo_correspondences.py (live_cases, scan_120k_case; the test regenerates the inputs and checks them against the stored hash)."""
 import os
 import sys
 
@@ -31,9 +33,24 @@ def cases():
     return out
 
 
+def live_fixture(ob):
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_geo_correspondences as t
+    z = {}
+    cases = [(key, src, tgt, md) for key, src, tgt, md in t.live_cases()] + [("scan120k",) + t.scan_120k_case()]
+    for key, src, tgt, md in cases:
+        z[key + "_pairs_src"], z[key + "_pairs_tgt"] = ob.geo_correspondences("ref", src, np.asarray(tgt, np.float64), md)
+        z[key + "_in_sha256"] = t.inputs_sha256(src, tgt)
+        print(key, len(src), len(tgt), md, "->", len(z[key + "_pairs_src"]), "pairs")
+    np.savez_compressed(os.path.join(HERE, "geo_corr_nanoflann_v150_live.npz"), **z)
+
+
 if __name__ == "__main__":
     from oracle import binding as ob
     assert ob.ref_lib() is not None, "oracle/_ref not built (needs /root/reference)"
+    if len(sys.argv) > 1 and sys.argv[1] == "live":
+        live_fixture(ob)
+        sys.exit(0)
     z = {}
     for name, (src, tgt, md) in cases().items():
         s, t = ob.geo_correspondences("ref", src, tgt, md)

@@ -117,6 +117,21 @@ def knn_big_fixture():
     print("wrote knn_nanoflann_v150_big.npz: %d points, %d x 30 + %d x 1 indices" % (n, len(sel), len(q)))
 
 
+def knn_live_fixture():
+    """nanoflann's kNN outputs on the seeded clouds of tests/test_oracle_kdtree.py (live_cases: the test regenerates the inputs and
+    checks them against the stored hash), so that the comparison runs where oracle/_ref is not built."""
+    from oracle import binding as ob
+    assert ob.ref_lib() is not None, "oracle/_ref not built (oracle/Makefile builds it when the reference tree is present)"
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_oracle_kdtree as t
+    out = {}
+    for key, dim, leaf, pts, q, k in t.live_cases():
+        out[key + "_idx"], out[key + "_d2"], out[key + "_cnt"] = ob.knn("ref", dim, pts, leaf, q, k)
+        out[key + "_in_sha256"] = t.inputs_sha256(pts, q)
+    np.savez_compressed(os.path.join(HERE, "knn_nanoflann_v150_live.npz"), **out)
+    print("wrote knn_nanoflann_v150_live.npz", len(out), "arrays")
+
+
 def path_fixtures():
     """Small scene + the oracle's outputs on it (regression pin of the restated path)."""
     synth = importlib.import_module(PKG + ".synth")
@@ -150,7 +165,11 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "big":
         knn_big_fixture()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "live":
+        knn_live_fixture()
+        sys.exit(0)
     knn_fixtures()
     knn_gpu_fixtures()
     knn_big_fixture()
+    knn_live_fixture()
     path_fixtures()

@@ -1,12 +1,14 @@
 """Pins the oracle's kd-tree/kNN restatement (oracle/oracle_kdtree.hpp) to the reference's vendored
 nanoflann v1.5.0: (1) committed golden vectors generated from the reference's own headers
-(tests/golden/make_golden.py), (2) live comparison against oracle/_ref when that build is present."""
+(tests/golden/make_golden.py), (2) seeded clouds against nanoflann's recorded outputs on them (tests/golden/knn_nanoflann_v150_live.npz)
+and, when oracle/_ref is built, against that build live."""
 import os
 
 import numpy as np
 import pytest
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "knn_nanoflann_v150.npz")
+LIVE = os.path.join(os.path.dirname(__file__), "golden", "knn_nanoflann_v150_live.npz")
 CASES = ["2d_leaf10", "3d_leaf30", "3d_leaf30_small", "2d_leaf10_dups"]
 
 
@@ -22,9 +24,9 @@ def test_oracle_knn_matches_nanoflann_golden(ob, name, k):
     assert np.array_equal(d2, z[f"{name}_k{k}_d2"])
 
 
-def test_oracle_knn_matches_live_reference_build(ob):
-    if ob.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this box)")
+def live_cases():
+    """The seeded clouds of the live comparison: (key, dim, leaf, pts, queries, k). tests/golden/make_golden.py live records
+    nanoflann's (idx, d2, cnt) for each of them, with a hash of the inputs."""
     rng = np.random.default_rng(1)
     for dim, leaf in ((2, 10), (3, 30), (3, 1)):
         for n in (1, 7, 31, 2500):
@@ -33,9 +35,27 @@ def test_oracle_knn_matches_live_reference_build(ob):
                 pts[50:60] = pts[40:50]
             q = np.vstack([rng.normal(size=(64, dim)), pts[: min(n, 32)]])
             for k in (1, 30):
-                a = ob.knn("oracle", dim, pts, leaf, q, k)
-                b = ob.knn("ref", dim, pts, leaf, q, k)
-                assert all(np.array_equal(x, y) for x, y in zip(a, b)), (dim, leaf, n, k)
+                yield "d%d_leaf%d_n%d_k%d" % (dim, leaf, n, k), dim, leaf, pts, q, k
+
+
+def inputs_sha256(*arrays):
+    import hashlib
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a, np.float64).tobytes())
+    return np.frombuffer(h.digest(), np.uint8)
+
+
+def test_oracle_knn_matches_live_reference_build(ob):
+    z = np.load(LIVE)
+    live = ob.ref_lib() is not None
+    for key, dim, leaf, pts, q, k in live_cases():
+        assert np.array_equal(inputs_sha256(pts, q), z[key + "_in_sha256"]), "inputs differ from the recorded ones: rerun tests/golden/make_golden.py live"
+        a = ob.knn("oracle", dim, pts, leaf, q, k)
+        assert all(np.array_equal(x, z[key + "_" + f]) for x, f in zip(a, ("idx", "d2", "cnt"))), key
+        if live:
+            b = ob.knn("ref", dim, pts, leaf, q, k)
+            assert all(np.array_equal(x, y) for x, y in zip(a, b)), key
 
 
 def test_knn_is_exact_vs_brute_force(ob):

@@ -28,7 +28,7 @@ def counters(sub):
 
 
 rows = list(csv.DictReader(open(glob.glob(os.path.join(src, "stats", "**", "*kernel_stats.csv"), recursive=True)[0])))
-lines = ["# rocprofv3 --kernel-trace --stats summary (%s): python3 bench.py --steps 15 --warmup 2 --no-cpu-baseline --no-extras" % tag, "",
+lines = ["# rocprofv3 --kernel-trace --stats summary (%s): python3 bench.py --full --steps 15 --warmup 2 --no-cpu-baseline --no-extras" % tag, "",
          "| kernel | calls | avg us | min us | max us | % |", "|---|---|---|---|---|---|"]
 avg_us = {}
 for r in rows:
@@ -73,7 +73,7 @@ pmc = {"round": tag, "git_head": head + ("+uncommitted kernel changes" if dirty 
        "kernels": "iba_pairs_kernel + iba_assoc2_kernel + iba_nn_kernel", "hbm_bytes_per_launch": tot_hbm, "valu_issue_frac": act / (N_SIMD * gui) if gui else None,
        "hbm_bytes_per_step": step_hbm, "valu_issue_frac_step": step_act / (N_SIMD * step_gui) if step_gui else None, "per_kernel": per_kernel,
        "counters": "FETCH_SIZE x2 + WRITE_SIZE (KiB); 4 x SQ_ACTIVE_INST_VALU / (1024 SIMDs x GRBM_GUI_ACTIVE / 8); TCC_REQ_sum / TCC_HIT_sum (64-byte L2 requests)",
-       "note": "one rocprofv3 --pmc pass per counter list on `python3 bench.py --steps 15 --warmup 2 --no-cpu-baseline --no-extras`; mean per launch"}
+       "note": "one rocprofv3 --pmc pass per counter list on `python3 bench.py --full --steps 15 --warmup 2 --no-cpu-baseline --no-extras`; mean per launch"}
 json.dump(pmc, open(os.path.join(out_dir, "pmc_latest.json"), "w"), indent=1)
 lines += ["", "association (pairs + assoc2) + search kernels per launch: HBM %.1f MB, VALU-active share of the SIMD cycles %.2f  (source stamp %s, head %s)" % (tot_hbm / 1e6, pmc["valu_issue_frac"] or float("nan"), pmc["source_stamp"], pmc["git_head"])]
 if bench_line:
