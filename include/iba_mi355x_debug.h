@@ -22,7 +22,7 @@
  *   IBA_CHAIN_FOLD          chain_fold                    staging / reduction launches folded into their neighbours
  *   IBA_MAX_CHAIN           max_chain_batch               candidates one launch chain takes
  *   -- no field: pure diagnostics, results unaffected unless stated --
- *   IBA_NN_CG, IBA_PAIRS_DENSE_MIN, IBA_COMMON_MIN_BATCH, IBA_PAIR_BOUND, IBA_ASSOC2_FLREG, IBA_ASSOC2_THREADS (256 / 512 threads per
+ *   IBA_NN_CG, IBA_PAIRS_DENSE_MIN, IBA_PAIRS_WAVE (the pair search's form: iba_debug_last_pairs_threads), IBA_COMMON_MIN_BATCH, IBA_PAIR_BOUND, IBA_ASSOC2_FLREG, IBA_ASSOC2_THREADS (256 / 512 threads per
  *   block of the shared-pair association, else chosen per launch), IBA_ASSOC2_SMALL_MIN, IBA_ASSOC_BLOCKS, IBA_CAND_BYTES,
  *   IBA_PAIR_BYTES                                        launch-shape / LDS-plan knobs of single kernels (A/B timing)
  *   IBA_NN_ROUNDS                                         0: the entries the anchored lists leave over are searched leaf by leaf (rounds 3-4) instead of
@@ -89,6 +89,15 @@ int32_t iba_debug_anchor_builds(const iba_handle* h);
 /* diagnostic: how many times the shared pair search has run on this handle (an evaluation whose batch stays inside the bound of
  * the lists an earlier call built reuses them: IBA_PAIR_MEMO, default on) */
 int32_t iba_debug_pairs_builds(const iba_handle* h);
+/* debug: the form of the last shared pair search: 64 / 256 / 512 = one wave per 64-position culling chunk in blocks of that many
+ * threads (the default, 64, while the scans are below pairs_dense_min points), 0 = the 512-thread block kernel (the default on
+ * dense scans); -1 before any. IBA_PAIRS_WAVE=0 / 64 / 256 / 512 forces a form. Same results whichever form runs. */
+int32_t iba_debug_last_pairs_threads(const iba_handle* h);
+/* debug: the (scan point, keypoint) pair list of (list slot, local frame) that the last pair search left: out_pairs[2 i] = original
+ * scan point index, out_pairs[2 i + 1] = keypoint id, in list order (which varies from run to run); at most cap entries are copied.
+ * slot -1: the slot of the last call's first group. Returns the length of the list (capped at the list capacity), -1 on a bad argument.
+ * The list is a superset of the pairs any candidate of the batch can accept (see iba_pairs_kernel). */
+int32_t iba_debug_pair_list(iba_handle* h, int32_t slot, int32_t frame, uint32_t* out_pairs, int32_t cap);
 /* diagnostic: list entries of the last evaluation (all candidates) that the anchored neighbour lists could not settle and the
  * tree search took over; -1 when no search ran */
 double iba_debug_nn_left_to_tree(iba_handle* h);

@@ -383,6 +383,27 @@ class IbaHandle:
         self._chk(self.lib.iba_debug_pair_lists(self.h, out))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def pair_list(self, frame, slot=-1):
+        """the (original scan point index, keypoint id) pairs of one (list slot, frame) pair list of the last pair search, as an
+        (n, 2) uint32 array in list order (slot -1: the slot of the last call's first group)"""
+        self.lib.iba_debug_pair_list.restype = C.c_int32
+        self.lib.iba_debug_pair_list.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
+        n = int(self.lib.iba_debug_pair_list(self.h, int(slot), int(frame), None, 0))
+        if n < 0:
+            raise ValueError("iba_debug_pair_list: bad slot or frame")
+        out = np.zeros((max(n, 1), 2), dtype=np.uint32)
+        n2 = int(self.lib.iba_debug_pair_list(self.h, int(slot), int(frame), out.ctypes.data, n))
+        if n2 != n:
+            raise RuntimeError("iba_debug_pair_list: the list changed between the calls")
+        return out[:n]
+
+    @property
+    def last_pairs_threads(self):
+        """form of the last shared pair search: threads per block of the one-wave-per-chunk kernel (64, 256, 512), 0 for the block kernel"""
+        self.lib.iba_debug_last_pairs_threads.restype = C.c_int32
+        self.lib.iba_debug_last_pairs_threads.argtypes = [C.c_void_p]
+        return int(self.lib.iba_debug_last_pairs_threads(self.h))
+
     @property
     def mean_pairs(self):
         self.lib.iba_debug_mean_pairs.restype = C.c_double

@@ -139,6 +139,9 @@ struct iba_handle {
     int last_assoc2_threads = 0;          // block size of the last iba_assoc2_kernel launch (iba_debug_last_assoc2_threads)
     int assoc2_threads_forced = 0;        // IBA_ASSOC2_THREADS: 256 / 512 (0: chosen per launch, assoc2_threads)
     int assoc2_small_min_blocks = 1024;   // launches of at least this many (candidate, keyframe) blocks run iba_assoc2_kernel with 256 threads per block (IBA_ASSOC2_SMALL_MIN)
+    int pairs_threads = -1;               // the pair search's form: 64 / 256 / 512 = iba_pairs_wave_kernel (one wave per culling chunk) in blocks of that many threads, 0 = iba_pairs_kernel;
+                                          // -1 (default): 64 while the keyframes' scans are below pairs_dense_min points, else 0 (IBA_PAIRS_WAVE forces a form)
+    int last_pairs_threads = -1;          // the form of the last pair-search launch (iba_debug_last_pairs_threads)
     uint32_t pairs_dense_min = 32768u;    // scans of at least this many points: the pair search tests a block's boxes before it loads the block's points and the keypoint grid (IBA_PAIRS_DENSE_MIN)
     int common_mode = 1;                  // IBA_COMMON_PAIRS: 0 = never, 1 = when the batch is tight (default), 2 = whenever the bound allows
     bool spin_wait = true;                // IBA_SPIN_WAIT=0: blocking waits only
@@ -783,6 +786,20 @@ iba_status run_split(iba_handle* h, const Cand* dc, int B, int want, bool frozen
         const uint32_t lds = kuv_off + 8u * std::max(h->maxK, 1u);
         const PairsProblem pp{dp.frames, dp.pts4, dp.chunk_box, dp.kp_uv, dp.coarse_start};
         // the pair search needs nothing but its arguments: it goes first and, in one more z-plane of its grid, carries the candidates to the device
+        const dim3 pgrid_z(1, nf, h->n_build + (head_open ? 1 : 0));
+        // The form (r07): one wave per 64-position culling chunk at the bench shape (200 KF x 10 k points: 46 -> 39 us, same bits), the
+        // 512-thread blocks on dense scans (200 KF x 120 k points: 322 us vs 386 us in one-wave blocks — tools/experiments/README.md)
+        const int pt = kChunk != 64 ? 0 : h->pairs_threads >= 0 ? h->pairs_threads : (h->maxP >= h->pairs_dense_min ? 0 : 64);
+        h->last_pairs_threads = pt;
+        auto wave_form = [&](auto kern, int threads) {   // one wave per culling chunk (its LDS is static: 5.5 KB per wave)
+            const uint32_t per_block = (uint32_t)threads;   // tree positions per block: kChunk per wave
+            hipLaunchKernelGGL(kern, dim3(std::max(1u, (h->maxP + per_block - 1u) / per_block), pgrid_z.y, pgrid_z.z), dim3(threads), 0, st, PairsArgs{pp, h->pplan}, h->params.max_pixel_dist,
+                               nf, h->d_pairs.p, h->d_hard.p, h->d_pcounts.p, h->pair_cap, h->hard_cap, head_open ? head_src : nullptr, (uint4*)dc, head_open ? head_n16 : 0u, h->pairs_dense_min);
+        };
+        if (pt == 64) wave_form(iba_pairs_wave_kernel<64>, 64);
+        else if (pt == 256) wave_form(iba_pairs_wave_kernel<256>, 256);
+        else if (pt == 512) wave_form(iba_pairs_wave_kernel<512>, 512);
+        else
         hipLaunchKernelGGL(iba_pairs_kernel, dim3(std::max(1u, (h->maxP + (uint32_t)kPairsThreads - 1u) / (uint32_t)kPairsThreads), nf, h->n_build + (head_open ? 1 : 0)), dim3(kPairsThreads), lds, st, PairsArgs{pp, h->pplan}, h->params.max_pixel_dist, kuv_off,
                            nf, h->d_pairs.p, h->d_hard.p, h->d_pcounts.p, h->pair_cap, h->hard_cap, head_open ? head_src : nullptr, (uint4*)dc, head_open ? head_n16 : 0u, h->pairs_dense_min);
         HIP_TRY(h, hipGetLastError());
@@ -1296,6 +1313,7 @@ iba_status iba_create_ex(const iba_problem_desc* d, const iba_params* params, in
     if (const char* e = dbg_env("IBA_PAIR_MEMO_MAX_B")) h->pair_memo_max_b = std::atoi(e);
     if (const char* e = dbg_env("IBA_COMMON_MIN_BATCH")) h->common_min_batch = std::max(1, std::atoi(e));
     if (const char* e = dbg_env("IBA_COMMON_MAX_PX")) h->common_max_px = std::atof(e);
+    if (const char* e = dbg_env("IBA_PAIRS_WAVE")) { const int v = std::atoi(e); h->pairs_threads = (v == 64 || v == 256 || v == 512) ? v : 0; }
     if (const char* e = dbg_env("IBA_PAIRS_DENSE_MIN")) h->pairs_dense_min = (uint32_t)std::max(0, std::atoi(e));
     if (const char* e = dbg_env("IBA_ASSOC2_THREADS")) { const int v = std::atoi(e); h->assoc2_threads_forced = (v == 256 || v == kThreads) ? v : 0; }
     if (const char* e = dbg_env("IBA_ASSOC2_SMALL_MIN")) h->assoc2_small_min_blocks = std::max(0, std::atoi(e));
@@ -1691,6 +1709,26 @@ iba_status iba_debug_phase_cycles12(iba_handle* h, uint64_t out12[12], int32_t r
 int32_t iba_debug_last_nn_threads(const iba_handle* h) { return h ? h->last_nn_threads : -1; }   // threads per block of the last search launch (64: one-wave blocks, 256)
 int32_t iba_debug_last_nn_list(const iba_handle* h) { return h ? h->last_nn_list : -1; }   // workers per (XCD, group) of the last search launch if it was iba_nn_list_kernel's (0: iba_nn_kernel)
 int32_t iba_debug_pairs_builds(const iba_handle* h) { return h ? h->pairs_builds : -1; }
+int32_t iba_debug_last_pairs_threads(const iba_handle* h) { return h ? h->last_pairs_threads : -1; }
+// debug: the pair list of (list slot, local frame) as the last pair search left it: {original scan point index, keypoint id} per entry, in
+// list order (slot -1: the slot the last call's first group read); returns the number of entries the list holds (up to its capacity; more than cap: only cap copied), -1 on a bad argument
+int32_t iba_debug_pair_list(iba_handle* h, int32_t slot, int32_t frame, uint32_t* out_pairs, int32_t cap) {
+    if (h && slot < 0) slot = h->last_mean_pairs_slot;   // (-1: the slot of the last call's first group)
+    if (!h || slot < 0 || slot >= kMaxPairGroups || frame < 0 || frame >= h->n_frames || cap < 0 || (cap > 0 && !out_pairs)) return -1;
+    if (!h->d_pairs.p || !h->d_pcounts.p || h->pair_cap <= 0) return 0;
+    if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return -1;
+    uint32_t c = 0;
+    if (hipMemcpy(&c, h->d_pcounts.p + h->amap.cnt_off[slot] + (size_t)frame * kCountStride, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    const int32_t n = (int32_t)std::min<uint32_t>(c, (uint32_t)h->pair_cap);
+    const int32_t m = std::min(n, cap);
+    if (m > 0) {
+        std::vector<PairRec> v((size_t)m);
+        if (hipMemcpy(v.data(), h->d_pairs.p + ((size_t)slot * h->n_frames + (size_t)frame) * (size_t)h->pair_cap, (size_t)m * sizeof(PairRec), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        const uint64_t k0 = h->h_kp_off[frame];   // (the list holds internal keypoint ids: Morton order of the pixel)
+        for (int32_t i = 0; i < m; ++i) { out_pairs[2 * i] = v[i].idx; out_pairs[2 * i + 1] = h->h_kp_ext[k0 + v[i].k]; }
+    }
+    return n;
+}
 int32_t iba_debug_anchor_builds(const iba_handle* h) { return h ? h->anchor_builds : -1; }
 
 // debug: exact 1-NN of n LiDAR-frame queries in the scan of a local frame, through the frame kernels' own search

@@ -27,7 +27,10 @@
 namespace iba {
 
 #ifndef IBA_PAIRS_CUT
-#define IBA_PAIRS_CUT 0   /* timing experiment (tools/pairs_cuts.sh): iba_pairs_kernel ends behind its k-th phase; results invalid */
+#define IBA_PAIRS_CUT 0   /* timing experiment (tools/pairs_cuts.sh): iba_pairs_wave_kernel ends behind its k-th phase; results invalid */
+#endif
+#ifndef IBA_PAIRS_BLOCK_CUT
+#define IBA_PAIRS_BLOCK_CUT 0   /* the same for the 512-thread iba_pairs_kernel (IBA_PAIRS_WAVE=0) */
 #endif
 #ifndef IBA_NN_EXP
 #define IBA_NN_EXP 0
@@ -873,7 +876,7 @@ __global__ __launch_bounds__(kPairsThreads) void iba_pairs_kernel(PairsArgs pa_b
     }
     __syncthreads();
     if (!s_n[3]) return;   // no candidate sees any point of this block
-#if IBA_PAIRS_CUT == 1
+#if IBA_PAIRS_BLOCK_CUT == 1
     return;
 #endif
     if (dense && pos < P) pv = p4[pos];
@@ -927,7 +930,7 @@ __global__ __launch_bounds__(kPairsThreads) void iba_pairs_kernel(PairsArgs pa_b
         __syncthreads();
         wdx = (double)s_delta[0]; wdy = (double)s_delta[1]; wdz = (double)s_delta[2];
     }
-#if IBA_PAIRS_CUT == 2
+#if IBA_PAIRS_BLOCK_CUT == 2
     return;
 #endif
     // ---- the point under the reference candidate, the batch's bound on its motion, its search window ----
@@ -973,7 +976,7 @@ __global__ __launch_bounds__(kPairsThreads) void iba_pairs_kernel(PairsArgs pa_b
         for (int w = 0; w < kPairsThreads / 64; ++w) walk |= s_n[4 + w];
         if (!walk) return;   // no point of this block can meet a keypoint under any candidate
     }
-#if IBA_PAIRS_CUT == 3
+#if IBA_PAIRS_BLOCK_CUT == 3
     return;
 #endif
     if (dense) {
@@ -993,7 +996,7 @@ __global__ __launch_bounds__(kPairsThreads) void iba_pairs_kernel(PairsArgs pa_b
     for (uint32_t i = threadIdx.x + 2u * kPairsThreads; i < ncs; i += kPairsThreads) s_cstart[i] = (uint16_t)gcs[i];
     for (uint32_t i = threadIdx.x + 2u * kPairsThreads; i < K; i += kPairsThreads) s_kuv[i] = guv[i];
     __syncthreads();
-#if IBA_PAIRS_CUT == 4
+#if IBA_PAIRS_BLOCK_CUT == 4
     return;
 #endif
     if (kind == 1) {
@@ -1019,7 +1022,7 @@ __global__ __launch_bounds__(kPairsThreads) void iba_pairs_kernel(PairsArgs pa_b
         }
     }
     __syncthreads();
-#if IBA_PAIRS_CUT == 5
+#if IBA_PAIRS_BLOCK_CUT == 5
     return;
 #endif
     const uint32_t n = min(s_n[0], (uint32_t)kPairStage);
@@ -1036,6 +1039,294 @@ __global__ __launch_bounds__(kPairsThreads) void iba_pairs_kernel(PairsArgs pa_b
             out[g] = pr;
         } else cnt[2] = 1u;
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// iba_pairs_wave_kernel<THREADS>: the same search with ONE WAVE PER CULLING CHUNK (kChunk = 64 consecutive tree positions) and no
+// workgroup barrier. iba_pairs_kernel's 512-thread block is a chain of six __syncthreads with a global round trip between most of
+// them (r06: VALU 0.33, 70 % of its time waiting); a wave that owns its chunk runs box test, batch bound, windows, staging, walk and
+// write-out straight through, and the waves of a launch start and retire one by one (the search kernel's lesson).
+// THREADS / 64 waves share a workgroup only as a launch unit (64: one wave per block; 256 and 512 for the A/B). Scans of pairs_dense_min
+// points or more keep iba_pairs_kernel: there most chunks are culled and 8 x the workgroups cost more than the barriers (host rule, run_split).
+//   1. the chunk's box against the batch (as iba_pairs_kernel, every lane computes the wave-uniform test); a sparse scan has the
+//      chunk's 64 points in flight with the box, a dense one loads them behind the test;
+//   2. the batch bound over THIS chunk's box (lane b: candidate b, then a shuffle maximum) — iba_pairs_kernel's arithmetic and
+//      margins on the 64-point box instead of the union of eight, so never wider; the entrywise (rho, tau) bound below it as before;
+//   3. per-point window and hard points: iba_pairs_kernel's expressions (r <= 64 rule included); one atomic per wave on cnt[1];
+//   4. only the part of the keypoint grid the wave's windows reach is staged in the wave's LDS slice: coarse rows ymin..ymax,
+//      columns xmin..xmax+1 of the CSR (<= kPwCs starts) and the keypoints [cs(ymin, xmin), cs(ymax, xmax + 1)) (<= kPwKuv); a
+//      wider span walks the grid in global memory (same pairs, slower);
+//   5. the walk in lockstep, two keypoints per lane and step, each lane moving to its window's next coarse row on its own; the
+//      hits of a step are packed into the wave's LDS stage with a ballot and prefix (no LDS atomics);
+//   6. a full stage (and the last one) is flushed behind ONE atomic on the frame's cnt[0]; the point of a hit comes from its lane
+//      by a shuffle, not from memory.
+// The list differs from iba_pairs_kernel's only by the pairs the tighter per-chunk bound drops, and in order (atomic reservations
+// order it from run to run anyway): iba_assoc2_kernel's decisions depend on neither (see above).
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int kPwKuv = 512;     // keypoints (u, v) a wave stages: 4 KB
+constexpr int kPwCs = 256;      // coarse CSR starts a wave stages (u16): 512 B
+constexpr int kPwStage = 256;   // hits a wave parks before a flush (u32: lane | keypoint << 6): 1 KB
+constexpr uint32_t kPwWaveLds = 8u * kPwKuv + 2u * kPwCs + 4u * kPwStage;   // 5.5 KB per wave: 24 waves per CU (6 per SIMD, what 80 VGPRs allow) need 132 KB of 160
+__device__ __forceinline__ void wave_lds_sync() {   // the lanes of ONE wave see each other's LDS writes (no workgroup barrier)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ uint32_t lane_prefix(unsigned long long m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
+__device__ __forceinline__ int wave_min_i(int x) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) x = min(x, __shfl_xor(x, o));
+    return x;
+}
+__device__ __forceinline__ int wave_max_i(int x) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) x = max(x, __shfl_xor(x, o));
+    return x;
+}
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void iba_pairs_wave_kernel(PairsArgs pa_by_value, double max_pixel_dist, int n_frames,
+                                                                 PairRec* __restrict__ pairs_all, uint32_t* __restrict__ hard_all,
+                                                                 uint32_t* __restrict__ counts_all, int pair_cap, int hard_cap,
+                                                                 const uint4* __restrict__ head_src, uint4* __restrict__ head_dst, uint32_t head_n16, uint32_t dense_min_pts) {
+    constexpr int kWaves = THREADS / 64;
+    __shared__ __align__(16) unsigned char smem[kWaves * kPwWaveLds];
+    if (head_n16 != 0u && blockIdx.z + 1u == gridDim.z) {   // the chain's head (see iba_pairs_kernel)
+        chain_head_copy(head_src, head_dst, head_n16, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, (uint32_t)THREADS);
+        return;
+    }
+    typedef __attribute__((address_space(4))) const PairsArgs PairsArgsC;
+    PairsArgsC* pa = (PairsArgsC*)__builtin_amdgcn_kernarg_segment_ptr();
+    (void)pa_by_value;
+    const uint32_t lane = threadIdx.x & 63u, wave = kWaves == 1 ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int grp = blockIdx.z;
+    const FrameHdr& h = pa->dp.frames[blockIdx.y];
+    const uint32_t P = h.P;
+    const uint32_t chunk = blockIdx.x * (uint32_t)kWaves + wave;
+    const int f = blockIdx.y;
+    uint32_t* cnt = counts_all + pa->pl.cnt_off[grp] + (size_t)f * kCountStride;
+    // the counters of the NEXT call's lists: cleared by the first chunk of the (frame, group), before any return
+    if (chunk == 0u && lane < 4u) counts_all[pa->pl.next_off[grp] + (size_t)f * kCountStride + lane] = 0u;
+    if (chunk * (uint32_t)kChunk >= P) return;
+    GroupRef cr;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { cr.R[i] = pa->pl.g[grp].R[i]; cr.rho[i] = pa->pl.g[grp].rho[i]; }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { cr.t[i] = pa->pl.g[grp].t[i]; cr.tau[i] = pa->pl.g[grp].tau[i]; }
+    const int B = (int)pa->pl.count[grp], rel0 = (int)pa->pl.first[grp];
+    const size_t slot = (size_t)pa->pl.slot[grp];
+    PairRec* out = pairs_all + (slot * (size_t)n_frames + (size_t)f) * (size_t)pair_cap;
+    uint32_t* hout = hard_all + (slot * (size_t)n_frames + (size_t)f) * (size_t)hard_cap;
+    const float4* p4 = pa->dp.pts4 + h.pt_base;
+    const float2* guv = pa->dp.kp_uv + h.kp_base;
+    const uint32_t* gcs = pa->dp.coarse_start + h.coarse_base;
+    const int gw = (int)h.gw, gh = (int)h.gh, gwc = (int)h.gwc;
+    const double fx = h.fx, cx = h.cx, cy = h.cy, W = h.W, H = h.H;
+    const uint32_t pos = chunk * (uint32_t)kChunk + lane;
+    const bool dense = P >= dense_min_pts;   // (a property of the keyframe: a dense scan tests the box before it loads the points)
+    const float4* bx = (const float4*)(pa->dp.chunk_box + 8 * (h.box_base + chunk));
+    const float4 lo = bx[0], hi = bx[1];
+    float4 pv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!dense && pos < P) pv = p4[pos];
+    // ---- 1. the chunk's box against every candidate's frustum (iba_pairs_kernel's test, wave-uniform) ----
+    {
+        const double c3[3] = {0.5 * ((double)lo.x + (double)hi.x), 0.5 * ((double)lo.y + (double)hi.y), 0.5 * ((double)lo.z + (double)hi.z)};
+        const double e3[3] = {0.5 * ((double)hi.x - (double)lo.x), 0.5 * ((double)hi.y - (double)lo.y), 0.5 * ((double)hi.z - (double)lo.z)};
+        double qc[3], ex[3], m[3];
+        for (int i = 0; i < 3; ++i) {
+            qc[i] = ((cr.R[i * 3] * c3[0] + cr.R[i * 3 + 1] * c3[1]) + cr.R[i * 3 + 2] * c3[2]) + cr.t[i];
+            ex[i] = (fabs(cr.R[i * 3]) * e3[0] + fabs(cr.R[i * 3 + 1]) * e3[1]) + fabs(cr.R[i * 3 + 2]) * e3[2];
+        }
+        const double a3[3] = {fabs(qc[0]) + ex[0], fabs(qc[1]) + ex[1], fabs(qc[2]) + ex[2]};
+        for (int i = 0; i < 3; ++i)
+            m[i] = (ex[i] + ((cr.rho[i * 3] * a3[0] + cr.rho[i * 3 + 1] * a3[1]) + cr.rho[i * 3 + 2] * a3[2]) + cr.tau[i]) * (1.0 + 1e-9) + 1e-9 * ((a3[0] + a3[1]) + a3[2]) + 1e-9;
+        const double zhi = qc[2] + m[2];
+        const bool behind = zhi <= 0.0;
+        const bool right = fx * (qc[0] - m[0]) + (cx - W) * zhi >= 1e-6 * (fx * a3[0] + W * a3[2]);
+        const bool left = fx * (qc[0] + m[0]) + cx * zhi < -1e-6 * (fx * a3[0] + W * a3[2]);
+        const bool below = fx * (qc[1] - m[1]) + (cy - H) * zhi >= 1e-6 * (fx * a3[1] + H * a3[2]);
+        const bool above = fx * (qc[1] + m[1]) + cy * zhi < -1e-6 * (fx * a3[1] + H * a3[2]);
+        if (behind || right || left || below || above) return;   // (a NaN box compares false everywhere: kept, harmless)
+    }
+#if IBA_PAIRS_CUT == 1
+    return;
+#endif
+    if (dense && pos < P) pv = p4[pos];
+    // ---- 2. how far the candidates move the points of THIS chunk: iba_pairs_kernel's bound over the chunk's own box ----
+    double wdx = INFINITY, wdy = INFINITY, wdz = INFINITY;
+    if (B > 0) {   // (B = 0: a lone candidate or a reusable list — the entrywise bound only)
+        const float l[3] = {lo.x, lo.y, lo.z}, u[3] = {hi.x, hi.y, hi.z};
+        const double c3[3] = {0.5 * ((double)l[0] + (double)u[0]), 0.5 * ((double)l[1] + (double)u[1]), 0.5 * ((double)l[2] + (double)u[2])};
+        const double e3[3] = {0.5 * ((double)u[0] - (double)l[0]), 0.5 * ((double)u[1] - (double)l[1]), 0.5 * ((double)u[2] - (double)l[2])};
+        double qc[3], ex[3];
+        for (int i = 0; i < 3; ++i) {
+            qc[i] = ((cr.R[i * 3] * c3[0] + cr.R[i * 3 + 1] * c3[1]) + cr.R[i * 3 + 2] * c3[2]) + cr.t[i];
+            ex[i] = ((fabs(cr.R[i * 3]) * e3[0] + fabs(cr.R[i * 3 + 1]) * e3[1]) + fabs(cr.R[i * 3 + 2]) * e3[2]) * (1.0 + 1e-9) + 1e-9 * ((fabs(c3[0]) + fabs(c3[1])) + fabs(c3[2])) + 1e-12;   // (+ the rounding of qc itself)
+        }
+        const double scale = (fabs(qc[0]) + fabs(qc[1])) + fabs(qc[2]) + (ex[0] + ex[1]) + ex[2];
+        float m[3] = {0.f, 0.f, 0.f};
+        const int b = (int)lane;
+        if (b < B) {
+            double rl[12];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) rl[i] = (double)pa->pl.rel[rel0 + b][i];
+            for (int i = 0; i < 3; ++i) {
+                const double lin = (fabs(rl[i * 3]) * (fabs(qc[0]) + ex[0]) + fabs(rl[i * 3 + 1]) * (fabs(qc[1]) + ex[1])) + fabs(rl[i * 3 + 2]) * (fabs(qc[2]) + ex[2]);
+                const double mi = (fabs(((rl[i * 3] * qc[0] + rl[i * 3 + 1] * qc[1]) + rl[i * 3 + 2] * qc[2]) + rl[9 + i]) + ((fabs(rl[i * 3]) * ex[0] + fabs(rl[i * 3 + 1]) * ex[1]) + fabs(rl[i * 3 + 2]) * ex[2])) * (1.0 + 1e-9) + 1e-12 * scale + 1e-13
+                                  + 6.1e-8 * (lin + fabs(rl[9 + i]));
+                m[i] = (float)mi * 1.0000002f + 1e-30f;   // >= mi (NaN stays NaN)
+            }
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1)
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { const float other = __shfl_xor(m[i], o); m[i] = (m[i] != m[i] || other != other) ? __builtin_nanf("") : fmaxf(m[i], other); }
+        // NaN (an empty chunk's box, a NaN candidate): the entrywise bound alone
+        wdx = (double)(m[0] == m[0] ? m[0] : INFINITY); wdy = (double)(m[1] == m[1] ? m[1] : INFINITY); wdz = (double)(m[2] == m[2] ? m[2] : INFINITY);
+    }
+#if IBA_PAIRS_CUT == 2
+    return;
+#endif
+    // ---- 3. the point under the reference candidate, the batch's bound on its motion, its search window (iba_pairs_kernel's) ----
+    int kind = 0;   // 0: nothing to do, 1: walk the grid, 2: hard point
+    double u0 = 0, v0 = 0, r = 0;
+    if (pos < P) {
+        const double x = (double)pv.x, y = (double)pv.y, z = (double)pv.z;
+        const double x0 = ((cr.R[0] * x + cr.R[1] * y) + cr.R[2] * z) + cr.t[0];
+        const double y0 = ((cr.R[3] * x + cr.R[4] * y) + cr.R[5] * z) + cr.t[1];
+        const double z0 = ((cr.R[6] * x + cr.R[7] * y) + cr.R[8] * z) + cr.t[2];
+        const double ax = fabs(x0), ay = fabs(y0), az = fabs(z0);
+        const double round_off = 1e-13 * ((ax + ay) + az) + 1e-13;
+        const double dx = fmin(((cr.rho[0] * ax + cr.rho[1] * ay) + cr.rho[2] * az) + cr.tau[0], wdx) + round_off;
+        const double dy = fmin(((cr.rho[3] * ax + cr.rho[4] * ay) + cr.rho[5] * az) + cr.tau[1], wdy) + round_off;
+        const double dz = fmin(((cr.rho[6] * ax + cr.rho[7] * ay) + cr.rho[8] * az) + cr.tau[2], wdz) + round_off;
+        if (!(z0 == z0) || z0 < -dz) kind = 0;
+        else if (!(z0 > 2.0 * dz)) {
+            const double zmax = z0 + dz;
+            const bool out_u = fx * (ax - dx) > zmax * (fmax(cx, W - cx) + 1.0), out_v = fx * (ay - dy) > zmax * (fmax(cy, H - cy) + 1.0);
+            kind = (out_u || out_v) ? 0 : 2;
+        } else {
+            const double den = z0 * (z0 - dz);
+            const double Du = fx * (dx * z0 + ax * dz) / den, Dv = fx * (dy * z0 + ay * dz) / den;
+            u0 = fx * x0 / z0 + cx; v0 = fx * y0 / z0 + cy;
+            if (u0 + Du < -1.0 || u0 - Du >= W + 1.0 || v0 + Dv < -1.0 || v0 - Dv >= H + 1.0) kind = 0;
+            else {
+                r = max_pixel_dist + sqrt(Du * Du + Dv * Dv) + 0.02;
+                kind = (r <= 64.0) ? 1 : 2;
+            }
+        }
+    }
+    {   // hard points: one reservation per wave
+        const unsigned long long hm = __ballot(kind == 2);
+        if (hm != 0ull) {
+            uint32_t hb = 0u;
+            if (lane == 0u) hb = atomicAdd(&cnt[1], (uint32_t)__popcll(hm));
+            hb = (uint32_t)__shfl((int)hb, 0);
+            if (kind == 2) {
+                const uint32_t s = hb + lane_prefix(hm);
+                if (s < (uint32_t)hard_cap) hout[s] = pos; else cnt[2] = 1u;
+            }
+        }
+    }
+    const bool walk = kind == 1;
+    if (__ballot(walk) == 0ull) return;   // no point of this chunk can meet a keypoint under any candidate
+#if IBA_PAIRS_CUT == 3
+    return;
+#endif
+    // ---- 4. the part of the keypoint grid the wave's windows reach, into the wave's LDS slice ----
+    int x0c = 0x7fff, x1c = -1, y0c = 0x7fff, y1c = -1;
+    if (walk) {
+        x0c = grid_cell((float)(u0 - r) - 0.01f, gw) >> kCoarseShift; x1c = grid_cell((float)(u0 + r) + 0.01f, gw) >> kCoarseShift;
+        y0c = grid_cell((float)(v0 - r) - 0.01f, gh) >> kCoarseShift; y1c = grid_cell((float)(v0 + r) + 0.01f, gh) >> kCoarseShift;
+    }
+    const int xmin = __builtin_amdgcn_readfirstlane(wave_min_i(x0c)), xmax = __builtin_amdgcn_readfirstlane(wave_max_i(x1c));
+    const int ymin = __builtin_amdgcn_readfirstlane(wave_min_i(y0c)), ymax = __builtin_amdgcn_readfirstlane(wave_max_i(y1c));
+    const int ncol = xmax - xmin + 2, ncs = (ymax - ymin + 1) * ncol;
+    const uint32_t E0 = gcs[ymin * gwc + xmin], E1 = gcs[ymax * gwc + xmax + 1];
+    unsigned char* wl = smem + wave * kPwWaveLds;
+    float2* s_kuv = (float2*)wl;
+    uint16_t* s_cs = (uint16_t*)(wl + 8u * kPwKuv);
+    uint32_t* s_hit = (uint32_t*)(wl + 8u * kPwKuv + 2u * kPwCs);
+    const uint32_t nE = E1 - E0;
+    const bool staged = ncs <= kPwCs && nE <= (uint32_t)kPwKuv;   // (wave-uniform)
+    if (staged) {
+        float2 kr[kPwKuv / 64]; uint32_t cr4[kPwCs / 64];
+#pragma unroll
+        for (int j = 0; j < kPwCs / 64; ++j) {
+            const int i = (int)lane + 64 * j;
+            cr4[j] = i < ncs ? gcs[(ymin + i / ncol) * gwc + xmin + i % ncol] : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < kPwKuv / 64; ++j) {
+            const uint32_t i = lane + 64u * (uint32_t)j;
+            kr[j] = i < nE ? guv[E0 + i] : make_float2(0.f, 0.f);
+        }
+#pragma unroll
+        for (int j = 0; j < kPwCs / 64; ++j) { const int i = (int)lane + 64 * j; if (i < ncs) s_cs[i] = (uint16_t)cr4[j]; }
+#pragma unroll
+        for (int j = 0; j < kPwKuv / 64; ++j) { const uint32_t i = lane + 64u * (uint32_t)j; if (i < nE) s_kuv[i] = kr[j]; }
+        wave_lds_sync();
+    }
+#if IBA_PAIRS_CUT == 4
+    return;
+#endif
+    auto cs_at = [&](int yy, int xx) -> uint32_t { return staged ? (uint32_t)s_cs[(yy - ymin) * ncol + (xx - xmin)] : gcs[yy * gwc + xx]; };
+    auto kuv_at = [&](uint32_t e) -> float2 { return staged ? s_kuv[e - E0] : guv[e]; };
+    // ---- 6. write-out of the staged hits behind one reservation (wave-uniform n) ----
+    auto flush = [&](uint32_t n) {
+        wave_lds_sync();
+        uint32_t base = 0u;
+        if (lane == 0u) base = atomicAdd(&cnt[0], n);
+        base = (uint32_t)__shfl((int)base, 0);
+        for (uint32_t i0 = 0; i0 < n; i0 += 64u) {
+            const uint32_t i = i0 + lane;
+            const uint32_t hw = i < n ? s_hit[i] : 0u;
+            const int l = (int)(hw & 63u);
+            const float qx = __shfl(pv.x, l), qy = __shfl(pv.y, l), qz = __shfl(pv.z, l), qw = __shfl(pv.w, l);
+            if (i < n) {
+                const uint32_t g = base + i;
+                if (g < (uint32_t)pair_cap) {
+                    const uint32_t e = hw >> 6;
+                    const float2 kv = kuv_at(e);
+                    PairRec pr; pr.x = qx; pr.y = qy; pr.z = qz; pr.idx = __float_as_uint(qw); pr.u = kv.x; pr.v = kv.y; pr.k = e; pr.pad = 0u;
+                    out[g] = pr;
+                } else cnt[2] = 1u;
+            }
+        }
+        wave_lds_sync();   // (the stage is refilled next)
+    };
+    // ---- 5. the walk: every lane its own window, row by row, two keypoints per step, all lanes in step ----
+    const double r2 = r * r;
+    int yy = y0c;
+    uint32_t e = 0u, e1 = 0u;
+    bool act = walk;
+    uint32_t n = 0u;   // hits staged (wave-uniform)
+    for (;;) {
+        while (act && e >= e1) {   // the lane's next non-empty coarse row
+            if (yy > y1c) { act = false; break; }
+            e = cs_at(yy, x0c); e1 = cs_at(yy, x1c + 1); ++yy;
+        }
+        if (__ballot(act) == 0ull) break;
+        bool h0 = false, h1 = false;
+        const uint32_t ea = e, eb = e + 1u;
+        if (act) {
+            const bool two = eb < e1;
+            const float2 ka = kuv_at(ea), kb = kuv_at(two ? eb : ea);
+            const double dua = (double)ka.x - u0, dva = (double)ka.y - v0, dub = (double)kb.x - u0, dvb = (double)kb.y - v0;
+            h0 = dua * dua + dva * dva <= r2;
+            h1 = two && dub * dub + dvb * dvb <= r2;
+            e += two ? 2u : 1u;
+        }
+        const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1);
+        if (h0) s_hit[n + lane_prefix(m0)] = lane | (ea << 6);
+        if (h1) s_hit[n + (uint32_t)__popcll(m0) + lane_prefix(m1)] = lane | (eb << 6);
+        n += (uint32_t)(__popcll(m0) + __popcll(m1));
+        if (n > (uint32_t)(kPwStage - 128)) { flush(n); n = 0u; }
+    }
+#if IBA_PAIRS_CUT == 5
+    return;
+#endif
+    if (n != 0u) flush(n);
 }
 
 // exact association of one scan point against the keypoint grid in GLOBAL memory (hard points, overflow rescans): grid_match
