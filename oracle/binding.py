@@ -53,6 +53,19 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def ldbl_mant_dig():
+    """LDBL_MANT_DIG of the compiler that built the oracle (64: x87 80-bit extended; 53: long double is plain double)"""
+    return int(lib().oracle_ldbl_mant_dig())
+
+
+def require_long_double():
+    """the truth (set_exact_sums(2)) is a long-double evaluation only where long double carries at least 64 mantissa bits: with 53 it is one more
+    double evaluation, its error against the double oracle reads as about 0 and the gate of tests/parity_gate.py falls back to its strict floor"""
+    m = ldbl_mant_dig()
+    if m < 64:
+        raise RuntimeError("the oracle's long double has %d mantissa bits (LDBL_MANT_DIG); the long-double truth needs at least 64 (x87 80-bit)" % m)
+
+
 def geo_correspondences(which, src, tgt, max_distance):
     """GeoCalib.h:18-33 computeCorrespondence. which: 'oracle' (this directory's restatement) | 'ref' (the reference's own nanoflann, oracle/_ref).
     src [n, 3], tgt [m, 3] doubles -> (source indices, target indices) of the kept pairs."""
@@ -151,9 +164,15 @@ class Oracle:
     def eval_normal_truth(self, params, x):
         """the normal equations with rows, weights and sums in long double (x87 80-bit), rounded to double at the end: what the reference's formulas are
         worth at x. Single-threaded (one candidate: ~1 s per 50 k blocks)."""
+        return self.eval_normal_truth_batch(params, x, nthreads=1)
+
+    def eval_normal_truth_batch(self, params, xs, nthreads=1):
+        """eval_normal_truth of every candidate of xs in one call: the long-double sums stay one sequential loop per candidate (the same bits as
+        eval_normal_truth), only the problem building of each candidate runs on nthreads"""
+        require_long_double()
         Oracle.set_exact_sums(2)
         try:
-            return self.eval_normal(params, x, nthreads=1)
+            return self.eval_normal(params, xs, nthreads=nthreads)
         finally:
             Oracle.set_exact_sums(0)
 

@@ -18,6 +18,7 @@
 // closed-form math pinned by known-answer tests; the remainder "parity unpinned" because the
 // reference has no tests and its third-party dependencies (Eigen, OpenCV, g2o, Ceres) are absent.
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -624,6 +625,7 @@ int oracle_eval_factors(void* h, const iba_params* p, const double* x, int B, ib
     return 0;
 }
 void oracle_set_exact_sums(int on) { g_exact_sums = on; }   // 0 off, 1 long-double sums of the double rows, 2 long-double rows and sums
+int oracle_ldbl_mant_dig() { return LDBL_MANT_DIG; }   // mode 2 is "the truth" only with the x87 80-bit long double (64); 53 would make it a second double evaluation
 void oracle_set_frame_range(void* h, int f_begin, int f_end) { ((Oracle*)h)->bp_f_begin = f_begin; ((Oracle*)h)->bp_f_end = f_end; }
 int oracle_eval_normal(void* h, const iba_params* p, const double* x, int B, iba_normal_out* out, int nthreads) {
 #ifdef _OPENMP

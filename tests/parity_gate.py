@@ -31,21 +31,53 @@ def worst_rel(a, t, floor=FLOOR):
     return w_big, w_small
 
 
-def entries_vs_truth(g, o, t, what=""):
-    """device g, double oracle o, long-double truth t (arrays of one shape)"""
+def check_entries_vs_truth(g, o, t):
+    """-> (ok, {"device": (big, small), "oracle": (big, small), "bar": (big, small)}): the figures of worst_rel for g and o against t, and the bars
+    the device's are held to"""
     gb, gs = worst_rel(g, t)
     ob_, os_ = worst_rel(o, t)
-    assert gb <= max(REL, SLACK * ob_), "%s: device %.2e from the long-double value, the double oracle %.2e" % (what, gb, ob_)
-    assert gs <= max(REL * FLOOR * 10, SLACK * os_), "%s (small entries): device %.2e, the double oracle %.2e of the largest entry" % (what, gs, os_)
-    return gb, ob_
+    bar = (max(REL, SLACK * ob_), max(REL * FLOOR * 10, SLACK * os_))
+    return gb <= bar[0] and gs <= bar[1], {"device": (gb, gs), "oracle": (ob_, os_), "bar": bar}
+
+
+def check_normal_vs_truth(g, o, t):
+    """-> (ok, report) without raising. g, o, t: iba_normal_out-like objects (counts(), H_np(), b_np(), cost, chi2) of the device, the double oracle and
+    the long-double oracle. report: "counts" (equal or not), "H" / "b" (check_entries_vs_truth's figures), "cost" / "chi2" ({"device", "oracle": |v - t|
+    relative to |t|}), "failed" (the names of what missed its bar)"""
+    rep = {"counts": g.counts() == o.counts() == t.counts(), "failed": []}
+    if not rep["counts"]:
+        rep["failed"].append("counts")
+    for k, a, b, c in (("H", g.H_np(), o.H_np(), t.H_np()), ("b", g.b_np(), o.b_np(), t.b_np())):
+        ok, rep[k] = check_entries_vs_truth(a, b, c)
+        if not ok:
+            rep["failed"].append(k)
+    for k in ("cost", "chi2"):
+        gv, ov, tv = getattr(g, k), getattr(o, k), getattr(t, k)
+        rel = abs(tv) if tv != 0 else 1.0
+        rep[k] = {"device": abs(gv - tv) / rel, "oracle": abs(ov - tv) / rel}
+        if not abs(gv - tv) <= max(REL * abs(tv), SLACK * abs(ov - tv)):
+            rep["failed"].append(k)
+    return not rep["failed"], rep
 
 
 def normal_vs_truth(g, o, t):
     """iba_normal_out-like objects (counts(), H_np(), b_np(), cost, chi2): device, double oracle, long-double oracle"""
-    assert g.counts() == o.counts() == t.counts(), (g.counts(), o.counts())
-    rH = entries_vs_truth(g.H_np(), o.H_np(), t.H_np(), "H")
-    rb = entries_vs_truth(g.b_np(), o.b_np(), t.b_np(), "b")
+    ok, rep = check_normal_vs_truth(g, o, t)
+    assert rep["counts"], (g.counts(), o.counts())
+    for k in ("H", "b"):
+        (gb, gs), (ob_, os_), (bb, bs) = rep[k]["device"], rep[k]["oracle"], rep[k]["bar"]
+        assert gb <= bb, "%s: device %.2e from the long-double value, the double oracle %.2e" % (k, gb, ob_)
+        assert gs <= bs, "%s (small entries): device %.2e, the double oracle %.2e of the largest entry" % (k, gs, os_)
     for k in ("cost", "chi2"):
-        gv, ov, tv = getattr(g, k), getattr(o, k), getattr(t, k)
-        assert abs(gv - tv) <= max(REL * abs(tv), SLACK * abs(ov - tv)), (k, gv, ov, tv)
-    return {"H": rH, "b": rb}
+        assert k not in rep["failed"], (k, getattr(g, k), getattr(o, k), getattr(t, k))
+    assert ok
+    return {"H": (rep["H"]["device"][0], rep["H"]["oracle"][0]), "b": (rep["b"]["device"][0], rep["b"]["oracle"][0])}
+
+
+def explained_within(explained, flagged, cap, block_cap, what=""):
+    """the candidates of one launch that missed the plain gates and passed parity_explain.explain instead (explained: their indices, flagged: the
+    deviating blocks of each) may number at most cap, their flagged blocks at most block_cap: an explanation is accepted for a few candidates, not as
+    the rule"""
+    assert len(explained) == len(flagged), (explained, flagged)
+    assert len(explained) <= cap, "%s: %d candidates needed the block-by-block explanation (%s), at most %d allowed" % (what, len(explained), explained, cap)
+    assert sum(flagged) <= block_cap, "%s: %d flagged blocks over the explained candidates (%s), at most %d allowed" % (what, sum(flagged), flagged, block_cap)
