@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define IBA_ABI_VERSION 2 /* 2: iba_params.factor_3d2d_kind */
+#define IBA_ABI_VERSION 3 /* 2: iba_params.factor_3d2d_kind; 3: iba_icp_* */
 #define IBA_MAX_BATCH 64 /* the batch unit of the callers in this library (one MADS poll block, the planner's diagnostics); NOT a limit of the evaluators */
 #define IBA_MAX_CHAIN 512 /* most candidates ONE launch chain takes (iba_create_options.max_chain_batch <= this); a call with more runs as consecutive chains */
 
@@ -156,6 +156,80 @@ typedef struct iba_params {
  * there); this entry point exists so that the one name north_star lists is not missing, and is pinned against the reference's own nanoflann. */
 iba_status iba_geo_correspondences(iba_handle* h, int32_t frame, const double* src_xyz, int32_t n_src, double max_distance,
                                    uint32_t* out_src, uint32_t* out_tgt, int32_t* n_out);
+
+/*
+ * ---- Scaled point-to-point ICP on the device kd search [SURVEY.md 2 row 18: icp_calib.cpp:10-86, the geometry-only ablation baseline] ----
+ * icp_calib registers the ORB map cloud (source) to the LiDAR map cloud (target) with Open3D's RegistrationICP and
+ * TransformationEstimationPointToPoint(true), starting from the hand-eye Sim(3), and writes a Sim(3). Open3D is not part of the reference
+ * tree: the loop is RESTATED here from its public sources and its parity is UNPINNED (the kd search underneath stays pinned to the reference's
+ * nanoflann). What is restated:
+ *   RegistrationICP                              evaluate at init; up to max_iter times: update = estimation(correspondences), T = update * T,
+ *                                                re-evaluate, stop when |d fitness| < relative_fitness AND |d inlier_rmse| < relative_rmse
+ *   GetRegistrationResultAndCorrespondences      per source point the nearest target point inside the gate; fitness = kept / n_src,
+ *                                                inlier_rmse = sqrt(sum d^2 / kept) (both 0 when nothing is kept)
+ *   KDTreeFlann::SearchHybrid(query, r, 1)       a k = 1 search followed by lower_bound(d^2, r^2): a pair is kept when d^2 < r^2, STRICTLY
+ *                                                (iba_geo_correspondences, GeoCalib.h:29, keeps d^2 <= its parameter)
+ *   Eigen::umeyama(src, dst, with_scaling)       sigma = 1/n sum (p - mean_p)(q - mean_q)^T = U D V^T; S = diag(1, 1, -1) when
+ *                                                det(U) det(V) < 0; R = U S V^T; c = tr(D S) / var_q (1 without scaling); t = mean_p - c R mean_q
+ * Two deviations, both known: (1) Open3D transforms its working copy of the source cumulatively, one more rounding per point and iteration;
+ * here the composed T is applied to the ORIGINAL source points in every pass (one rounding, whatever the iteration). (2) Between two target
+ * points at exactly the same distance the lower (frame, index) wins, the tie rule of the kd search; FLANN keeps the first it visits.
+ *
+ * Target cloud: the scans of local frames [frame_begin, frame_end) of the handle, read as TILES of one cloud in one coordinate frame (a
+ * scans-only handle is enough). A target point is the pair (local frame, original index in that scan). frame_end - frame_begin == 1 is the
+ * common case and runs the single search; with more tiles a lane searches them in ascending order, carries its best distance into the next
+ * tile's search and skips a tile whose bounding box lies further away than that. No limit on the tiles but the handle's frames; a tile holds
+ * what a scan holds.
+ * Source cloud: n_src points (x, y, z doubles). q = T x is evaluated in f64, row r as fma(T[r][2], z, fma(T[r][1], y, fma(T[r][0], x, T[r][3])))
+ * (the library is built without floating-point contraction: exactly these three operations fuse). T: row-major 4x4, rows 0-2 are read.
+ *
+ * Moments of one pass (iba_icp_step; IBA_ICP_NMOM doubles per transform), summed on the device over the kept pairs (q, p), p the target point,
+ * about the PIVOT v = T * centroid(source) (centroid: plain sequential f64 mean of src_xyz on the host), dq = q - v, dp = p - v:
+ *   [0] kept pairs   [1] sum d^2 (d^2 = ((qx-px)^2 + (qy-py)^2) + (qz-pz)^2, the search's own value)   [2..4] sum dq   [5..7] sum dp
+ *   [8] sum |dq|^2   [9..17] sum dp dq^T, row-major (entry 9 + 3 i + j = sum dp_i dq_j)   [18..20] the pivot v
+ * The sums have a fixed order (a wave's 64 lanes by DPP, the waves of a transform by position): two calls give the same bits, and a
+ * transform's block does not depend on what else is in the batch. No atomics on floating-point values.
+ */
+#define IBA_ICP_NMOM 21
+#define IBA_ICP_CONVERGED 1      /* iba_icp_result.converged: both criteria met */
+#define IBA_ICP_MAX_ITER 0       /* max_iter updates applied (max_iter = 0: evaluation only) */
+#define IBA_ICP_DEGENERATE (-1)  /* fewer than 3 kept pairs, or a source set without spread: no update is defined; T is the last valid one */
+typedef struct iba_icp_options {
+    int32_t struct_size;
+    double  max_corr_dist;      /* icp_calib.cpp:26; a pair is kept when d^2 < max_corr_dist^2 (strict) */
+    int32_t max_iter;           /* icp_calib.cpp:27,62 */
+    double  relative_fitness;   /* Open3D ICPConvergenceCriteria defaults: 1e-6 */
+    double  relative_rmse;      /* 1e-6 */
+    int32_t with_scaling;       /* 1 = TransformationEstimationPointToPoint(true), what icp_calib uses; 0 = rigid */
+} iba_icp_options;
+typedef struct iba_icp_result {
+    double  T[16];              /* row-major 4x4, source -> target, upper-left block = c * R */
+    double  scale;              /* c = sqrt((A A^T)_00) of the upper-left block A */
+    double  fitness;            /* kept pairs / n_src */
+    double  inlier_rmse;        /* sqrt(sum d^2 / kept pairs) */
+    int32_t n_corr, iterations, converged;   /* iterations: updates applied; converged: IBA_ICP_* */
+} iba_icp_result;
+/* max_corr_dist 1.0, max_iter 30 (Open3D's default), 1e-6, 1e-6, with_scaling 1 */
+iba_status iba_default_icp_options(iba_icp_options* opt);
+/* One correspondence pass per transform (GeoCalib.h computeCorrespondenceList: one tree, B clouds that are transforms of one cloud, one launch
+ * chain). pair_frame / pair_idx: both NULL (nothing of size n_src leaves the device) or B x n_src entries each: the target of every source
+ * point, 0xFFFFFFFF in both where the pair is not kept. B in [1, 4096]; n_src = 0 answers zero moments. */
+iba_status iba_icp_step(iba_handle* h, int32_t frame_begin, int32_t frame_end, const double* src_xyz, int32_t n_src,
+                        const double* T /* B x 16 */, int32_t B, double max_corr_dist, double* moments /* B x IBA_ICP_NMOM */,
+                        uint32_t* pair_frame, uint32_t* pair_idx);
+/* RegistrationICP from B independent starts. The source is uploaded once and stays on the device; per iteration the transforms of the starts
+ * still running go down and their moment blocks come back. The 3x3 Umeyama runs on the host. A start's result does not depend on the batch. */
+iba_status iba_icp_register(iba_handle* h, int32_t frame_begin, int32_t frame_end, const double* src_xyz, int32_t n_src,
+                            const double* T_init /* B x 16 */, int32_t B, const iba_icp_options* opt, iba_icp_result* out /* B */);
+/* icp_calib.cpp:43-71 around the loop: iba_read_sim3 -> this -> iba_write_sim3 is the program (PCD reading is the caller's: clouds are arrays).
+ * (rigid12_init, scale_init) in readSim3 form is inverted (R^T, -R^T t) and its rotation multiplied by the scale (:55-60); the result's
+ * scale is sqrt((A A^T)_00) of its upper-left block, the block is divided by it and the transform inverted back (:67-71).
+ * ref_lidar_pose12 (NULL: none): the LiDAR pose of the camera reference frame, lidar_poses[FrameId[0]] (:43-51). The reference moves the
+ * LiDAR cloud by refpose^-1; here the stored scans stay untouched and the QUERIES are moved instead — the registration runs from
+ * refpose * init and its result is multiplied by refpose^-1: the same registration in another frame (distances do not change). */
+iba_status iba_icp_calib(iba_handle* h, int32_t frame_begin, int32_t frame_end, const double* cam_xyz, int32_t n,
+                         const double rigid12_init[12], double scale_init, const double* ref_lidar_pose12,
+                         const iba_icp_options* opt, double rigid12_out[12], double* scale_out, iba_icp_result* res);
 
 /* The ABI version the LIBRARY was built with (IBA_ABI_VERSION of its header). iba_params carries no struct_size: a caller compiled against
  * an older header would pass a shorter struct. Callers compare iba_abi_version() with their own IBA_ABI_VERSION before iba_create(). */

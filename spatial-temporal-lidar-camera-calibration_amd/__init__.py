@@ -14,7 +14,7 @@ import subprocess
 
 import numpy as np
 
-from .abi import (IBA_MAX_BATCH, IbaCreateOptions, IbaLmOptions, IbaLmResult, IbaMadsOptions, IbaMadsResult, IbaBbo, IbaCostOut, IbaNormalOut, IbaParams, IbaProblemDesc, Problem, copy_params,
+from .abi import (ICP_NMOM, IbaIcpOptions, IbaIcpResult, IBA_MAX_BATCH, IbaCreateOptions, IbaLmOptions, IbaLmResult, IbaMadsOptions, IbaMadsResult, IbaBbo, IbaCostOut, IbaNormalOut, IbaParams, IbaProblemDesc, Problem, copy_params,
                   reference_yaml_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -44,7 +44,7 @@ def build_extension(force=False):
 
 
 _lib = None
-ABI_VERSION = 2   # IBA_ABI_VERSION of include/iba_mi355x.h these ctypes structs mirror
+ABI_VERSION = 3   # IBA_ABI_VERSION of include/iba_mi355x.h these ctypes structs mirror
 
 
 def load_library():
@@ -321,6 +321,51 @@ class IbaHandle:
         self.lib.iba_geo_correspondences.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         self._chk(self.lib.iba_geo_correspondences(self.h, C.c_int32(frame), _p(src), C.c_int32(n), C.c_double(max_distance), _p(o_s), _p(o_t), C.byref(cnt)))
         return o_s[: cnt.value].copy(), o_t[: cnt.value].copy()
+
+    def icp_options(self, **fields):
+        o = IbaIcpOptions()
+        self._chk(self.lib.iba_default_icp_options(C.byref(o)))
+        for k, v in fields.items():
+            setattr(o, k, v)
+        return o
+
+    def icp_step(self, src_xyz, T, max_corr_dist, frames=(0, 1), pairs=False):
+        """iba_icp_step: one correspondence pass per transform against the scans of local frames [frames[0], frames[1]) read as tiles of one cloud
+        -> moments [B, ICP_NMOM] (layout: include/iba_mi355x.h), and with pairs=True (pair_frame, pair_idx) [B, n] (0xFFFFFFFF: not kept)"""
+        src = np.ascontiguousarray(np.asarray(src_xyz, np.float64).reshape(-1, 3))
+        T = np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1, 16))
+        n, B = len(src), len(T)
+        mom = np.zeros((B, ICP_NMOM))
+        pf = np.zeros((B, max(n, 1)), np.uint32) if pairs else None
+        pi = np.zeros((B, max(n, 1)), np.uint32) if pairs else None
+        self.lib.iba_icp_step.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.iba_icp_step(self.h, C.c_int32(frames[0]), C.c_int32(frames[1]), _p(src) if n else None, C.c_int32(n), _p(T), C.c_int32(B), C.c_double(max_corr_dist),
+                                        _p(mom), _p(pf) if pairs else None, _p(pi) if pairs else None))
+        return (mom, pf[:, :n], pi[:, :n]) if pairs else mom
+
+    def icp_register(self, src_xyz, T_init, frames=(0, 1), **opts):
+        """iba_icp_register: Open3D's RegistrationICP (point-to-point, with_scaling) from B independent starts -> list of IbaIcpResult"""
+        src = np.ascontiguousarray(np.asarray(src_xyz, np.float64).reshape(-1, 3))
+        T = np.ascontiguousarray(np.asarray(T_init, np.float64).reshape(-1, 16))
+        n, B = len(src), len(T)
+        o = self.icp_options(**opts)
+        out = (IbaIcpResult * B)()
+        self.lib.iba_icp_register.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(IbaIcpOptions), C.POINTER(IbaIcpResult)]
+        self._chk(self.lib.iba_icp_register(self.h, C.c_int32(frames[0]), C.c_int32(frames[1]), _p(src) if n else None, C.c_int32(n), _p(T), C.c_int32(B), C.byref(o), out))
+        return list(out)
+
+    def icp_calib(self, cam_xyz, rigid12_init, scale_init, ref_lidar_pose12=None, frames=(0, 1), **opts):
+        """iba_icp_calib: icp_calib.cpp:43-71 around the loop -> (rigid12 [3, 4], scale, IbaIcpResult) in readSim3 / writeSim3 form"""
+        src = np.ascontiguousarray(np.asarray(cam_xyz, np.float64).reshape(-1, 3))
+        r0 = np.ascontiguousarray(np.asarray(rigid12_init, np.float64).reshape(12))
+        ref = None if ref_lidar_pose12 is None else np.ascontiguousarray(np.asarray(ref_lidar_pose12, np.float64).reshape(12))
+        o = self.icp_options(**opts)
+        out12 = np.zeros(12); sc = C.c_double(0.0); res = IbaIcpResult()
+        self.lib.iba_icp_calib.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.POINTER(IbaIcpOptions), C.c_void_p,
+                                           C.POINTER(C.c_double), C.POINTER(IbaIcpResult)]
+        self._chk(self.lib.iba_icp_calib(self.h, C.c_int32(frames[0]), C.c_int32(frames[1]), _p(src) if len(src) else None, C.c_int32(len(src)), _p(r0), C.c_double(scale_init),
+                                         None if ref is None else _p(ref), C.byref(o), _p(out12), C.byref(sc), C.byref(res)))
+        return out12.reshape(3, 4), sc.value, res
 
     def debug_factor_ranges(self, B):
         """ranges per candidate iba_factor2_kernel would cut a batch of B into; 0 = the default factor kernel runs"""

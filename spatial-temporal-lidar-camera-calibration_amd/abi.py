@@ -129,6 +129,23 @@ class IbaMadsResult(C.Structure):
                 ("evaluations", C.c_int32), ("iterations", C.c_int32), ("batches", C.c_int32), ("cache_hits", C.c_int32), ("restarts", C.c_int32), ("stop_reason", C.c_int32)]
 
 
+class IbaIcpOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("max_corr_dist", C.c_double), ("max_iter", C.c_int32), ("relative_fitness", C.c_double),
+                ("relative_rmse", C.c_double), ("with_scaling", C.c_int32)]
+
+
+class IbaIcpResult(C.Structure):
+    _fields_ = [("T", C.c_double * 16), ("scale", C.c_double), ("fitness", C.c_double), ("inlier_rmse", C.c_double),
+                ("n_corr", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32)]
+
+    def T_np(self):
+        return np.array(self.T[:]).reshape(4, 4)
+
+
+ICP_NMOM = 21            # IBA_ICP_NMOM
+ICP_CONVERGED, ICP_MAX_ITER, ICP_DEGENERATE = 1, 0, -1
+
+
 class IbaBbo(C.Structure):
     _fields_ = [("f", C.c_double), ("c1", C.c_double), ("c2", C.c_double), ("c3", C.c_double)]
 

@@ -33,6 +33,8 @@ const char* debug_env(const char* name) {   // (read at every handle creation: a
 #include "iba_split_kernels.hpp"
 #include "iba_factor2_kernel.hpp"
 #include "iba_nn_list_kernel.hpp"
+#include "iba_icp_kernels.hpp"
+#include "iba_icp_math.hpp"
 #include "iba_types.hpp"
 
 using namespace iba;
@@ -209,6 +211,12 @@ struct iba_handle {
     std::vector<uint64_t> h_kp_off;       // local frame -> kp offset (K+1)
     std::vector<uint32_t> h_kp_ext;       // internal (Morton) keypoint id -> reference keypoint id
     std::vector<float> h_kp_uv;           // (u, v) of every keypoint in internal order: the reject bitmap is rebuilt from it when max_pixel_dist changes
+    // iba_icp_* (iba_icp_host.hpp): the bounding box of every local frame's scan ([frame][8]: min xyz, -, max xyz, -) and the work buffers of a pass, grown on demand
+    DevBuf<float> d_frame_box;
+    struct IcpWork {
+        DevBuf<double> d_src, d_part, d_mom; DevBuf<IcpXf> d_xf; DevBuf<uint32_t> d_pair;   // source cloud, wave partials, moment blocks, transforms, (frame, index) pairs
+        IcpXf* h_xf = nullptr; double* h_mom = nullptr; int pinned_B = 0;                    // pinned staging of the transforms and the moment blocks
+    } icp;
 
     DevProblem dev_problem() const {
         DevProblem dp{};
@@ -1063,6 +1071,9 @@ void iba_destroy(iba_handle* h) {
     h->d_ffr.release(); h->d_kp_c.release(); h->d_kp_rec.release(); h->d_scan_rec.release();
     h->nodes.release(); h->kp_uv.release(); h->kp_mp.release(); h->kp_fl.release(); h->coarse_start.release(); h->bitmap.release(); h->crec.release();
     h->match_uv.release(); h->plane_cost.release(); h->plane_local.release(); h->plane_ok.release(); h->scratch_cost.release(); h->scratch_local.release(); h->d_assoc_frozen.release(); h->d_flist.release(); h->d_flist_frozen.release(); h->d_fcount.release(); h->d_fcount_frozen.release(); h->d_cands.release(); h->d_frame_partials.release(); h->d_partials.release(); h->d_corr.release(); h->d_he.release(); h->d_lcount.release(); h->d_lcount_frozen.release(); h->d_nn_partials.release(); h->d_frefit.release(); h->d_pairs.release(); h->d_hard.release(); h->d_pcounts.release(); h->mpk.release(); h->fkp.release(); h->kp_fl2.release(); h->d_diag.release(); h->d_anchor.release();
+    h->d_frame_box.release(); h->icp.d_src.release(); h->icp.d_part.release(); h->icp.d_mom.release(); h->icp.d_xf.release(); h->icp.d_pair.release();
+    if (h->icp.h_xf) (void)hipHostFree(h->icp.h_xf);
+    if (h->icp.h_mom) (void)hipHostFree(h->icp.h_mom);
     if (h->ev_mid) (void)hipEventDestroy(h->ev_mid);
     if (h->h_cands) (void)hipHostFree(h->h_cands);
     if (h->h_partials) (void)hipHostFree(h->h_partials);
@@ -1338,6 +1349,18 @@ iba_status iba_create_ex(const iba_problem_desc* d, const iba_params* params, in
 
     auto bail = [&](const char* what, hipError_t er) { std::string m = std::string(what) + ": " + hipGetErrorString(er); iba_destroy(h); return fail(nullptr, IBA_ERR_HIP, m); };
 #define UP(buf, vec) do { hipError_t _e = h->buf.upload(vec); if (_e != hipSuccess) return bail("upload " #buf, _e); } while (0)
+    {   // the box of every frame's scan out of its chunk boxes (iba_icp_pass_kernel skips a tile that lies out of a lane's reach)
+        std::vector<float> frame_box(8 * (size_t)std::max(nf, 1), qnan);
+        for (int lf = 0; lf < nf; ++lf) {
+            float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+            for (uint32_t c0 = 0; c0 < hdr[lf].P; c0 += (uint32_t)kChunk) {
+                const float* bx = &chunk_box[8 * (size_t)(hdr[lf].box_base + c0 / (uint32_t)kChunk)];
+                for (int a = 0; a < 3; ++a) { if (bx[a] < mn[a]) mn[a] = bx[a]; if (bx[4 + a] > mx[a]) mx[a] = bx[4 + a]; }
+            }
+            if (hdr[lf].P > 0) for (int a = 0; a < 3; ++a) { frame_box[8 * (size_t)lf + a] = mn[a]; frame_box[8 * (size_t)lf + 4 + a] = mx[a]; }
+        }
+        UP(d_frame_box, frame_box);
+    }
     UP(frames, hdr); UP(slots, slots); UP(xs, xs); UP(ys, ys); UP(zs, zs); UP(perm, perm); UP(inv_perm, inv_perm); UP(nodes, nodes); UP(chunk_box, chunk_box); UP(pts4, pts4);
     h->h_kp_uv.resize(2 * (size_t)kp_base);
     for (size_t k = 0; k < (size_t)kp_base; ++k) { h->h_kp_uv[2 * k] = kp_uv[k].x; h->h_kp_uv[2 * k + 1] = kp_uv[k].y; }
@@ -2108,3 +2131,5 @@ iba_status reserve_batch(iba_handle* h, int B) {
     return ensure_lists(h, B, h->stream);
 }
 }  // namespace iba
+
+#include "iba_icp_host.hpp"   // iba_icp_step / iba_icp_register / iba_icp_calib

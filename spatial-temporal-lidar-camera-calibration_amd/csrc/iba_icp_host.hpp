@@ -1,0 +1,206 @@
+// Host side of iba_icp_step / iba_icp_register / iba_icp_calib (include/iba_mi355x.h; included at the end of iba_capi.hip, whose handle it uses).
+// A pass = the transforms of the starts still running copied to the device from pinned memory, iba_icp_pass_kernel, iba_icp_sum_kernel, the
+// moment blocks copied back to pinned memory, one stream synchronise: 128 B down and 168 B up per start and iteration. The source cloud is
+// uploaded once per call. The buffers live in the handle and only grow.
+
+namespace {
+
+constexpr int kIcpMaxB = 4096;
+
+iba_status icp_check_target(iba_handle* h, int32_t fb, int32_t fe) {
+    if (fb < 0 || fe > h->n_frames || fb >= fe) return fail(h, IBA_ERR_INVALID_ARG, "iba_icp: frame range [" + std::to_string(fb) + ", " + std::to_string(fe) + ") is empty or outside the handle's " + std::to_string(h->n_frames) + " local frames");
+    return IBA_OK;
+}
+
+template <class T>
+hipError_t icp_grow(DevBuf<T>& b, size_t count) {
+    if (b.p && b.n >= count) return hipSuccess;
+    b.release();
+    return b.alloc(count + count / 4);
+}
+
+// threads per block of the pass kernel for this target (the rule of DESIGN.md 5b) and the bytes of its node table
+void icp_shape(const iba_handle* h, int fb, int fe, int& threads, size_t& lds) {
+    uint32_t nodes = 1;
+    for (int f = fb; f < fe; ++f) if (h->h_frames[(size_t)f].P > 0) nodes = std::max(nodes, (1u << h->h_frames[(size_t)f].depth) - 1u);
+    lds = 8u * (size_t)nodes;
+    threads = lds <= 6144u ? 64 : 256;
+}
+
+iba_status icp_reserve(iba_handle* h, int n, int B, int threads, bool pairs) {
+    auto& w = h->icp;
+    const size_t nw = ((size_t)n + (size_t)threads - 1) / (size_t)threads * (size_t)(threads / 64);
+    HIP_TRY(h, icp_grow(w.d_src, 3 * (size_t)n));
+    HIP_TRY(h, icp_grow(w.d_part, (size_t)B * nw * kIcpSums));
+    HIP_TRY(h, icp_grow(w.d_mom, (size_t)B * kIcpMom));
+    HIP_TRY(h, icp_grow(w.d_xf, (size_t)B));
+    if (pairs) HIP_TRY(h, icp_grow(w.d_pair, 2 * (size_t)B * (size_t)n));
+    if (w.pinned_B < B) {
+        if (w.h_xf) (void)hipHostFree(w.h_xf);
+        if (w.h_mom) (void)hipHostFree(w.h_mom);
+        w.h_xf = nullptr; w.h_mom = nullptr; w.pinned_B = 0;
+        const int cap = std::max(64, B);
+        HIP_TRY(h, hipHostMalloc((void**)&w.h_xf, sizeof(IcpXf) * (size_t)cap, hipHostMallocDefault));
+        HIP_TRY(h, hipHostMalloc((void**)&w.h_mom, sizeof(double) * kIcpMom * (size_t)cap, hipHostMallocDefault));
+        w.pinned_B = cap;
+    }
+    return IBA_OK;
+}
+
+// plain sequential f64 mean of the source points (the pivot of the sums is its image)
+void icp_centroid(const double* src, int n, double c[3]) {
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int i = 0; i < n; ++i) { s0 += src[3 * (size_t)i]; s1 += src[3 * (size_t)i + 1]; s2 += src[3 * (size_t)i + 2]; }
+    c[0] = s0 / (double)n; c[1] = s1 / (double)n; c[2] = s2 / (double)n;
+}
+// the transform as the kernel takes it; the pivot by the kernel's own expression (icp_transform)
+void icp_make_xf(const double* T16, const double c[3], double gate, IcpXf& x) {
+    std::memcpy(x.T, T16, 12 * sizeof(double));
+    for (int r = 0; r < 3; ++r) x.piv[r] = std::fma(T16[r * 4 + 2], c[2], std::fma(T16[r * 4 + 1], c[1], std::fma(T16[r * 4], c[0], T16[r * 4 + 3])));
+    x.gate2 = gate * gate;
+}
+
+// one pass over the nb transforms staged in h->icp.h_xf[0 .. nb): their moment blocks land in h->icp.h_mom (the source is on the device)
+iba_status icp_pass(iba_handle* h, int fb, int fe, int n, int nb, int threads, size_t lds, bool pairs) {
+    auto& w = h->icp;
+    const hipStream_t st = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(w.d_xf.p, w.h_xf, sizeof(IcpXf) * (size_t)nb, hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)(((size_t)n + (size_t)threads - 1) / (size_t)threads), (unsigned)nb);
+    uint32_t* pf = pairs ? w.d_pair.p : nullptr; uint32_t* pi = pairs ? w.d_pair.p + (size_t)nb * (size_t)n : nullptr;
+    if (threads == 64) hipLaunchKernelGGL(iba_icp_pass_kernel<64>, grid, dim3(64), lds, st, h->dev_problem(), h->d_frame_box.p, fb, fe, w.d_src.p, n, w.d_xf.p, w.d_part.p, pf, pi);
+    else hipLaunchKernelGGL(iba_icp_pass_kernel<256>, grid, dim3(256), lds, st, h->dev_problem(), h->d_frame_box.p, fb, fe, w.d_src.p, n, w.d_xf.p, w.d_part.p, pf, pi);
+    HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(iba_icp_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, w.d_part.p, (int)(grid.x * (unsigned)(threads / 64)), w.d_xf.p, w.d_mom.p);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(w.h_mom, w.d_mom.p, sizeof(double) * kIcpMom * (size_t)nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return IBA_OK;
+}
+
+bool icp_finite16(const double* T) { for (int i = 0; i < 16; ++i) if (!std::isfinite(T[i])) return false; return true; }
+
+iba_status icp_check_options(iba_handle* h, const iba_icp_options* o) {
+    if (!o) return fail(h, IBA_ERR_INVALID_ARG, "iba_icp: options are NULL (iba_default_icp_options fills them)");
+    if (o->struct_size != (int32_t)sizeof(iba_icp_options)) return fail(h, IBA_ERR_INVALID_ARG, "iba_icp_options.struct_size does not match this library");
+    if (!(o->max_corr_dist > 0.0) || !std::isfinite(o->max_corr_dist) || o->max_iter < 0 || !(o->relative_fitness >= 0.0) || !(o->relative_rmse >= 0.0))
+        return fail(h, IBA_ERR_INVALID_ARG, "iba_icp_options: max_corr_dist must be positive and finite, max_iter and the two thresholds non-negative");
+    return IBA_OK;
+}
+
+void icp_fill_result(const double* T, const double* m, int n_src, int iterations, int converged, iba_icp_result& r) {
+    std::memcpy(r.T, T, 16 * sizeof(double));
+    r.scale = iba::icp::scale_of(T);
+    r.fitness = iba::icp::fitness_of(m, n_src); r.inlier_rmse = iba::icp::rmse_of(m);
+    r.n_corr = (int32_t)m[0]; r.iterations = iterations; r.converged = converged;
+}
+
+}  // namespace
+
+iba_status iba_default_icp_options(iba_icp_options* o) {
+    if (!o) return IBA_ERR_INVALID_ARG;
+    std::memset(o, 0, sizeof(*o));
+    o->struct_size = (int32_t)sizeof(iba_icp_options);
+    o->max_corr_dist = 1.0; o->max_iter = 30; o->relative_fitness = 1e-6; o->relative_rmse = 1e-6; o->with_scaling = 1;
+    return IBA_OK;
+}
+
+iba_status iba_icp_step(iba_handle* h, int32_t frame_begin, int32_t frame_end, const double* src_xyz, int32_t n_src, const double* T, int32_t B,
+                        double max_corr_dist, double* moments, uint32_t* pair_frame, uint32_t* pair_idx) {
+    if (!h) return IBA_ERR_INVALID_ARG;
+    if (!T || !moments || n_src < 0 || (n_src > 0 && !src_xyz)) return fail(h, IBA_ERR_INVALID_ARG, "iba_icp_step: NULL transform, moments or source");
+    if (B < 1 || B > kIcpMaxB) return fail(h, IBA_ERR_INVALID_ARG, "iba_icp_step: B must be in [1, 4096]");
+    if ((pair_frame == nullptr) != (pair_idx == nullptr)) return fail(h, IBA_ERR_INVALID_ARG, "iba_icp_step: pair_frame and pair_idx go together (both NULL or both given)");
+    if (!(max_corr_dist > 0.0) || !std::isfinite(max_corr_dist)) return fail(h, IBA_ERR_INVALID_ARG, "iba_icp_step: max_corr_dist must be positive and finite");
+    if (const iba_status s = icp_check_target(h, frame_begin, frame_end)) return s;
+    for (int b = 0; b < B; ++b) if (!icp_finite16(T + 16 * (size_t)b)) return fail(h, IBA_ERR_INVALID_ARG, "iba_icp_step: transform " + std::to_string(b) + " is not finite");
+    std::memset(moments, 0, sizeof(double) * IBA_ICP_NMOM * (size_t)B);
+    if (n_src == 0) return IBA_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const bool pairs = pair_idx != nullptr;
+    int threads; size_t lds; icp_shape(h, frame_begin, frame_end, threads, lds);
+    if (const iba_status s = icp_reserve(h, n_src, B, threads, pairs)) return s;
+    auto& w = h->icp;
+    HIP_TRY(h, hipMemcpyAsync(w.d_src.p, src_xyz, sizeof(double) * 3 * (size_t)n_src, hipMemcpyHostToDevice, h->stream));
+    double c[3]; icp_centroid(src_xyz, n_src, c);
+    for (int b = 0; b < B; ++b) icp_make_xf(T + 16 * (size_t)b, c, max_corr_dist, w.h_xf[b]);
+    if (const iba_status s = icp_pass(h, frame_begin, frame_end, n_src, B, threads, lds, pairs)) return s;
+    std::memcpy(moments, w.h_mom, sizeof(double) * IBA_ICP_NMOM * (size_t)B);
+    if (pairs) {
+        HIP_TRY(h, hipMemcpy(pair_frame, w.d_pair.p, sizeof(uint32_t) * (size_t)B * (size_t)n_src, hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(pair_idx, w.d_pair.p + (size_t)B * (size_t)n_src, sizeof(uint32_t) * (size_t)B * (size_t)n_src, hipMemcpyDeviceToHost));
+    }
+    return IBA_OK;
+}
+
+iba_status iba_icp_register(iba_handle* h, int32_t frame_begin, int32_t frame_end, const double* src_xyz, int32_t n_src, const double* T_init, int32_t B,
+                            const iba_icp_options* opt, iba_icp_result* out) {
+    if (!h) return IBA_ERR_INVALID_ARG;
+    if (!T_init || !out || n_src < 0 || (n_src > 0 && !src_xyz)) return fail(h, IBA_ERR_INVALID_ARG, "iba_icp_register: NULL transforms, results or source");
+    if (B < 1 || B > kIcpMaxB) return fail(h, IBA_ERR_INVALID_ARG, "iba_icp_register: B must be in [1, 4096]");
+    if (const iba_status s = icp_check_options(h, opt)) return s;
+    if (const iba_status s = icp_check_target(h, frame_begin, frame_end)) return s;
+    for (int b = 0; b < B; ++b) if (!icp_finite16(T_init + 16 * (size_t)b)) return fail(h, IBA_ERR_INVALID_ARG, "iba_icp_register: start " + std::to_string(b) + " is not finite");
+    const double zero[IBA_ICP_NMOM] = {0.0};
+    if (n_src == 0) {   // nothing to register: the starts come back as they are, marked degenerate
+        for (int b = 0; b < B; ++b) icp_fill_result(T_init + 16 * (size_t)b, zero, 0, 0, IBA_ICP_DEGENERATE, out[b]);
+        return IBA_OK;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    int threads; size_t lds; icp_shape(h, frame_begin, frame_end, threads, lds);
+    if (const iba_status s = icp_reserve(h, n_src, B, threads, false)) return s;
+    auto& w = h->icp;
+    HIP_TRY(h, hipMemcpyAsync(w.d_src.p, src_xyz, sizeof(double) * 3 * (size_t)n_src, hipMemcpyHostToDevice, h->stream));
+    double c[3]; icp_centroid(src_xyz, n_src, c);
+    struct Start { double T[16]; double m[IBA_ICP_NMOM]; int iterations; };
+    std::vector<Start> st((size_t)B);
+    std::vector<int> live((size_t)B), next;   // the starts of the current pass, in ascending order
+    for (int b = 0; b < B; ++b) { std::memcpy(st[(size_t)b].T, T_init + 16 * (size_t)b, sizeof(double) * 16); st[(size_t)b].iterations = 0; live[(size_t)b] = b; }
+    // evaluation at the init (GetRegistrationResultAndCorrespondences before the loop)
+    for (size_t k = 0; k < live.size(); ++k) icp_make_xf(st[(size_t)live[k]].T, c, opt->max_corr_dist, w.h_xf[k]);
+    if (const iba_status s = icp_pass(h, frame_begin, frame_end, n_src, (int)live.size(), threads, lds, false)) return s;
+    for (size_t k = 0; k < live.size(); ++k) std::memcpy(st[(size_t)live[k]].m, w.h_mom + kIcpMom * k, sizeof(double) * kIcpMom);
+    for (int it = 0; it < opt->max_iter && !live.empty(); ++it) {
+        next.clear();
+        std::vector<double> cand(16 * live.size());
+        for (size_t k = 0; k < live.size(); ++k) {   // update = umeyama(q, p); T = update * T
+            Start& s = st[(size_t)live[k]];
+            double U4[16];
+            if (!iba::icp::umeyama_from_moments(s.m, opt->with_scaling != 0, U4)) { icp_fill_result(s.T, s.m, n_src, s.iterations, IBA_ICP_DEGENERATE, out[live[k]]); continue; }
+            double Tn[16]; iba::icp::mat4_mul(U4, s.T, Tn);
+            if (!icp_finite16(Tn)) { icp_fill_result(s.T, s.m, n_src, s.iterations, IBA_ICP_DEGENERATE, out[live[k]]); continue; }
+            std::memcpy(&cand[16 * next.size()], Tn, sizeof(Tn));
+            next.push_back(live[k]);
+        }
+        live.swap(next);
+        if (live.empty()) break;
+        for (size_t k = 0; k < live.size(); ++k) icp_make_xf(&cand[16 * k], c, opt->max_corr_dist, w.h_xf[k]);
+        if (const iba_status s = icp_pass(h, frame_begin, frame_end, n_src, (int)live.size(), threads, lds, false)) return s;
+        next.clear();
+        for (size_t k = 0; k < live.size(); ++k) {
+            Start& s = st[(size_t)live[k]];
+            const double* m = w.h_mom + kIcpMom * k;
+            const double df = std::fabs(iba::icp::fitness_of(s.m, n_src) - iba::icp::fitness_of(m, n_src)), dr = std::fabs(iba::icp::rmse_of(s.m) - iba::icp::rmse_of(m));
+            std::memcpy(s.T, &cand[16 * k], sizeof(double) * 16); std::memcpy(s.m, m, sizeof(double) * kIcpMom); ++s.iterations;
+            if (df < opt->relative_fitness && dr < opt->relative_rmse) icp_fill_result(s.T, s.m, n_src, s.iterations, IBA_ICP_CONVERGED, out[live[k]]);
+            else next.push_back(live[k]);
+        }
+        live.swap(next);
+    }
+    for (int b : live) { const Start& s = st[(size_t)b]; icp_fill_result(s.T, s.m, n_src, s.iterations, s.m[0] >= 3.0 ? IBA_ICP_MAX_ITER : IBA_ICP_DEGENERATE, out[b]); }
+    return IBA_OK;
+}
+
+iba_status iba_icp_calib(iba_handle* h, int32_t frame_begin, int32_t frame_end, const double* cam_xyz, int32_t n, const double rigid12_init[12], double scale_init,
+                         const double* ref_lidar_pose12, const iba_icp_options* opt, double rigid12_out[12], double* scale_out, iba_icp_result* res) {
+    if (!h) return IBA_ERR_INVALID_ARG;
+    if (!rigid12_init || !rigid12_out || !scale_out) return fail(h, IBA_ERR_INVALID_ARG, "iba_icp_calib: NULL init or output");
+    if (!(scale_init > 0.0) || !std::isfinite(scale_init)) return fail(h, IBA_ERR_INVALID_ARG, "iba_icp_calib: scale_init must be positive and finite");
+    double T0[16]; iba::icp::init_from_sim3(rigid12_init, scale_init, T0);
+    if (ref_lidar_pose12) { double Tr[16]; iba::icp::rigid12_mul_T16(ref_lidar_pose12, T0, Tr); std::memcpy(T0, Tr, sizeof(T0)); }   // the queries move, the scans stay
+    iba_icp_result r;
+    if (const iba_status s = iba_icp_register(h, frame_begin, frame_end, cam_xyz, n, T0, 1, opt, &r)) return s;
+    if (ref_lidar_pose12) { double inv[12], Tr[16]; iba::icp::inv_rigid12(ref_lidar_pose12, inv); iba::icp::rigid12_mul_T16(inv, r.T, Tr); std::memcpy(r.T, Tr, sizeof(Tr)); r.scale = iba::icp::scale_of(r.T); }
+    iba::icp::sim3_from_result(r.T, rigid12_out, scale_out);
+    if (res) *res = r;
+    return IBA_OK;
+}

@@ -1,0 +1,88 @@
+// Host side of the ICP driver (include/iba_mi355x.h, iba_icp_*): what happens to the moment block of one pass. Plain C++, no HIP:
+//  * Eigen::umeyama (Eigen/src/Geometry/Umeyama.h) restated on the pivoted sums the device returns, the SVD by svd3 (iba_svd3.hpp);
+//  * T = update * T, the bookkeeping of Open3D's RegistrationICP (fitness, inlier_rmse, the two convergence criteria);
+//  * the conventions of icp_calib.cpp:55-71 (readSim3 form <-> the 4x4 the loop runs on).
+// Parity with Open3D / Eigen is unpinned (neither is in the reference tree); tests/icp_ref.py restates the same in numpy.
+#pragma once
+#include <cmath>
+#include <cstring>
+
+#include "../../include/iba_mi355x.h"
+#include "iba_svd3.hpp"
+
+namespace iba { namespace icp {
+
+// C = A * B, row-major 4x4, each entry ((a0 b0 + a1 b1) + a2 b2) + a3 b3
+inline void mat4_mul(const double* A, const double* B, double* C) {
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c)
+        C[r * 4 + c] = ((A[r * 4] * B[c] + A[r * 4 + 1] * B[4 + c]) + A[r * 4 + 2] * B[8 + c]) + A[r * 4 + 3] * B[12 + c];
+}
+
+// Eigen::umeyama(src = q, dst = p, with_scaling) from the moments of iba_icp_step (sums about the pivot v = m[18..20]) -> row-major 4x4.
+// false: fewer than 3 pairs or a source set without spread (Eigen would divide by src_var = 0): no update, U4 untouched.
+inline bool umeyama_from_moments(const double* m, bool with_scaling, double* U4) {
+    const double n = m[0];
+    if (!(n >= 3.0)) return false;
+    const double inv = 1.0 / n;
+    const double mq[3] = {m[2] * inv, m[3] * inv, m[4] * inv}, mp[3] = {m[5] * inv, m[6] * inv, m[7] * inv};   // means, relative to the pivot
+    const double var_q = m[8] * inv - ((mq[0] * mq[0] + mq[1] * mq[1]) + mq[2] * mq[2]);
+    if (!(var_q > 0.0) || !std::isfinite(var_q)) return false;
+    double sigma[9];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) sigma[i * 3 + j] = m[9 + 3 * i + j] * inv - mp[i] * mq[j];
+    for (int i = 0; i < 9; ++i) if (!std::isfinite(sigma[i])) return false;
+    double U[9], V[9];
+    la3::svd3(sigma, U, V);   // sigma = U diag(d) V^T, columns
+    double d[3];
+    for (int c = 0; c < 3; ++c) {   // d_c = u_c^T sigma v_c
+        const double v[3] = {V[c], V[3 + c], V[6 + c]};
+        double sv[3]; la3::mat3_vec(sigma, v, sv);
+        d[c] = (U[c] * sv[0] + U[3 + c] * sv[1]) + U[6 + c] * sv[2];
+    }
+    const double S2 = la3::det3(U) * la3::det3(V) < 0.0 ? -1.0 : 1.0;
+    double R[9];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) R[i * 3 + j] = (U[i * 3] * V[j * 3] + U[i * 3 + 1] * V[j * 3 + 1]) + S2 * (U[i * 3 + 2] * V[j * 3 + 2]);
+    const double c = with_scaling ? ((d[0] + d[1]) + S2 * d[2]) / var_q : 1.0;
+    if (!std::isfinite(c) || !(c > 0.0)) return false;
+    const double aq[3] = {m[18] + mq[0], m[19] + mq[1], m[20] + mq[2]}, ap[3] = {m[18] + mp[0], m[19] + mp[1], m[20] + mp[2]};   // the means themselves
+    double Rq[3]; la3::mat3_vec(R, aq, Rq);
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) U4[i * 4 + j] = c * R[i * 3 + j];
+        U4[i * 4 + 3] = ap[i] - c * Rq[i];
+    }
+    U4[12] = 0.0; U4[13] = 0.0; U4[14] = 0.0; U4[15] = 1.0;
+    return true;
+}
+
+inline double fitness_of(const double* m, int n_src) { return n_src > 0 ? m[0] / (double)n_src : 0.0; }
+inline double rmse_of(const double* m) { return m[0] > 0.0 ? std::sqrt(m[1] / m[0]) : 0.0; }
+// sqrt((A A^T)_00) of the upper-left block (icp_calib.cpp:67-68)
+inline double scale_of(const double* T) { return std::sqrt((T[0] * T[0] + T[1] * T[1]) + T[2] * T[2]); }
+
+// rigid 3x4 inverse (R^T, -R^T t), row-major 12
+inline void inv_rigid12(const double* a, double* o) {
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) o[r * 4 + c] = a[c * 4 + r];
+        o[r * 4 + 3] = -((a[0 * 4 + r] * a[3] + a[1 * 4 + r] * a[7]) + a[2 * 4 + r] * a[11]);
+    }
+}
+// icp_calib.cpp:55-60: readSim3 form -> the init of the loop (R^T, -R^T t, rotation times the scale)
+inline void init_from_sim3(const double* rigid12, double scale, double* T16) {
+    double inv[12]; inv_rigid12(rigid12, inv);
+    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) T16[r * 4 + c] = inv[r * 4 + c] * scale; T16[r * 4 + 3] = inv[r * 4 + 3]; }
+    T16[12] = 0.0; T16[13] = 0.0; T16[14] = 0.0; T16[15] = 1.0;
+}
+// icp_calib.cpp:67-71: the loop's result -> (rigid 3x4, scale) in writeSim3 form
+inline void sim3_from_result(const double* T16, double* rigid12, double* scale) {
+    const double s = scale_of(T16);
+    double a[12];
+    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) a[r * 4 + c] = T16[r * 4 + c] / s; a[r * 4 + 3] = T16[r * 4 + 3]; }
+    inv_rigid12(a, rigid12);
+    *scale = s;
+}
+// rigid 3x4 (as 4x4 with the row 0 0 0 1) times a 4x4
+inline void rigid12_mul_T16(const double* a12, const double* T16, double* out16) {
+    double A[16]; std::memcpy(A, a12, 12 * sizeof(double)); A[12] = 0.0; A[13] = 0.0; A[14] = 0.0; A[15] = 1.0;
+    mat4_mul(A, T16, out16);
+}
+
+} }  // namespace iba::icp
