@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define IBA_ABI_VERSION 3 /* 2: iba_params.factor_3d2d_kind; 3: iba_icp_* */
+#define IBA_ABI_VERSION 4 /* 2: iba_params.factor_3d2d_kind; 3: iba_icp_*; 4: iba_scan_* */
 #define IBA_MAX_BATCH 64 /* the batch unit of the callers in this library (one MADS poll block, the planner's diagnostics); NOT a limit of the evaluators */
 #define IBA_MAX_CHAIN 512 /* most candidates ONE launch chain takes (iba_create_options.max_chain_batch <= this); a call with more runs as consecutive chains */
 
@@ -230,6 +230,84 @@ iba_status iba_icp_register(iba_handle* h, int32_t frame_begin, int32_t frame_en
 iba_status iba_icp_calib(iba_handle* h, int32_t frame_begin, int32_t frame_end, const double* cam_xyz, int32_t n,
                          const double rigid12_init[12], double scale_init, const double* ref_lidar_pose12,
                          const iba_icp_options* opt, double rigid12_out[12], double* scale_out, iba_icp_result* res);
+
+/*
+ * ---- Batched scan-to-scan ICP edges: point-to-point, point-to-plane, information matrix [SURVEY.md 2 row 16: backend_opt.cpp:27-45 Registration,
+ * :64-82 PLRegistration, :446-511 MultiRegistration; GeoCalib.h:76-105] ----
+ * The reference's LiDAR back end registers keyframe scans against each other: for every odometry edge (i-1, i) and every loop edge it takes
+ * relPose = pose[j] * pose[i]^-1 (:158-161), optionally refines it with Open3D's RegistrationICP (one stage or coarse -> refine) and attaches
+ * GetInformationMatrixFromPointClouds(src, tgt, MRmaxCorrDist, T). Here a BATCH OF EDGES between local frames of one handle is evaluated
+ * together: per ICP iteration one launch chain and one synchronise for all edges still running, and nothing of scan size crosses PCIe —
+ * source and target scans, the target's kd tree and its memoised normals are already resident. A scans-only handle is enough.
+ * The pose-graph optimiser, ScanContext, PCD IO, voxel down-sampling and merged sub-map targets stay the caller's.
+ *
+ * Restated from Open3D's public sources (not part of the reference tree: parity with it is UNPINNED; the kd search stays pinned to nanoflann):
+ *   RegistrationICP, GetRegistrationResultAndCorrespondences, SearchHybrid's strict gate    the loop of iba_icp_register (one implementation)
+ *   TransformationEstimationPointToPoint(false)     Eigen::umeyama without scaling on the pivoted sums (as iba_icp_*, with_scaling = 0)
+ *   TransformationEstimationPointToPlane            per kept pair (q = T x, target point p, unit normal n of p): r = (q - p) . n,
+ *                                                   J = [q x n, n]; JtJ x = -Jtr solved on the host (6x6 LDL^T); update = Rz(x2) Ry(x1) Rx(x0)
+ *                                                   with translation x[3..5] (TransformVector6dToMatrix4d); T = update * T
+ *   GetInformationMatrixFromPointClouds             over the pairs kept at max_dist under T, t the TARGET point: sum G^T G, G's rows
+ *                                                   [0, tz, -ty, 1, 0, 0], [-tz, 0, tx, 0, 1, 0], [ty, -tx, 0, 0, 0, 1] (row-major 6x6 out)
+ * Rules fixed here:
+ *   * Normals: the cost path's plane memo (iba_params.norm_radius / norm_max_pts; plane_cache = 1), the analogue of
+ *     EstimateNormals(KDTreeSearchParamHybrid(r, 30)). A target point whose record kept fewer than max(norm_min_pts, 3) neighbours (or whose
+ *     normal is not finite) has NO normal: a pair on it stays in fitness / inlier_rmse (inside the gate) and adds nothing to JtJ / Jtr;
+ *     n_planar counts the pairs that carried one. Point-to-plane does not depend on the sign of n: no orientation step.
+ *   * A point-to-plane update is defined with at least 6 pairs that carry a normal and a system whose LDL^T pivots are positive, finite and,
+ *     within the rotation and the translation block each, not below 1e-12 of the block's largest (a scene of parallel planes fails this);
+ *     otherwise the edge ends IBA_ICP_DEGENERATE with the last valid T. (Open3D tests the determinant instead; unpinned.)
+ *   * Coarse -> refine: the refine stage starts from the coarse stage's T (backend_opt.cpp:36-44); the result is the refine stage's.
+ *   * backend_opt.cpp:31,39,43 pass the correspondence DISTANCE as the third argument of ICPConvergenceCriteria, which is (as its public
+ *     signature is remembered: relative_fitness, relative_rmse, max_iteration) the ITERATION COUNT: config/loam/backend.yml (icp_corase_dist
+ *     1.0, icp_refine_dist 0.3) thereby asks for 1 coarse iteration and 0 refine iterations. This API takes the counts explicitly
+ *     (INTEGRATION.md names the values that reproduce the call as written).
+ *   * Known deviations, as for iba_icp_*: the composed T is applied to the original source points in every pass; distance ties go to the
+ *     lowest index; the source points are the scan's float32 values widened to double.
+ * Sums of one pass (iba_scan_step; IBA_SCAN_NMOM doubles per edge, unused entries 0), in a fixed order (one partial per 64 positions of the
+ * source scan in kd-tree order, a wave's lanes by DPP, the partials of an edge by position): two calls give the same bytes and an edge's block
+ * does not depend on the batch. No floating-point atomics.
+ *   IBA_SCAN_POINT_TO_POINT   the layout of IBA_ICP_NMOM ([0] pairs, [1] sum d^2, .. [18..20] pivot), the pivot = T * centre of the source
+ *                             scan's bounding box
+ *   IBA_SCAN_POINT_TO_PLANE   [0] pairs  [1] sum d^2  [2] pairs with a normal  [3..23] JtJ, upper triangle by rows  [24..29] Jtr  [30] sum r^2
+ *   IBA_SCAN_INFORMATION      [0] pairs  [1..3] sum t  [4..9] sum t t^T (xx, xy, xz, yy, yz, zz)
+ * The point-to-plane and information sums are taken about the origin of the target frame, as the definitions are.
+ * Limits: one target scan per edge; rigid only (the scaled form is iba_icp_*); no robust kernel; one GPU — both frames of an edge are
+ * local frames of this handle.
+ */
+typedef struct iba_scan_edge { int32_t src_frame, tgt_frame; double T[16]; } iba_scan_edge; /* row-major 4x4, src scan frame -> tgt scan frame */
+#define IBA_SCAN_POINT_TO_POINT 0   /* TransformationEstimationPointToPoint(false) */
+#define IBA_SCAN_POINT_TO_PLANE 1   /* TransformationEstimationPointToPlane() */
+#define IBA_SCAN_INFORMATION 2      /* iba_scan_step only: the sums of the information matrix */
+#define IBA_SCAN_NMOM 32
+typedef struct iba_scan_options {
+    int32_t struct_size, estimation;
+    double  coarse_dist;        /* <= 0: one stage (refine only) */
+    int32_t coarse_max_iter;
+    double  coarse_rel_fitness, coarse_rel_rmse;
+    double  refine_dist;
+    int32_t refine_max_iter;    /* 0: evaluation only */
+    double  refine_rel_fitness, refine_rel_rmse;
+    double  info_dist;          /* <= 0: no information matrix */
+} iba_scan_options;
+typedef struct iba_scan_result {
+    iba_icp_result reg;         /* of the last stage; scale is 1 up to rounding */
+    int32_t n_planar;           /* point-to-plane: pairs of the last evaluation that carried a normal (0 under point-to-point) */
+    double  info[36];           /* row-major 6x6 at reg.T (zeros without info_dist) */
+    int32_t n_info;             /* pairs kept at info_dist */
+} iba_scan_result;
+/* point-to-point, one stage: refine 0.3 m, 30 iterations, 1e-6, 1e-6 (Open3D's defaults); coarse off (dist 0; 30, 1e-4, 1e-4 once enabled); info off */
+iba_status iba_default_scan_options(iba_scan_options* opt);
+/* One correspondence pass per edge. E in [1, 4096]. pair_idx: NULL, or sum over the edges of P(src_frame) entries, edge after edge, each
+ * edge's block in the ORIGINAL point order of its source scan: the original index of the target point, 0xFFFFFFFF = not kept.
+ * IBA_ERR_INVALID_ARG with a message, before any launch: a frame outside the handle, src_frame == tgt_frame, a non-finite T, point-to-plane
+ * on a handle with plane_cache = 0. An edge with an empty source or target scan answers zero sums. */
+iba_status iba_scan_step(iba_handle* h, const iba_scan_edge* edges, int32_t E, double max_corr_dist, int32_t estimation,
+                         double* moments /* E x IBA_SCAN_NMOM */, uint32_t* pair_idx);
+/* RegistrationICP per edge from edges[e].T, all edges together. An edge with an empty scan comes back as it is, IBA_ICP_DEGENERATE. */
+iba_status iba_scan_register(iba_handle* h, const iba_scan_edge* edges, int32_t E, const iba_scan_options* opt, iba_scan_result* out /* E */);
+/* GetInformationMatrixFromPointClouds per edge at edges[e].T */
+iba_status iba_scan_information(iba_handle* h, const iba_scan_edge* edges, int32_t E, double max_dist, double* info /* E x 36 */, int32_t* n_pairs /* E */);
 
 /* The ABI version the LIBRARY was built with (IBA_ABI_VERSION of its header). iba_params carries no struct_size: a caller compiled against
  * an older header would pass a shorter struct. Callers compare iba_abi_version() with their own IBA_ABI_VERSION before iba_create(). */

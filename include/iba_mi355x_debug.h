@@ -127,6 +127,10 @@ iba_status iba_debug_nn(iba_handle* h, int32_t frame, const double* q_xyz, int32
  * normal into the oracle's residual block: the device fits planes with its own libm, and an ill-conditioned block amplifies the
  * last-bit difference of the two normals (tests/parity_explain.py). */
 iba_status iba_debug_plane(iba_handle* h, int32_t frame, uint32_t point, int32_t which, double out5[5], int32_t* k);
+/* debug: force the block shape of iba_scan_* passes (64: one-wave blocks, 256: four waves; 0: the rule of DESIGN.md 5b on the largest target
+ * tree of the pass). The sums do not depend on the shape. iba_debug_last_scan_threads: the shape the last pass ran with. */
+iba_status iba_debug_scan_threads(iba_handle* h, int32_t threads);
+int32_t iba_debug_last_scan_threads(const iba_handle* h);
 
 /* the same driver on built-in analytic black boxes (host only; for tests of the search logic without a GPU):
  * 0 smooth bowl, 1 bowl with an active constraint and an infeasible start, 2 nonsmooth with two constraints,

@@ -14,7 +14,7 @@ import subprocess
 
 import numpy as np
 
-from .abi import (ICP_NMOM, IbaIcpOptions, IbaIcpResult, IBA_MAX_BATCH, IbaCreateOptions, IbaLmOptions, IbaLmResult, IbaMadsOptions, IbaMadsResult, IbaBbo, IbaCostOut, IbaNormalOut, IbaParams, IbaProblemDesc, Problem, copy_params,
+from .abi import (ICP_NMOM, SCAN_NMOM, IbaScanEdge, IbaScanOptions, IbaScanResult, IbaIcpOptions, IbaIcpResult, IBA_MAX_BATCH, IbaCreateOptions, IbaLmOptions, IbaLmResult, IbaMadsOptions, IbaMadsResult, IbaBbo, IbaCostOut, IbaNormalOut, IbaParams, IbaProblemDesc, Problem, copy_params,
                   reference_yaml_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -44,7 +44,7 @@ def build_extension(force=False):
 
 
 _lib = None
-ABI_VERSION = 3   # IBA_ABI_VERSION of include/iba_mi355x.h these ctypes structs mirror
+ABI_VERSION = 4   # IBA_ABI_VERSION of include/iba_mi355x.h these ctypes structs mirror
 
 
 def load_library():
@@ -366,6 +366,74 @@ class IbaHandle:
         self._chk(self.lib.iba_icp_calib(self.h, C.c_int32(frames[0]), C.c_int32(frames[1]), _p(src) if len(src) else None, C.c_int32(len(src)), _p(r0), C.c_double(scale_init),
                                          None if ref is None else _p(ref), C.byref(o), _p(out12), C.byref(sc), C.byref(res)))
         return out12.reshape(3, 4), sc.value, res
+
+    # --- scan-to-scan edges (iba_scan_*): a batch of (source frame, target frame, start) evaluated together ---
+    @staticmethod
+    def _edges(edges):
+        """edges: iterable of (src_frame, tgt_frame, T 4x4) -> ctypes array of IbaScanEdge"""
+        edges = list(edges)
+        arr = (IbaScanEdge * max(len(edges), 1))()
+        for k, (s, t, T) in enumerate(edges):
+            arr[k].src_frame, arr[k].tgt_frame = int(s), int(t)
+            arr[k].T[:] = np.asarray(T, np.float64).reshape(16).tolist()
+        return arr, len(edges)
+
+    def _scan_src_sizes(self, edges):
+        o = self.problem.arrays["pt_offset"]
+        return [int(o[self.frame_begin + int(s) + 1] - o[self.frame_begin + int(s)]) for s, _, _ in edges]
+
+    def scan_step(self, edges, max_corr_dist, estimation=0, pairs=False):
+        """iba_scan_step: one correspondence pass per edge -> sums [E, SCAN_NMOM] (layout: include/iba_mi355x.h), and with pairs=True a list of E
+        uint32 arrays: per source point in ORIGINAL order the original index of its target point (0xFFFFFFFF: not kept)"""
+        edges = list(edges)
+        arr, E = self._edges(edges)
+        mom = np.zeros((max(E, 1), SCAN_NMOM))
+        sizes = self._scan_src_sizes(edges) if pairs else []
+        pi = np.zeros(max(sum(sizes), 1), np.uint32) if pairs else None
+        self.lib.iba_scan_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.iba_scan_step(self.h, arr, C.c_int32(E), C.c_double(max_corr_dist), C.c_int32(estimation), _p(mom), _p(pi) if pairs else None))
+        if not pairs:
+            return mom[:E]
+        cuts = np.cumsum([0] + sizes)
+        return mom[:E], [pi[cuts[k]:cuts[k + 1]].copy() for k in range(E)]
+
+    def scan_options(self, **fields):
+        o = IbaScanOptions()
+        self._chk(self.lib.iba_default_scan_options(C.byref(o)))
+        for k, v in fields.items():
+            if k not in dict(IbaScanOptions._fields_):
+                raise AttributeError(k)
+            setattr(o, k, v)
+        return o
+
+    def scan_register(self, edges, **opts):
+        """iba_scan_register: RegistrationICP per edge (estimation 0 point-to-point, 1 point-to-plane; one stage or coarse -> refine), all edges
+        together -> list of IbaScanResult"""
+        arr, E = self._edges(edges)
+        o = self.scan_options(**opts)
+        out = (IbaScanResult * max(E, 1))()
+        self.lib.iba_scan_register.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(IbaScanOptions), C.POINTER(IbaScanResult)]
+        self._chk(self.lib.iba_scan_register(self.h, arr, C.c_int32(E), C.byref(o), out))
+        return list(out)[:E]
+
+    def scan_information(self, edges, max_dist):
+        """iba_scan_information: GetInformationMatrixFromPointClouds per edge at its T -> (info [E, 6, 6], n_pairs [E])"""
+        arr, E = self._edges(edges)
+        info = np.zeros((max(E, 1), 36)); n = np.zeros(max(E, 1), np.int32)
+        self.lib.iba_scan_information.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.iba_scan_information(self.h, arr, C.c_int32(E), C.c_double(max_dist), _p(info), _p(n)))
+        return info[:E].reshape(E, 6, 6), n[:E]
+
+    def debug_scan_threads(self, threads):
+        """force the block shape of the scan pass kernel (64 / 256; 0: the rule)"""
+        self.lib.iba_debug_scan_threads.argtypes = [C.c_void_p, C.c_int32]
+        self._chk(self.lib.iba_debug_scan_threads(self.h, C.c_int32(threads)))
+
+    @property
+    def last_scan_threads(self):
+        self.lib.iba_debug_last_scan_threads.argtypes = [C.c_void_p]
+        self.lib.iba_debug_last_scan_threads.restype = C.c_int32
+        return int(self.lib.iba_debug_last_scan_threads(self.h))
 
     def debug_factor_ranges(self, B):
         """ranges per candidate iba_factor2_kernel would cut a batch of B into; 0 = the default factor kernel runs"""

@@ -146,6 +146,27 @@ ICP_NMOM = 21            # IBA_ICP_NMOM
 ICP_CONVERGED, ICP_MAX_ITER, ICP_DEGENERATE = 1, 0, -1
 
 
+class IbaScanEdge(C.Structure):
+    _fields_ = [("src_frame", C.c_int32), ("tgt_frame", C.c_int32), ("T", C.c_double * 16)]
+
+
+class IbaScanOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("estimation", C.c_int32), ("coarse_dist", C.c_double), ("coarse_max_iter", C.c_int32), ("coarse_rel_fitness", C.c_double),
+                ("coarse_rel_rmse", C.c_double), ("refine_dist", C.c_double), ("refine_max_iter", C.c_int32), ("refine_rel_fitness", C.c_double), ("refine_rel_rmse", C.c_double),
+                ("info_dist", C.c_double)]
+
+
+class IbaScanResult(C.Structure):
+    _fields_ = [("reg", IbaIcpResult), ("n_planar", C.c_int32), ("info", C.c_double * 36), ("n_info", C.c_int32)]
+
+    def info_np(self):
+        return np.array(self.info[:]).reshape(6, 6)
+
+
+SCAN_NMOM = 32           # IBA_SCAN_NMOM
+SCAN_POINT_TO_POINT, SCAN_POINT_TO_PLANE, SCAN_INFORMATION = 0, 1, 2
+
+
 class IbaBbo(C.Structure):
     _fields_ = [("f", C.c_double), ("c1", C.c_double), ("c2", C.c_double), ("c3", C.c_double)]
 

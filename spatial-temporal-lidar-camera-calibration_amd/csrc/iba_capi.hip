@@ -34,6 +34,7 @@ const char* debug_env(const char* name) {   // (read at every handle creation: a
 #include "iba_factor2_kernel.hpp"
 #include "iba_nn_list_kernel.hpp"
 #include "iba_icp_kernels.hpp"
+#include "iba_scan_kernels.hpp"
 #include "iba_icp_math.hpp"
 #include "iba_types.hpp"
 
@@ -217,6 +218,13 @@ struct iba_handle {
         DevBuf<double> d_src, d_part, d_mom; DevBuf<IcpXf> d_xf; DevBuf<uint32_t> d_pair;   // source cloud, wave partials, moment blocks, transforms, (frame, index) pairs
         IcpXf* h_xf = nullptr; double* h_mom = nullptr; int pinned_B = 0;                    // pinned staging of the transforms and the moment blocks
     } icp;
+    // iba_scan_* (iba_scan_host.hpp): the frame boxes again on the host (the pivot of an edge's point-to-point sums) and the work buffers of a pass
+    std::vector<float> h_frame_box;
+    struct ScanWork {
+        DevBuf<double> d_part, d_mom; DevBuf<ScanXf> d_xf; DevBuf<uint32_t> d_pair;   // chunk partials, sums per edge, edges, target index per source point
+        ScanXf* h_xf = nullptr; double* h_mom = nullptr; int pinned_E = 0;           // pinned staging of the edges and their sums
+    } scan;
+    int scan_threads = 0, scan_last_threads = 0;   // iba_debug_scan_threads: a forced block shape (0: the rule); the shape of the last pass
 
     DevProblem dev_problem() const {
         DevProblem dp{};
@@ -1074,6 +1082,9 @@ void iba_destroy(iba_handle* h) {
     h->d_frame_box.release(); h->icp.d_src.release(); h->icp.d_part.release(); h->icp.d_mom.release(); h->icp.d_xf.release(); h->icp.d_pair.release();
     if (h->icp.h_xf) (void)hipHostFree(h->icp.h_xf);
     if (h->icp.h_mom) (void)hipHostFree(h->icp.h_mom);
+    h->scan.d_part.release(); h->scan.d_mom.release(); h->scan.d_xf.release(); h->scan.d_pair.release();
+    if (h->scan.h_xf) (void)hipHostFree(h->scan.h_xf);
+    if (h->scan.h_mom) (void)hipHostFree(h->scan.h_mom);
     if (h->ev_mid) (void)hipEventDestroy(h->ev_mid);
     if (h->h_cands) (void)hipHostFree(h->h_cands);
     if (h->h_partials) (void)hipHostFree(h->h_partials);
@@ -1359,6 +1370,7 @@ iba_status iba_create_ex(const iba_problem_desc* d, const iba_params* params, in
             }
             if (hdr[lf].P > 0) for (int a = 0; a < 3; ++a) { frame_box[8 * (size_t)lf + a] = mn[a]; frame_box[8 * (size_t)lf + 4 + a] = mx[a]; }
         }
+        h->h_frame_box = frame_box;
         UP(d_frame_box, frame_box);
     }
     UP(frames, hdr); UP(slots, slots); UP(xs, xs); UP(ys, ys); UP(zs, zs); UP(perm, perm); UP(inv_perm, inv_perm); UP(nodes, nodes); UP(chunk_box, chunk_box); UP(pts4, pts4);
@@ -2133,3 +2145,4 @@ iba_status reserve_batch(iba_handle* h, int B) {
 }  // namespace iba
 
 #include "iba_icp_host.hpp"   // iba_icp_step / iba_icp_register / iba_icp_calib
+#include "iba_scan_host.hpp"  // iba_scan_step / iba_scan_register / iba_scan_information

@@ -87,6 +87,50 @@ iba_status icp_check_options(iba_handle* h, const iba_icp_options* o) {
     return IBA_OK;
 }
 
+// RegistrationICP over independent items (starts of iba_icp_register, edges of iba_scan_register), parameterised on the device pass and on the
+// host update. pass(live, Ts, mom): one correspondence pass at the transforms Ts (16 doubles per live item), mom receives the moment blocks
+// (nmom doubles per live item); update(item, U4): the estimation's update from item.m, false when none is defined. Finished items drop out of
+// the passes; item.status is IBA_ICP_* at the end.
+struct IcpItem { double T[16]; double m[32]; int iterations = 0; int n_src = 0; int status = IBA_ICP_MAX_ITER; };
+template <class Pass, class Update>
+iba_status icp_run_loop(std::vector<IcpItem>& st, std::vector<int> live, int nmom, int max_iter, double rel_fitness, double rel_rmse, Pass pass, Update update) {
+    if (live.empty()) return IBA_OK;
+    std::vector<int> next;
+    std::vector<double> cand(16 * live.size());
+    const double* mom = nullptr;
+    // evaluation at the init (GetRegistrationResultAndCorrespondences before the loop)
+    for (size_t k = 0; k < live.size(); ++k) std::memcpy(&cand[16 * k], st[(size_t)live[k]].T, sizeof(double) * 16);
+    if (const iba_status s = pass(live, cand.data(), mom)) return s;
+    for (size_t k = 0; k < live.size(); ++k) std::memcpy(st[(size_t)live[k]].m, mom + (size_t)nmom * k, sizeof(double) * (size_t)nmom);
+    for (int it = 0; it < max_iter && !live.empty(); ++it) {
+        next.clear();
+        for (size_t k = 0; k < live.size(); ++k) {   // T = update * T
+            IcpItem& s = st[(size_t)live[k]];
+            double U4[16];
+            if (!update(s, U4)) { s.status = IBA_ICP_DEGENERATE; continue; }
+            double Tn[16]; iba::icp::mat4_mul(U4, s.T, Tn);
+            if (!icp_finite16(Tn)) { s.status = IBA_ICP_DEGENERATE; continue; }
+            std::memcpy(&cand[16 * next.size()], Tn, sizeof(Tn));
+            next.push_back(live[k]);
+        }
+        live.swap(next);
+        if (live.empty()) break;
+        if (const iba_status s = pass(live, cand.data(), mom)) return s;
+        next.clear();
+        for (size_t k = 0; k < live.size(); ++k) {
+            IcpItem& s = st[(size_t)live[k]];
+            const double* m = mom + (size_t)nmom * k;
+            const double df = std::fabs(iba::icp::fitness_of(s.m, s.n_src) - iba::icp::fitness_of(m, s.n_src)), dr = std::fabs(iba::icp::rmse_of(s.m) - iba::icp::rmse_of(m));
+            std::memcpy(s.T, &cand[16 * k], sizeof(double) * 16); std::memcpy(s.m, m, sizeof(double) * (size_t)nmom); ++s.iterations;
+            if (df < rel_fitness && dr < rel_rmse) s.status = IBA_ICP_CONVERGED;
+            else next.push_back(live[k]);
+        }
+        live.swap(next);
+    }
+    for (int b : live) { IcpItem& s = st[(size_t)b]; s.status = s.m[0] >= 3.0 ? IBA_ICP_MAX_ITER : IBA_ICP_DEGENERATE; }
+    return IBA_OK;
+}
+
 void icp_fill_result(const double* T, const double* m, int n_src, int iterations, int converged, iba_icp_result& r) {
     std::memcpy(r.T, T, 16 * sizeof(double));
     r.scale = iba::icp::scale_of(T);
@@ -151,42 +195,17 @@ iba_status iba_icp_register(iba_handle* h, int32_t frame_begin, int32_t frame_en
     auto& w = h->icp;
     HIP_TRY(h, hipMemcpyAsync(w.d_src.p, src_xyz, sizeof(double) * 3 * (size_t)n_src, hipMemcpyHostToDevice, h->stream));
     double c[3]; icp_centroid(src_xyz, n_src, c);
-    struct Start { double T[16]; double m[IBA_ICP_NMOM]; int iterations; };
-    std::vector<Start> st((size_t)B);
-    std::vector<int> live((size_t)B), next;   // the starts of the current pass, in ascending order
-    for (int b = 0; b < B; ++b) { std::memcpy(st[(size_t)b].T, T_init + 16 * (size_t)b, sizeof(double) * 16); st[(size_t)b].iterations = 0; live[(size_t)b] = b; }
-    // evaluation at the init (GetRegistrationResultAndCorrespondences before the loop)
-    for (size_t k = 0; k < live.size(); ++k) icp_make_xf(st[(size_t)live[k]].T, c, opt->max_corr_dist, w.h_xf[k]);
-    if (const iba_status s = icp_pass(h, frame_begin, frame_end, n_src, (int)live.size(), threads, lds, false)) return s;
-    for (size_t k = 0; k < live.size(); ++k) std::memcpy(st[(size_t)live[k]].m, w.h_mom + kIcpMom * k, sizeof(double) * kIcpMom);
-    for (int it = 0; it < opt->max_iter && !live.empty(); ++it) {
-        next.clear();
-        std::vector<double> cand(16 * live.size());
-        for (size_t k = 0; k < live.size(); ++k) {   // update = umeyama(q, p); T = update * T
-            Start& s = st[(size_t)live[k]];
-            double U4[16];
-            if (!iba::icp::umeyama_from_moments(s.m, opt->with_scaling != 0, U4)) { icp_fill_result(s.T, s.m, n_src, s.iterations, IBA_ICP_DEGENERATE, out[live[k]]); continue; }
-            double Tn[16]; iba::icp::mat4_mul(U4, s.T, Tn);
-            if (!icp_finite16(Tn)) { icp_fill_result(s.T, s.m, n_src, s.iterations, IBA_ICP_DEGENERATE, out[live[k]]); continue; }
-            std::memcpy(&cand[16 * next.size()], Tn, sizeof(Tn));
-            next.push_back(live[k]);
-        }
-        live.swap(next);
-        if (live.empty()) break;
-        for (size_t k = 0; k < live.size(); ++k) icp_make_xf(&cand[16 * k], c, opt->max_corr_dist, w.h_xf[k]);
-        if (const iba_status s = icp_pass(h, frame_begin, frame_end, n_src, (int)live.size(), threads, lds, false)) return s;
-        next.clear();
-        for (size_t k = 0; k < live.size(); ++k) {
-            Start& s = st[(size_t)live[k]];
-            const double* m = w.h_mom + kIcpMom * k;
-            const double df = std::fabs(iba::icp::fitness_of(s.m, n_src) - iba::icp::fitness_of(m, n_src)), dr = std::fabs(iba::icp::rmse_of(s.m) - iba::icp::rmse_of(m));
-            std::memcpy(s.T, &cand[16 * k], sizeof(double) * 16); std::memcpy(s.m, m, sizeof(double) * kIcpMom); ++s.iterations;
-            if (df < opt->relative_fitness && dr < opt->relative_rmse) icp_fill_result(s.T, s.m, n_src, s.iterations, IBA_ICP_CONVERGED, out[live[k]]);
-            else next.push_back(live[k]);
-        }
-        live.swap(next);
-    }
-    for (int b : live) { const Start& s = st[(size_t)b]; icp_fill_result(s.T, s.m, n_src, s.iterations, s.m[0] >= 3.0 ? IBA_ICP_MAX_ITER : IBA_ICP_DEGENERATE, out[b]); }
+    std::vector<IcpItem> st((size_t)B);
+    std::vector<int> live((size_t)B);   // the starts of the current pass, in ascending order
+    for (int b = 0; b < B; ++b) { std::memcpy(st[(size_t)b].T, T_init + 16 * (size_t)b, sizeof(double) * 16); st[(size_t)b].n_src = n_src; live[(size_t)b] = b; }
+    const auto pass = [&](const std::vector<int>& lv, const double* Ts, const double*& mom) -> iba_status {
+        for (size_t k = 0; k < lv.size(); ++k) icp_make_xf(Ts + 16 * k, c, opt->max_corr_dist, w.h_xf[k]);
+        mom = w.h_mom;
+        return icp_pass(h, frame_begin, frame_end, n_src, (int)lv.size(), threads, lds, false);
+    };
+    const auto update = [&](const IcpItem& s, double* U4) { return iba::icp::umeyama_from_moments(s.m, opt->with_scaling != 0, U4); };
+    if (const iba_status s = icp_run_loop(st, live, kIcpMom, opt->max_iter, opt->relative_fitness, opt->relative_rmse, pass, update)) return s;
+    for (int b = 0; b < B; ++b) { const IcpItem& s = st[(size_t)b]; icp_fill_result(s.T, s.m, n_src, s.iterations, s.status, out[b]); }
     return IBA_OK;
 }
 

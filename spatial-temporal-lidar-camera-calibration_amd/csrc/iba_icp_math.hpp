@@ -53,6 +53,69 @@ inline bool umeyama_from_moments(const double* m, bool with_scaling, double* U4)
     return true;
 }
 
+// ---- scan-to-scan edges (iba_scan_*): the point-to-plane step and the information matrix, from the sums of one pass ----
+// A x = b for a symmetric 6x6 A (row-major, both triangles filled) by LDL^T without pivoting (what Eigen's ldlt() does on a positive definite
+// matrix up to its pivoting). false: a pivot that is not positive and finite, or a non-finite solution: the system is singular to working precision.
+inline bool ldlt6_solve(const double* A, const double* b, double* x) {
+    double L[36] = {0.0}, d[6];
+    for (int j = 0; j < 6; ++j) {
+        double s = A[j * 6 + j];
+        for (int k = 0; k < j; ++k) s -= L[j * 6 + k] * L[j * 6 + k] * d[k];
+        if (!(s > 0.0) || !std::isfinite(s)) return false;
+        d[j] = s;
+        for (int i = j + 1; i < 6; ++i) {
+            double v = A[i * 6 + j];
+            for (int k = 0; k < j; ++k) v -= L[i * 6 + k] * L[j * 6 + k] * d[k];
+            L[i * 6 + j] = v / s;
+        }
+    }
+    double y[6];
+    for (int i = 0; i < 6; ++i) { double v = b[i]; for (int k = 0; k < i; ++k) v -= L[i * 6 + k] * y[k]; y[i] = v; }
+    for (int i = 5; i >= 0; --i) { double v = y[i] / d[i]; for (int k = i + 1; k < 6; ++k) v -= L[k * 6 + i] * x[k]; x[i] = v; }
+    for (int i = 0; i < 6; ++i) if (!std::isfinite(x[i])) return false;
+    // a matrix of rank < 6 passes the pivot test on rounding noise alone: its smallest pivot is then negligible beside the largest of its kind
+    // (rotation block 0-2, translation block 3-5 have different units, so each block is compared with itself)
+    for (int blk = 0; blk < 2; ++blk) {
+        double mx = 0.0, mn = INFINITY;
+        for (int i = 3 * blk; i < 3 * blk + 3; ++i) { mx = std::fmax(mx, d[i]); mn = std::fmin(mn, d[i]); }
+        if (!(mn > 1e-12 * mx)) return false;
+    }
+    return true;
+}
+// Open3D TransformVector6dToMatrix4d: rotation Rz(x2) Ry(x1) Rx(x0), translation x[3..5] -> row-major 4x4
+inline void vec6_to_mat4(const double* x, double* U4) {
+    const double ca = std::cos(x[0]), sa = std::sin(x[0]), cb = std::cos(x[1]), sb = std::sin(x[1]), cg = std::cos(x[2]), sg = std::sin(x[2]);
+    U4[0] = cg * cb; U4[1] = cg * sb * sa - sg * ca; U4[2] = cg * sb * ca + sg * sa; U4[3] = x[3];
+    U4[4] = sg * cb; U4[5] = sg * sb * sa + cg * ca; U4[6] = sg * sb * ca - cg * sa; U4[7] = x[4];
+    U4[8] = -sb;     U4[9] = cb * sa;                U4[10] = cb * ca;               U4[11] = x[5];
+    U4[12] = 0.0; U4[13] = 0.0; U4[14] = 0.0; U4[15] = 1.0;
+}
+// TransformationEstimationPointToPlane from the moments of a point-to-plane pass (m[2] pairs with a normal, m[3..23] JtJ upper triangle by rows,
+// m[24..29] Jtr): JtJ x = -Jtr, update = vec6_to_mat4(x). false: fewer than 6 pairs with a normal or a singular system: no update, U4 untouched.
+inline bool point_to_plane_from_moments(const double* m, double* U4) {
+    if (!(m[2] >= 6.0)) return false;
+    double A[36], b[6], x[6];
+    int o = 3;
+    for (int i = 0; i < 6; ++i) for (int j = i; j < 6; ++j) { A[i * 6 + j] = m[o]; A[j * 6 + i] = m[o]; ++o; }
+    for (int i = 0; i < 6; ++i) b[i] = -m[24 + i];
+    for (int i = 0; i < 36; ++i) if (!std::isfinite(A[i])) return false;
+    if (!ldlt6_solve(A, b, x)) return false;
+    vec6_to_mat4(x, U4);
+    return true;
+}
+// GetInformationMatrixFromPointClouds from the sums of an information pass (s[0] pairs, s[1..3] sum t, s[4..9] sum t t^T upper triangle by rows):
+// sum G^T G with G = [-[t]x | I], row-major 6x6
+inline void information_from_sums(const double* s, double* I) {
+    const double n = s[0], tx = s[1], ty = s[2], tz = s[3], xx = s[4], xy = s[5], xz = s[6], yy = s[7], yz = s[8], zz = s[9];
+    const double M[36] = {yy + zz, -xy, -xz, 0.0, -tz, ty,
+                          -xy, xx + zz, -yz, tz, 0.0, -tx,
+                          -xz, -yz, xx + yy, -ty, tx, 0.0,
+                          0.0, tz, -ty, n, 0.0, 0.0,
+                          -tz, 0.0, tx, 0.0, n, 0.0,
+                          ty, -tx, 0.0, 0.0, 0.0, n};
+    std::memcpy(I, M, sizeof(M));
+}
+
 inline double fitness_of(const double* m, int n_src) { return n_src > 0 ? m[0] / (double)n_src : 0.0; }
 inline double rmse_of(const double* m) { return m[0] > 0.0 ? std::sqrt(m[1] / m[0]) : 0.0; }
 // sqrt((A A^T)_00) of the upper-left block (icp_calib.cpp:67-68)
