@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define IBA_ABI_VERSION 4 /* 2: iba_params.factor_3d2d_kind; 3: iba_icp_*; 4: iba_scan_* */
+#define IBA_ABI_VERSION 4 /* 2: iba_params.factor_3d2d_kind; 3: iba_icp_*; 4: iba_scan_*. An ADDED entry point (iba_submap_*) changes no existing struct and does not bump it: callers detect it by symbol */
 #define IBA_MAX_BATCH 64 /* the batch unit of the callers in this library (one MADS poll block, the planner's diagnostics); NOT a limit of the evaluators */
 #define IBA_MAX_CHAIN 512 /* most candidates ONE launch chain takes (iba_create_options.max_chain_batch <= this); a call with more runs as consecutive chains */
 
@@ -239,7 +239,8 @@ iba_status iba_icp_calib(iba_handle* h, int32_t frame_begin, int32_t frame_end, 
  * GetInformationMatrixFromPointClouds(src, tgt, MRmaxCorrDist, T). Here a BATCH OF EDGES between local frames of one handle is evaluated
  * together: per ICP iteration one launch chain and one synchronise for all edges still running, and nothing of scan size crosses PCIe —
  * source and target scans, the target's kd tree and its memoised normals are already resident. A scans-only handle is enough.
- * The pose-graph optimiser, ScanContext, PCD IO, voxel down-sampling and merged sub-map targets stay the caller's.
+ * Voxel down-sampling and the merged sub-map target of a loop closure are iba_submap_build (below); the pose-graph optimiser, ScanContext and PCD IO
+ * stay the caller's.
  *
  * Restated from Open3D's public sources (not part of the reference tree: parity with it is UNPINNED; the kd search stays pinned to nanoflann):
  *   RegistrationICP, GetRegistrationResultAndCorrespondences, SearchHybrid's strict gate    the loop of iba_icp_register (one implementation)
@@ -308,6 +309,57 @@ iba_status iba_scan_step(iba_handle* h, const iba_scan_edge* edges, int32_t E, d
 iba_status iba_scan_register(iba_handle* h, const iba_scan_edge* edges, int32_t E, const iba_scan_options* opt, iba_scan_result* out /* E */);
 /* GetInformationMatrixFromPointClouds per edge at edges[e].T */
 iba_status iba_scan_information(iba_handle* h, const iba_scan_edge* edges, int32_t E, double max_dist, double* info /* E x 36 */, int32_t* n_pairs /* E */);
+
+/*
+ * ---- Voxel down-sampling and merged sub-map clouds [backend_opt.cpp:164-172 LoadPCD, :174-185 MergeLoadPCD, target of every loop closure :259-262] ----
+ * The reference passes every keyframe scan through VoxelDownSample(voxel) (LoadPCD) and builds the target of a loop-closure registration from the
+ * 2 x LCSubmapSize scans around the history frame: each transformed by its pose, concatenated, VoxelDownSample(voxel), moved into the history
+ * frame by pose[ref]^-1 (MergeLoadPCD). Here a BATCH OF SUB-MAPS is built in one launch chain from scans that are already resident in the handle
+ * (a scans-only handle is enough): only the pose / descriptor blocks go down and only the voxel clouds come up, nothing of input-scan size
+ * crosses PCIe. A frame may be a member of many sub-maps and may appear twice in one. LoadPCD = the one-member sub-map with the identity pose
+ * and out12 = NULL.
+ *
+ * Restated from Open3D's public PointCloud::Transform, operator+= and VoxelDownSample (Open3D is not part of the reference tree: parity with it is
+ * UNPINNED). The rules, fixed here so that the result is a function of the input alone (tests/submap_ref.py restates them in numpy and the device
+ * result is compared with it byte for byte):
+ *   1 member point   the scan's float32 coordinates widened to double; q_r = ((T[r][0] x + T[r][1] y) + T[r][2] z) + T[r][3]: four separately
+ *                    rounded f64 operations in exactly this order, NO fused multiply-add (deliberately unlike the fma chain of iba_icp_* / iba_scan_*:
+ *                    voxel membership is a floor, so the restatement must reproduce q to the bit, and numpy has no fma). Known deviation: Eigen's
+ *                    product in Transform may round differently. A point with a non-finite coordinate before or after the transform is DROPPED
+ *                    and counted in n_dropped (Open3D would let it poison a voxel).
+ *   2 bounds         minb = min over the kept q - 0.5 voxel per axis; index = floor((q - minb) / voxel) (IEEE f64 division, floor), Open3D's expression.
+ *   3 accumulation   a voxel's point is (sum q) / double(count) per axis, the sum taken SEQUENTIALLY in concatenation order: members in list order,
+ *                    the points of a member in the scan's ORIGINAL index order (Open3D's accumulator). The same bytes on every call, whatever
+ *                    else is in the batch. No floating-point atomics.
+ *   4 output         out12 (NULL: none) applied to every averaged point with the expression of rule 1.
+ *   5 order          voxels in ascending (ix, iy, iz), lexicographic (Open3D's order is that of an unordered_map: unspecified).
+ * Answers IBA_ERR_INVALID_ARG with a message, before any launch: a NULL argument, struct_size, n_members < 1, a frame outside the handle, a
+ * non-finite pose or out12, voxel not finite or not > 0, M outside [1, 4096]. IBA_ERR_UNSUPPORTED: a sub-map whose kept points span more than
+ * 2^17 = 131072 voxels along an axis (the sort key holds the sub-map and three 17-bit indices; known after the first kernel, before the sort),
+ * more than 2^22 members or more than 2^32 - 256 member points in one call. A sub-map whose members hold no kept point answers zero voxels.
+ * Limits: the clouds come back to the host — a cloud becomes a registration target by creating a handle from the arrays (narrowed to float32 as
+ * every scan is), there is no device-to-device attach; its normals are the plane memo of that handle; Scan Context, the pose graph and PCD IO are
+ * not here; one GPU — the members of a sub-map are local frames of one handle.
+ */
+typedef struct iba_submap_desc {
+    int32_t struct_size;      /* sizeof(iba_submap_desc) */
+    int32_t n_members;
+    const int32_t* frames;    /* [n_members] local frames of the handle */
+    const double*  poses12;   /* [n_members x 12] row-major 3x4, scan frame -> common frame */
+    const double*  out12;     /* row-major 3x4 applied to the averaged points, or NULL (MergeLoadPCD: pose[ref]^-1) */
+    double voxel;             /* backend.yml: voxel */
+} iba_submap_desc;
+typedef struct iba_submap_clouds iba_submap_clouds;
+/* The result is allocated by the library (its size is not known up front); release it with iba_submap_free. *out is NULL on failure. */
+iba_status iba_submap_build(iba_handle* h, const iba_submap_desc* subs, int32_t M, iba_submap_clouds** out);
+/* Of a result: its sub-maps (0 for NULL); of sub-map s: voxels and dropped points (-1 for NULL or s out of range), the points as doubles
+ * (x, y, z per voxel) and the points that went into each voxel (n_voxels entries each, valid until iba_submap_free; NULL for NULL or s out of range). */
+int32_t iba_submap_num(const iba_submap_clouds* c);
+int64_t iba_submap_n_voxels(const iba_submap_clouds* c, int32_t s);
+int64_t iba_submap_n_dropped(const iba_submap_clouds* c, int32_t s);
+const double* iba_submap_xyz(const iba_submap_clouds* c, int32_t s);
+const int32_t* iba_submap_counts(const iba_submap_clouds* c, int32_t s);
+void iba_submap_free(iba_submap_clouds* c);
 
 /* The ABI version the LIBRARY was built with (IBA_ABI_VERSION of its header). iba_params carries no struct_size: a caller compiled against
  * an older header would pass a shorter struct. Callers compare iba_abi_version() with their own IBA_ABI_VERSION before iba_create(). */

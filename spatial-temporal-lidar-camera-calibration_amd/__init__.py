@@ -14,7 +14,7 @@ import subprocess
 
 import numpy as np
 
-from .abi import (ICP_NMOM, SCAN_NMOM, IbaScanEdge, IbaScanOptions, IbaScanResult, IbaIcpOptions, IbaIcpResult, IBA_MAX_BATCH, IbaCreateOptions, IbaLmOptions, IbaLmResult, IbaMadsOptions, IbaMadsResult, IbaBbo, IbaCostOut, IbaNormalOut, IbaParams, IbaProblemDesc, Problem, copy_params,
+from .abi import (ICP_NMOM, SCAN_NMOM, IbaSubmapDesc, IbaScanEdge, IbaScanOptions, IbaScanResult, IbaIcpOptions, IbaIcpResult, IBA_MAX_BATCH, IbaCreateOptions, IbaLmOptions, IbaLmResult, IbaMadsOptions, IbaMadsResult, IbaBbo, IbaCostOut, IbaNormalOut, IbaParams, IbaProblemDesc, Problem, copy_params,
                   reference_yaml_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -423,6 +423,48 @@ class IbaHandle:
         self.lib.iba_scan_information.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]
         self._chk(self.lib.iba_scan_information(self.h, arr, C.c_int32(E), C.c_double(max_dist), _p(info), _p(n)))
         return info[:E].reshape(E, 6, 6), n[:E]
+
+    # --- voxel down-sampling and merged sub-map clouds (iba_submap_build) ---
+    def submap_build(self, subs):
+        """iba_submap_build: subs = iterable of (frames, poses, out, voxel) — local frames [n], poses [n, 3, 4] (or [n, 12] / 4x4 each; scan frame ->
+        common frame), out = None or a 3x4 / 4x4 applied to the averaged points, voxel size. -> list of dict(xyz [V, 3] float64 in ascending
+        (ix, iy, iz), count [V] int32, n_dropped) per sub-map. LoadPCD of frame f: ([f], [np.eye(4)], None, voxel)."""
+        subs = list(subs)
+        M = len(subs)
+        arr = (IbaSubmapDesc * max(M, 1))()
+        keep = []
+        for k, (frames, poses, out, voxel) in enumerate(subs):
+            fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+            ps = np.asarray(poses, np.float64)
+            ps = np.ascontiguousarray(ps.reshape(len(fr), -1, 4)[:, :3, :] if len(fr) and ps.size == 16 * len(fr) else ps.reshape(len(fr), 12)).reshape(-1)
+            o12 = None if out is None else np.ascontiguousarray(np.asarray(out, np.float64).reshape(-1, 4)[:3]).reshape(-1)
+            keep.append((fr, ps, o12))
+            arr[k].struct_size = C.sizeof(IbaSubmapDesc); arr[k].n_members = len(fr)
+            arr[k].frames = fr.ctypes.data if len(fr) else None; arr[k].poses12 = ps.ctypes.data if len(fr) else None
+            arr[k].out12 = None if o12 is None else o12.ctypes.data
+            arr[k].voxel = float(voxel)
+        return self.submap_build_raw(arr, M)
+
+    def submap_build_raw(self, arr, M):
+        """iba_submap_build on a ctypes array of IbaSubmapDesc (what submap_build fills)"""
+        L = self.lib
+        L.iba_submap_build.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+        L.iba_submap_num.argtypes = [C.c_void_p]; L.iba_submap_num.restype = C.c_int32
+        for f, rt in ((L.iba_submap_n_voxels, C.c_int64), (L.iba_submap_n_dropped, C.c_int64), (L.iba_submap_xyz, C.POINTER(C.c_double)), (L.iba_submap_counts, C.POINTER(C.c_int32))):
+            f.argtypes = [C.c_void_p, C.c_int32]; f.restype = rt
+        L.iba_submap_free.argtypes = [C.c_void_p]; L.iba_submap_free.restype = None
+        res = C.c_void_p(None)
+        self._chk(L.iba_submap_build(self.h, arr, C.c_int32(M), C.byref(res)))
+        try:
+            out = []
+            for s in range(L.iba_submap_num(res)):
+                V = int(L.iba_submap_n_voxels(res, s))
+                xyz = np.ctypeslib.as_array(L.iba_submap_xyz(res, s), shape=(V, 3)).copy() if V else np.zeros((0, 3))
+                cnt = np.ctypeslib.as_array(L.iba_submap_counts(res, s), shape=(V,)).copy() if V else np.zeros(0, np.int32)
+                out.append(dict(xyz=xyz, count=cnt, n_dropped=int(L.iba_submap_n_dropped(res, s))))
+        finally:
+            L.iba_submap_free(res)
+        return out
 
     def debug_scan_threads(self, threads):
         """force the block shape of the scan pass kernel (64 / 256; 0: the rule)"""

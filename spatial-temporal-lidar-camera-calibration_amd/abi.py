@@ -167,6 +167,15 @@ SCAN_NMOM = 32           # IBA_SCAN_NMOM
 SCAN_POINT_TO_POINT, SCAN_POINT_TO_PLANE, SCAN_INFORMATION = 0, 1, 2
 
 
+class IbaSubmapDesc(C.Structure):
+    """iba_submap_desc: one sub-map of iba_submap_build (members = local frames + poses, optional output transform, voxel size)"""
+    _fields_ = [("struct_size", C.c_int32), ("n_members", C.c_int32), ("frames", C.c_void_p), ("poses12", C.c_void_p), ("out12", C.c_void_p), ("voxel", C.c_double)]
+
+
+SUBMAP_MAX_BATCH = 4096          # M of iba_submap_build
+SUBMAP_MAX_AXIS_VOXELS = 1 << 17  # voxels per axis the sort key holds
+
+
 class IbaBbo(C.Structure):
     _fields_ = [("f", C.c_double), ("c1", C.c_double), ("c2", C.c_double), ("c3", C.c_double)]
 

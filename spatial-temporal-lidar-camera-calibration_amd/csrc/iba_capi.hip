@@ -35,6 +35,7 @@ const char* debug_env(const char* name) {   // (read at every handle creation: a
 #include "iba_nn_list_kernel.hpp"
 #include "iba_icp_kernels.hpp"
 #include "iba_scan_kernels.hpp"
+#include "iba_voxel_kernels.hpp"
 #include "iba_icp_math.hpp"
 #include "iba_types.hpp"
 
@@ -225,6 +226,12 @@ struct iba_handle {
         ScanXf* h_xf = nullptr; double* h_mom = nullptr; int pinned_E = 0;           // pinned staging of the edges and their sums
     } scan;
     int scan_threads = 0, scan_last_threads = 0;   // iba_debug_scan_threads: a forced block shape (0: the rule); the shape of the last pass
+    // iba_submap_build (iba_voxel_host.hpp): the work buffers of a call, grown on demand
+    struct VoxWork {
+        DevBuf<VoxMember> d_mem; DevBuf<VoxSub> d_sub; DevBuf<VoxPartial> d_part, d_bounds;   // members, sub-maps, block partials of the bounds, bounds per sub-map
+        DevBuf<double> d_q3; DevBuf<uint64_t> d_key[2]; DevBuf<uint32_t> d_val[2]; DevBuf<unsigned char> d_tmp;   // staged q, the sort's double buffers and its temporary storage
+        DevBuf<uint32_t> d_blockc, d_subfirst, d_seg; DevBuf<double> d_xyz; DevBuf<int32_t> d_cnt;   // head counts per block (+ total), first voxel per sub-map, segment starts, the clouds
+    } vox;
 
     DevProblem dev_problem() const {
         DevProblem dp{};
@@ -1085,6 +1092,8 @@ void iba_destroy(iba_handle* h) {
     h->scan.d_part.release(); h->scan.d_mom.release(); h->scan.d_xf.release(); h->scan.d_pair.release();
     if (h->scan.h_xf) (void)hipHostFree(h->scan.h_xf);
     if (h->scan.h_mom) (void)hipHostFree(h->scan.h_mom);
+    h->vox.d_mem.release(); h->vox.d_sub.release(); h->vox.d_part.release(); h->vox.d_bounds.release(); h->vox.d_q3.release(); h->vox.d_key[0].release(); h->vox.d_key[1].release();
+    h->vox.d_val[0].release(); h->vox.d_val[1].release(); h->vox.d_tmp.release(); h->vox.d_blockc.release(); h->vox.d_subfirst.release(); h->vox.d_seg.release(); h->vox.d_xyz.release(); h->vox.d_cnt.release();
     if (h->ev_mid) (void)hipEventDestroy(h->ev_mid);
     if (h->h_cands) (void)hipHostFree(h->h_cands);
     if (h->h_partials) (void)hipHostFree(h->h_partials);
@@ -2146,3 +2155,4 @@ iba_status reserve_batch(iba_handle* h, int B) {
 
 #include "iba_icp_host.hpp"   // iba_icp_step / iba_icp_register / iba_icp_calib
 #include "iba_scan_host.hpp"  // iba_scan_step / iba_scan_register / iba_scan_information
+#include "iba_voxel_host.hpp" // iba_submap_build and the accessors of its result

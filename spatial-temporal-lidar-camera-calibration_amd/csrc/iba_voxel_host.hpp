@@ -1,0 +1,182 @@
+// Host side of iba_submap_build (include/iba_mi355x.h; included at the end of iba_capi.hip, after iba_icp_host.hpp whose icp_grow it uses).
+// One call = one launch chain for the whole batch of sub-maps (iba_voxel_kernels.hpp) with three synchronisations: after the bounds (the
+// extent is checked and the key fields are sized on the host), after the count of the voxels (the outputs are sized) and at the end. Down go
+// the member and sub-map blocks (128 B per member, 152 B per sub-map), up come the bounds (56 B per sub-map) and the voxel clouds: nothing of
+// input-scan size crosses PCIe. The work buffers live in the handle (h->vox), only grow, and are released in iba_destroy.
+#include <rocprim/device/device_radix_sort.hpp>
+
+struct iba_submap_clouds {
+    int32_t M = 0;
+    std::vector<int64_t> first;     // M + 1: sub-map s owns the voxels first[s] .. first[s + 1]
+    std::vector<int64_t> dropped;   // M
+    std::vector<double> xyz;        // 3 per voxel
+    std::vector<int32_t> count;     // 1 per voxel
+};
+
+namespace {
+
+constexpr int kVoxMaxSubs = 4096;
+constexpr int kVoxMaxMembers = 1 << 22;        // members of one call, all sub-maps together
+constexpr uint64_t kVoxMaxPoints = 0xFFFFFF00ull;   // member points of one call: a concatenation position is a 32-bit value of the sort
+
+bool vox_finite12(const double* T) { for (int i = 0; i < 12; ++i) if (!std::isfinite(T[i])) return false; return true; }
+int vox_bits(uint64_t v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }   // bits that hold 0 .. v
+
+iba_status vox_check(iba_handle* h, const iba_submap_desc* subs, int32_t M) {
+    const std::string who = "iba_submap_build: ";
+    if (!subs) return fail(h, IBA_ERR_INVALID_ARG, who + "the sub-map descriptors are NULL");
+    if (M < 1 || M > kVoxMaxSubs) return fail(h, IBA_ERR_INVALID_ARG, who + "M must be in [1, 4096]");
+    int64_t members = 0;
+    for (int s = 0; s < M; ++s) {
+        const iba_submap_desc& d = subs[s];
+        const std::string at = who + "sub-map " + std::to_string(s) + ": ";
+        if (d.struct_size != (int32_t)sizeof(iba_submap_desc)) return fail(h, IBA_ERR_INVALID_ARG, at + "iba_submap_desc.struct_size does not match this library");
+        if (d.n_members < 1) return fail(h, IBA_ERR_INVALID_ARG, at + "n_members must be at least 1");
+        if (!d.frames || !d.poses12) return fail(h, IBA_ERR_INVALID_ARG, at + "frames / poses12 are NULL");
+        if (!(d.voxel > 0.0) || !std::isfinite(d.voxel)) return fail(h, IBA_ERR_INVALID_ARG, at + "voxel must be positive and finite");
+        if (d.out12 && !vox_finite12(d.out12)) return fail(h, IBA_ERR_INVALID_ARG, at + "out12 is not finite");
+        for (int m = 0; m < d.n_members; ++m) {
+            if (d.frames[m] < 0 || d.frames[m] >= h->n_frames)
+                return fail(h, IBA_ERR_INVALID_ARG, at + "member " + std::to_string(m) + " names frame " + std::to_string(d.frames[m]) + " outside the handle's " + std::to_string(h->n_frames) + " local frames");
+            if (!vox_finite12(d.poses12 + 12 * (size_t)m)) return fail(h, IBA_ERR_INVALID_ARG, at + "the pose of member " + std::to_string(m) + " is not finite");
+        }
+        members += d.n_members;
+    }
+    if (members > kVoxMaxMembers) return fail(h, IBA_ERR_UNSUPPORTED, who + "more than 2^22 members in one call");
+    return IBA_OK;
+}
+
+}  // namespace
+
+iba_status iba_submap_build(iba_handle* h, const iba_submap_desc* subs, int32_t M, iba_submap_clouds** out) {
+    if (!h) return IBA_ERR_INVALID_ARG;
+    if (!out) return fail(h, IBA_ERR_INVALID_ARG, "iba_submap_build: the result pointer is NULL");
+    *out = nullptr;
+    if (const iba_status s = vox_check(h, subs, M)) return s;
+
+    // ---- the batch as the kernels take it: members that hold points, sub-map after sub-map ----
+    std::vector<VoxMember> mem;
+    std::vector<VoxSub> sub((size_t)M);
+    std::vector<uint64_t> n_in((size_t)M, 0);   // member points per sub-map
+    uint64_t N = 0, blocks = 0;
+    for (int s = 0; s < M; ++s) {
+        const iba_submap_desc& d = subs[s];
+        VoxSub& S = sub[(size_t)s];
+        std::memset(&S, 0, sizeof(S));
+        S.voxel = d.voxel; S.has_out = d.out12 ? 1 : 0;
+        if (d.out12) std::memcpy(S.out, d.out12, sizeof(S.out));
+        S.blk0 = (uint32_t)blocks;
+        for (int m = 0; m < d.n_members; ++m) {
+            const uint32_t P = h->h_frames[(size_t)d.frames[m]].P;
+            if (P == 0u) continue;
+            VoxMember x;
+            std::memset(&x, 0, sizeof(x));
+            std::memcpy(x.T, d.poses12 + 12 * (size_t)m, sizeof(x.T));
+            x.pos0 = N; x.blk0 = (uint32_t)blocks; x.frame = d.frames[m]; x.sub = s;
+            mem.push_back(x);
+            N += P; n_in[(size_t)s] += P; blocks += (P + (uint32_t)kVoxThreads - 1u) / (uint32_t)kVoxThreads;
+            if (N > kVoxMaxPoints || blocks > 0x7FFFFFFFull) return fail(h, IBA_ERR_UNSUPPORTED, "iba_submap_build: the members of one call hold more than 2^32 - 256 points (split the batch)");
+        }
+        S.blk1 = (uint32_t)blocks;
+    }
+    iba_submap_clouds* res = new iba_submap_clouds;
+    res->M = M; res->first.assign((size_t)M + 1, 0); res->dropped.assign((size_t)M, 0);
+    if (N == 0) { *out = res; return IBA_OK; }   // every member is an empty scan: zero voxels, no launch
+
+    struct Guard { iba_submap_clouds* p; ~Guard() { delete p; } } guard{res};   // (released on every error path below)
+    HIP_TRY(h, hipSetDevice(h->device));
+    auto& w = h->vox;
+    const hipStream_t st = h->stream;
+    HIP_TRY(h, icp_grow(w.d_mem, mem.size()));
+    HIP_TRY(h, icp_grow(w.d_sub, (size_t)M));
+    HIP_TRY(h, icp_grow(w.d_part, (size_t)blocks));
+    HIP_TRY(h, icp_grow(w.d_bounds, (size_t)M));
+    HIP_TRY(h, icp_grow(w.d_q3, 3 * (size_t)N));
+    HIP_TRY(h, hipMemcpyAsync(w.d_mem.p, mem.data(), sizeof(VoxMember) * mem.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(w.d_sub.p, sub.data(), sizeof(VoxSub) * (size_t)M, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(iba_vox_transform_kernel, dim3((unsigned)blocks), dim3(kVoxThreads), 0, st, h->frames.p, h->pts4.p, h->inv_perm.p, w.d_mem.p, (int)mem.size(), w.d_q3.p, w.d_part.p);
+    HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(iba_vox_bounds_kernel, dim3((unsigned)M), dim3(kVoxThreads), 0, st, w.d_sub.p, w.d_part.p, w.d_bounds.p);
+    HIP_TRY(h, hipGetLastError());
+    std::vector<VoxPartial> bounds((size_t)M);
+    HIP_TRY(h, hipMemcpyAsync(bounds.data(), w.d_bounds.p, sizeof(VoxPartial) * (size_t)M, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+
+    // ---- minb, the extent, the key fields ----
+    uint64_t n_kept = 0, imax[3] = {0, 0, 0};
+    for (int s = 0; s < M; ++s) {
+        const VoxPartial& b = bounds[(size_t)s];
+        VoxSub& S = sub[(size_t)s];
+        res->dropped[(size_t)s] = (int64_t)b.dropped;
+        const uint64_t kept = n_in[(size_t)s] - b.dropped;
+        n_kept += kept;
+        if (kept == 0) continue;
+        for (int a = 0; a < 3; ++a) {
+            S.minb[a] = b.mn[a] - 0.5 * S.voxel;
+            const double top = vox_index(b.mx[a], S.minb[a], S.voxel);   // the kernels' expression on the largest kept q: no index of this axis is above it
+            if (!(top >= 0.0 && top < (double)(1u << kVoxAxisBits)))
+                return fail(h, IBA_ERR_UNSUPPORTED, "iba_submap_build: sub-map " + std::to_string(s) + ": the extent along axis " + std::to_string(a) + " is " + (std::isfinite(top) ? std::to_string((long long)top + 1) : std::string("more than 2^63")) +
+                                                        " voxels; the key holds " + std::to_string(1u << kVoxAxisBits) + " per axis (choose a larger voxel or split the sub-map)");
+            imax[a] = std::max(imax[a], (uint64_t)top);
+        }
+    }
+    if (n_kept == 0) { guard.p = nullptr; *out = res; return IBA_OK; }   // nothing but dropped points
+    VoxBits bits{};
+    bits.y_shift = vox_bits(imax[2]); bits.x_shift = bits.y_shift + vox_bits(imax[1]); bits.sub_shift = bits.x_shift + vox_bits(imax[0]);
+    const unsigned end_bit = (unsigned)(bits.sub_shift + vox_bits((uint64_t)M));   // (sub-map M is the key of the dropped points; at most 51 + 13 bits)
+
+    HIP_TRY(h, icp_grow(w.d_key[0], (size_t)N)); HIP_TRY(h, icp_grow(w.d_key[1], (size_t)N));
+    HIP_TRY(h, icp_grow(w.d_val[0], (size_t)N)); HIP_TRY(h, icp_grow(w.d_val[1], (size_t)N));
+    HIP_TRY(h, hipMemcpyAsync(w.d_sub.p, sub.data(), sizeof(VoxSub) * (size_t)M, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(iba_vox_key_kernel, dim3((unsigned)blocks), dim3(kVoxThreads), 0, st, h->frames.p, w.d_mem.p, (int)mem.size(), w.d_sub.p, (int)M, bits, w.d_q3.p, w.d_key[0].p, w.d_val[0].p);
+    HIP_TRY(h, hipGetLastError());
+    rocprim::double_buffer<uint64_t> kb(w.d_key[0].p, w.d_key[1].p);
+    rocprim::double_buffer<uint32_t> vb(w.d_val[0].p, w.d_val[1].p);
+    size_t tmp_bytes = 0;
+    HIP_TRY(h, rocprim::radix_sort_pairs(nullptr, tmp_bytes, kb, vb, (size_t)N, 0u, end_bit, st));
+    HIP_TRY(h, icp_grow(w.d_tmp, tmp_bytes));
+    tmp_bytes = w.d_tmp.n;
+    HIP_TRY(h, rocprim::radix_sort_pairs((void*)w.d_tmp.p, tmp_bytes, kb, vb, (size_t)N, 0u, end_bit, st));
+    const uint64_t* keys = kb.current();
+    const uint32_t* vals = vb.current();
+
+    // ---- heads, slots, averages ----
+    const uint32_t nhb = (uint32_t)((n_kept + (uint64_t)kVoxHeadBlock - 1) / (uint64_t)kVoxHeadBlock);
+    HIP_TRY(h, icp_grow(w.d_blockc, (size_t)nhb + 1));
+    HIP_TRY(h, icp_grow(w.d_subfirst, (size_t)M + 1));
+    hipLaunchKernelGGL(iba_vox_count_heads_kernel, dim3(nhb), dim3(kVoxThreads), 0, st, keys, n_kept, w.d_blockc.p);
+    HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(iba_vox_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, w.d_blockc.p, nhb, w.d_blockc.p + nhb);
+    HIP_TRY(h, hipGetLastError());
+    uint32_t V = 0;
+    HIP_TRY(h, hipMemcpyAsync(&V, w.d_blockc.p + nhb, sizeof(V), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (V == 0 || (uint64_t)V > n_kept) return fail(h, IBA_ERR_HIP, "iba_submap_build: the voxel count came back outside (0, kept points]");
+    HIP_TRY(h, icp_grow(w.d_seg, (size_t)V));
+    HIP_TRY(h, icp_grow(w.d_xyz, 3 * (size_t)V));
+    HIP_TRY(h, icp_grow(w.d_cnt, (size_t)V));
+    HIP_TRY(h, hipMemsetAsync(w.d_subfirst.p, 0xFF, sizeof(uint32_t) * ((size_t)M + 1), st));
+    hipLaunchKernelGGL(iba_vox_heads_kernel, dim3(nhb), dim3(kVoxThreads), 0, st, keys, n_kept, w.d_blockc.p, (int)bits.sub_shift, w.d_seg.p, w.d_subfirst.p);
+    HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(iba_vox_average_kernel, dim3((V + (uint32_t)kVoxThreads - 1u) / (uint32_t)kVoxThreads), dim3(kVoxThreads), 0, st, w.d_sub.p, (int)bits.sub_shift, keys, vals, w.d_q3.p, w.d_seg.p, V, n_kept,
+                       w.d_xyz.p, w.d_cnt.p);
+    HIP_TRY(h, hipGetLastError());
+    res->xyz.resize(3 * (size_t)V); res->count.resize((size_t)V);
+    std::vector<uint32_t> first((size_t)M + 1);
+    HIP_TRY(h, hipMemcpyAsync(res->xyz.data(), w.d_xyz.p, sizeof(double) * 3 * (size_t)V, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(res->count.data(), w.d_cnt.p, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(first.data(), w.d_subfirst.p, sizeof(uint32_t) * ((size_t)M + 1), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    res->first[(size_t)M] = (int64_t)V;
+    for (int s = M - 1; s >= 0; --s) res->first[(size_t)s] = first[(size_t)s] == kVoxNoSlot ? res->first[(size_t)s + 1] : (int64_t)first[(size_t)s];   // (a sub-map without voxels owns an empty range)
+    guard.p = nullptr;
+    *out = res;
+    return IBA_OK;
+}
+
+int32_t iba_submap_num(const iba_submap_clouds* c) { return c ? c->M : 0; }
+int64_t iba_submap_n_voxels(const iba_submap_clouds* c, int32_t s) { return (c && s >= 0 && s < c->M) ? c->first[(size_t)s + 1] - c->first[(size_t)s] : -1; }
+int64_t iba_submap_n_dropped(const iba_submap_clouds* c, int32_t s) { return (c && s >= 0 && s < c->M) ? c->dropped[(size_t)s] : -1; }
+const double* iba_submap_xyz(const iba_submap_clouds* c, int32_t s) { return (c && s >= 0 && s < c->M) ? c->xyz.data() + 3 * (size_t)c->first[(size_t)s] : nullptr; }
+const int32_t* iba_submap_counts(const iba_submap_clouds* c, int32_t s) { return (c && s >= 0 && s < c->M) ? c->count.data() + (size_t)c->first[(size_t)s] : nullptr; }
+void iba_submap_free(iba_submap_clouds* c) { delete c; }
