@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define IBA_ABI_VERSION 4 /* 2: iba_params.factor_3d2d_kind; 3: iba_icp_*; 4: iba_scan_*. An ADDED entry point (iba_submap_*) changes no existing struct and does not bump it: callers detect it by symbol */
+#define IBA_ABI_VERSION 4 /* 2: iba_params.factor_3d2d_kind; 3: iba_icp_*; 4: iba_scan_*. An ADDED entry point (iba_submap_*, iba_sc_*) changes no existing struct and does not bump it: callers detect it by symbol */
 #define IBA_MAX_BATCH 64 /* the batch unit of the callers in this library (one MADS poll block, the planner's diagnostics); NOT a limit of the evaluators */
 #define IBA_MAX_CHAIN 512 /* most candidates ONE launch chain takes (iba_create_options.max_chain_batch <= this); a call with more runs as consecutive chains */
 
@@ -239,8 +239,8 @@ iba_status iba_icp_calib(iba_handle* h, int32_t frame_begin, int32_t frame_end, 
  * GetInformationMatrixFromPointClouds(src, tgt, MRmaxCorrDist, T). Here a BATCH OF EDGES between local frames of one handle is evaluated
  * together: per ICP iteration one launch chain and one synchronise for all edges still running, and nothing of scan size crosses PCIe —
  * source and target scans, the target's kd tree and its memoised normals are already resident. A scans-only handle is enough.
- * Voxel down-sampling and the merged sub-map target of a loop closure are iba_submap_build (below); the pose-graph optimiser, ScanContext and PCD IO
- * stay the caller's.
+ * Voxel down-sampling and the merged sub-map target of a loop closure are iba_submap_build, and choosing WHICH keyframe pairs to close a loop between
+ * (Scan Context) is iba_sc_describe / iba_sc_detect (both below); the pose-graph optimiser and PCD IO stay the caller's.
  *
  * Restated from Open3D's public sources (not part of the reference tree: parity with it is UNPINNED; the kd search stays pinned to nanoflann):
  *   RegistrationICP, GetRegistrationResultAndCorrespondences, SearchHybrid's strict gate    the loop of iba_icp_register (one implementation)
@@ -338,7 +338,7 @@ iba_status iba_scan_information(iba_handle* h, const iba_scan_edge* edges, int32
  * 2^17 = 131072 voxels along an axis (the sort key holds the sub-map and three 17-bit indices; known after the first kernel, before the sort),
  * more than 2^22 members or more than 2^32 - 256 member points in one call. A sub-map whose members hold no kept point answers zero voxels.
  * Limits: the clouds come back to the host — a cloud becomes a registration target by creating a handle from the arrays (narrowed to float32 as
- * every scan is), there is no device-to-device attach; its normals are the plane memo of that handle; Scan Context, the pose graph and PCD IO are
+ * every scan is), there is no device-to-device attach; its normals are the plane memo of that handle; loop detection is iba_sc_* (below), the pose graph and PCD IO are
  * not here; one GPU — the members of a sub-map are local frames of one handle.
  */
 typedef struct iba_submap_desc {
@@ -360,6 +360,117 @@ int64_t iba_submap_n_dropped(const iba_submap_clouds* c, int32_t s);
 const double* iba_submap_xyz(const iba_submap_clouds* c, int32_t s);
 const int32_t* iba_submap_counts(const iba_submap_clouds* c, int32_t s);
 void iba_submap_free(iba_submap_clouds* c);
+
+/*
+ * ---- Scan Context: descriptors, ring keys, batched loop search [src/scancontext/Scancontext.cpp: makeScancontext(vector<Vector3d>) :198-240, ring / sector
+ * keys :242-271, distDirectSC :70-91, fastAlignUsingVkey :94-114, distanceBtnScanContext :117-149, detectLoopClosureID :393-486; called per keyframe from
+ * backend_opt.cpp:325,361 and :305] ----
+ * The reference describes every keyframe scan by a num_ring x num_sector matrix of the highest z per polar bin, keeps its row means (ring key) and column
+ * means (sector key), and asks per keyframe for the nearest older descriptor: 3 ring-key neighbours from a kd tree that is rebuilt every 30th call and
+ * leaves out the 30 most recent keyframes, each compared by the column-cosine distance under the best of 7 column shifts; below 0.2 it is a loop, which
+ * LoopClosureRegThread turns into a MergeLoadPCD target and a coarse -> refine registration. Scan Context depends on the scans alone, never on the
+ * optimised poses: here the descriptors of a BATCH OF RESIDENT SCANS are built in one launch chain into a database that stays on the device
+ * (iba_sc_describe; a scans-only handle is enough), and the whole detection sequence of a run is one batch of queries over it (iba_sc_detect).
+ * iba_sc_replay_plan (host only) turns the reference's call sequence into those queries; iba_sc_replay_plan -> iba_sc_detect -> iba_submap_build ->
+ * iba_scan_register is PerformLoopClosure + LoopClosureRegThread.
+ *
+ * Rules, fixed here so that the result is a function of the input alone (tests/sc_ref.py restates them in numpy; the device result is compared with it byte
+ * for byte). Every f64 operation below is rounded on its own: NO fused multiply-add; sqrt and / are IEEE. No floating-point atomics anywhere.
+ *   1 point      the scan's float32 coordinates widened to double. A point with a non-finite coordinate is SKIPPED and counted. zz = z + lidar_height;
+ *                range = sqrt((x x + y y) + zz zz), the 3-D norm as the back end's overload takes it (not the xy range of the PCL overload);
+ *                angle = atan2(y, x) * (180 / pi), + 360 when negative; x == 0 && y == 0 has angle 0 (the reference divides 0 / 0 there). Known
+ *                deviation: the reference narrows range and angle to float and takes atan of a float quotient by quadrant; here both stay f64.
+ *   2 bins       a point with range > max_radius is skipped; ring = max(min(num_ring, int(ceil(range / max_radius * num_ring))), 1), sector =
+ *                max(min(num_sector, int(ceil(angle / 360 * num_sector))), 1): the reference's expressions. Range and ring are IEEE and reproduce to the
+ *                bit; the f64 atan2 of two correct libraries may differ by a few ulp (about 1e-14 in bin units), which matters only for a point whose
+ *                angle sits on a sector boundary. y == +-0 with x > 0 is exact (atan2 answers +-0: sector 1).
+ *   3 bin value  the largest float32 z of the points that entered, widened, + lidar_height; an empty bin is 0. A point enters only with zz > -1000: the
+ *                reference's strict '<' against its -1000 initial value, and its final pass turns -1000 into 0 (a real z of exactly -1000 is 0 too).
+ *                On the device: integer atomic max on an order-preserving 32-bit key of the float32 z (+0 orders above -0), in LDS first, then global.
+ *                A maximum does not depend on the order: the descriptor is exact once the bins agree.
+ *   4 sums       ring key[r] = (sum over the sectors ascending) / num_sector; sector key[c] = (sum over the rings ascending) / num_ring; column norm[c]
+ *                = sqrt(sum over the rings ascending of v v), computed once per descriptor (a shift does not change it); dot products rings ascending;
+ *                the sum over the columns of a distance and over the sectors of an alignment ascending. The search takes the ring key narrowed to float.
+ *                (Eigen's own reductions may associate differently: a known deviation in the last bits.)
+ *   5 distance   alignment = the first shift in 0 .. num_sector - 1 that minimises |sector key 1 - circshift(sector key 2, shift)| (square root taken,
+ *                compared with '<' from the reference's initial 10000000). SEARCH_RADIUS = round(0.5 * search_ratio * num_sector); the shifts within it
+ *                of the alignment (mod num_sector) are tried ASCENDING; distance(shift) = 1 - (sum of dot / (norm1 * norm2) over the columns where both
+ *                norms are non-zero) / their count, 0 / 0 = NaN without such a column; the first minimum under '<' wins. A NaN never wins: when no shift
+ *                wins, the distance is the reference's initial 10000000 with shift 0.
+ *   6 search     the num_candidates nearest ring keys by EXACT brute force over [0, db_end) on the float keys, f64 squared distances summed rings
+ *                ascending, nearest first, equal distances to the lower node. Known deviation: nanoflann accumulates in float and keeps the first
+ *                visited (the index SETS agree on the golden fixture tests/golden/sc_ringkey_nanoflann.npz). With db_end < num_candidates only the
+ *                existing nodes are candidates and the other slots are -1 (node and shift) / NaN (distance): the reference reads uninitialised indices.
+ *   7 detection  the candidates in search order, the first strict minimum from 10000000 wins; loop_node = that node when min_dist < dist_thres, else -1;
+ *                yaw_rad = (float)(shift * (360.0 / num_sector) * M_PI / 180.0). A query's result does not depend on the batch, and two calls give
+ *                the same bytes.
+ * Answers IBA_ERR_INVALID_ARG with a message, before any launch: a NULL argument, a struct_size of another library, num_ring outside [1, 64], num_sector
+ * outside [1, 256], num_candidates outside [1, 16], max_radius not finite or not > 0, lidar_height / search_ratio / dist_thres not finite (search_ratio < 0),
+ * num_exclude_recent < 0, tree_period < 1, a frame outside the handle, n outside [1, 2^20], Q outside [1, 65536], P outside [1, 2^20], a node outside the
+ * database, db_end outside [0, size], options whose num_ring / num_sector differ from the database's. iba_last_error(h) carries the message of
+ * iba_sc_describe, iba_sc_last_error(db) of the calls on a database (db = NULL: of the calls that have neither, on this thread).
+ * Limits: a node is a resident scan of a handle. A voxel-averaged cloud (the reference describes LoadPCD's output) becomes a node the way it becomes a
+ * registration target: a handle created from the arrays iba_submap_build returned; there is no device-to-device attach. A database does not grow: describe
+ * the whole run at once (Scan Context does not depend on poses) and bound each query with db_end. The PCL overload of makeScancontext and
+ * detectLoopClosureIDBetweenSession are not restated (a query with an explicit db_end covers the latter's search). One GPU. The database has a stream of
+ * its own and outlives the handle it was described from.
+ */
+#define IBA_SC_MAX_RING 64
+#define IBA_SC_MAX_SECTOR 256
+#define IBA_SC_MAX_CANDIDATES 16
+#define IBA_SC_NO_WINNER 10000000.0
+typedef struct iba_sc_options {
+    int32_t struct_size;         /* sizeof(iba_sc_options) */
+    int32_t num_ring;            /* PC_NUM_RING 20 */
+    int32_t num_sector;          /* PC_NUM_SECTOR 60 */
+    int32_t num_exclude_recent;  /* NUM_EXCLUDE_RECENT 30 (iba_sc_replay_plan) */
+    int32_t num_candidates;      /* NUM_CANDIDATES_FROM_TREE 3 */
+    int32_t tree_period;         /* TREE_MAKING_PERIOD_ 30 (iba_sc_replay_plan) */
+    double  max_radius;          /* PC_MAX_RADIUS 80 */
+    double  lidar_height;        /* LIDAR_HEIGHT 0 */
+    double  search_ratio;        /* SEARCH_RATIO 0.1 */
+    double  dist_thres;          /* SC_DIST_THRES 0.2 */
+} iba_sc_options;
+typedef struct iba_sc_query {
+    int32_t struct_size;         /* sizeof(iba_sc_query) */
+    int32_t node;                /* the descriptor that asks */
+    int32_t db_end;              /* it is searched against the nodes [0, db_end); 0: no search (an early-returned call) */
+    int32_t reserved;            /* 0 */
+} iba_sc_query;
+typedef struct iba_sc_result {
+    int32_t struct_size;         /* written by the library: sizeof(iba_sc_result) */
+    int32_t loop_node;           /* -1: none */
+    int32_t shift;               /* of the winning candidate (0 when none won) */
+    int32_t n_candidates;        /* min(num_candidates, db_end) */
+    double  min_dist;            /* IBA_SC_NO_WINNER when no candidate won */
+    float   yaw_rad;
+    int32_t reserved;
+    int32_t cand_node[IBA_SC_MAX_CANDIDATES];   /* in search order; -1 beyond n_candidates */
+    int32_t cand_shift[IBA_SC_MAX_CANDIDATES];  /* -1 beyond n_candidates */
+    double  cand_dist[IBA_SC_MAX_CANDIDATES];   /* NaN beyond n_candidates */
+} iba_sc_result;
+typedef struct iba_sc_db iba_sc_db;
+/* the reference's constants (Scancontext.h) */
+iba_status iba_default_sc_options(iba_sc_options* opt);
+/* Descriptors, ring keys, sector keys and column norms of n resident scans (local frames of the handle; a frame may repeat) as nodes 0 .. n - 1 of a
+ * database on the device: one launch chain (bins by integer atomic max, finalise + keys) and one synchronise. *out is NULL on failure. */
+iba_status iba_sc_describe(iba_handle* h, const int32_t* frames, int32_t n, const iba_sc_options* opt, iba_sc_db** out);
+int32_t iba_sc_db_size(const iba_sc_db* db);   /* nodes; 0 for NULL */
+/* Copies of nodes [first, first + count) to the host; every output may be NULL. desc: count x num_ring x num_sector doubles, row-major [ring][sector];
+ * ring_key: count x num_ring doubles; ring_key_f: their float narrowing (what the search reads); sector_key: count x num_sector doubles; n_skipped: the
+ * points of the node's scan with a non-finite coordinate. */
+iba_status iba_sc_db_read(iba_sc_db* db, int32_t first, int32_t count, double* desc, double* ring_key, float* ring_key_f, double* sector_key, int64_t* n_skipped);
+void iba_sc_db_free(iba_sc_db* db);
+const char* iba_sc_last_error(const iba_sc_db* db);   /* never NULL */
+/* distanceBtnScanContext(node pairs[p][0], node pairs[p][1]) for P pairs in one launch: rule 5 */
+iba_status iba_sc_distance(iba_sc_db* db, const int32_t* pairs /* P x 2 */, int32_t P, const iba_sc_options* opt, double* dist /* P */, int32_t* shift /* P */);
+/* Q queries in one launch chain (search, distances of every (query, candidate), pick) and one synchronise: rules 6 and 7 */
+iba_status iba_sc_detect(iba_sc_db* db, const iba_sc_query* queries, int32_t Q, const iba_sc_options* opt, iba_sc_result* out /* Q */);
+/* Host only, no device: detectLoopClosureID's statefulness as a pure function. sizes_at_call[i] = the descriptors the manager holds at its i-th call (the
+ * query of that call is node sizes_at_call[i] - 1). With fewer than num_exclude_recent + 1 descriptors the call returns early WITHOUT advancing the
+ * counter: db_end[i] = 0. Otherwise, when counter % tree_period == 0 the search set becomes the first size - num_exclude_recent keys, then the counter
+ * advances; between rebuilds the set is stale. db_end[i] = the size of the set call i searches. */
+iba_status iba_sc_replay_plan(const int32_t* sizes_at_call, int32_t n, const iba_sc_options* opt, int32_t* db_end /* n */);
 
 /* The ABI version the LIBRARY was built with (IBA_ABI_VERSION of its header). iba_params carries no struct_size: a caller compiled against
  * an older header would pass a shorter struct. Callers compare iba_abi_version() with their own IBA_ABI_VERSION before iba_create(). */

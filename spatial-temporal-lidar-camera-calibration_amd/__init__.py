@@ -14,7 +14,7 @@ import subprocess
 
 import numpy as np
 
-from .abi import (ICP_NMOM, SCAN_NMOM, IbaSubmapDesc, IbaScanEdge, IbaScanOptions, IbaScanResult, IbaIcpOptions, IbaIcpResult, IBA_MAX_BATCH, IbaCreateOptions, IbaLmOptions, IbaLmResult, IbaMadsOptions, IbaMadsResult, IbaBbo, IbaCostOut, IbaNormalOut, IbaParams, IbaProblemDesc, Problem, copy_params,
+from .abi import (ICP_NMOM, SCAN_NMOM, IbaScOptions, IbaScQuery, IbaScResult, IbaSubmapDesc, IbaScanEdge, IbaScanOptions, IbaScanResult, IbaIcpOptions, IbaIcpResult, IBA_MAX_BATCH, IbaCreateOptions, IbaLmOptions, IbaLmResult, IbaMadsOptions, IbaMadsResult, IbaBbo, IbaCostOut, IbaNormalOut, IbaParams, IbaProblemDesc, Problem, copy_params,
                   reference_yaml_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -466,6 +466,16 @@ class IbaHandle:
             L.iba_submap_free(res)
         return out
 
+    # --- Scan Context (iba_sc_describe): descriptors of resident scans as a database on the device ---
+    def sc_describe(self, frames, opt=None, **fields):
+        """iba_sc_describe: local frames [n] -> ScDb (nodes 0 .. n - 1). opt = an IbaScOptions, or fields of one over the reference's defaults."""
+        o = sc_options(**fields) if opt is None else opt
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        self.lib.iba_sc_describe.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
+        db = C.c_void_p(None)
+        self._chk(self.lib.iba_sc_describe(self.h, _p(fr) if len(fr) else None, C.c_int32(len(fr)), C.byref(o), C.byref(db)))
+        return ScDb(self.lib, db, o)
+
     def debug_scan_threads(self, threads):
         """force the block shape of the scan pass kernel (64 / 256; 0: the rule)"""
         self.lib.iba_debug_scan_threads.argtypes = [C.c_void_p, C.c_int32]
@@ -592,6 +602,96 @@ class IbaHandle:
     @property
     def n_keypoints(self):
         return int(self.lib.iba_num_keypoints(self.h))
+
+
+def sc_options(**fields):
+    """iba_default_sc_options (the reference's Scancontext.h constants) with fields overridden"""
+    o = IbaScOptions()
+    st = load_library().iba_default_sc_options(C.byref(o))
+    if st != 0:
+        raise IbaError(st, "iba_default_sc_options")
+    for k, v in fields.items():
+        if k not in dict(IbaScOptions._fields_):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def sc_replay_plan(sizes_at_call, opt=None, **fields):
+    """iba_sc_replay_plan (host only): the descriptors held at each detectLoopClosureID call -> db_end per call (0: the early return)"""
+    L = load_library()
+    o = sc_options(**fields) if opt is None else opt
+    sizes = np.ascontiguousarray(sizes_at_call, np.int32).reshape(-1)
+    out = np.zeros(max(len(sizes), 1), np.int32)
+    L.iba_sc_replay_plan.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.iba_sc_last_error.argtypes = [C.c_void_p]; L.iba_sc_last_error.restype = C.c_char_p
+    st = L.iba_sc_replay_plan(_p(sizes) if len(sizes) else None, C.c_int32(len(sizes)), C.byref(o), _p(out))
+    if st != 0:
+        raise IbaError(st, L.iba_sc_last_error(None).decode())
+    return out[:len(sizes)]
+
+
+class ScDb:
+    """iba_sc_db wrapper: the Scan Context database of iba_sc_describe (on the device until close())"""
+
+    def __init__(self, lib, db, opt):
+        self.lib, self.db, self.opt = lib, db, opt
+        L = lib
+        L.iba_sc_last_error.argtypes = [C.c_void_p]; L.iba_sc_last_error.restype = C.c_char_p
+        L.iba_sc_db_size.argtypes = [C.c_void_p]; L.iba_sc_db_size.restype = C.c_int32
+        L.iba_sc_db_free.argtypes = [C.c_void_p]; L.iba_sc_db_free.restype = None
+        L.iba_sc_db_read.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5
+        L.iba_sc_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.iba_sc_detect.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+
+    def _chk(self, st):
+        if st != 0:
+            raise IbaError(st, self.lib.iba_sc_last_error(self.db).decode())
+
+    def __len__(self):
+        return int(self.lib.iba_sc_db_size(self.db))
+
+    def read(self, first=0, count=None):
+        """iba_sc_db_read -> dict(desc [count, R, S], ring [count, R], ring_f float32, sector [count, S], skipped [count] int64)"""
+        n = len(self) - first if count is None else count
+        R, S = self.opt.num_ring, self.opt.num_sector
+        m = max(n, 0)
+        out = dict(desc=np.zeros((m, R, S)), ring=np.zeros((m, R)), ring_f=np.zeros((m, R), np.float32), sector=np.zeros((m, S)), skipped=np.zeros(m, np.int64))
+        self._chk(self.lib.iba_sc_db_read(self.db, C.c_int32(first), C.c_int32(n), _p(out["desc"]), _p(out["ring"]), _p(out["ring_f"]), _p(out["sector"]), _p(out["skipped"])))
+        return out
+
+    def distance(self, pairs, opt=None):
+        """iba_sc_distance: pairs [P, 2] of nodes -> (dist [P] float64, shift [P] int32)"""
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        P = len(pr)
+        dist, shift = np.zeros(max(P, 1)), np.zeros(max(P, 1), np.int32)
+        self._chk(self.lib.iba_sc_distance(self.db, _p(pr) if P else None, C.c_int32(P), C.byref(opt or self.opt), _p(dist), _p(shift)))
+        return dist[:P], shift[:P]
+
+    def detect(self, queries, opt=None):
+        """iba_sc_detect: queries = [(node, db_end)] -> ctypes array of IbaScResult"""
+        qs = list(queries)
+        Q = len(qs)
+        arr = (IbaScQuery * max(Q, 1))()
+        for i, (node, db_end) in enumerate(qs):
+            arr[i].struct_size = C.sizeof(IbaScQuery); arr[i].node = int(node); arr[i].db_end = int(db_end)
+        return self.detect_raw(arr, Q, opt)
+
+    def detect_raw(self, arr, Q, opt=None):
+        out = (IbaScResult * max(Q, 1))()
+        self._chk(self.lib.iba_sc_detect(self.db, arr, C.c_int32(Q), C.byref(opt or self.opt), out))
+        return out
+
+    def close(self):
+        if getattr(self, "db", None) and self.db.value:
+            self.lib.iba_sc_db_free(self.db)
+            self.db = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class IbaGroup:

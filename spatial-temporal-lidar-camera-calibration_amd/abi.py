@@ -176,6 +176,27 @@ SUBMAP_MAX_BATCH = 4096          # M of iba_submap_build
 SUBMAP_MAX_AXIS_VOXELS = 1 << 17  # voxels per axis the sort key holds
 
 
+SC_MAX_RING, SC_MAX_SECTOR, SC_MAX_CANDIDATES = 64, 256, 16   # IBA_SC_MAX_*
+SC_NO_WINNER = 10000000.0                                      # IBA_SC_NO_WINNER
+
+
+class IbaScOptions(C.Structure):
+    """iba_sc_options: the constants of the reference's Scancontext.h (iba_default_sc_options fills them)"""
+    _fields_ = [("struct_size", C.c_int32), ("num_ring", C.c_int32), ("num_sector", C.c_int32), ("num_exclude_recent", C.c_int32), ("num_candidates", C.c_int32), ("tree_period", C.c_int32),
+                ("max_radius", C.c_double), ("lidar_height", C.c_double), ("search_ratio", C.c_double), ("dist_thres", C.c_double)]
+
+
+class IbaScQuery(C.Structure):
+    """iba_sc_query: descriptor `node` searched against the nodes [0, db_end)"""
+    _fields_ = [("struct_size", C.c_int32), ("node", C.c_int32), ("db_end", C.c_int32), ("reserved", C.c_int32)]
+
+
+class IbaScResult(C.Structure):
+    """iba_sc_result: the loop of one query (loop_node -1: none) and its candidates in search order"""
+    _fields_ = [("struct_size", C.c_int32), ("loop_node", C.c_int32), ("shift", C.c_int32), ("n_candidates", C.c_int32), ("min_dist", C.c_double), ("yaw_rad", C.c_float), ("reserved", C.c_int32),
+                ("cand_node", C.c_int32 * SC_MAX_CANDIDATES), ("cand_shift", C.c_int32 * SC_MAX_CANDIDATES), ("cand_dist", C.c_double * SC_MAX_CANDIDATES)]
+
+
 class IbaBbo(C.Structure):
     _fields_ = [("f", C.c_double), ("c1", C.c_double), ("c2", C.c_double), ("c3", C.c_double)]
 

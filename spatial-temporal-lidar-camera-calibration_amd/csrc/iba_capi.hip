@@ -36,6 +36,7 @@ const char* debug_env(const char* name) {   // (read at every handle creation: a
 #include "iba_icp_kernels.hpp"
 #include "iba_scan_kernels.hpp"
 #include "iba_voxel_kernels.hpp"
+#include "iba_sc_kernels.hpp"
 #include "iba_icp_math.hpp"
 #include "iba_types.hpp"
 
@@ -2156,3 +2157,4 @@ iba_status reserve_batch(iba_handle* h, int B) {
 #include "iba_icp_host.hpp"   // iba_icp_step / iba_icp_register / iba_icp_calib
 #include "iba_scan_host.hpp"  // iba_scan_step / iba_scan_register / iba_scan_information
 #include "iba_voxel_host.hpp" // iba_submap_build and the accessors of its result
+#include "iba_sc_host.hpp"    // iba_sc_describe / iba_sc_distance / iba_sc_detect / iba_sc_replay_plan
