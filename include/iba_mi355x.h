@@ -274,7 +274,8 @@ iba_status iba_icp_calib(iba_handle* h, int32_t frame_begin, int32_t frame_end, 
  *   IBA_SCAN_INFORMATION      [0] pairs  [1..3] sum t  [4..9] sum t t^T (xx, xy, xz, yy, yz, zz)
  * The point-to-plane and information sums are taken about the origin of the target frame, as the definitions are.
  * Limits: one target scan per edge; rigid only (the scaled form is iba_icp_*); no robust kernel; one GPU — both frames of an edge are
- * local frames of this handle.
+ * local frames of this handle. The reference registers voxel clouds, never raw scans: iba_submap_handle (below) gives a handle whose frames
+ * ARE voxel clouds, built on the device, and every entry point of this block runs on it unchanged.
  */
 typedef struct iba_scan_edge { int32_t src_frame, tgt_frame; double T[16]; } iba_scan_edge; /* row-major 4x4, src scan frame -> tgt scan frame */
 #define IBA_SCAN_POINT_TO_POINT 0   /* TransformationEstimationPointToPoint(false) */
@@ -337,9 +338,10 @@ iba_status iba_scan_information(iba_handle* h, const iba_scan_edge* edges, int32
  * non-finite pose or out12, voxel not finite or not > 0, M outside [1, 4096]. IBA_ERR_UNSUPPORTED: a sub-map whose kept points span more than
  * 2^17 = 131072 voxels along an axis (the sort key holds the sub-map and three 17-bit indices; known after the first kernel, before the sort),
  * more than 2^22 members or more than 2^32 - 256 member points in one call. A sub-map whose members hold no kept point answers zero voxels.
- * Limits: the clouds come back to the host — a cloud becomes a registration target by creating a handle from the arrays (narrowed to float32 as
- * every scan is), there is no device-to-device attach; its normals are the plane memo of that handle; loop detection is iba_sc_* (below), the pose graph and PCD IO are
- * not here; one GPU — the members of a sub-map are local frames of one handle.
+ * Limits: iba_submap_build brings the clouds back to the host; iba_submap_handle (below) keeps them on the device instead and makes them the
+ * frames of a new handle — registration targets, Scan Context nodes, members of further sub-maps — whose normals are that handle's plane memo.
+ * Clouds cannot be attached to an EXISTING handle. Loop detection is iba_sc_* (below), the pose graph and PCD IO are not here; one GPU — the
+ * members of a sub-map are local frames of one handle.
  */
 typedef struct iba_submap_desc {
     int32_t struct_size;      /* sizeof(iba_submap_desc) */
@@ -360,6 +362,18 @@ int64_t iba_submap_n_dropped(const iba_submap_clouds* c, int32_t s);
 const double* iba_submap_xyz(const iba_submap_clouds* c, int32_t s);
 const int32_t* iba_submap_counts(const iba_submap_clouds* c, int32_t s);
 void iba_submap_free(iba_submap_clouds* c);
+/* A scans-only handle whose local frame s is the voxel cloud of sub-map s, built without the clouds leaving the device.
+ * subs / M: the argument rules of iba_submap_build and its messages (headed by this function's name), checked before any launch; they are left
+ * in iba_last_error(src). Frame s of *out holds exactly the points iba_submap_xyz(c, s) would return, each coordinate narrowed to float32 with
+ * round-to-nearest-even (the C cast a caller of iba_create applies), original index = voxel order, ascending (ix, iy, iz). The kd index, the
+ * leaf-ordered arrays and the boxes are built on the device (csrc/iba_index_kernels.hpp) and are BIT-IDENTICAL to what iba_create builds on the
+ * host for the same float32 points, so every result on *out equals the result on such a handle. A sub-map without voxels is an empty frame
+ * (edges on it answer as empty scans do). A coordinate that is not finite after narrowing, or a sub-map of 2^22 voxels or more:
+ * IBA_ERR_UNSUPPORTED. *out lives on src's device, has its own stream, does not depend on src's lifetime and is released with iba_destroy; it
+ * is NULL on failure. params: as for iba_create (plane_cache = 1 builds the plane memo, which point-to-plane edges need). The keypoint side
+ * is empty: iba_scan_*, iba_icp_*, iba_geo_correspondences, iba_sc_describe, iba_submap_build / iba_submap_handle (a sub-map of sub-maps) and
+ * the debug probes work on it. Up go the bounds and voxel counts per sub-map and 32 B of frame box per frame; nothing of cloud size crosses PCIe. */
+iba_status iba_submap_handle(iba_handle* src, const iba_submap_desc* subs, int32_t M, const iba_params* params, iba_handle** out);
 
 /*
  * ---- Scan Context: descriptors, ring keys, batched loop search [src/scancontext/Scancontext.cpp: makeScancontext(vector<Vector3d>) :198-240, ring / sector
@@ -410,7 +424,7 @@ void iba_submap_free(iba_submap_clouds* c);
  * database, db_end outside [0, size], options whose num_ring / num_sector differ from the database's. iba_last_error(h) carries the message of
  * iba_sc_describe, iba_sc_last_error(db) of the calls on a database (db = NULL: of the calls that have neither, on this thread).
  * Limits: a node is a resident scan of a handle. A voxel-averaged cloud (the reference describes LoadPCD's output) becomes a node the way it becomes a
- * registration target: a handle created from the arrays iba_submap_build returned; there is no device-to-device attach. A database does not grow: describe
+ * registration target: as a frame of the handle iba_submap_handle returns, without leaving the device. A database does not grow: describe
  * the whole run at once (Scan Context does not depend on poses) and bound each query with db_end. The PCL overload of makeScancontext and
  * detectLoopClosureIDBetweenSession are not restated (a query with an explicit db_end covers the latter's search). One GPU. The database has a stream of
  * its own and outlives the handle it was described from.
@@ -640,6 +654,7 @@ iba_status iba_eval_factors_partial(iba_handle* h, const double* x, int32_t B, v
  * iba_mi355x_debug.h: test and benchmark tooling, not part of the drop-in surface. */
 int64_t iba_num_points(const iba_handle* h);
 int64_t iba_num_keypoints(const iba_handle* h);
+int64_t iba_frame_num_points(const iba_handle* h, int32_t frame);   /* points of one local frame; -1 for NULL or a frame out of range */
 
 /*
  * Batch-aware mesh adaptive direct search for the global stage [SURVEY.md 8(f) row 2]: the caller the reference gets

@@ -129,6 +129,16 @@ iba_status iba_debug_nn(iba_handle* h, int32_t frame, const double* q_xyz, int32
 iba_status iba_debug_plane(iba_handle* h, int32_t frame, uint32_t point, int32_t which, double out5[5], int32_t* k);
 /* debug: force the block shape of iba_scan_* passes (64: one-wave blocks, 256: four waves; 0: the rule of DESIGN.md 5b on the largest target
  * tree of the pass). The sums do not depend on the shape. iba_debug_last_scan_threads: the shape the last pass ran with. */
+/* debug: the scan-side index of local frame `frame` as the kernels read it, on any handle: perm (tree position -> original index), the points in
+ * tree order as three planes x[P], y[P], z[P], the inner nodes in heap order ((1 << depth) - 1 each), the boxes of the 64-position chunks (8
+ * floats each: min xyz, NaN, max xyz, the largest |coordinate|), the frame's box, the depth. Every output may be NULL; P = iba_frame_num_points.
+ * tests/test_gpu_submap_handle.py holds the device-built index of iba_submap_handle to the host-built one of iba_create with it, byte for byte. */
+iba_status iba_debug_scan_index(iba_handle* h, int32_t frame, uint32_t* perm /* P */, float* xyz_tree /* 3 x P, tree order */,
+                                uint32_t* node_dim, float* node_split /* (1<<depth)-1 each */, float* chunk_box /* 8 per chunk */,
+                                float frame_box[8], int32_t* depth);
+/* debug, HOST ONLY (no device is touched): the host build of the same index (build_tree, csrc/iba_build.hpp) on P points given as x, y, z triples:
+ * perm, the nodes, the depth. tests/test_index_rules_cpu.py pins the numpy restatement of the build rules to it. */
+iba_status iba_debug_build_tree(const float* xyz, uint32_t P, uint32_t* perm, uint32_t* node_dim, float* node_split, int32_t* depth);
 iba_status iba_debug_scan_threads(iba_handle* h, int32_t threads);
 int32_t iba_debug_last_scan_threads(const iba_handle* h);
 

@@ -429,6 +429,12 @@ class IbaHandle:
         """iba_submap_build: subs = iterable of (frames, poses, out, voxel) — local frames [n], poses [n, 3, 4] (or [n, 12] / 4x4 each; scan frame ->
         common frame), out = None or a 3x4 / 4x4 applied to the averaged points, voxel size. -> list of dict(xyz [V, 3] float64 in ascending
         (ix, iy, iz), count [V] int32, n_dropped) per sub-map. LoadPCD of frame f: ([f], [np.eye(4)], None, voxel)."""
+        arr, M, _keep = self._submap_descs(subs)
+        return self.submap_build_raw(arr, M)
+
+    @staticmethod
+    def _submap_descs(subs):
+        """-> (ctypes array of IbaSubmapDesc, M, the numpy arrays its pointers refer to)"""
         subs = list(subs)
         M = len(subs)
         arr = (IbaSubmapDesc * max(M, 1))()
@@ -443,7 +449,7 @@ class IbaHandle:
             arr[k].frames = fr.ctypes.data if len(fr) else None; arr[k].poses12 = ps.ctypes.data if len(fr) else None
             arr[k].out12 = None if o12 is None else o12.ctypes.data
             arr[k].voxel = float(voxel)
-        return self.submap_build_raw(arr, M)
+        return arr, M, keep
 
     def submap_build_raw(self, arr, M):
         """iba_submap_build on a ctypes array of IbaSubmapDesc (what submap_build fills)"""
@@ -465,6 +471,50 @@ class IbaHandle:
         finally:
             L.iba_submap_free(res)
         return out
+
+    # --- voxel clouds as the frames of a new handle, built on the device (iba_submap_handle) ---
+    def submap_handle(self, subs, params=None):
+        """iba_submap_handle: subs as for submap_build -> an IbaHandle whose local frame s is the voxel cloud of sub-map s (float32, voxel order),
+        with the kd index built on the device. params: None = this handle's. The new handle does not depend on this one; close() it."""
+        arr, M, _keep = self._submap_descs(subs)
+        return self.submap_handle_raw(arr, M, params)
+
+    def submap_handle_raw(self, arr, M, params=None):
+        """iba_submap_handle on a ctypes array of IbaSubmapDesc"""
+        L = self.lib
+        L.iba_submap_handle.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(IbaParams), C.POINTER(C.c_void_p)]
+        prm = copy_params(params if params is not None else self.params)
+        out = C.c_void_p(None)
+        self._chk(L.iba_submap_handle(self.h, arr, C.c_int32(M), C.byref(prm), C.byref(out)))
+        return IbaHandle._adopt(L, out, prm, M)
+
+    @classmethod
+    def _adopt(cls, lib, h, params, n_frames):
+        """wrap a handle the library created itself (scans only: the point counts are asked from the library)"""
+        self = cls.__new__(cls)
+        self.lib, self.h, self.params = lib, h, params
+        self.frame_begin, self.frame_end = 0, n_frames
+        counts = [self.frame_num_points(f) for f in range(n_frames)]
+        self.problem = _ScanCounts(np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64))
+        return self
+
+    def frame_num_points(self, frame):
+        self.lib.iba_frame_num_points.argtypes = [C.c_void_p, C.c_int32]
+        self.lib.iba_frame_num_points.restype = C.c_int64
+        return int(self.lib.iba_frame_num_points(self.h, C.c_int32(frame)))
+
+    def debug_scan_index(self, frame):
+        """iba_debug_scan_index: dict(perm [P] u32, xyz_tree [3, P] f32, node_dim / node_split [(1 << depth) - 1], chunk_box [chunks, 8] f32, frame_box [8] f32, depth)"""
+        P = self.frame_num_points(frame)
+        depth = C.c_int32(0)
+        self.lib.iba_debug_scan_index.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.POINTER(C.c_int32)]
+        self._chk(self.lib.iba_debug_scan_index(self.h, C.c_int32(frame), None, None, None, None, None, None, C.byref(depth)))
+        nn, nc = (1 << depth.value) - 1, (P + 63) // 64
+        r = dict(perm=np.zeros(P, np.uint32), xyz_tree=np.zeros((3, P), np.float32), node_dim=np.zeros(nn, np.uint32), node_split=np.zeros(nn, np.float32),
+                 chunk_box=np.zeros((nc, 8), np.float32), frame_box=np.zeros(8, np.float32))
+        self._chk(self.lib.iba_debug_scan_index(self.h, C.c_int32(frame), _p(r["perm"]), _p(r["xyz_tree"]), _p(r["node_dim"]), _p(r["node_split"]), _p(r["chunk_box"]), _p(r["frame_box"]), C.byref(depth)))
+        r["depth"] = depth.value
+        return r
 
     # --- Scan Context (iba_sc_describe): descriptors of resident scans as a database on the device ---
     def sc_describe(self, frames, opt=None, **fields):
@@ -602,6 +652,32 @@ class IbaHandle:
     @property
     def n_keypoints(self):
         return int(self.lib.iba_num_keypoints(self.h))
+
+
+class _ScanCounts:
+    """what IbaHandle's wrappers read of a problem, for a handle whose scans never were on the host (IbaHandle.submap_handle)"""
+
+    def __init__(self, pt_offset):
+        self.n_frames = len(pt_offset) - 1
+        self.arrays = dict(pt_offset=pt_offset, kp_offset=np.zeros(len(pt_offset), np.uint64))
+
+
+def debug_build_tree(xyz):
+    """iba_debug_build_tree (host only, no GPU): the host build of the kd index on [P, 3] float32 points -> dict(perm, node_dim, node_split, depth)"""
+    L = load_library()
+    pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    P = len(pts)
+    L.iba_debug_build_tree.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+    depth = C.c_int32(0)
+    st = L.iba_debug_build_tree(_p(pts), C.c_uint32(P), None, None, None, C.byref(depth))
+    if st != 0:
+        raise IbaError(st, "iba_debug_build_tree")
+    nn = (1 << depth.value) - 1
+    r = dict(perm=np.zeros(P, np.uint32), node_dim=np.zeros(nn, np.uint32), node_split=np.zeros(nn, np.float32), depth=depth.value)
+    st = L.iba_debug_build_tree(_p(pts), C.c_uint32(P), _p(r["perm"]), _p(r["node_dim"]), _p(r["node_split"]), C.byref(depth))
+    if st != 0:
+        raise IbaError(st, "iba_debug_build_tree")
+    return r
 
 
 def sc_options(**fields):

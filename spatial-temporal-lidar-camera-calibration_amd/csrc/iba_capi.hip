@@ -37,6 +37,7 @@ const char* debug_env(const char* name) {   // (read at every handle creation: a
 #include "iba_scan_kernels.hpp"
 #include "iba_voxel_kernels.hpp"
 #include "iba_sc_kernels.hpp"
+#include "iba_index_kernels.hpp"
 #include "iba_icp_math.hpp"
 #include "iba_types.hpp"
 
@@ -1072,6 +1073,13 @@ iba_status eval_cost_partial_impl(iba_handle* h, const double* x, int B, double*
 
 }  // namespace
 
+namespace {
+// iba_submap_handle (iba_index_host.hpp): where the scans of a new handle come from when they are already on the device
+struct ScanSource { iba_handle* src; const uint32_t* first; };   // the handle whose voxel chain holds the clouds (src->vox), first voxel of every frame (n_frames + 1)
+iba_status index_build_device(iba_handle* dst, const ScanSource& from, std::string& why);
+iba_status create_impl(const iba_problem_desc* d, const iba_params* params, int device, int32_t frame_begin, int32_t frame_end, const iba_create_options* user_opt, const ScanSource* pre, iba_handle** out);
+}  // namespace
+
 extern "C" {
 
 int32_t iba_abi_version(void) { return IBA_ABI_VERSION; }
@@ -1112,6 +1120,16 @@ iba_status iba_create(const iba_problem_desc* d, const iba_params* params, int d
 }
 
 iba_status iba_create_ex(const iba_problem_desc* d, const iba_params* params, int device, int32_t frame_begin, int32_t frame_end, const iba_create_options* user_opt, iba_handle** out) {
+    return create_impl(d, params, device, frame_begin, frame_end, user_opt, nullptr, out);
+}
+
+}  // extern "C"
+
+namespace {
+// One function for both ways into a handle. `pre` == nullptr: the scans come from the descriptor (iba_create*): the host builds every tree,
+// flattens and uploads. `pre` given (iba_submap_handle, iba_index_host.hpp): d->pts_xyz is not read; the scan-side arrays are allocated here
+// from the point counts alone and filled on the device by index_build_device. Everything that is not scan data is the same code.
+iba_status create_impl(const iba_problem_desc* d, const iba_params* params, int device, int32_t frame_begin, int32_t frame_end, const iba_create_options* user_opt, const ScanSource* pre, iba_handle** out) {
     g_create_error.clear();
     iba_create_options opt;
     iba_default_create_options(&opt);
@@ -1137,7 +1155,7 @@ iba_status iba_create_ex(const iba_problem_desc* d, const iba_params* params, in
         if (F > 0 && (!d->pt_offset || !d->kp_offset || !d->covis_offset || !d->intrinsics || !d->Tcw || !d->Tc_next || !d->Tl_next)) { return fail(nullptr, IBA_ERR_INVALID_ARG, "null array in the problem descriptor"); }
         if (F > 0 && (!monotonic(d->pt_offset, F) || !monotonic(d->kp_offset, F) || !monotonic(d->covis_offset, F))) { return fail(nullptr, IBA_ERR_INVALID_ARG, "pt_offset / kp_offset / covis_offset must be non-decreasing"); }
         const uint64_t S = F > 0 ? d->covis_offset[F] : 0, Ntot = F > 0 ? d->pt_offset[F] : 0, Ktot = F > 0 ? d->kp_offset[F] : 0;
-        if ((Ntot > 0 && !d->pts_xyz) || (Ktot > 0 && (!d->kp_uv || !d->kp_has_mappoint || !d->kp_mappoint_w))) { return fail(nullptr, IBA_ERR_INVALID_ARG, "null point / keypoint array in the problem descriptor"); }
+        if ((Ntot > 0 && !d->pts_xyz && !pre) || (Ktot > 0 && (!d->kp_uv || !d->kp_has_mappoint || !d->kp_mappoint_w))) { return fail(nullptr, IBA_ERR_INVALID_ARG, "null point / keypoint array in the problem descriptor"); }
         if (S > 0 && (!d->covis_frame || !d->covis_relpose || !d->match_offset || !monotonic(d->match_offset, (int64_t)S))) { return fail(nullptr, IBA_ERR_INVALID_ARG, "covisibility arrays missing or match_offset not non-decreasing"); }
         if (S > 0 && d->match_offset[S] > 0 && (!d->match_kp_ref || !d->match_kp_covis)) { return fail(nullptr, IBA_ERR_INVALID_ARG, "null match arrays in the problem descriptor"); }
     }
@@ -1176,7 +1194,7 @@ iba_status iba_create_ex(const iba_problem_desc* d, const iba_params* params, in
         const uint32_t K = (uint32_t)(d->kp_offset[f + 1] - d->kp_offset[f]);
         FrameBuild& b = fb[lf];
         b.D = tree_depth_for(P);
-        build_tree(d->pts_xyz + 3 * d->pt_offset[f], P, b.D, b.idx, b.nodes);
+        if (!pre) build_tree(d->pts_xyz + 3 * d->pt_offset[f], P, b.D, b.idx, b.nodes);
         const double* in = d->intrinsics + 6 * f;
         auto part1by1 = [](uint32_t v) { v &= 0xFFFFu; v = (v | (v << 8)) & 0x00FF00FFu; v = (v | (v << 4)) & 0x0F0F0F0Fu; v = (v | (v << 2)) & 0x33333333u; v = (v | (v << 1)) & 0x55555555u; return v; };
         const float* uv0 = d->kp_uv + 2 * d->kp_offset[f];
@@ -1199,13 +1217,14 @@ iba_status iba_create_ex(const iba_problem_desc* d, const iba_params* params, in
 
     // ---- flatten ----
     std::vector<FrameHdr>& hdr = h->h_frames; hdr.resize(nf);
+    auto n_nodes = [&](int lf) { return (uint32_t)((1u << fb[lf].D) - 1u); };   // (= fb[lf].nodes.size() of a host build)
     uint64_t pt_base = 0, kp_base = 0, coarse_base = 0, bm_base = 0, match_base = 0, box_base = 0; uint32_t node_base = 0, slot_base = 0;
     for (int lf = 0; lf < nf; ++lf) {
         const int f = frame_begin + lf;
         FrameHdr& x = hdr[lf]; std::memset(&x, 0, sizeof(x));
         x.P = (uint32_t)(d->pt_offset[f + 1] - d->pt_offset[f]); x.Ppad = (x.P + 3u) & ~3u; x.pt_base = pt_base; pt_base += x.Ppad;
         x.box_base = box_base; box_base += (x.P + (uint32_t)kChunk - 1u) / (uint32_t)kChunk;
-        x.depth = fb[lf].D; x.node_base = node_base; node_base += (uint32_t)fb[lf].nodes.size();
+        x.depth = fb[lf].D; x.node_base = node_base; node_base += n_nodes(lf);
         x.K = (uint32_t)(d->kp_offset[f + 1] - d->kp_offset[f]); x.kp_base = kp_base; kp_base += x.K;
         x.gw = fb[lf].grid.gw; x.gh = fb[lf].grid.gh; x.gwc = fb[lf].grid.gwc; x.ghc = fb[lf].grid.ghc;
         x.coarse_base = coarse_base; coarse_base += (uint64_t)x.gwc * x.ghc + 1;
@@ -1219,7 +1238,7 @@ iba_status iba_create_ex(const iba_problem_desc* d, const iba_params* params, in
         x.he_valid = f < F - 1 ? 1 : 0; x.global_frame = f;
         h->maxP = std::max(h->maxP, x.P); h->maxPpad = std::max(h->maxPpad, x.Ppad); h->maxK = std::max(h->maxK, x.K);
         h->max_fx = std::max(h->max_fx, std::max(std::fabs(x.fx), std::fabs(x.fy)));
-        h->maxNodes = std::max<uint32_t>(h->maxNodes, (uint32_t)fb[lf].nodes.size());
+        h->maxNodes = std::max<uint32_t>(h->maxNodes, n_nodes(lf));
         h->maxBitmapWords = std::max<uint32_t>(h->maxBitmapWords, (uint32_t)fb[lf].grid.bitmap.size());
     }
     h->n_points = 0; for (auto& x : hdr) h->n_points += x.P;
@@ -1228,11 +1247,12 @@ iba_status iba_create_ex(const iba_problem_desc* d, const iba_params* params, in
     h->h_kp_off.resize(nf + 1); for (int lf = 0; lf < nf; ++lf) h->h_kp_off[lf] = hdr[lf].kp_base; h->h_kp_off[nf] = kp_base;
 
     const float qnan = std::numeric_limits<float>::quiet_NaN();
-    std::vector<float> xs(pt_base, qnan), ys(pt_base, qnan), zs(pt_base, qnan);
-    std::vector<uint32_t> perm(pt_base, 0u), inv_perm(pt_base, 0u);
-    std::vector<float4> pts4(pt_base, float4{qnan, qnan, qnan, 0.f});
-    std::vector<float> chunk_box(8 * (size_t)box_base, qnan);   // [chunk][8]: min xyz, -, max xyz, - (two 16-byte loads)
-    std::vector<TreeNode> nodes(node_base);
+    const size_t host_pts = pre ? 0 : (size_t)pt_base, host_boxes = pre ? 0 : (size_t)box_base;   // (device build: no host image of the scan side)
+    std::vector<float> xs(host_pts, qnan), ys(host_pts, qnan), zs(host_pts, qnan);
+    std::vector<uint32_t> perm(host_pts, 0u), inv_perm(host_pts, 0u);
+    std::vector<float4> pts4(host_pts, float4{qnan, qnan, qnan, 0.f});
+    std::vector<float> chunk_box(8 * host_boxes, qnan);   // [chunk][8]: min xyz, -, max xyz, - (two 16-byte loads)
+    std::vector<TreeNode> nodes(pre ? 0u : node_base);
     std::vector<float2> kp_uv(kp_base); std::vector<float4> kp_mp(kp_base), crec(kp_base);
     std::vector<uint32_t>& kp_ext = h->h_kp_ext; kp_ext.resize(kp_base);
     std::vector<uint32_t> coarse_start(coarse_base), bitmap(bm_base);
@@ -1243,15 +1263,15 @@ iba_status iba_create_ex(const iba_problem_desc* d, const iba_params* params, in
     std::atomic<bool> bad_match(false);
     parallel_for(nf, [&](int lf) {
         const int f = frame_begin + lf; const FrameHdr& x = hdr[lf]; const FrameBuild& b = fb[lf];
-        const float* src = d->pts_xyz + 3 * d->pt_offset[f];
-        for (uint32_t i = 0; i < x.P; ++i) {
+        const float* src = pre ? nullptr : d->pts_xyz + 3 * d->pt_offset[f];
+        for (uint32_t i = 0; i < (pre ? 0u : x.P); ++i) {
             const uint32_t o = b.idx[i];
             xs[x.pt_base + i] = src[3 * (size_t)o]; ys[x.pt_base + i] = src[3 * (size_t)o + 1]; zs[x.pt_base + i] = src[3 * (size_t)o + 2];
             perm[x.pt_base + i] = o; inv_perm[x.pt_base + o] = i;
             float ob; std::memcpy(&ob, &o, 4);
             pts4[x.pt_base + i] = float4{src[3 * (size_t)o], src[3 * (size_t)o + 1], src[3 * (size_t)o + 2], ob};
         }
-        for (uint32_t c0 = 0; c0 < x.P; c0 += (uint32_t)kChunk) {   // static AABB of every kChunk consecutive tree positions
+        for (uint32_t c0 = 0; c0 < (pre ? 0u : x.P); c0 += (uint32_t)kChunk) {   // static AABB of every kChunk consecutive tree positions
             float* bx = &chunk_box[8 * (size_t)(x.box_base + c0 / (uint32_t)kChunk)];
             float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
             for (uint32_t i = c0; i < std::min<uint32_t>(c0 + (uint32_t)kChunk, x.P); ++i) {
@@ -1263,7 +1283,7 @@ iba_status iba_create_ex(const iba_problem_desc* d, const iba_params* params, in
             for (int a = 0; a < 3; ++a) rmax = std::max(rmax, std::max(std::fabs(mn[a]), std::fabs(mx[a])));
             bx[7] = (mn[0] <= mx[0]) ? rmax : qnan;
         }
-        std::copy(b.nodes.begin(), b.nodes.end(), nodes.begin() + x.node_base);
+        if (!pre) std::copy(b.nodes.begin(), b.nodes.end(), nodes.begin() + x.node_base);
         const uint64_t k0 = d->kp_offset[f];
         for (uint32_t k = 0; k < x.K; ++k) {   // k = internal (Morton) id, e = reference id
             const uint64_t e = k0 + b.kp_order[k];
@@ -1370,7 +1390,16 @@ iba_status iba_create_ex(const iba_problem_desc* d, const iba_params* params, in
 
     auto bail = [&](const char* what, hipError_t er) { std::string m = std::string(what) + ": " + hipGetErrorString(er); iba_destroy(h); return fail(nullptr, IBA_ERR_HIP, m); };
 #define UP(buf, vec) do { hipError_t _e = h->buf.upload(vec); if (_e != hipSuccess) return bail("upload " #buf, _e); } while (0)
-    {   // the box of every frame's scan out of its chunk boxes (iba_icp_pass_kernel skips a tile that lies out of a lane's reach)
+    if (pre) {   // the scan side on the device: allocated from the counts, filled by the index build
+        hipError_t ea;
+        if ((ea = h->xs.alloc(pt_base)) != hipSuccess || (ea = h->ys.alloc(pt_base)) != hipSuccess || (ea = h->zs.alloc(pt_base)) != hipSuccess || (ea = h->perm.alloc(pt_base)) != hipSuccess ||
+            (ea = h->inv_perm.alloc(pt_base)) != hipSuccess || (ea = h->pts4.alloc(pt_base)) != hipSuccess || (ea = h->nodes.alloc(node_base)) != hipSuccess ||
+            (ea = h->chunk_box.alloc(8 * (size_t)box_base)) != hipSuccess || (ea = h->d_frame_box.alloc(8 * (size_t)std::max(nf, 1))) != hipSuccess) return bail("alloc scan arrays", ea);
+        std::string why;
+        const iba_status bs = index_build_device(h, *pre, why);
+        if (bs != IBA_OK) { iba_destroy(h); return fail(nullptr, bs, why); }
+        UP(frames, hdr); UP(slots, slots);
+    } else {   // the box of every frame's scan out of its chunk boxes (iba_icp_pass_kernel skips a tile that lies out of a lane's reach)
         std::vector<float> frame_box(8 * (size_t)std::max(nf, 1), qnan);
         for (int lf = 0; lf < nf; ++lf) {
             float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -1383,7 +1412,7 @@ iba_status iba_create_ex(const iba_problem_desc* d, const iba_params* params, in
         h->h_frame_box = frame_box;
         UP(d_frame_box, frame_box);
     }
-    UP(frames, hdr); UP(slots, slots); UP(xs, xs); UP(ys, ys); UP(zs, zs); UP(perm, perm); UP(inv_perm, inv_perm); UP(nodes, nodes); UP(chunk_box, chunk_box); UP(pts4, pts4);
+    if (!pre) { UP(frames, hdr); UP(slots, slots); UP(xs, xs); UP(ys, ys); UP(zs, zs); UP(perm, perm); UP(inv_perm, inv_perm); UP(nodes, nodes); UP(chunk_box, chunk_box); UP(pts4, pts4); }
     h->h_kp_uv.resize(2 * (size_t)kp_base);
     for (size_t k = 0; k < (size_t)kp_base; ++k) { h->h_kp_uv[2 * k] = kp_uv[k].x; h->h_kp_uv[2 * k + 1] = kp_uv[k].y; }
     UP(kp_uv, kp_uv); UP(kp_mp, kp_mp); UP(kp_fl, kp_fl); UP(coarse_start, coarse_start); UP(crec, crec); UP(bitmap, bitmap); UP(match_uv, match_uv); UP(mpk, mpk); UP(fkp, fkp);
@@ -1521,6 +1550,9 @@ iba_status iba_create_ex(const iba_problem_desc* d, const iba_params* params, in
     *out = h;
     return IBA_OK;
 }
+}  // namespace
+
+extern "C" {
 
 iba_status iba_set_params(iba_handle* h, const iba_params* p) {
     if (!h || !p) return IBA_ERR_INVALID_ARG;
@@ -2158,3 +2190,4 @@ iba_status reserve_batch(iba_handle* h, int B) {
 #include "iba_scan_host.hpp"  // iba_scan_step / iba_scan_register / iba_scan_information
 #include "iba_voxel_host.hpp" // iba_submap_build and the accessors of its result
 #include "iba_sc_host.hpp"    // iba_sc_describe / iba_sc_distance / iba_sc_detect / iba_sc_replay_plan
+#include "iba_index_host.hpp" // iba_submap_handle (the device index build) / iba_debug_scan_index

@@ -22,8 +22,7 @@ constexpr uint64_t kVoxMaxPoints = 0xFFFFFF00ull;   // member points of one call
 bool vox_finite12(const double* T) { for (int i = 0; i < 12; ++i) if (!std::isfinite(T[i])) return false; return true; }
 int vox_bits(uint64_t v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }   // bits that hold 0 .. v
 
-iba_status vox_check(iba_handle* h, const iba_submap_desc* subs, int32_t M) {
-    const std::string who = "iba_submap_build: ";
+iba_status vox_check(iba_handle* h, const iba_submap_desc* subs, int32_t M, const std::string& who) {
     if (!subs) return fail(h, IBA_ERR_INVALID_ARG, who + "the sub-map descriptors are NULL");
     if (M < 1 || M > kVoxMaxSubs) return fail(h, IBA_ERR_INVALID_ARG, who + "M must be in [1, 4096]");
     int64_t members = 0;
@@ -46,13 +45,10 @@ iba_status vox_check(iba_handle* h, const iba_submap_desc* subs, int32_t M) {
     return IBA_OK;
 }
 
-}  // namespace
-
-iba_status iba_submap_build(iba_handle* h, const iba_submap_desc* subs, int32_t M, iba_submap_clouds** out) {
-    if (!h) return IBA_ERR_INVALID_ARG;
-    if (!out) return fail(h, IBA_ERR_INVALID_ARG, "iba_submap_build: the result pointer is NULL");
-    *out = nullptr;
-    if (const iba_status s = vox_check(h, subs, M)) return s;
+// The launch chain of iba_submap_build. clouds = true: the voxel clouds come up into the result. false (iba_submap_handle, iba_index_host.hpp):
+// they stay on the device (h->vox.d_xyz, in the order of the result's `first`) and only first / dropped are filled. `who` heads the messages.
+iba_status vox_build(iba_handle* h, const iba_submap_desc* subs, int32_t M, const std::string& who, bool clouds, iba_submap_clouds** out) {
+    if (const iba_status s = vox_check(h, subs, M, who)) return s;
 
     // ---- the batch as the kernels take it: members that hold points, sub-map after sub-map ----
     std::vector<VoxMember> mem;
@@ -75,7 +71,7 @@ iba_status iba_submap_build(iba_handle* h, const iba_submap_desc* subs, int32_t 
             x.pos0 = N; x.blk0 = (uint32_t)blocks; x.frame = d.frames[m]; x.sub = s;
             mem.push_back(x);
             N += P; n_in[(size_t)s] += P; blocks += (P + (uint32_t)kVoxThreads - 1u) / (uint32_t)kVoxThreads;
-            if (N > kVoxMaxPoints || blocks > 0x7FFFFFFFull) return fail(h, IBA_ERR_UNSUPPORTED, "iba_submap_build: the members of one call hold more than 2^32 - 256 points (split the batch)");
+            if (N > kVoxMaxPoints || blocks > 0x7FFFFFFFull) return fail(h, IBA_ERR_UNSUPPORTED, who + "the members of one call hold more than 2^32 - 256 points (split the batch)");
         }
         S.blk1 = (uint32_t)blocks;
     }
@@ -115,7 +111,7 @@ iba_status iba_submap_build(iba_handle* h, const iba_submap_desc* subs, int32_t 
             S.minb[a] = b.mn[a] - 0.5 * S.voxel;
             const double top = vox_index(b.mx[a], S.minb[a], S.voxel);   // the kernels' expression on the largest kept q: no index of this axis is above it
             if (!(top >= 0.0 && top < (double)(1u << kVoxAxisBits)))
-                return fail(h, IBA_ERR_UNSUPPORTED, "iba_submap_build: sub-map " + std::to_string(s) + ": the extent along axis " + std::to_string(a) + " is " + (std::isfinite(top) ? std::to_string((long long)top + 1) : std::string("more than 2^63")) +
+                return fail(h, IBA_ERR_UNSUPPORTED, who + "sub-map " + std::to_string(s) + ": the extent along axis " + std::to_string(a) + " is " + (std::isfinite(top) ? std::to_string((long long)top + 1) : std::string("more than 2^63")) +
                                                         " voxels; the key holds " + std::to_string(1u << kVoxAxisBits) + " per axis (choose a larger voxel or split the sub-map)");
             imax[a] = std::max(imax[a], (uint64_t)top);
         }
@@ -151,7 +147,7 @@ iba_status iba_submap_build(iba_handle* h, const iba_submap_desc* subs, int32_t 
     uint32_t V = 0;
     HIP_TRY(h, hipMemcpyAsync(&V, w.d_blockc.p + nhb, sizeof(V), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
-    if (V == 0 || (uint64_t)V > n_kept) return fail(h, IBA_ERR_HIP, "iba_submap_build: the voxel count came back outside (0, kept points]");
+    if (V == 0 || (uint64_t)V > n_kept) return fail(h, IBA_ERR_HIP, who + "the voxel count came back outside (0, kept points]");
     HIP_TRY(h, icp_grow(w.d_seg, (size_t)V));
     HIP_TRY(h, icp_grow(w.d_xyz, 3 * (size_t)V));
     HIP_TRY(h, icp_grow(w.d_cnt, (size_t)V));
@@ -161,10 +157,12 @@ iba_status iba_submap_build(iba_handle* h, const iba_submap_desc* subs, int32_t 
     hipLaunchKernelGGL(iba_vox_average_kernel, dim3((V + (uint32_t)kVoxThreads - 1u) / (uint32_t)kVoxThreads), dim3(kVoxThreads), 0, st, w.d_sub.p, (int)bits.sub_shift, keys, vals, w.d_q3.p, w.d_seg.p, V, n_kept,
                        w.d_xyz.p, w.d_cnt.p);
     HIP_TRY(h, hipGetLastError());
-    res->xyz.resize(3 * (size_t)V); res->count.resize((size_t)V);
     std::vector<uint32_t> first((size_t)M + 1);
-    HIP_TRY(h, hipMemcpyAsync(res->xyz.data(), w.d_xyz.p, sizeof(double) * 3 * (size_t)V, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(res->count.data(), w.d_cnt.p, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost, st));
+    if (clouds) {
+        res->xyz.resize(3 * (size_t)V); res->count.resize((size_t)V);
+        HIP_TRY(h, hipMemcpyAsync(res->xyz.data(), w.d_xyz.p, sizeof(double) * 3 * (size_t)V, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipMemcpyAsync(res->count.data(), w.d_cnt.p, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(h, hipMemcpyAsync(first.data(), w.d_subfirst.p, sizeof(uint32_t) * ((size_t)M + 1), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     res->first[(size_t)M] = (int64_t)V;
@@ -172,6 +170,15 @@ iba_status iba_submap_build(iba_handle* h, const iba_submap_desc* subs, int32_t 
     guard.p = nullptr;
     *out = res;
     return IBA_OK;
+}
+
+}  // namespace
+
+iba_status iba_submap_build(iba_handle* h, const iba_submap_desc* subs, int32_t M, iba_submap_clouds** out) {
+    if (!h) return IBA_ERR_INVALID_ARG;
+    if (!out) return fail(h, IBA_ERR_INVALID_ARG, "iba_submap_build: the result pointer is NULL");
+    *out = nullptr;
+    return vox_build(h, subs, M, "iba_submap_build: ", true, out);
 }
 
 int32_t iba_submap_num(const iba_submap_clouds* c) { return c ? c->M : 0; }
