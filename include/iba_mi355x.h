@@ -836,7 +836,8 @@ iba_status iba_handeye_lineprocess(const double* Ta12, const double* Tb12, int64
  * N unary reprojection edges (calibEdge, Optimizer.cc:65-205): X_c0 = s * Xw; X_l0 = T_cl^-1 X_c0; X_li = T_lw X_l0;
  * X_ci = T_cl X_li; e = obs - project(X_ci). Per edge: information invSigma2 * I, Huber(sqrt(5.991)).
  * The device evaluates every edge (residual, Jacobian by forward-mode duals exactly as g2o's auto-diff does, robust
- * weight) and reduces the normal equations; the host runs g2o's Levenberg-Marquardt and the reference's four
+ * weight; one expression is rearranged: 1 - cos(theta) of the angle-axis block is sin^2 / (1 + cos) where cos > 0, so that the
+ * Jacobian keeps its digits at a small non-zero rotation) and reduces the normal equations; the host runs g2o's Levenberg-Marquardt and the reference's four
  * optimise / classify rounds (Optimizer.cc:1511-1556 = 1698-1743). csrc/iba_ba.hip.
  */
 typedef struct iba_ba_handle iba_ba_handle;
@@ -850,7 +851,8 @@ typedef struct iba_ba_desc {
     const double* edge_obs;     /* [N*2] kpUn.pt */
     const double* edge_info;    /* [N] invSigma2 = mvInvLevelSigma2[octave] */
     const int32_t* edge_slot;   /* [N] vnIndexEdgeMono: MapPoint slot inside its keyframe — the reference indexes its
-                                   outlier flags with it, so flags alias across keyframes (reproduced) */
+                                   outlier flags with it, so flags alias across keyframes (reproduced). NULL = the edge's own
+                                   index; every slot must be >= 0 (iba_ba_create answers IBA_ERR_INVALID_ARG otherwise) */
 } iba_ba_desc;
 typedef struct iba_ba_result {
     double x[7];

@@ -30,7 +30,8 @@ inline Vec3<T> rotate(const Vec3<T>& w, const Vec3<T>& p) {
         const T cth = cos(theta), sth = sin(theta);
         const Vec3<T> vxp = cross(v, p);
         const T vdp = dot(v, p);
-        const T omc = T(1.0) - cth;
+        // 1 - cos(theta) as sin^2 / (1 + cos) where cos > 0 (the same number; the literal difference loses the Jacobian at eps / theta)
+        const T omc = oracle::scalar_of(cth) > 0.0 ? sth * sth / (T(1.0) + cth) : T(1.0) - cth;
         return {{p.v[0] * cth + vxp.v[0] * sth + v.v[0] * vdp * omc, p.v[1] * cth + vxp.v[1] * sth + v.v[1] * vdp * omc, p.v[2] * cth + vxp.v[2] * sth + v.v[2] * vdp * omc}};
     }
     const Vec3<T> wxp = cross(w, p);

@@ -51,7 +51,10 @@ __device__ __forceinline__ DV3 drotate(const DV3& w, const DV3& p) {
         const DJ cth = dj_cos(theta), sth = dj_sin(theta);
         const DV3 vxp = dcross(v, p);
         const DJ vdp = ddot(v, p);
-        const DJ omc = dj(1.0) - cth;
+        // 1 - cos(theta) as sin^2 / (1 + cos) where cos > 0: the literal difference of the reference is good to one epsilon of 1
+        // only, and dv ~ 1 / theta multiplies it, which costs the Jacobian eps / theta at a small non-zero theta
+        DJ omc; omc.a = cth.a > 0.0 ? sth.a * sth.a / (1.0 + cth.a) : 1.0 - cth.a;
+        for (int i = 0; i < 7; ++i) omc.v[i] = sth.a * theta.v[i];
         return DV3{p.x * cth + vxp.x * sth + v.x * vdp * omc, p.y * cth + vxp.y * sth + v.y * vdp * omc, p.z * cth + vxp.z * sth + v.z * vdp * omc};
     }
     const DV3 wxp = dcross(w, p);
@@ -191,11 +194,11 @@ void iba_ba_destroy(iba_ba_handle* h) {
 }
 
 iba_status iba_ba_create(const iba_ba_desc* d, int device, iba_ba_handle** out) {
+    if (out) *out = nullptr;
     if (!d || !out || d->n_edges < 0 || d->n_frames < 1 || !d->frame_Tlw6 || !d->frame_intr || (d->n_edges && (!d->edge_frame || !d->edge_Xw || !d->edge_obs || !d->edge_info)))
         return IBA_ERR_INVALID_ARG;
-    *out = nullptr;
     for (int64_t i = 0; i < d->n_edges; ++i)
-        if (d->edge_frame[i] < 0 || d->edge_frame[i] >= d->n_frames) return IBA_ERR_INVALID_ARG;
+        if (d->edge_frame[i] < 0 || d->edge_frame[i] >= d->n_frames || (d->edge_slot && d->edge_slot[i] < 0)) return IBA_ERR_INVALID_ARG;   // the slot indexes the outlier flags
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device || device < 0) return IBA_ERR_NO_DEVICE;   // no CPU fallback
     if (hipSetDevice(device) != hipSuccess) return IBA_ERR_NO_DEVICE;

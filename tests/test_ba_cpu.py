@@ -60,3 +60,109 @@ def test_oracle_schedule_recovers_planted_extrinsic():
     assert np.linalg.norm(x[3:6] - x_gt[3:6]) < 0.05 and abs(x[6] - x_gt[6]) < 0.05
     assert 0.85 * len(prob.edge_frame) < n_in < len(prob.edge_frame)      # the planted 5 % gross outliers are rejected
     assert log[-1][0] < chi0
+
+
+# ---- tests/ba_ref.py (long double) pinned against mpmath, the double oracle pinned against tests/ba_ref.py ----
+import ba_ref  # noqa: E402
+
+
+def _mp_edge(mp, x, Xw, T6, intr, obs):
+    """closed matrix form at mpmath precision: exact Rodrigues, its limit I + [w]x at 0; nothing here is a dual"""
+    def R(w):
+        th = mp.sqrt(w[0] ** 2 + w[1] ** 2 + w[2] ** 2)
+        K = mp.matrix([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+        if th == 0:
+            return mp.eye(3) + K
+        return mp.eye(3) + (mp.sin(th) / th) * K + (2 * mp.sin(th / 2) ** 2 / th ** 2) * K * K
+    Rcl, t = R(x[:3]), mp.matrix(x[3:6])
+    Xli = R(T6[:3]) * (Rcl.T * (x[6] * mp.matrix(Xw) - t)) + mp.matrix(T6[3:])
+    Xci = Rcl * Xli + t
+    return [obs[0] - (intr[0] * Xci[0] / Xci[2] + intr[2]), obs[1] - (intr[1] * Xci[1] / Xci[2] + intr[3])]
+
+
+def _to_mp(mp, v):
+    hi = float(v)
+    return mp.mpf(hi) + mp.mpf(float(v - ba_ref.LD(hi)))
+
+
+def test_ba_ref_matches_mpmath():
+    """Value against the closed form and Jacobian against mpmath.diff at 40 digits. Bound: 1e-16 of the largest term, about
+    1000 long-double epsilons for the few hundred operations of an edge, six orders below the 1e-10 gates ba_ref stands behind."""
+    import mpmath as mp
+    mp.mp.dps = 40
+    pg, xg = ba_ref.scene_g(ba)
+    pi_, xi = ba_ref.scene_i(ba)
+    th = np.linalg.norm(ba_ref.OMEGA_G)
+    picks = [(pi_, np.zeros(3), 57 + 3),                                   # omega = 0, pose with rotation exactly 0
+             (pi_, np.zeros(3), 4 * 57 + 9),                               # omega = 0, pose of norm 3.1
+             (pi_, np.array([1e-160, 0, 0]), 2 * 57 + 5),                  # omega and pose of 1e-160-sized components
+             (pi_, np.array([1e-160, 0, 0]), 7 * 57 + 1),
+             (pg, ba_ref.OMEGA_G, 5 * 57 + 2),
+             (pg, ba_ref.OMEGA_G * ((th + 2 * np.pi) / th), 4 * 57 + 30),  # |omega| > pi
+             (pg, ba_ref.OMEGA_G * ((th + 16 * np.pi) / th), 8 * 57 + 11),
+             (pg, 4.0 * ba_ref.OMEGA_G / th, 3 * 57 + 40)]
+    worst_e = worst_J = 0.0
+    for prob, w, e in picks:
+        x = np.concatenate([w, (xi if prob is pi_ else xg)[3:] + [0.02, -0.03, 0.05, 0.1]])
+        one = ba_ref.subset(prob, [e], ba)
+        d, _ = ba_ref.edges(one, x)
+        f = int(one.edge_frame[0])
+        a = [[mp.mpf(float(v)) for v in arr] for arr in (one.edge_Xw[0], one.frame_Tlw6[f], one.frame_intr[f], one.edge_obs[0])]
+        xm = [mp.mpf(float(v)) for v in x]
+        em = _mp_edge(mp, xm, *a)
+        scale_e = max(abs(float(v)) for v in a[3]) + abs(float(em[0])) + abs(float(em[1]))
+        Jm = [[mp.diff(lambda *q, r=r: _mp_edge(mp, list(q), *a)[r], xm, tuple(int(j == k) for j in range(7))) for k in range(7)] for r in range(2)]
+        scale_J = max(abs(float(v)) for row in Jm for v in row)
+        for r in range(2):
+            worst_e = max(worst_e, float(abs(_to_mp(mp, d[0, r, 0]) - em[r])) / scale_e)
+            for k in range(7):
+                worst_J = max(worst_J, float(abs(_to_mp(mp, d[0, r, 1 + k]) - Jm[r][k])) / scale_J)
+    print("ba_ref vs mpmath (40 digits): residual %.2e, Jacobian %.2e of the largest term" % (worst_e, worst_J))
+    assert worst_e <= 1e-16 and worst_J <= 1e-16
+
+
+_lin_cache = {}
+
+
+def _lin(case):
+    if id(case) not in _lin_cache:
+        _lin_cache[id(case)] = ba_ref.linearise(case.prob, case.x, case.active, case.robust)
+    return _lin_cache[id(case)]
+
+
+_cases = None
+
+
+def _all_cases():
+    global _cases
+    if _cases is None:
+        _cases = ba_ref.cpu_cases(ba)
+    return _cases
+
+
+def test_edge_case_inputs_are_what_they_claim():
+    """From the long-double reference alone: every active edge of every shared input lies in front of its camera, and a case
+    that claims edges on both sides of the Huber knee has them."""
+    for c in _all_cases():
+        L = _lin(c)
+        sel = np.ones(len(L.z), bool) if c.active is None else c.active != 0
+        assert np.all(L.z[sel] > ba_ref.Z_FLOOR), (c.family, c.name)
+        if c.both_sides:
+            over = L.chi2_edges[sel] > ba_ref.DSQR
+            assert over.any() and (~over).any(), (c.family, c.name)
+    poisoned, _, x, active, bad = ba_ref.poison_problems(ba)
+    L = ba_ref.linearise(poisoned, x, active)
+    assert L.z[bad[0]] == 0 and not active[list(bad)].any()
+    assert np.array_equal(np.flatnonzero(~np.isfinite(L.chi2_edges.astype(np.float64))), np.array(bad))
+
+
+def test_oracle_matches_long_double_on_edge_case_inputs():
+    for c in _all_cases():
+        ba_ref.check(c.family, "oracle", oba.evaluate(c.prob, c.x, c.active, c.robust), _lin(c))
+    for fam in ("lane", "ragged", "rotation", "stride", "poison", "small"):
+        ba_ref.report(fam)
+
+
+def test_oracle_at_the_huber_knee():
+    ba_ref.knee_check("oracle", lambda prob: (lambda x, a, r: oba.evaluate(prob, x, a, r)), ba)
+    ba_ref.report("knee")
