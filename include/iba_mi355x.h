@@ -240,7 +240,8 @@ iba_status iba_icp_calib(iba_handle* h, int32_t frame_begin, int32_t frame_end, 
  * together: per ICP iteration one launch chain and one synchronise for all edges still running, and nothing of scan size crosses PCIe —
  * source and target scans, the target's kd tree and its memoised normals are already resident. A scans-only handle is enough.
  * Voxel down-sampling and the merged sub-map target of a loop closure are iba_submap_build, and choosing WHICH keyframe pairs to close a loop between
- * (Scan Context) is iba_sc_describe / iba_sc_detect (both below); the pose-graph optimiser and PCD IO stay the caller's.
+ * (Scan Context) is iba_sc_describe / iba_sc_detect (both below); the pose-graph optimisation over the resulting edges is iba_pgo_* (below:
+ * Open3D's GlobalOptimization; iSAM2 stays the caller's), and PCD IO stays the caller's.
  *
  * Restated from Open3D's public sources (not part of the reference tree: parity with it is UNPINNED; the kd search stays pinned to nanoflann):
  *   RegistrationICP, GetRegistrationResultAndCorrespondences, SearchHybrid's strict gate    the loop of iba_icp_register (one implementation)
@@ -340,7 +341,7 @@ iba_status iba_scan_information(iba_handle* h, const iba_scan_edge* edges, int32
  * more than 2^22 members or more than 2^32 - 256 member points in one call. A sub-map whose members hold no kept point answers zero voxels.
  * Limits: iba_submap_build brings the clouds back to the host; iba_submap_handle (below) keeps them on the device instead and makes them the
  * frames of a new handle — registration targets, Scan Context nodes, members of further sub-maps — whose normals are that handle's plane memo.
- * Clouds cannot be attached to an EXISTING handle. Loop detection is iba_sc_* (below), the pose graph and PCD IO are not here; one GPU — the
+ * Clouds cannot be attached to an EXISTING handle. Loop detection is iba_sc_* and the pose graph iba_pgo_* (both below), PCD IO is not here; one GPU — the
  * members of a sub-map are local frames of one handle.
  */
 typedef struct iba_submap_desc {
@@ -485,6 +486,106 @@ iba_status iba_sc_detect(iba_sc_db* db, const iba_sc_query* queries, int32_t Q, 
  * counter: db_end[i] = 0. Otherwise, when counter % tree_period == 0 the search set becomes the first size - num_exclude_recent keys, then the counter
  * advances; between rebuilds the set is stale. db_end[i] = the size of the set call i searches. */
 iba_status iba_sc_replay_plan(const int32_t* sizes_at_call, int32_t n, const iba_sc_options* opt, int32_t* db_end /* n */);
+
+/*
+ * ---- Pose-graph optimisation: Levenberg-Marquardt with line process [backend_opt.cpp:433-528 MultiRegistration: nodes pose[i]^-1 :441, odometry
+ * edges (i-1, i) :454 / :472, loop edges (uncertain) :507, GlobalOptimization(PoseGraph, GlobalOptimizationLevenbergMarquardt(), criteria,
+ * GlobalOptimizationOption(MRmaxCorrDist, MREdgePruneThre, 1.0, 0)) :515-525] ----
+ * The last step of the reference's LiDAR back end: the edges and 6x6 informations that leave iba_scan_register become a pose graph, LM runs on it,
+ * uncertain edges whose line-process weight stayed below edge_prune_threshold are dropped, and LM runs again on what is left. Open3D solves every LM
+ * trial with a dense 6N x 6N ldlt(); here the graph is what it is in that back end — a chain with a few cross edges — and a trial is a block
+ * arrowhead elimination on the device (below). An iba_pgo is a stand-alone object on one device (no iba_handle needed); everything of size N or E stays
+ * on the device between LM trials, the host reads a handful of scalars per trial.
+ *
+ * Restated from Open3D's public GlobalOptimization sources AS REMEMBERED (Open3D is not part of the reference tree: parity with it is UNPINNED).
+ * WHERE THIS RESTATEMENT AND OPEN3D DIFFER, THIS TEXT IS THE CONTRACT: tests/pgo_ref.py restates it in numpy and the tests hold the device to that.
+ * Transforms are row-major 4x4 with the last row 0 0 0 1; a rigid inverse is always formed as [R^T, -R^T t]; all arithmetic is IEEE f64.
+ *   1 vec6           v = [a, b, c, tx, ty, tz] of a transform M: sy = sqrt(M00^2 + M10^2); sy >= 1e-6: a = atan2(M21, M22), b = atan2(-M20, sy),
+ *                    c = atan2(M10, M00); otherwise a = atan2(-M12, M11), b = atan2(-M20, sy), c = 0. Its inverse T(v) = Rz(c) Ry(b) Rx(a) with the
+ *                    translation (the map of the point-to-plane update of iba_scan_*).
+ *   2 misalignment   of edge (s, t, X, L): M = X^-1 pose_t^-1 pose_s, zeta = vec6(M).
+ *   3 Jacobian       column k of Js = lin6(X^-1 pose_t^-1 G_k pose_s), lin6(M) = [(M21 - M12) / 2, (M02 - M20) / 2, (M10 - M01) / 2, M03, M13, M23]; G_0..2 the
+ *                    so(3) generators about x, y, z (as 4x4), G_3..5 the unit translations. Jt = -Js exactly, so an edge has ONE block A = w Js^T L Js
+ *                    and one vector g = w Js^T L zeta: H_ss += A, H_tt += A, H_st = H_ts -= A, b_s -= g, b_t += g. Only the upper triangle of L
+ *                    (info) is read; it is mirrored.
+ *   4 line process   mu = preference_loop_closure * max_corr_dist^2 * (mean of L(5,5) over the uncertain edges of the graph being solved, in edge order),
+ *                    0 without one. An uncertain edge: w = (mu / (mu + zeta^T L zeta))^2 (mu + zeta^T L zeta == 0: w = 1); a certain edge: w = 1. Weights start
+ *                    at 1 and are recomputed after every ACCEPTED step, at the accepted poses, before the system is rebuilt.
+ *   5 residual       r = sum over the edges of w zeta^T L zeta with the weights in force (a trial's r_new: the trial poses, the weights of the last
+ *                    linearisation; after an accepted step r is the residual of the relinearisation, i.e. with the NEW weights).
+ *   6 LM             linearise; lambda = 1e-5 * (largest diagonal entry of H), nu = 2. An OUTER ITERATION: (a) max |b| < min_right_term stops
+ *                    IBA_PGO_STOP_RIGHT_TERM; (e) after max_iteration outer iterations IBA_PGO_STOP_MAX_ITERATION; then up to max_iteration_lm TRIALS:
+ *                    delta = (H + lambda I)^-1 b; (b) |delta| < min_relative_increment * (|x| + min_relative_increment), x the stacked vec6 of the
+ *                    poses, stops IBA_PGO_STOP_INCREMENT (the trial counts, nothing is applied); trial pose_i = T(delta_i) pose_i; rho = (r - r_new) /
+ *                    (delta . (lambda delta + b) + 1e-3). rho > 0: lambda *= max(lower_scale_factor, min(1 - (2 rho - 1)^3, upper_scale_factor)), nu = 2,
+ *                    the step is accepted (weights, relinearisation), (c) r_before - r_new < min_relative_residual_increment * r_before stops
+ *                    IBA_PGO_STOP_RESIDUAL_INCREMENT, and the outer iteration ends. Otherwise lambda *= nu, nu *= 2, next trial. An outer iteration
+ *                    whose trials are all rejected ends as it is. After an outer iteration (d) r < min_residual stops IBA_PGO_STOP_RESIDUAL.
+ *                    Checks in the order a, e, b, c, d as the loop meets them. The system is NOT gauge-fixed: lambda I makes it definite (lambda = 0 or a
+ *                    pivot that is not positive and finite: IBA_ERR_UNSUPPORTED). After a pass, with reference_node >= 0, every pose is left-multiplied by
+ *                    pose_ref(before the pass) * pose_ref(after)^-1.
+ *   7 pruning        after pass 1 an uncertain edge with w < edge_prune_threshold is dropped; pass 2 runs on what is left from pass 1's poses, weights
+ *                    reset to 1, mu recomputed, lambda and nu started anew.
+ * The linear solve (iba_pgo_solve, every trial): a CHAIN EDGE is the first edge, in edge order, between nodes i and i + 1 in either direction; every
+ * other edge is a CROSS EDGE. The separator set S = the endpoints of all cross edges and every node i with i % K == 0; K = segment, doubled until
+ * |S| <= IBA_PGO_MAX_SEPARATORS (cross-edge endpoints alone beyond the cap: IBA_ERR_INVALID_ARG naming the count). The maximal runs of
+ * non-separator nodes are block tridiagonal and independent: forward block LDL^T of D + lambda I along each run, its Schur complement added to the
+ * run's two bounding separators, in run order; the 6|S| x 6|S| separator system by a blocked right-looking Cholesky and two triangular solves; back
+ * substitution along the runs. No floating-point atomics, every sum in a fixed order: two calls give the same bytes. iba_pgo_plan (host only) answers
+ * the separators and runs for a graph. Memory: O((N + E) 36 + |S|^2 36) doubles.
+ * Answers IBA_ERR_INVALID_ARG with a message, BEFORE the device is probed: a NULL argument, struct_size, N < 1, E < 0, a source / target outside [0, N)
+ * or source == target, a number that is not finite (poses, T, the upper triangle of info, the options), a pose or T whose last row is not exactly
+ * 0 0 0 1, reference_node outside [-1, N), segment < 1, max_iteration / max_iteration_lm < 0. iba_pgo_last_error(pg) carries the message of a call
+ * on pg; iba_pgo_last_error(NULL) of the calls without one (create, plan), on this thread.
+ * Limits: one GPU; iSAM2 and the incremental path (UpdateISAM) are not here; a graph whose cross edges touch more than IBA_PGO_MAX_SEPARATORS nodes.
+ */
+#define IBA_PGO_MAX_SEPARATORS 1024
+#define IBA_PGO_STOP_NONE 0               /* the pass did not run */
+#define IBA_PGO_STOP_RIGHT_TERM 1
+#define IBA_PGO_STOP_INCREMENT 2
+#define IBA_PGO_STOP_RESIDUAL_INCREMENT 3
+#define IBA_PGO_STOP_RESIDUAL 4
+#define IBA_PGO_STOP_MAX_ITERATION 5
+typedef struct iba_pgo_edge { int32_t source, target; double T[16]; double info[36]; int32_t uncertain; } iba_pgo_edge; /* PoseGraphEdge: T row-major 4x4, info row-major 6x6 [rotation, translation] as iba_scan_result.info */
+typedef struct iba_pgo_options {
+    int32_t struct_size;               /* sizeof(iba_pgo_options) */
+    int32_t reference_node;            /* 0; -1: no compensation */
+    double  max_corr_dist;             /* backend.yml MRmaxCorrDist 1.2 */
+    double  edge_prune_threshold;      /* MREdgePruneThre 0.25 */
+    double  preference_loop_closure;   /* 1.0 */
+    int32_t max_iteration;             /* MRmaxIter 100 */
+    int32_t max_iteration_lm;          /* 20 */
+    double  min_relative_increment, min_relative_residual_increment, min_right_term, min_residual;   /* 1e-6 each */
+    double  upper_scale_factor, lower_scale_factor;   /* 2/3, 1/3 */
+    int32_t segment;                   /* separator spacing K; 128, the fastest of 8 .. 128 in profiles/pgo_bench.md */
+    int32_t reserved;                  /* 0 */
+} iba_pgo_options;
+typedef struct iba_pgo_pass { int32_t iterations, trials, stop, reserved; double residual, lambda; } iba_pgo_pass;   /* outer iterations, LM trials, IBA_PGO_STOP_*, final r and lambda */
+typedef struct iba_pgo_result {
+    int32_t struct_size;               /* written by the library: sizeof(iba_pgo_result) */
+    int32_t n_pruned;                  /* uncertain edges dropped after pass 1 */
+    iba_pgo_pass pass[2];
+} iba_pgo_result;
+typedef struct iba_pgo iba_pgo;
+iba_status iba_default_pgo_options(iba_pgo_options* opt);
+/* nodes16: N row-major 4x4 poses (the reference passes pose[i]^-1). The graph is copied; *out is NULL on failure. */
+iba_status iba_pgo_create(const double* nodes16, int32_t N, const iba_pgo_edge* edges, int32_t E, const iba_pgo_options* opt, int device, iba_pgo** out);
+void iba_pgo_destroy(iba_pgo* pg);
+const char* iba_pgo_last_error(const iba_pgo* pg);   /* never NULL */
+/* Host only, no device: the separators (ascending; up to sep_cap written, *n_separators their number), the runs as (first, last) node pairs in
+ * ascending order (up to run_cap pairs written, *n_runs their number) and the K actually used. Every output may be NULL. Pose values are not needed:
+ * of an edge only source and target are read. */
+iba_status iba_pgo_plan(int32_t N, const iba_pgo_edge* edges, int32_t E, const iba_pgo_options* opt, int32_t* separators, int32_t sep_cap, int32_t* n_separators,
+                        int32_t* runs /* 2 per run */, int32_t run_cap, int32_t* n_runs, int32_t* K_used);
+/* Linearises at the current poses with the weights in force (rules 2, 3, 5; a dropped edge has A = 0 and adds nothing). Every output may be NULL:
+ * zeta E x 6, weight E, A E x 36 (row-major, w Js^T L Js), b N x 6, *residual. */
+iba_status iba_pgo_linearize(iba_pgo* pg, double* zeta, double* weight, double* A, double* b, double* residual);
+/* (H + lambda I) delta = b at the last linearisation (IBA_ERR_STATE without one); delta N x 6 */
+iba_status iba_pgo_solve(iba_pgo* pg, double lambda, double* delta);
+/* The whole GlobalOptimization: rules 6 and 7 */
+iba_status iba_pgo_optimize(iba_pgo* pg, iba_pgo_result* result);
+/* The state: poses N x 16, weights E, dropped flags E bytes. Every output may be NULL. */
+iba_status iba_pgo_read(iba_pgo* pg, double* nodes16, double* weight, uint8_t* pruned);
 
 /* The ABI version the LIBRARY was built with (IBA_ABI_VERSION of its header). iba_params carries no struct_size: a caller compiled against
  * an older header would pass a shorter struct. Callers compare iba_abi_version() with their own IBA_ABI_VERSION before iba_create(). */

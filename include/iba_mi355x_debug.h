@@ -39,6 +39,8 @@
  *   IBA_LAYOUT_DEBUG, IBA_DEBUG_LEFT_HIST                 print the LDS plan / a histogram of left-over searches to stderr
  *   IBA_GROUP_TIMEOUT_MS                                  bound (ms, default 20 000; x4 for a group's first call) of a device thread's
  *                                                         wait for its stream before the group is declared broken
+ *   IBA_PGO_MAX_SEP                                       the separator cap of iba_pgo_create / iba_pgo_plan in place of IBA_PGO_MAX_SEPARATORS (1 .. 1024; tests reach
+ *                                                         the doubling of K at a small graph)
  *   IBA_GROUP_REDUCE_HOST (flag of iba_group_create_ex, not a variable), IBA_DEBUG_FAIL_RANK / IBA_DEBUG_FAIL_PHASE: inject one
  *                                                         failure into a group's evaluation (tests of the fail-not-hang path)
  */
@@ -175,6 +177,10 @@ iba_status iba_debug_call_latency(iba_handle* h, const double* x, int32_t B, int
  * the plain division does; *n_fast = triples that took the shared-reciprocal path (the others fall back to the plain division inside). The
  * two must agree bit for bit on every operand (tests/test_gpu_division.py; iba_global.cpp:70-75, :308-313 are the divisions they stand for). */
 iba_status iba_debug_div2_selftest(int32_t device, const double* num0, const double* num1, const double* den, int64_t n, double* q0, double* q1, double* ref0, double* ref1, int64_t* n_fast);
+
+/* debug: the LM trials of the last iba_pgo_optimize in order, one byte each: 1 accepted, 0 rejected, 2 the trial that stopped on the increment; bit 7
+ * set on the trials of pass 2. Up to cap bytes are written; *n = the number of trials. */
+iba_status iba_debug_pgo_trace(iba_pgo* pg, uint8_t* trials, int32_t cap, int32_t* n);
 
 #ifdef __cplusplus
 }

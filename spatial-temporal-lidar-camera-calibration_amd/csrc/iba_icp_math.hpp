@@ -10,10 +10,17 @@
 #include "../../include/iba_mi355x.h"
 #include "iba_svd3.hpp"
 
+// the pieces the pose-graph kernels (iba_pgo_kernels.hpp) share with the host run on the device as well
+#if defined(__HIPCC__)
+#define IBA_ICP_HD __host__ __device__
+#else
+#define IBA_ICP_HD
+#endif
+
 namespace iba { namespace icp {
 
 // C = A * B, row-major 4x4, each entry ((a0 b0 + a1 b1) + a2 b2) + a3 b3
-inline void mat4_mul(const double* A, const double* B, double* C) {
+IBA_ICP_HD inline void mat4_mul(const double* A, const double* B, double* C) {
     for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c)
         C[r * 4 + c] = ((A[r * 4] * B[c] + A[r * 4 + 1] * B[4 + c]) + A[r * 4 + 2] * B[8 + c]) + A[r * 4 + 3] * B[12 + c];
 }
@@ -56,12 +63,12 @@ inline bool umeyama_from_moments(const double* m, bool with_scaling, double* U4)
 // ---- scan-to-scan edges (iba_scan_*): the point-to-plane step and the information matrix, from the sums of one pass ----
 // A x = b for a symmetric 6x6 A (row-major, both triangles filled) by LDL^T without pivoting (what Eigen's ldlt() does on a positive definite
 // matrix up to its pivoting). false: a pivot that is not positive and finite, or a non-finite solution: the system is singular to working precision.
-inline bool ldlt6_solve(const double* A, const double* b, double* x) {
-    double L[36] = {0.0}, d[6];
+// The factor alone: L (unit lower, row-major 36, entries on and above the diagonal untouched) and d. false at a pivot that is not positive and finite.
+IBA_ICP_HD inline bool ldlt6_factor(const double* A, double* L, double* d) {
     for (int j = 0; j < 6; ++j) {
         double s = A[j * 6 + j];
         for (int k = 0; k < j; ++k) s -= L[j * 6 + k] * L[j * 6 + k] * d[k];
-        if (!(s > 0.0) || !std::isfinite(s)) return false;
+        if (!(s > 0.0) || !(s <= 1.7976931348623157e308)) return false;
         d[j] = s;
         for (int i = j + 1; i < 6; ++i) {
             double v = A[i * 6 + j];
@@ -69,9 +76,18 @@ inline bool ldlt6_solve(const double* A, const double* b, double* x) {
             L[i * 6 + j] = v / s;
         }
     }
+    return true;
+}
+// x = (L D L^T)^-1 b
+IBA_ICP_HD inline void ldlt6_apply(const double* L, const double* d, const double* b, double* x) {
     double y[6];
     for (int i = 0; i < 6; ++i) { double v = b[i]; for (int k = 0; k < i; ++k) v -= L[i * 6 + k] * y[k]; y[i] = v; }
     for (int i = 5; i >= 0; --i) { double v = y[i] / d[i]; for (int k = i + 1; k < 6; ++k) v -= L[k * 6 + i] * x[k]; x[i] = v; }
+}
+inline bool ldlt6_solve(const double* A, const double* b, double* x) {
+    double L[36] = {0.0}, d[6];
+    if (!ldlt6_factor(A, L, d)) return false;
+    ldlt6_apply(L, d, b, x);
     for (int i = 0; i < 6; ++i) if (!std::isfinite(x[i])) return false;
     // a matrix of rank < 6 passes the pivot test on rounding noise alone: its smallest pivot is then negligible beside the largest of its kind
     // (rotation block 0-2, translation block 3-5 have different units, so each block is compared with itself)
@@ -83,8 +99,8 @@ inline bool ldlt6_solve(const double* A, const double* b, double* x) {
     return true;
 }
 // Open3D TransformVector6dToMatrix4d: rotation Rz(x2) Ry(x1) Rx(x0), translation x[3..5] -> row-major 4x4
-inline void vec6_to_mat4(const double* x, double* U4) {
-    const double ca = std::cos(x[0]), sa = std::sin(x[0]), cb = std::cos(x[1]), sb = std::sin(x[1]), cg = std::cos(x[2]), sg = std::sin(x[2]);
+IBA_ICP_HD inline void vec6_to_mat4(const double* x, double* U4) {
+    const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
     U4[0] = cg * cb; U4[1] = cg * sb * sa - sg * ca; U4[2] = cg * sb * ca + sg * sa; U4[3] = x[3];
     U4[4] = sg * cb; U4[5] = sg * sb * sa + cg * ca; U4[6] = sg * sb * ca - cg * sa; U4[7] = x[4];
     U4[8] = -sb;     U4[9] = cb * sa;                U4[10] = cb * ca;               U4[11] = x[5];

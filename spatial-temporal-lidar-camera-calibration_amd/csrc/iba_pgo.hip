@@ -1,0 +1,386 @@
+// Pose-graph optimisation on the device (include/iba_mi355x.h, iba_pgo_*): Open3D's GlobalOptimization — LM, pruning of uncertain edges by
+// line-process weight, LM again — on a graph that stays on the device. Kernels: iba_pgo_kernels.hpp; plan and checks: iba_pgo_host.hpp.
+// The LM loop below reads kScal doubles per trial and nothing else.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/iba_mi355x.h"
+#include "../../include/iba_mi355x_debug.h"
+#include "iba_internal.hpp"
+#include "iba_pgo_host.hpp"
+#include "iba_pgo_kernels.hpp"
+
+namespace {
+
+using namespace iba::pgo;
+
+template <class T>
+struct DBuf {
+    T* p = nullptr;
+    hipError_t alloc(size_t count) { release(); return hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T)); }
+    hipError_t upload(const std::vector<T>& v) {
+        hipError_t e = alloc(v.size());
+        if (e != hipSuccess || v.empty()) return e;
+        return hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; }
+};
+
+thread_local std::string t_err;
+
+int sep_cap() {
+    int cap = IBA_PGO_MAX_SEPARATORS;
+    if (const char* e = iba::debug_env("IBA_PGO_MAX_SEP")) { const int v = std::atoi(e); if (v >= 1 && v <= IBA_PGO_MAX_SEPARATORS) cap = v; }
+    return cap;
+}
+
+}  // namespace
+
+struct iba_pgo {
+    int device = 0;
+    int32_t N = 0, E = 0;
+    iba_pgo_options opt{};
+    std::vector<int32_t> src, tgt;
+    std::vector<uint8_t> flags;
+    std::vector<double> info55;
+    Plan plan;
+    double mu = 0.0;
+    int cur = 0;                 // poses[cur] are the poses, poses[1 - cur] the trial
+    bool linearized = false;
+    int nbE = 0, nbN = 0;
+    DBuf<double> poses[2], Xinv, info, weight, zeta, A, g, epart, D, b, npart, G, F, y, delta, upart, run_S, run_b, S, rhs, xs, scal;
+    DBuf<int32_t> d_src, d_tgt, inc_off, inc_edge, chain, run_first, run_last, sep_node, sep_of_node, brow, bcol, boff, kind, idx;
+    DBuf<uint8_t> d_flags;
+    std::vector<uint8_t> trace;
+    std::string err;
+    hipStream_t stream = nullptr;
+};
+
+namespace {
+
+iba_status fail(iba_pgo* pg, iba_status s, const std::string& m) { if (pg) pg->err = m; else t_err = m; return s; }
+
+EdgeDev edge_dev(const iba_pgo* pg) { return EdgeDev{pg->E, pg->d_src.p, pg->d_tgt.p, pg->Xinv.p, pg->info.p, pg->d_flags.p}; }
+RunDev run_dev(const iba_pgo* pg) { return RunDev{(int)pg->plan.run_first.size(), pg->run_first.p, pg->run_last.p, pg->chain.p, pg->N}; }
+
+// the plan of the active edges onto the device (create and prune time)
+iba_status upload_plan(iba_pgo* pg) {
+    std::vector<uint8_t> active(pg->E);
+    for (int32_t e = 0; e < pg->E; ++e) active[e] = (pg->flags[e] & 2) ? 0 : 1;
+    std::string why;
+    if (!make_plan(pg->N, pg->src.data(), pg->tgt.data(), active.data(), pg->E, pg->opt.segment, sep_cap(), pg->plan, why)) return fail(pg, IBA_ERR_INVALID_ARG, "iba_pgo: " + why);
+    pg->mu = line_process_mu(pg->opt, pg->info55.data(), pg->flags.data(), pg->E);
+    const Plan& p = pg->plan;
+    const size_t n = 6 * p.sep.size(), R = p.run_first.size();
+    hipError_t e = hipSuccess;
+    auto up = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    up(pg->d_flags.upload(pg->flags));
+    up(pg->inc_off.upload(p.inc_off)); up(pg->inc_edge.upload(p.inc_edge)); up(pg->chain.upload(p.chain));
+    up(pg->run_first.upload(p.run_first)); up(pg->run_last.upload(p.run_last));
+    up(pg->sep_node.upload(p.sep)); up(pg->sep_of_node.upload(p.sep_of_node));
+    up(pg->brow.upload(p.brow)); up(pg->bcol.upload(p.bcol)); up(pg->boff.upload(p.boff)); up(pg->kind.upload(p.kind)); up(pg->idx.upload(p.idx));
+    up(pg->run_S.alloc(108 * R)); up(pg->run_b.alloc(12 * R));
+    up(pg->S.alloc(n * n)); up(pg->rhs.alloc(n)); up(pg->xs.alloc(n));
+    if (e != hipSuccess) return fail(pg, IBA_ERR_HIP, std::string("iba_pgo: plan upload: ") + hipGetErrorString(e));
+    pg->linearized = false;
+    return IBA_OK;
+}
+
+// linearise at poses[cur]; scal[0..3] on the host afterwards
+iba_status linearize(iba_pgo* pg, bool recompute_w, double* scal_host) {
+    hipStream_t st = pg->stream;
+    if (pg->E > 0)
+        hipLaunchKernelGGL(pgo_edge_kernel<true>, dim3(pg->nbE), dim3(kThreads), 0, st, edge_dev(pg), (const double*)pg->poses[pg->cur].p, pg->mu, recompute_w ? 1 : 0, pg->weight.p,
+                           pg->zeta.p, pg->A.p, pg->g.p, pg->epart.p);
+    hipLaunchKernelGGL(pgo_final_kernel, dim3(1), dim3(64), 0, st, (const double*)pg->epart.p, pg->nbE, 1, 0, pg->scal.p);
+    hipLaunchKernelGGL(pgo_node_kernel, dim3(pg->N), dim3(64), 0, st, (int)pg->N, (const int32_t*)pg->inc_off.p, (const int32_t*)pg->inc_edge.p, (const double*)pg->A.p,
+                       (const double*)pg->g.p, (const double*)pg->poses[pg->cur].p, pg->D.p, pg->b.p, pg->npart.p);
+    hipLaunchKernelGGL(pgo_final_kernel, dim3(1), dim3(64), 0, st, (const double*)pg->npart.p, (int)pg->N, 1, 2, pg->scal.p + 1);
+    if (hipMemcpyAsync(scal_host, pg->scal.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return fail(pg, IBA_ERR_HIP, "iba_pgo: download of the scalars");
+    const hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(pg, IBA_ERR_HIP, std::string("iba_pgo: linearise kernels: ") + hipGetErrorString(e));
+    pg->linearized = true;
+    return IBA_OK;
+}
+
+// the launch chain of (H + lambda I) delta = b; no synchronisation
+void solve_launch(iba_pgo* pg, double lambda) {
+    hipStream_t st = pg->stream;
+    const Plan& p = pg->plan;
+    const int R = (int)p.run_first.size(), ns = (int)p.sep.size(), n = 6 * ns, nblk = (int)p.brow.size();
+    (void)hipMemsetAsync(pg->scal.p + 7, 0, sizeof(double), st);
+    (void)hipMemsetAsync(pg->S.p, 0, (size_t)n * n * sizeof(double), st);
+    if (R > 0)
+        hipLaunchKernelGGL(pgo_run_forward_kernel, dim3((R + 3) / 4), dim3(64), 0, st, run_dev(pg), (const double*)pg->D.p, (const double*)pg->b.p, (const double*)pg->A.p, lambda,
+                           pg->G.p, pg->F.p, pg->y.p, pg->run_S.p, pg->run_b.p, pg->scal.p);
+    hipLaunchKernelGGL(pgo_sep_assemble_kernel, dim3(nblk), dim3(64), 0, st, (const int32_t*)pg->brow.p, (const int32_t*)pg->bcol.p, (const int32_t*)pg->boff.p,
+                       (const int32_t*)pg->kind.p, (const int32_t*)pg->idx.p, (const double*)pg->D.p, (const double*)pg->b.p, (const double*)pg->A.p,
+                       (const double*)pg->run_S.p, (const double*)pg->run_b.p, lambda, n, pg->S.p, pg->rhs.p);
+    for (int j0 = 0; j0 < n; j0 += kNB) {
+        const int w = std::min(kNB, n - j0);
+        hipLaunchKernelGGL(pgo_chol_panel_kernel, dim3(1), dim3(kThreads), 0, st, pg->S.p, n, j0, w, pg->scal.p);
+        const int rest = n - (j0 + w);
+        if (rest > 0) { const int nt = (rest + kTile - 1) / kTile; hipLaunchKernelGGL(pgo_chol_update_kernel, dim3(nt, nt), dim3(kThreads), 0, st, pg->S.p, n, j0, w); }
+    }
+    hipLaunchKernelGGL(pgo_sep_solve_kernel, dim3(1), dim3(kThreads), 0, st, (const double*)pg->S.p, n, (const double*)pg->rhs.p, pg->xs.p);
+    hipLaunchKernelGGL(pgo_run_back_kernel, dim3((std::max(R, ns) + 63) / 64), dim3(64), 0, st, run_dev(pg), ns, (const int32_t*)pg->sep_node.p, (const int32_t*)pg->sep_of_node.p,
+                       (const double*)pg->xs.p, (const double*)pg->G.p, (const double*)pg->F.p, (const double*)pg->y.p, pg->delta.p);
+}
+
+// trial poses into poses[1 - cur] from delta, the trial residual; scal[0..7] on the host afterwards
+iba_status trial(iba_pgo* pg, double lambda, double* scal_host) {
+    hipStream_t st = pg->stream;
+    hipLaunchKernelGGL(pgo_update_kernel, dim3(pg->nbN), dim3(kThreads), 0, st, (int)pg->N, (const double*)pg->poses[pg->cur].p, (const double*)pg->delta.p, (const double*)pg->b.p, lambda,
+                       pg->poses[1 - pg->cur].p, pg->upart.p);
+    hipLaunchKernelGGL(pgo_final_kernel, dim3(1), dim3(64), 0, st, (const double*)pg->upart.p, pg->nbN, 2, 0, pg->scal.p + 4);
+    if (pg->E > 0)
+        hipLaunchKernelGGL(pgo_edge_kernel<false>, dim3(pg->nbE), dim3(kThreads), 0, st, edge_dev(pg), (const double*)pg->poses[1 - pg->cur].p, pg->mu, 0, pg->weight.p,
+                           (double*)nullptr, (double*)nullptr, (double*)nullptr, pg->epart.p);
+    hipLaunchKernelGGL(pgo_final_kernel, dim3(1), dim3(64), 0, st, (const double*)pg->epart.p, pg->nbE, 1, 0, pg->scal.p + 6);
+    if (hipMemcpyAsync(scal_host, pg->scal.p, kScal * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return fail(pg, IBA_ERR_HIP, "iba_pgo: download of the scalars");
+    const hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(pg, IBA_ERR_HIP, std::string("iba_pgo: trial kernels: ") + hipGetErrorString(e));
+    if (scal_host[7] != 0.0) return fail(pg, IBA_ERR_UNSUPPORTED, "iba_pgo: H + lambda I is not positive definite to working precision (lambda = " + std::to_string(lambda) + ")");
+    return IBA_OK;
+}
+
+// one LM pass (rule 6), then the reference-node compensation
+iba_status lm_pass(iba_pgo* pg, iba_pgo_pass* out, uint8_t trace_bit) {
+    const iba_pgo_options& o = pg->opt;
+    double ref_before[16];
+    if (o.reference_node >= 0 && hipMemcpy(ref_before, pg->poses[pg->cur].p + 16 * (size_t)o.reference_node, sizeof(ref_before), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(pg, IBA_ERR_HIP, "iba_pgo: download of the reference node");
+    double sc[kScal];
+    iba_status st = linearize(pg, false, sc);
+    if (st != IBA_OK) return st;
+    double r = sc[0], lambda = 1e-5 * sc[3], nu = 2.0;
+    int stop = IBA_PGO_STOP_NONE, iterations = 0, trials = 0;
+    while (stop == IBA_PGO_STOP_NONE) {
+        if (sc[2] < o.min_right_term) { stop = IBA_PGO_STOP_RIGHT_TERM; break; }
+        if (iterations >= o.max_iteration) { stop = IBA_PGO_STOP_MAX_ITERATION; break; }
+        const double xnorm = std::sqrt(sc[1]);
+        for (int k = 0; k < o.max_iteration_lm; ++k) {
+            solve_launch(pg, lambda);
+            double ts[kScal];
+            st = trial(pg, lambda, ts);
+            if (st != IBA_OK) return st;
+            ++trials;
+            if (std::sqrt(ts[5]) < o.min_relative_increment * (xnorm + o.min_relative_increment)) { stop = IBA_PGO_STOP_INCREMENT; pg->trace.push_back(2 | trace_bit); break; }
+            const double r_new = ts[6], rho = (r - r_new) / (ts[4] + 1e-3);
+            if (rho > 0.0) {
+                const double t = 2.0 * rho - 1.0;
+                lambda *= std::max(o.lower_scale_factor, std::min(1.0 - t * t * t, o.upper_scale_factor));
+                nu = 2.0;
+                pg->trace.push_back(1 | trace_bit);
+                pg->cur = 1 - pg->cur;
+                const double r_before = r;
+                st = linearize(pg, true, sc);
+                if (st != IBA_OK) return st;
+                r = sc[0];
+                if (r_before - r_new < o.min_relative_residual_increment * r_before) stop = IBA_PGO_STOP_RESIDUAL_INCREMENT;
+                break;
+            }
+            pg->trace.push_back(0 | trace_bit);
+            lambda *= nu; nu *= 2.0;
+        }
+        ++iterations;
+        if (stop == IBA_PGO_STOP_NONE && r < o.min_residual) stop = IBA_PGO_STOP_RESIDUAL;
+    }
+    out->iterations = iterations; out->trials = trials; out->stop = stop; out->reserved = 0; out->residual = r; out->lambda = lambda;
+    if (o.reference_node >= 0) {
+        double ref_after[16], inv[12];
+        if (hipMemcpy(ref_after, pg->poses[pg->cur].p + 16 * (size_t)o.reference_node, sizeof(ref_after), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(pg, IBA_ERR_HIP, "iba_pgo: download of the reference node");
+        Rigid12 C;
+        inv12(ref_after, inv);
+        mul12(ref_before, inv, C.m);
+        hipLaunchKernelGGL(pgo_left_mul_kernel, dim3(pg->nbN), dim3(kThreads), 0, pg->stream, (int)pg->N, C, pg->poses[pg->cur].p);
+        const hipError_t e = hipStreamSynchronize(pg->stream);
+        if (e != hipSuccess) return fail(pg, IBA_ERR_HIP, std::string("iba_pgo: compensation kernel: ") + hipGetErrorString(e));
+        pg->linearized = false;
+    }
+    return IBA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+iba_status iba_default_pgo_options(iba_pgo_options* o) {
+    if (!o) return IBA_ERR_INVALID_ARG;
+    std::memset(o, 0, sizeof(*o));
+    o->struct_size = (int32_t)sizeof(*o);
+    o->reference_node = 0;
+    o->max_corr_dist = 1.2; o->edge_prune_threshold = 0.25; o->preference_loop_closure = 1.0;
+    o->max_iteration = 100; o->max_iteration_lm = 20;
+    o->min_relative_increment = 1e-6; o->min_relative_residual_increment = 1e-6; o->min_right_term = 1e-6; o->min_residual = 1e-6;
+    o->upper_scale_factor = 2.0 / 3.0; o->lower_scale_factor = 1.0 / 3.0;
+    o->segment = 128;   // profiles/pgo_bench.md: the fastest of 8 .. 128 at N = 512 and N = 4541
+    return IBA_OK;
+}
+
+const char* iba_pgo_last_error(const iba_pgo* pg) { return pg ? pg->err.c_str() : t_err.c_str(); }
+
+void iba_pgo_destroy(iba_pgo* pg) {
+    if (!pg) return;
+    (void)hipSetDevice(pg->device);
+    for (DBuf<double>* d : {&pg->poses[0], &pg->poses[1], &pg->Xinv, &pg->info, &pg->weight, &pg->zeta, &pg->A, &pg->g, &pg->epart, &pg->D, &pg->b, &pg->npart, &pg->G, &pg->F, &pg->y,
+                            &pg->delta, &pg->upart, &pg->run_S, &pg->run_b, &pg->S, &pg->rhs, &pg->xs, &pg->scal}) d->release();
+    for (DBuf<int32_t>* d : {&pg->d_src, &pg->d_tgt, &pg->inc_off, &pg->inc_edge, &pg->chain, &pg->run_first, &pg->run_last, &pg->sep_node, &pg->sep_of_node, &pg->brow, &pg->bcol,
+                             &pg->boff, &pg->kind, &pg->idx}) d->release();
+    pg->d_flags.release();
+    if (pg->stream) (void)hipStreamDestroy(pg->stream);
+    delete pg;
+}
+
+iba_status iba_pgo_plan(int32_t N, const iba_pgo_edge* edges, int32_t E, const iba_pgo_options* opt, int32_t* separators, int32_t sep_cap_out, int32_t* n_separators,
+                        int32_t* runs, int32_t run_cap, int32_t* n_runs, int32_t* K_used) {
+    std::string why = validate_topology(N, edges, E);
+    if (why.empty()) why = validate_options(opt, N);
+    if (why.empty() && ((separators && sep_cap_out < 0) || (runs && run_cap < 0))) why = "a negative capacity";
+    if (!why.empty()) return fail(nullptr, IBA_ERR_INVALID_ARG, "iba_pgo_plan: " + why);
+    std::vector<int32_t> src(E), tgt(E);
+    for (int32_t e = 0; e < E; ++e) { src[e] = edges[e].source; tgt[e] = edges[e].target; }
+    Plan p;
+    if (!make_plan(N, src.data(), tgt.data(), nullptr, E, opt->segment, sep_cap(), p, why)) return fail(nullptr, IBA_ERR_INVALID_ARG, "iba_pgo_plan: " + why);
+    if (separators) for (int32_t k = 0; k < sep_cap_out && k < (int32_t)p.sep.size(); ++k) separators[k] = p.sep[k];
+    if (n_separators) *n_separators = (int32_t)p.sep.size();
+    if (runs) for (int32_t k = 0; k < run_cap && k < (int32_t)p.run_first.size(); ++k) { runs[2 * k] = p.run_first[k]; runs[2 * k + 1] = p.run_last[k]; }
+    if (n_runs) *n_runs = (int32_t)p.run_first.size();
+    if (K_used) *K_used = p.K;
+    return IBA_OK;
+}
+
+iba_status iba_pgo_create(const double* nodes16, int32_t N, const iba_pgo_edge* edges, int32_t E, const iba_pgo_options* opt, int device, iba_pgo** out) {
+    if (out) *out = nullptr;
+    if (!out) return fail(nullptr, IBA_ERR_INVALID_ARG, "iba_pgo_create: out is NULL");
+    std::string why = validate_topology(N, edges, E);
+    if (why.empty()) why = validate_options(opt, N);
+    if (why.empty()) why = validate_values(nodes16, N, edges, E);
+    if (!why.empty()) return fail(nullptr, IBA_ERR_INVALID_ARG, "iba_pgo_create: " + why);
+    iba_pgo* pg = new iba_pgo();
+    pg->N = N; pg->E = E; pg->opt = *opt; pg->device = device;
+    pg->src.resize(E); pg->tgt.resize(E); pg->flags.resize(E); pg->info55.resize(E);
+    std::vector<double> xinv((size_t)E * 12), info((size_t)E * 36), ones((size_t)E, 1.0);
+    for (int32_t e = 0; e < E; ++e) {
+        pg->src[e] = edges[e].source; pg->tgt[e] = edges[e].target; pg->flags[e] = edges[e].uncertain ? 1 : 0; pg->info55[e] = edges[e].info[35];
+        inv12(edges[e].T, &xinv[(size_t)e * 12]);
+        for (int i = 0; i < 6; ++i) for (int j = i; j < 6; ++j) { info[(size_t)e * 36 + i * 6 + j] = edges[e].info[i * 6 + j]; info[(size_t)e * 36 + j * 6 + i] = edges[e].info[i * 6 + j]; }
+    }
+    {   // the plan (and with it the separator cap) is an argument check too: before the device probe
+        std::string w2; Plan p;
+        if (!make_plan(N, pg->src.data(), pg->tgt.data(), nullptr, E, opt->segment, sep_cap(), p, w2)) { delete pg; return fail(nullptr, IBA_ERR_INVALID_ARG, "iba_pgo_create: " + w2); }
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device || device < 0 || hipSetDevice(device) != hipSuccess) {
+        delete pg;
+        return fail(nullptr, IBA_ERR_NO_DEVICE, "iba_pgo_create: no usable gfx950 device " + std::to_string(device) + " (there is no CPU fallback)");
+    }
+    pg->nbE = (E + kThreads - 1) / kThreads; pg->nbN = (N + kThreads - 1) / kThreads;
+    hipError_t e = hipSuccess;
+    auto up = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    const size_t n = (size_t)N, m = (size_t)E;
+    up(pg->poses[0].alloc(16 * n)); up(pg->poses[1].alloc(16 * n));
+    if (e == hipSuccess) up(hipMemcpy(pg->poses[0].p, nodes16, 16 * n * sizeof(double), hipMemcpyHostToDevice));
+    up(pg->d_src.upload(pg->src)); up(pg->d_tgt.upload(pg->tgt)); up(pg->Xinv.upload(xinv)); up(pg->info.upload(info)); up(pg->weight.upload(ones));
+    up(pg->zeta.alloc(6 * m)); up(pg->A.alloc(36 * m)); up(pg->g.alloc(6 * m)); up(pg->epart.alloc(pg->nbE));
+    up(pg->D.alloc(36 * n)); up(pg->b.alloc(6 * n)); up(pg->npart.alloc(3 * n)); up(pg->G.alloc(36 * n)); up(pg->F.alloc(36 * n)); up(pg->y.alloc(6 * n));
+    up(pg->delta.alloc(6 * n)); up(pg->upart.alloc(2 * (size_t)pg->nbN)); up(pg->scal.alloc(kScal));
+    up(hipStreamCreate(&pg->stream));
+    if (e != hipSuccess) { const std::string msg = hipGetErrorString(e); iba_pgo_destroy(pg); return fail(nullptr, IBA_ERR_HIP, "iba_pgo_create: " + msg); }
+    const iba_status st = upload_plan(pg);
+    if (st != IBA_OK) { t_err = pg->err; iba_pgo_destroy(pg); return st; }
+    *out = pg;
+    return IBA_OK;
+}
+
+iba_status iba_pgo_linearize(iba_pgo* pg, double* zeta, double* weight, double* A, double* b, double* residual) {
+    if (!pg) return fail(nullptr, IBA_ERR_INVALID_ARG, "iba_pgo_linearize: pg is NULL");
+    if (hipSetDevice(pg->device) != hipSuccess) return fail(pg, IBA_ERR_HIP, "iba_pgo_linearize: hipSetDevice");
+    double sc[kScal];
+    const iba_status st = linearize(pg, false, sc);
+    if (st != IBA_OK) return st;
+    const size_t m = (size_t)pg->E, n = (size_t)pg->N;
+    hipError_t e = hipSuccess;
+    auto dn = [&](double* dst, const double* srcp, size_t count) { if (dst && count && e == hipSuccess) e = hipMemcpy(dst, srcp, count * sizeof(double), hipMemcpyDeviceToHost); };
+    dn(zeta, pg->zeta.p, 6 * m); dn(weight, pg->weight.p, m); dn(A, pg->A.p, 36 * m); dn(b, pg->b.p, 6 * n);
+    if (e != hipSuccess) return fail(pg, IBA_ERR_HIP, std::string("iba_pgo_linearize: ") + hipGetErrorString(e));
+    if (residual) *residual = sc[0];
+    return IBA_OK;
+}
+
+iba_status iba_pgo_solve(iba_pgo* pg, double lambda, double* delta) {
+    if (!pg) return fail(nullptr, IBA_ERR_INVALID_ARG, "iba_pgo_solve: pg is NULL");
+    if (!delta) return fail(pg, IBA_ERR_INVALID_ARG, "iba_pgo_solve: delta is NULL");
+    if (!std::isfinite(lambda) || lambda < 0.0) return fail(pg, IBA_ERR_INVALID_ARG, "iba_pgo_solve: lambda is not finite or negative");
+    if (!pg->linearized) return fail(pg, IBA_ERR_STATE, "iba_pgo_solve: no linearisation at the current poses (call iba_pgo_linearize)");
+    if (hipSetDevice(pg->device) != hipSuccess) return fail(pg, IBA_ERR_HIP, "iba_pgo_solve: hipSetDevice");
+    solve_launch(pg, lambda);
+    double flag = 0.0;
+    hipError_t e = hipMemcpyAsync(delta, pg->delta.p, 6 * (size_t)pg->N * sizeof(double), hipMemcpyDeviceToHost, pg->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&flag, pg->scal.p + 7, sizeof(double), hipMemcpyDeviceToHost, pg->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(pg->stream);
+    if (e != hipSuccess) return fail(pg, IBA_ERR_HIP, std::string("iba_pgo_solve: ") + hipGetErrorString(e));
+    if (flag != 0.0) return fail(pg, IBA_ERR_UNSUPPORTED, "iba_pgo_solve: H + lambda I is not positive definite to working precision (lambda = " + std::to_string(lambda) + ")");
+    return IBA_OK;
+}
+
+iba_status iba_pgo_optimize(iba_pgo* pg, iba_pgo_result* res) {
+    if (!pg) return fail(nullptr, IBA_ERR_INVALID_ARG, "iba_pgo_optimize: pg is NULL");
+    if (!res) return fail(pg, IBA_ERR_INVALID_ARG, "iba_pgo_optimize: result is NULL");
+    if (hipSetDevice(pg->device) != hipSuccess) return fail(pg, IBA_ERR_HIP, "iba_pgo_optimize: hipSetDevice");
+    std::memset(res, 0, sizeof(*res));
+    res->struct_size = (int32_t)sizeof(*res);
+    pg->trace.clear();
+    // weights of the edges in the graph to 1 (a dropped edge keeps the weight it was dropped with); with prune: rule 7 first
+    const size_t m = (size_t)pg->E;
+    std::vector<double> w(m);
+    int32_t n_pruned = 0;
+    auto reset_weights = [&](bool prune) -> iba_status {
+        if (!m) return IBA_OK;
+        if (hipMemcpy(w.data(), pg->weight.p, m * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(pg, IBA_ERR_HIP, "iba_pgo_optimize: download of the weights");
+        for (size_t e = 0; e < m; ++e) {
+            if (prune && (pg->flags[e] & 1) && !(pg->flags[e] & 2) && w[e] < pg->opt.edge_prune_threshold) { pg->flags[e] |= 2; ++n_pruned; }
+            if (!(pg->flags[e] & 2)) w[e] = 1.0;
+        }
+        if (hipMemcpy(pg->weight.p, w.data(), m * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(pg, IBA_ERR_HIP, "iba_pgo_optimize: upload of the weights");
+        return IBA_OK;
+    };
+    iba_status st = reset_weights(false);
+    if (st != IBA_OK) return st;
+    st = lm_pass(pg, &res->pass[0], 0);
+    if (st != IBA_OK) return st;
+    st = reset_weights(true);
+    if (st != IBA_OK) return st;
+    res->n_pruned = n_pruned;
+    st = upload_plan(pg);
+    if (st != IBA_OK) return st;
+    return lm_pass(pg, &res->pass[1], 0x80);
+}
+
+iba_status iba_pgo_read(iba_pgo* pg, double* nodes16, double* weight, uint8_t* pruned) {
+    if (!pg) return fail(nullptr, IBA_ERR_INVALID_ARG, "iba_pgo_read: pg is NULL");
+    if (hipSetDevice(pg->device) != hipSuccess) return fail(pg, IBA_ERR_HIP, "iba_pgo_read: hipSetDevice");
+    hipError_t e = hipSuccess;
+    if (nodes16) e = hipMemcpy(nodes16, pg->poses[pg->cur].p, 16 * (size_t)pg->N * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && weight && pg->E) e = hipMemcpy(weight, pg->weight.p, (size_t)pg->E * sizeof(double), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(pg, IBA_ERR_HIP, std::string("iba_pgo_read: ") + hipGetErrorString(e));
+    if (pruned) for (int32_t k = 0; k < pg->E; ++k) pruned[k] = (pg->flags[k] & 2) ? 1 : 0;
+    return IBA_OK;
+}
+
+iba_status iba_debug_pgo_trace(iba_pgo* pg, uint8_t* trials, int32_t cap, int32_t* n) {
+    if (!pg || !n || cap < 0 || (cap && !trials)) return fail(pg, IBA_ERR_INVALID_ARG, "iba_debug_pgo_trace: bad argument");
+    for (int32_t k = 0; k < cap && k < (int32_t)pg->trace.size(); ++k) trials[k] = pg->trace[k];
+    *n = (int32_t)pg->trace.size();
+    return IBA_OK;
+}
+
+}  // extern "C"

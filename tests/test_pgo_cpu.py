@@ -1,0 +1,199 @@
+"""CPU tier of the pose-graph optimiser (include/iba_mi355x.h, iba_pgo_*): the numpy restatement of the rules (tests/pgo_ref.py) checked against
+finite differences and on graphs with a known answer, the host-only plan of the library against the Python plan, and the argument checks,
+which run before the device is probed."""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+
+import pgo_ref as R
+
+PKG = "spatial-temporal-lidar-camera-calibration_amd"
+
+
+@pytest.fixture(scope="module")
+def pgo(pkg):
+    pkg.build_extension()
+    return importlib.import_module(PKG + ".pgo")
+
+
+def _has_gpu():
+    try:
+        import torch
+        return torch.cuda.is_available()
+    except Exception:
+        return False
+
+
+def _consistent(N=12, seed=3):
+    g = R.make_graph(N, loops=2, seed=seed, noise_free=True)
+    return R.Graph(g.truth, g.src, g.tgt, g.X, g.info, g.uncertain, truth=g.truth)
+
+
+def _step(k, h):
+    v = np.zeros(6)
+    v[k] = h
+    return R.T_of(v)[0]   # exp(h G_k): a rotation about one axis / a unit translation
+
+
+def test_js_is_the_derivative_of_zeta_along_the_generators():
+    """At a consistent graph M = I, where lin6 IS the derivative of vec6: central differences of zeta with pose <- exp(h G_k) pose. h = 1e-5: the
+    truncation error is O(h^2) = 1e-10 times third derivatives of order |pose| ~ 10 m, the rounding error eps |pose| / h ~ 1e-10: held to 1e-7."""
+    g = _consistent()
+    _, Js, _, _ = R.edge_terms(g.nodes, g)
+    h = 1e-5
+    for e in range(g.E):
+        for which, sign in (("src", 1.0), ("tgt", -1.0)):
+            node = int(g.src[e] if which == "src" else g.tgt[e])
+            J = np.zeros((6, 6))
+            for k in range(6):
+                z = []
+                for hh in (h, -h):
+                    nd = g.nodes.copy()
+                    nd[node] = _step(k, hh) @ nd[node]
+                    z.append(R.edge_terms(nd, g, want_js=False)[0][e])
+                J[:, k] = (z[0] - z[1]) / (2 * h)
+            assert np.max(np.abs(J - sign * Js[e])) <= 1e-7 * max(1.0, np.max(np.abs(Js[e]))), (e, which)
+
+
+def test_jt_is_minus_js():
+    """rule 3 with plain 4x4 products: the structured Js of the restatement equals it, and the target's Jacobian is its exact negative"""
+    g = R.make_graph(20, loops=3, seed=2)
+    _, Js, _, _ = R.edge_terms(g.nodes, g)
+    for e in range(g.E):
+        Pt, Ps = g.nodes[g.tgt[e]], g.nodes[g.src[e]]
+        Jd, Jt = R.jacobian_dense(g.X[e], Pt, Ps), R.jacobian_dense(g.X[e], Pt, Ps, of_target=True)
+        assert np.array_equal(Jt, -Jd)
+        assert np.max(np.abs(Js[e] - Jd)) <= 64 * R.EPS * max(1.0, np.max(np.abs(Jd)))
+
+
+def test_a_consistent_graph_has_no_residual_and_no_right_term():
+    g = _consistent(N=30)
+    lin = R.linearize(g.nodes, g, np.ones(g.E))
+    # zeta is rounding only: a few eps of the largest coordinate that enters M
+    tol_z = 32 * R.EPS * (1.0 + np.max(np.abs(g.nodes[:, :3, 3])))
+    Lmax = np.max(np.abs(g.info))
+    assert np.max(np.abs(lin["zeta"])) <= tol_z
+    assert 0.0 <= lin["residual"] <= g.E * 36 * Lmax * tol_z ** 2
+    _, Js, _, _ = R.edge_terms(g.nodes, g)
+    assert np.max(np.abs(lin["b"])) <= 4 * 36 * Lmax * np.max(np.abs(Js)) * tol_z
+    res = R.optimize(g, R.options())
+    assert [(p["stop"], p["trials"]) for p in res["passes"]] == [(R.STOP_RIGHT_TERM, 0)] * 2
+
+
+def test_lm_returns_a_noise_free_graph_to_the_ground_truth():
+    """Nodes perturbed by centimetres, edges exact. The tolerance is what the run's own stopping point allows, measured: with the final residual r
+    evaluated in long double, an edge's misalignment is at most sqrt(r / lambda_min(L)), and a node is reached from node 0 over at most N - 1 chain
+    edges, each acting with a lever arm of at most the extent of the trajectory."""
+    g0 = R.make_graph(25, loops=3, seed=4, noise_free=True)
+    rng = np.random.default_rng(0)
+    nodes = g0.truth.copy()
+    for i in range(1, g0.N):
+        nodes[i] = nodes[i] @ R.T_of(np.concatenate([rng.normal(0, 2e-3, 3), rng.normal(0, 3e-2, 3)]))[0]
+    g = R.Graph(nodes, g0.src, g0.tgt, g0.X, g0.info, g0.uncertain, truth=g0.truth)
+    res = R.optimize(g, R.options())
+    r_ld = float(R.linearize(res["nodes"], g, np.ones(g.E), res["pruned"], np.longdouble)["residual"])
+    lam_min = min(np.linalg.eigvalsh(L)[0] for L in g.info)
+    extent = 1.0 + np.max(np.abs(g.truth[:, :3, 3]))
+    tol = (g.N - 1) * np.sqrt(r_ld / lam_min) * extent
+    err = float(np.max(np.abs(R.align_at(res["nodes"], g.truth) - g.truth)))
+    start = float(np.max(np.abs(R.align_at(g.nodes, g.truth) - g.truth)))
+    print("pgo-figures noise_free final_residual_ld=%.3e tolerance=%.3e error=%.3e start=%.3e" % (r_ld, tol, err, start))
+    assert res["n_pruned"] == 0 and err <= tol and tol < 0.1 * start
+
+
+def test_the_two_false_loops_are_pruned_and_only_they():
+    g = R.make_graph(60, loops=6, false_loops=2, seed=5)
+    res = R.optimize(g, R.options())
+    R.check_margins(res)
+    expect = np.zeros(g.E, bool)
+    expect[-2:] = True
+    assert np.array_equal(res["pruned"], expect) and res["n_pruned"] == 2
+    assert np.all(res["weight"][g.uncertain & ~expect] > 0.9) and np.all(res["weight"][expect] < 0.05)
+
+
+def test_the_seeds_of_the_device_tests_have_no_near_tie():
+    """tests/test_gpu_pgo.py compares decision sequences on these runs: none of their decisions may be close"""
+    for N, loops, seed in ((40, 3, 15), (130, 4, 81)):
+        res = R.optimize(R.make_graph(N, loops=loops, false_loops=1, seed=seed), R.options())
+        R.check_margins(res)
+        assert res["n_pruned"] == 1 and res["pruned"][-1]
+
+
+@pytest.mark.parametrize("case", R.SOLVE_CASES, ids=[c[0] for c in R.SOLVE_CASES])
+def test_plan_of_the_library_is_the_python_plan(pgo, monkeypatch, case):
+    name, N, cross, missing, segment, cap = case
+    if cap is not None:
+        monkeypatch.setenv("IBA_DEBUG_ENV", "1")
+        monkeypatch.setenv("IBA_PGO_MAX_SEP", str(cap))
+    g = R.case_graph(N, cross, missing, seed=1)
+    got = pgo.pgo_plan(N, g.edge_tuples(), segment=segment)
+    ref = R.plan(N, g.src, g.tgt, segment, cap or R.MAX_SEPARATORS)
+    assert got["K"] == ref["K"] and got["separators"].tolist() == ref["separators"] and [tuple(r) for r in got["runs"].tolist()] == ref["runs"]
+    if name == "k_doubles_once":
+        assert got["K"] == 2 * segment
+    if name == "three_panels_ragged":
+        assert 6 * len(got["separators"]) == 108
+
+
+def test_plan_refuses_cross_edges_beyond_the_cap(pgo, monkeypatch):
+    monkeypatch.setenv("IBA_DEBUG_ENV", "1")
+    monkeypatch.setenv("IBA_PGO_MAX_SEP", "3")
+    g = R.case_graph(17, ((2, 9), (5, 14)), seed=1)
+    with pytest.raises(ValueError):
+        R.plan(17, g.src, g.tgt, 4, 3)
+    with pytest.raises(pgo.IbaError) as e:
+        pgo.pgo_plan(17, g.edge_tuples(), segment=4)
+    assert e.value.status == 1 and "4 nodes" in str(e.value)
+    with pytest.raises(pgo.IbaError) as e:
+        pgo.PoseGraph(g.nodes, g.edge_tuples(), segment=4)
+    assert e.value.status == 1 and "4 nodes" in str(e.value)
+
+
+def test_default_options_fill_the_mirror(pgo):
+    o = pgo.pgo_options()
+    assert o.struct_size == C.sizeof(pgo.IbaPgoOptions) and C.sizeof(pgo.IbaPgoEdge) == 432
+    assert (o.max_corr_dist, o.edge_prune_threshold, o.preference_loop_closure, o.reference_node) == (1.2, 0.25, 1.0, 0)
+    assert (o.max_iteration, o.max_iteration_lm, o.segment) == (100, 20, 128)
+    assert (o.min_relative_increment, o.min_relative_residual_increment, o.min_right_term, o.min_residual) == (1e-6,) * 4
+    assert (o.upper_scale_factor, o.lower_scale_factor) == (2.0 / 3.0, 1.0 / 3.0)
+
+
+def test_argument_checks_precede_the_device_probe(pgo):
+    """every refusal is IBA_ERR_INVALID_ARG (1) with its own message — with or without a GPU, never IBA_ERR_NO_DEVICE (2)"""
+    g = R.case_graph(6, ((1, 4),), seed=2)
+    ed = g.edge_tuples()
+
+    def refused(nodes, edges, needle, **kw):
+        with pytest.raises(pgo.IbaError) as e:
+            pgo.PoseGraph(nodes, edges, **kw)
+        assert e.value.status == 1 and needle in str(e.value), str(e.value)
+
+    refused(np.zeros((0, 4, 4)), [], "N = 0")
+    bad = list(ed); bad[2] = (2, 9) + ed[2][2:]
+    refused(g.nodes, bad, "edge 2")
+    bad = list(ed); bad[1] = (3, 3) + ed[1][2:]
+    refused(g.nodes, bad, "source == target")
+    nd = g.nodes.copy(); nd[4, 1, 2] = np.nan
+    refused(nd, ed, "node 4 is not finite")
+    nd = g.nodes.copy(); nd[5, 3, 3] = 1.0 + 1e-12
+    refused(nd, ed, "node 5 has a last row")
+    X = ed[0][2].copy(); X[3, 0] = 1e-300
+    refused(g.nodes, [(ed[0][0], ed[0][1], X) + ed[0][3:]] + ed[1:], "edge 0: T has a last row")
+    info = ed[3][3].copy(); info[1, 4] = np.inf
+    refused(g.nodes, ed[:3] + [ed[3][:3] + (info, ed[3][4])] + ed[4:], "edge 3: info is not finite")
+    refused(g.nodes, ed, "reference_node", reference_node=6)
+    refused(g.nodes, ed, "segment", segment=0)
+    refused(g.nodes, ed, "not finite", max_corr_dist=float("nan"))
+    o = pgo.pgo_options(); o.struct_size = 8
+    refused(g.nodes, ed, "struct_size", opt=o)
+
+
+def test_no_cpu_fallback(pgo):
+    if _has_gpu():
+        pytest.skip("GPU present")
+    g = R.case_graph(6, seed=2)
+    with pytest.raises(pgo.IbaError) as e:
+        pgo.PoseGraph(g.nodes, g.edge_tuples())
+    assert e.value.status == 2 and "no CPU fallback" in str(e.value)
