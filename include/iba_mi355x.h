@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define IBA_ABI_VERSION 4 /* 2: iba_params.factor_3d2d_kind; 3: iba_icp_*; 4: iba_scan_*. An ADDED entry point (iba_submap_*, iba_sc_*) changes no existing struct and does not bump it: callers detect it by symbol */
+#define IBA_ABI_VERSION 4 /* 2: iba_params.factor_3d2d_kind; 3: iba_icp_*; 4: iba_scan_*. An ADDED entry point (iba_submap_*, iba_sc_*, iba_floam_*) changes no existing struct and does not bump it: callers detect it by symbol */
 #define IBA_MAX_BATCH 64 /* the batch unit of the callers in this library (one MADS poll block, the planner's diagnostics); NOT a limit of the evaluators */
 #define IBA_MAX_CHAIN 512 /* most candidates ONE launch chain takes (iba_create_options.max_chain_batch <= this); a call with more runs as consecutive chains */
 
@@ -486,6 +486,86 @@ iba_status iba_sc_detect(iba_sc_db* db, const iba_sc_query* queries, int32_t Q, 
  * counter: db_end[i] = 0. Otherwise, when counter % tree_period == 0 the search set becomes the first size - num_exclude_recent keys, then the counter
  * advances; between rebuilds the set is stale. db_end[i] = the size of the set call i searches. */
 iba_status iba_sc_replay_plan(const int32_t* sizes_at_call, int32_t n, const iba_sc_options* opt, int32_t* db_end /* n */);
+
+/*
+ * ---- F-LOAM feature extraction: the edge cloud and the surf cloud of every scan [src/floam/src/laserProcessingClass.cpp: featureExtraction :12-98,
+ * featureExtractionFromSector :101-211; called once per scan from System::Track] ----
+ * The first half of the reference's LiDAR front end splits every raw scan into edge points (the sharpest of each sector of each laser ring) and surf
+ * points (the rest); everything after it (updatePointsToMap, the edge and surf factors, the local map) reads only those two clouds. It depends on the
+ * scan alone, never on a pose: here a BATCH OF RESIDENT SCANS (local frames of a handle, a frame may repeat; a scans-only handle is enough) is split in
+ * one launch chain, and the two clouds of every scan come back in an object the library allocates, as iba_submap_build's do.
+ *
+ * Rules, fixed here so that the result is a function of the input alone (tests/floam_ref.py restates them in numpy; the device result equals it byte
+ * for byte, indices and coordinates). Every operation below is rounded on its own: NO fused multiply-add; sqrt and / are IEEE. No floating-point atomics.
+ *   1 point      the scan's float32 coordinates in the scan's ORIGINAL index order (the handle stores a scan in kd-leaf order; the original order is
+ *                recovered on the device). A point with a non-finite coordinate is skipped and counted (n_nonfinite). d = sqrt(x x + y y) in f64 on
+ *                the widened coordinates; a point with d < min_distance || d > max_distance is skipped and counted (n_out_of_range); angle =
+ *                atan(z / d) * 180 / pi in f64. Known deviation: the reference forms x x + y y in float.
+ *   2 ring       the reference's three expressions with C truncation towards zero. 16 lines: int((angle + 15) / 2 + 0.5). 32 lines: int((angle +
+ *                92.0 / 3.0) * 3.0 / 4.0). 64 lines: int((2 - angle) * 3.0 + 0.5) when angle >= -8.83, else 32 + int((-8.83 - angle) * 2.0 + 0.5), and
+ *                the point is skipped when angle > 2 || angle < -24.33. For every line count the point is skipped when the id is outside [0, num_lines)
+ *                (or the angle is NaN: d == 0 with min_distance <= 0). These points are counted in n_no_ring. d is IEEE and reproduces to the bit; the
+ *                f64 atan of two correct libraries may differ by an ulp, which matters only for a point whose angle sits on a boundary of these
+ *                expressions (the tests keep their inputs 0.01 degrees away from every boundary).
+ *   3 ring list  the points of a ring in original index order (a stable partition). A ring with fewer than min_ring_points points gives nothing; one
+ *                with more than IBA_FLOAM_MAX_RING_POINTS answers IBA_ERR_UNSUPPORTED with a message naming the scan and the ring.
+ *   4 curvature  for the positions j in [5, n - 5) of a ring of n points, per axis IN FLOAT32 and left to right as the reference writes it:
+ *                ((((p[j-5] + p[j-4]) + p[j-3]) + p[j-2]) + p[j-1]) - 10 p[j] + p[j+1] + p[j+2] + p[j+3] + p[j+4] + p[j+5], the product rounded before
+ *                the subtraction; value = (dx dx + dy dy) + dz dz in f64 on the widened differences; a NaN value counts as +inf. neighbour_span = 5 is
+ *                the only supported window (any other value: IBA_ERR_INVALID_ARG).
+ *   5 sectors    the reference's off-by-one is kept: with total = n - 10 and len = total / num_sectors (integer division), sector s holds the
+ *                curvature entries [len s, end), end = len (s + 1) - 1 for s < num_sectors - 1 and total - 1 for the last sector. The last entry of
+ *                every sector belongs to no sector and appears in neither cloud. A sector with no entries gives nothing.
+ *   6 order      a sector's entries ascending by (value, position). Known deviation: std::sort leaves the order of equal values unspecified; here
+ *                the lower position comes first.
+ *   7 edges      the entries are walked in DESCENDING order with a picked set that starts empty per sector. For each entry whose position is not
+ *                picked: stop when value <= edge_curvature; count it and mark it; when the count exceeds max_edges_per_sector stop (that entry stays
+ *                marked and is in neither cloud); otherwise it is an edge point, and for k = 1 .. 5 upwards and, separately, k = -1 .. -5 downwards
+ *                position ind + k is marked, a direction stopping at the first consecutive pair whose squared gap exceeds neighbour_gap2 (per-axis
+ *                differences in float32, squared and summed in f64 as (dx dx + dy dy) + dz dz, strict '>'). A mark outside the sector has no effect.
+ *   8 surf       the entries in ASCENDING order of rule 6 whose position is not marked.
+ *   9 output     rings ascending, sectors ascending; within a sector the edges in pick order and the surfs in rule-8 order. *_xyz are the scan's own
+ *                float32 values, untouched; *_index is the original index in the scan. A scan's result does not depend on what else is in the batch,
+ *                and two calls give the same bytes.
+ * Answers IBA_ERR_INVALID_ARG with a message, before any launch: a NULL argument, a struct_size of another library, num_lines not 16, 32 or 64, n outside
+ * [1, 2^20], a frame outside the handle, distances not finite or min_distance > max_distance, min_ring_points < 11, num_sectors outside [1, 64],
+ * max_edges_per_sector outside [0, 64], neighbour_span != 5, thresholds not finite. On failure *out is NULL and iba_last_error(h) carries the message.
+ * Limits: the clouds come back to the host. To register against them, build a handle from them with iba_create; keeping them on the device as frames
+ * of a new handle (as iba_submap_handle does for voxel clouds) is not done. The ring of a point is always derived from its elevation (a per-point
+ * ring field supplied by the caller is not read). The scan-to-map step that consumes the clouds (odomEstimationClass.cpp), PCL's VoxelGrid and crop
+ * box and the local map are not restated. One GPU.
+ */
+#define IBA_FLOAM_MAX_RING_POINTS 8192
+typedef struct iba_floam_options {
+    int32_t struct_size;          /* sizeof(iba_floam_options) */
+    int32_t num_lines;            /* 16, 32 or 64 (lidar.h num_lines); default 64 */
+    double  min_distance;         /* 3.0 (floamClass.cpp, HDL_64) */
+    double  max_distance;         /* 90.0 (floamClass.h) */
+    int32_t min_ring_points;      /* 131 */
+    int32_t num_sectors;          /* 6 */
+    int32_t max_edges_per_sector; /* 20 */
+    int32_t neighbour_span;       /* 5 */
+    double  edge_curvature;       /* 0.1 */
+    double  neighbour_gap2;       /* 0.05 */
+} iba_floam_options;
+typedef struct iba_floam_features iba_floam_features;
+/* the reference's constants */
+iba_status iba_default_floam_options(iba_floam_options* opt);
+/* The edge and surf clouds of n resident scans (local frames of the handle; a frame may repeat) as scans 0 .. n - 1 of the result: one launch chain
+ * (classify, stable partition by (scan, ring), one block per sector, gather). The result is allocated by the library; release it with iba_floam_free. */
+iba_status iba_floam_extract(iba_handle* h, const int32_t* frames, int32_t n, const iba_floam_options* opt, iba_floam_features** out);
+/* Scans in the result (0 for NULL); edge / surf points of scan s (-1 for NULL or s out of range); their coordinates (3 floats per point) and their
+ * original indices in the scan (valid until iba_floam_free; NULL for NULL or s out of range). */
+int32_t iba_floam_num(const iba_floam_features* f);
+int64_t iba_floam_n_edge(const iba_floam_features* f, int32_t s);
+int64_t iba_floam_n_surf(const iba_floam_features* f, int32_t s);
+const float* iba_floam_edge_xyz(const iba_floam_features* f, int32_t s);
+const int32_t* iba_floam_edge_index(const iba_floam_features* f, int32_t s);
+const float* iba_floam_surf_xyz(const iba_floam_features* f, int32_t s);
+const int32_t* iba_floam_surf_index(const iba_floam_features* f, int32_t s);
+/* The skipped points of scan s by reason and the points of each of its num_lines rings (before rule 3); every output may be NULL. */
+iba_status iba_floam_stats(const iba_floam_features* f, int32_t s, int64_t* n_nonfinite, int64_t* n_out_of_range, int64_t* n_no_ring, int32_t* ring_points /* num_lines */);
+void iba_floam_free(iba_floam_features* f);
 
 /*
  * ---- Pose-graph optimisation: Levenberg-Marquardt with line process [backend_opt.cpp:433-528 MultiRegistration: nodes pose[i]^-1 :441, odometry

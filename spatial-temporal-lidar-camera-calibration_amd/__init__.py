@@ -14,7 +14,7 @@ import subprocess
 
 import numpy as np
 
-from .abi import (ICP_NMOM, SCAN_NMOM, IbaScOptions, IbaScQuery, IbaScResult, IbaSubmapDesc, IbaScanEdge, IbaScanOptions, IbaScanResult, IbaIcpOptions, IbaIcpResult, IBA_MAX_BATCH, IbaCreateOptions, IbaLmOptions, IbaLmResult, IbaMadsOptions, IbaMadsResult, IbaBbo, IbaCostOut, IbaNormalOut, IbaParams, IbaProblemDesc, Problem, copy_params,
+from .abi import (ICP_NMOM, SCAN_NMOM, IbaFloamOptions, IbaScOptions, IbaScQuery, IbaScResult, IbaSubmapDesc, IbaScanEdge, IbaScanOptions, IbaScanResult, IbaIcpOptions, IbaIcpResult, IBA_MAX_BATCH, IbaCreateOptions, IbaLmOptions, IbaLmResult, IbaMadsOptions, IbaMadsResult, IbaBbo, IbaCostOut, IbaNormalOut, IbaParams, IbaProblemDesc, Problem, copy_params,
                   reference_yaml_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -525,6 +525,13 @@ class IbaHandle:
         db = C.c_void_p(None)
         self._chk(self.lib.iba_sc_describe(self.h, _p(fr) if len(fr) else None, C.c_int32(len(fr)), C.byref(o), C.byref(db)))
         return ScDb(self.lib, db, o)
+
+    # --- F-LOAM feature extraction (iba_floam_extract): the edge and surf clouds of resident scans ---
+    def floam_extract(self, frames, opt=None, **fields):
+        """iba_floam_extract: local frames [n] -> list of dict(edge_xyz, edge_index, surf_xyz, surf_index, n_nonfinite, n_out_of_range, n_no_ring,
+        ring_points) per scan (floam.py). opt = an IbaFloamOptions, or fields of one over the reference's defaults."""
+        from . import floam
+        return floam.extract(self, frames, opt, **fields)
 
     def debug_scan_threads(self, threads):
         """force the block shape of the scan pass kernel (64 / 256; 0: the rule)"""

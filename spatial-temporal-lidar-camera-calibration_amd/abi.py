@@ -197,6 +197,15 @@ class IbaScResult(C.Structure):
                 ("cand_node", C.c_int32 * SC_MAX_CANDIDATES), ("cand_shift", C.c_int32 * SC_MAX_CANDIDATES), ("cand_dist", C.c_double * SC_MAX_CANDIDATES)]
 
 
+FLOAM_MAX_RING_POINTS = 8192    # IBA_FLOAM_MAX_RING_POINTS
+
+
+class IbaFloamOptions(C.Structure):
+    """iba_floam_options: the constants of the reference's laserProcessingClass.cpp (iba_default_floam_options fills them)"""
+    _fields_ = [("struct_size", C.c_int32), ("num_lines", C.c_int32), ("min_distance", C.c_double), ("max_distance", C.c_double), ("min_ring_points", C.c_int32), ("num_sectors", C.c_int32),
+                ("max_edges_per_sector", C.c_int32), ("neighbour_span", C.c_int32), ("edge_curvature", C.c_double), ("neighbour_gap2", C.c_double)]
+
+
 class IbaBbo(C.Structure):
     _fields_ = [("f", C.c_double), ("c1", C.c_double), ("c2", C.c_double), ("c3", C.c_double)]
 

@@ -13,6 +13,7 @@
 #include <limits>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "../../include/iba_mi355x.h"
@@ -38,6 +39,7 @@ const char* debug_env(const char* name) {   // (read at every handle creation: a
 #include "iba_voxel_kernels.hpp"
 #include "iba_sc_kernels.hpp"
 #include "iba_index_kernels.hpp"
+#include "iba_floam_kernels.hpp"
 #include "iba_icp_math.hpp"
 #include "iba_types.hpp"
 
@@ -2191,3 +2193,4 @@ iba_status reserve_batch(iba_handle* h, int B) {
 #include "iba_voxel_host.hpp" // iba_submap_build and the accessors of its result
 #include "iba_sc_host.hpp"    // iba_sc_describe / iba_sc_distance / iba_sc_detect / iba_sc_replay_plan
 #include "iba_index_host.hpp" // iba_submap_handle (the device index build) / iba_debug_scan_index
+#include "iba_floam_host.hpp" // iba_floam_extract and the accessors of its result
