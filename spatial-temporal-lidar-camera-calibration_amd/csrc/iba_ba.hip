@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/iba_mi355x.h"
+#include "iba_device_buf.hpp"
 
 namespace {
 
@@ -149,27 +150,15 @@ __global__ __launch_bounds__(64) void ba_reduce_kernel(const double* __restrict_
     out[i] = t;
 }
 
-template <class T>
-struct Buf {
-    T* p = nullptr; size_t n = 0;
-    hipError_t upload(const T* src, size_t count) {
-        n = count;
-        hipError_t e = hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e != hipSuccess) return e;
-        return count ? hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-};
-
 }  // namespace
 
 struct iba_ba_handle {
     int device = 0;
     int64_t n_edges = 0;
     int n_frames = 0;
-    Buf<double> Tlw6, intr, Xw, obs, info, block_sums, out, chi2;
-    Buf<int32_t> frame;
-    Buf<uint8_t> active;
+    iba::DevBuf<double> Tlw6, intr, Xw, obs, info, block_sums, out, chi2;
+    iba::DevBuf<int32_t> frame;
+    iba::DevBuf<uint8_t> active;
     std::vector<int32_t> slot;
     int nblocks = 0;
     std::string err;
@@ -187,8 +176,6 @@ const char* iba_ba_last_error(const iba_ba_handle* h) { return h ? h->err.c_str(
 void iba_ba_destroy(iba_ba_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    h->Tlw6.release(); h->intr.release(); h->Xw.release(); h->obs.release(); h->info.release(); h->block_sums.release(); h->out.release(); h->chi2.release();
-    h->frame.release(); h->active.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }

@@ -11,14 +11,15 @@
 #include <cstdio>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <string>
 #include <thread>
-#include <tuple>
 #include <vector>
 
 #include "../../include/iba_mi355x.h"
 #include "../../include/iba_mi355x_debug.h"
 #include "iba_build.hpp"
+#include "iba_device_buf.hpp"
 #include "iba_host_math.hpp"
 #include "iba_internal.hpp"
 namespace iba {
@@ -54,18 +55,6 @@ thread_local std::string g_create_error = "";
 
 constexpr uint32_t kLdsBytes = 160u * 1024u;
 constexpr int kRing = 4;
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr; size_t n = 0;
-    hipError_t alloc(size_t count) { n = count; return hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T)); }
-    hipError_t upload(const std::vector<T>& v) {
-        hipError_t e = alloc(v.size()); if (e != hipSuccess) return e;
-        if (!v.empty()) e = hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
 
 }  // namespace
 
@@ -194,10 +183,10 @@ struct iba_handle {
     bool frozen_valid = false; int32_t frozen_frames = 0, frozen_ncorr = 0;
     int nfb = 0;                          // factor-kernel records per candidate (= n_frames)
     int nrec = 0;                         // partial records per candidate = n_frames + nfb
-    Cand* h_cands = nullptr;              // pinned, kRing * chain_cap
-    double* h_partials = nullptr;         // pinned
+    PinnedBuf<Cand> h_cands;              // pinned, kRing * chain_cap
+    PinnedBuf<double> h_partials;         // pinned
     double* h_partials_dev = nullptr;     // the same buffer as the kernels see it: the last kernel of a chain writes the sums there (no D2H copy)
-    unsigned long long* h_done = nullptr; unsigned long long* h_done_dev = nullptr;   // pinned: the sequence number of the last blocking call whose sums have landed (iba_reduce2_kernel)
+    PinnedBuf<unsigned long long> h_done; unsigned long long* h_done_dev = nullptr;   // pinned: the sequence number of the last blocking call whose sums have landed (iba_reduce2_kernel)
     DevBuf<uint32_t> d_done_ctr;          // blocks of the summing kernel that have finished (reset by the last one)
     unsigned long long done_seq = 0; bool done_armed = false;   // the call in flight publishes done_seq; done_flag (IBA_DONE_FLAG=0: poll the stream as rounds 3-4 did)
     bool done_flag_on = true;
@@ -221,13 +210,13 @@ struct iba_handle {
     DevBuf<float> d_frame_box;
     struct IcpWork {
         DevBuf<double> d_src, d_part, d_mom; DevBuf<IcpXf> d_xf; DevBuf<uint32_t> d_pair;   // source cloud, wave partials, moment blocks, transforms, (frame, index) pairs
-        IcpXf* h_xf = nullptr; double* h_mom = nullptr; int pinned_B = 0;                    // pinned staging of the transforms and the moment blocks
+        PinnedBuf<IcpXf> h_xf; PinnedBuf<double> h_mom; int pinned_B = 0;               // pinned staging of the transforms and the moment blocks
     } icp;
     // iba_scan_* (iba_scan_host.hpp): the frame boxes again on the host (the pivot of an edge's point-to-point sums) and the work buffers of a pass
     std::vector<float> h_frame_box;
     struct ScanWork {
         DevBuf<double> d_part, d_mom; DevBuf<ScanXf> d_xf; DevBuf<uint32_t> d_pair;   // chunk partials, sums per edge, edges, target index per source point
-        ScanXf* h_xf = nullptr; double* h_mom = nullptr; int pinned_E = 0;           // pinned staging of the edges and their sums
+        PinnedBuf<ScanXf> h_xf; PinnedBuf<double> h_mom; int pinned_E = 0;      // pinned staging of the edges and their sums
     } scan;
     int scan_threads = 0, scan_last_threads = 0;   // iba_debug_scan_threads: a forced block shape (0: the rule); the shape of the last pass
     // iba_submap_build (iba_voxel_host.hpp): the work buffers of a call, grown on demand
@@ -518,7 +507,7 @@ iba_status compute_plane_cache(iba_handle* h) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         // the factor kernel's scan-point records: the point and the normal of its memoised LOCAL plane side by side (one cache line). An optional memo:
         // 64 B per scan point; when the allocation fails the kernel gathers from the separate arrays
-        if (!h->d_scan_rec.p && h->d_scan_rec.alloc(h->plane_cost.n) != hipSuccess) { (void)hipGetLastError(); h->d_scan_rec.p = nullptr; h->d_scan_rec.n = 0; }
+        if (!h->d_scan_rec.p && h->d_scan_rec.alloc(h->plane_cost.n) != hipSuccess) (void)hipGetLastError();
         if (h->d_scan_rec.p) {
             hipLaunchKernelGGL(iba_scanrec_kernel, dim3((unsigned)((h->plane_cost.n + 255) / 256)), dim3(256), 0, h->stream, h->pts4.p, h->plane_local_aliases_cost ? h->plane_cost.p : h->plane_local.p, h->d_scan_rec.p, h->plane_cost.n);
             HIP_TRY(h, hipGetLastError());
@@ -555,7 +544,7 @@ iba_status ensure_scratch(iba_handle* h) {
 iba_status stage_cands(iba_handle* h, const double* x, int B, hipStream_t st, Cand** d_out, const Cand* pre = nullptr, int jets = 1, const std::atomic<int>* pre_flag = nullptr, bool plan = false) {
     const int slot = h->ring_next; h->ring_next = (h->ring_next + 1) % kRing;
     if (h->ring_used[slot]) HIP_TRY(h, hipEventSynchronize(h->ring_ev[slot]));
-    Cand* hc = h->h_cands + (size_t)slot * h->chain_cap;
+    Cand* hc = h->h_cands.p + (size_t)slot * h->chain_cap;
     Cand* dc = h->d_cands.p + (size_t)slot * h->chain_cap;
     h->last_hc = hc;
     h->jets_x = nullptr; h->jets_src = nullptr; h->jets_flag = nullptr;
@@ -596,7 +585,7 @@ struct JetsCopy { const uint4* src = nullptr; uint4* dst = nullptr; uint32_t B =
 // the host side: the derivatives are computed (or taken over from the group's calling thread) into the pinned slot. false: nothing is pending
 bool prepare_jets(iba_handle* h, JetsCopy& jc) {
     if (!h->jets_x && !h->jets_src) return false;
-    Cand* hc = h->h_cands + (size_t)h->jets_slot * h->chain_cap;
+    Cand* hc = h->h_cands.p + (size_t)h->jets_slot * h->chain_cap;
     Cand* dc = h->d_cands.p + (size_t)h->jets_slot * h->chain_cap;
     if (h->jets_src) {   // the group's calling thread has been differentiating while this device's kernels ran on the values
         while (h->jets_flag->load(std::memory_order_acquire) == 0) { /* microseconds */ }
@@ -646,7 +635,7 @@ hipError_t wait_done(iba_handle* h, hipStream_t st) {
     const bool armed = h->done_armed;
     h->done_armed = false;
     if (armed && h->spin_wait) {   // (a caller that asked for blocking waits only — spin_wait = 0 — never polls: not the stream, not this word)
-        const volatile unsigned long long* f = h->h_done;
+        const volatile unsigned long long* f = h->h_done.p;
         const auto t0 = std::chrono::steady_clock::now();
         for (int polls = 1;; ++polls) {
             if (*f == h->done_seq) { std::atomic_thread_fence(std::memory_order_acquire); return hipSuccess; }
@@ -1093,22 +1082,7 @@ void iba_destroy(iba_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->frames.release(); h->slots.release(); h->xs.release(); h->ys.release(); h->zs.release(); h->perm.release(); h->inv_perm.release(); h->chunk_box.release(); h->pts4.release();
-    h->d_ffr.release(); h->d_kp_c.release(); h->d_kp_rec.release(); h->d_scan_rec.release();
-    h->nodes.release(); h->kp_uv.release(); h->kp_mp.release(); h->kp_fl.release(); h->coarse_start.release(); h->bitmap.release(); h->crec.release();
-    h->match_uv.release(); h->plane_cost.release(); h->plane_local.release(); h->plane_ok.release(); h->scratch_cost.release(); h->scratch_local.release(); h->d_assoc_frozen.release(); h->d_flist.release(); h->d_flist_frozen.release(); h->d_fcount.release(); h->d_fcount_frozen.release(); h->d_cands.release(); h->d_frame_partials.release(); h->d_partials.release(); h->d_corr.release(); h->d_he.release(); h->d_lcount.release(); h->d_lcount_frozen.release(); h->d_nn_partials.release(); h->d_frefit.release(); h->d_pairs.release(); h->d_hard.release(); h->d_pcounts.release(); h->mpk.release(); h->fkp.release(); h->kp_fl2.release(); h->d_diag.release(); h->d_anchor.release();
-    h->d_frame_box.release(); h->icp.d_src.release(); h->icp.d_part.release(); h->icp.d_mom.release(); h->icp.d_xf.release(); h->icp.d_pair.release();
-    if (h->icp.h_xf) (void)hipHostFree(h->icp.h_xf);
-    if (h->icp.h_mom) (void)hipHostFree(h->icp.h_mom);
-    h->scan.d_part.release(); h->scan.d_mom.release(); h->scan.d_xf.release(); h->scan.d_pair.release();
-    if (h->scan.h_xf) (void)hipHostFree(h->scan.h_xf);
-    if (h->scan.h_mom) (void)hipHostFree(h->scan.h_mom);
-    h->vox.d_mem.release(); h->vox.d_sub.release(); h->vox.d_part.release(); h->vox.d_bounds.release(); h->vox.d_q3.release(); h->vox.d_key[0].release(); h->vox.d_key[1].release();
-    h->vox.d_val[0].release(); h->vox.d_val[1].release(); h->vox.d_tmp.release(); h->vox.d_blockc.release(); h->vox.d_subfirst.release(); h->vox.d_seg.release(); h->vox.d_xyz.release(); h->vox.d_cnt.release();
     if (h->ev_mid) (void)hipEventDestroy(h->ev_mid);
-    if (h->h_cands) (void)hipHostFree(h->h_cands);
-    if (h->h_partials) (void)hipHostFree(h->h_partials);
-    if (h->h_done) (void)hipHostFree(h->h_done);
     for (int i = 0; i < kRing; ++i) if (h->ring_ev[i]) (void)hipEventDestroy(h->ring_ev[i]);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1481,7 +1455,7 @@ iba_status create_impl(const iba_problem_desc* d, const iba_params* params, int 
         // 512 B per (frame, keypoint): 205 MB at 200 x 2000 keypoints, linear in the keyframes. The lists are an
         // optional memo: when the allocation fails the handle runs without them (every lane searches the tree), it does not fail.
         h->anchor_set_elems = (((size_t)std::max(nf, 1) * std::max(h->maxK, 1u) * kAnchorRowBytes + sizeof(SetPt) - 1) / sizeof(SetPt) + 1 + 7) / 8 * 8;   // (a multiple of 384 B: every set starts 128-byte aligned)
-        if (h->d_anchor.alloc((size_t)kAnchorSets * h->anchor_set_elems) != hipSuccess) { (void)hipGetLastError(); h->d_anchor.p = nullptr; h->d_anchor.n = 0; h->nn_sets = false; }
+        if (h->d_anchor.alloc((size_t)kAnchorSets * h->anchor_set_elems) != hipSuccess) { (void)hipGetLastError(); h->nn_sets = false; }
     }
     if (h->common_mode > 0) {   // common lists of one batch: (scan point, keypoint) pairs and hard points per frame
         // the pairs of a batch grow with the scan density (points per pixel) and with the batch's spread: 4 per keypoint serve 10 k-point
@@ -1499,13 +1473,13 @@ iba_status create_impl(const iba_problem_desc* d, const iba_params* params, int 
     }
     if ((er = h->d_partials.alloc((size_t)h->chain_cap * kPartialStride)) != hipSuccess) return bail("alloc partials", er);
     if ((er = h->d_corr.alloc((size_t)std::max<int64_t>(h->n_keypoints, 1))) != hipSuccess) return bail("alloc corr", er);
-    if ((er = hipHostMalloc((void**)&h->h_cands, sizeof(Cand) * kRing * h->chain_cap)) != hipSuccess) return bail("hipHostMalloc", er);
-    if ((er = hipHostMalloc((void**)&h->h_partials, sizeof(double) * h->chain_cap * kPartialStride)) != hipSuccess) return bail("hipHostMalloc", er);
-    if ((er = hipHostMalloc((void**)&h->h_done, 64)) != hipSuccess) return bail("hipHostMalloc", er);
-    *h->h_done = 0ull;
-    if ((er = hipHostGetDevicePointer((void**)&h->h_done_dev, h->h_done, 0)) != hipSuccess) return bail("hipHostGetDevicePointer", er);
+    if ((er = h->h_cands.alloc((size_t)kRing * h->chain_cap)) != hipSuccess) return bail("hipHostMalloc", er);
+    if ((er = h->h_partials.alloc((size_t)h->chain_cap * kPartialStride)) != hipSuccess) return bail("hipHostMalloc", er);
+    if ((er = h->h_done.alloc(8)) != hipSuccess) return bail("hipHostMalloc", er);
+    *h->h_done.p = 0ull;
+    if ((er = hipHostGetDevicePointer((void**)&h->h_done_dev, h->h_done.p, 0)) != hipSuccess) return bail("hipHostGetDevicePointer", er);
     if ((er = h->d_done_ctr.alloc(1)) != hipSuccess || (er = hipMemset(h->d_done_ctr.p, 0, sizeof(uint32_t))) != hipSuccess) return bail("done counter", er);
-    if ((er = hipHostGetDevicePointer((void**)&h->h_partials_dev, h->h_partials, 0)) != hipSuccess || (er = hipHostGetDevicePointer((void**)&h->h_cands_dev, h->h_cands, 0)) != hipSuccess) return bail("hipHostGetDevicePointer", er);
+    if ((er = hipHostGetDevicePointer((void**)&h->h_partials_dev, h->h_partials.p, 0)) != hipSuccess || (er = hipHostGetDevicePointer((void**)&h->h_cands_dev, h->h_cands.p, 0)) != hipSuccess) return bail("hipHostGetDevicePointer", er);
     if ((er = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", er);
     if ((er = hipEventCreate(&h->ev0)) != hipSuccess || (er = hipEventCreate(&h->ev1)) != hipSuccess || (er = hipEventCreate(&h->ev2)) != hipSuccess) return bail("hipEventCreate", er);
     for (int i = 0; i < kRing; ++i) if ((er = hipEventCreateWithFlags(&h->ring_ev[i], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", er);
@@ -1543,7 +1517,6 @@ iba_status create_impl(const iba_problem_desc* d, const iba_params* params, int 
         int32_t okv = 0;
         er = hipStreamSynchronize(h->stream);
         if (er == hipSuccess) er = hipMemcpy(&okv, okb.p, sizeof(okv), hipMemcpyDeviceToHost);
-        okb.release();
         if (er != hipSuccess) return bail("kernarg probe", er);
         if (!okv) { iba_destroy(h); return fail(nullptr, IBA_ERR_UNSUPPORTED, "kernel arguments do not start at offset 0 of the kernarg segment"); }
     }
@@ -1619,7 +1592,7 @@ iba_status iba_eval_cost(iba_handle* h, const double* x, int32_t B, iba_cost_out
         iba_status s = eval_cost_partial_impl(h, x + 7 * b0, Bc, h->h_partials_dev, h->stream); if (s != IBA_OK) return s;   // the sums land in pinned host memory: no copy behind the last kernel
         HIP_TRY(h, wait_done(h, h->stream));
         if (h->timing) { HIP_TRY(h, hipEventElapsedTime(&h->last_frame_ms, h->ev0, h->ev1)); HIP_TRY(h, hipEventElapsedTime(&h->last_total_ms, h->ev0, h->ev2)); }
-        return iba_finalize_cost(&h->params, h->h_partials, Bc, out + b0);
+        return iba_finalize_cost(&h->params, h->h_partials.p, Bc, out + b0);
     });
 }
 
@@ -1705,7 +1678,7 @@ iba_status iba_x_to_sim3(const double x[7], double rigid12[12], double* scale) {
 // debug: host copy of the last summed partial blocks (B x iba_partial_stride() doubles)
 iba_status iba_debug_last_partials(iba_handle* h, double* out, int32_t B) {
     if (!h || !out || B < 1 || B > h->chain_cap) return IBA_ERR_INVALID_ARG;   // the last launch chain's block
-    std::memcpy(out, h->h_partials, sizeof(double) * B * kPartialStride);
+    std::memcpy(out, h->h_partials.p, sizeof(double) * B * kPartialStride);
     return IBA_OK;
 }
 
@@ -1828,7 +1801,6 @@ iba_status iba_debug_nn(iba_handle* h, int32_t frame, const double* q, int32_t n
     er = hipStreamSynchronize(h->stream);
     if (er == hipSuccess) er = hipMemcpy(out_idx, di.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost);
     if (er == hipSuccess) er = hipMemcpy(out_d2, dd.p, sizeof(double) * n, hipMemcpyDeviceToHost);
-    dq.release(); dd.release(); di.release();
     if (er != hipSuccess) return fail(h, IBA_ERR_HIP, hipGetErrorString(er));
     return IBA_OK;
 }
@@ -1885,8 +1857,6 @@ iba_status iba_debug_div2_selftest(int32_t device, const double* num0, const dou
     for (int i = 0; i < 4 && er == hipSuccess; ++i) er = hipMemcpy(dst[i], d[3 + i].p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost);
     unsigned long long nf = 0;
     if (er == hipSuccess) er = hipMemcpy(&nf, dn.p, sizeof(nf), hipMemcpyDeviceToHost);
-    for (auto& b : d) b.release();
-    dn.release();
     if (er != hipSuccess) return fail(nullptr, IBA_ERR_HIP, hipGetErrorString(er));
     *n_fast = (int64_t)nf;
     return IBA_OK;
@@ -1918,7 +1888,6 @@ iba_status iba_debug_knn(iba_handle* h, int32_t frame, const uint32_t* points, i
     if (er == hipSuccess) er = hipMemcpy(hi.data(), di.p, sizeof(uint32_t) * hi.size(), hipMemcpyDeviceToHost);
     if (er == hipSuccess) er = hipMemcpy(hd.data(), dd.p, sizeof(double) * hd.size(), hipMemcpyDeviceToHost);
     if (er == hipSuccess) er = hipMemcpy(hc.data(), dc.p, sizeof(int32_t) * P, hipMemcpyDeviceToHost);
-    di.release(); dd.release(); dc.release();
     if (er != hipSuccess) return fail(h, IBA_ERR_HIP, hipGetErrorString(er));
     for (int i = 0; i < n; ++i) {
         const uint32_t pos = inv[points[i]];
@@ -1952,7 +1921,7 @@ iba_status iba_eval_normal(iba_handle* h, const double* x, int32_t B, iba_normal
         iba_status s = eval_normal_partial_impl(h, x + 7 * b0, Bc, h->h_partials_dev, h->stream); if (s != IBA_OK) return s;
         HIP_TRY(h, wait_done(h, h->stream));
         if (h->timing) { HIP_TRY(h, hipEventElapsedTime(&h->last_frame_ms, h->ev0, h->ev1)); HIP_TRY(h, hipEventElapsedTime(&h->last_total_ms, h->ev0, h->ev2)); }
-        return iba_finalize_normal(&h->params, h->h_partials, Bc, out + b0);
+        return iba_finalize_normal(&h->params, h->h_partials.p, Bc, out + b0);
     });
 }
 
@@ -1977,8 +1946,8 @@ iba_status iba_eval_full(iba_handle* h, const double* x, int32_t B, iba_cost_out
     return chunked(h, B, [&](int b0, int Bc) {
         iba_status s = eval_full_partial_impl(h, x + 7 * b0, Bc, h->h_partials_dev, h->stream); if (s != IBA_OK) return s;
         HIP_TRY(h, wait_done(h, h->stream));
-        s = iba_finalize_cost(&h->params, h->h_partials, Bc, cost + b0); if (s != IBA_OK) return s;
-        return iba_finalize_normal(&h->params, h->h_partials, Bc, normal + b0);
+        s = iba_finalize_cost(&h->params, h->h_partials.p, Bc, cost + b0); if (s != IBA_OK) return s;
+        return iba_finalize_normal(&h->params, h->h_partials.p, Bc, normal + b0);
     });
 }
 
@@ -1990,7 +1959,7 @@ static iba_status build_problem_impl(iba_handle* h, const double* x, const Cand*
     s = run_split(h, dc, 1, 1, true, false, h->h_partials_dev, h->stream); if (s != IBA_OK) return s;
     h->done_armed = false;   // (waited for on the stream: the flag this chain publishes is nobody's to poll)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->frozen_frames = (int32_t)h->h_partials[P_FRAMES_N]; h->frozen_ncorr = (int32_t)h->h_partials[P_NCORR_N]; h->frozen_valid = true;
+    h->frozen_frames = (int32_t)h->h_partials.p[P_FRAMES_N]; h->frozen_ncorr = (int32_t)h->h_partials.p[P_NCORR_N]; h->frozen_valid = true;
     return IBA_OK;
 }
 iba_status iba_build_problem(iba_handle* h, const double* x) { return build_problem_impl(h, x, nullptr); }
@@ -2026,7 +1995,7 @@ iba_status iba_eval_factors(iba_handle* h, const double* x, int32_t B, iba_norma
         iba_status s = eval_factors_partial_impl(h, x + 7 * b0, Bc, h->h_partials_dev, h->stream); if (s != IBA_OK) return s;
         HIP_TRY(h, wait_stream(h, h->stream));   // (this chain ends in iba_set_slots_kernel, not in the summing kernel that publishes the flag of wait_done)
         if (h->timing) { HIP_TRY(h, hipEventElapsedTime(&h->last_frame_ms, h->ev0, h->ev1)); HIP_TRY(h, hipEventElapsedTime(&h->last_total_ms, h->ev0, h->ev2)); }
-        return iba_finalize_normal(&h->params, h->h_partials, Bc, out + b0);
+        return iba_finalize_normal(&h->params, h->h_partials.p, Bc, out + b0);
     });
 }
 
@@ -2156,7 +2125,6 @@ iba_status iba_eval_residuals(iba_handle* h, const double* x, double* r, double*
     HIP_TRY(h, hipMemcpyAsync(r, d_r.p, sizeof(double) * rows, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(J, d_J.p, sizeof(double) * rows * 7, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    d_off.release(); d_r.release(); d_J.release();
     if (block_id) std::memcpy(block_id, bid.data(), sizeof(int32_t) * rows);
     if (block_kind) std::memcpy(block_kind, bkind.data(), sizeof(int32_t) * rows);
     return IBA_OK;

@@ -34,13 +34,6 @@ std::string floam_check_options(const iba_floam_options* o) {
     return "";
 }
 
-template <class... B>
-struct FloamRelease {   // the call's device buffers, released on every path
-    std::tuple<B&...> b;
-    explicit FloamRelease(B&... x) : b(x...) {}
-    ~FloamRelease() { std::apply([](auto&... x) { (x.release(), ...); }, b); }
-};
-
 }  // namespace
 
 iba_status iba_default_floam_options(iba_floam_options* o) {
@@ -75,18 +68,16 @@ iba_status iba_floam_extract(iba_handle* h, const int32_t* frames, int32_t n, co
     }
     const int lines = opt->num_lines, S = opt->num_sectors;
     const uint32_t eslots = (uint32_t)std::max(opt->max_edges_per_sector, 1);
-    iba_floam_features* res = new iba_floam_features;
-    struct Guard { iba_floam_features* p; ~Guard() { delete p; } } guard{res};   // (released on every error path below)
+    std::unique_ptr<iba_floam_features> res(new iba_floam_features);   // (freed on every error path below)
     res->n = n; res->lines = lines;
     res->efirst.assign((size_t)n + 1, 0); res->sfirst.assign((size_t)n + 1, 0); res->stats.assign(3 * (size_t)n, 0); res->ring_points.assign((size_t)n * (size_t)lines, 0);
-    if (N == 0) { guard.p = nullptr; *out = res; return IBA_OK; }   // every scan is empty: no launch
+    if (N == 0) { *out = res.release(); return IBA_OK; }   // every scan is empty: no launch
 
     const FloamShape sh{opt->min_distance, opt->max_distance, opt->edge_curvature, opt->neighbour_gap2, lines, opt->max_edges_per_sector};
     HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t st = h->stream;
     DevBuf<FloamScan> d_scans; DevBuf<FloamBlock> d_blocks; DevBuf<FloamTask> d_tasks; DevBuf<uint32_t> d_counts, d_key[2], d_val[2], d_epos, d_spos, d_ne, d_ns; DevBuf<unsigned char> d_tmp;
     DevBuf<float4> d_rp; DevBuf<float> d_exyz, d_sxyz; DevBuf<int32_t> d_eidx, d_sidx;
-    FloamRelease rel(d_scans, d_blocks, d_tasks, d_counts, d_key[0], d_key[1], d_val[0], d_val[1], d_epos, d_spos, d_ne, d_ns, d_tmp, d_rp, d_exyz, d_sxyz, d_eidx, d_sidx);
 
     // ---- rules 1-2 and the stable partition by (scan, ring) ----
     HIP_TRY(h, d_scans.alloc((size_t)n)); HIP_TRY(h, d_blocks.alloc(blocks.size())); HIP_TRY(h, d_counts.alloc((size_t)n * kFloamBins));
@@ -141,7 +132,7 @@ iba_status iba_floam_extract(iba_handle* h, const int32_t* frames, int32_t n, co
     }
     task_first[(size_t)n] = (uint32_t)tasks.size();
     const size_t T = tasks.size();
-    if (T == 0) { guard.p = nullptr; *out = res; return IBA_OK; }   // no ring reaches min_ring_points
+    if (T == 0) { *out = res.release(); return IBA_OK; }   // no ring reaches min_ring_points
     if ((uint64_t)T * eslots > 0xFFFFFFFFull) return fail(h, IBA_ERR_UNSUPPORTED, who + "more than 2^32 edge slots in one call (split the batch)");
 
     // ---- rules 4-8 per sector, then the counts scanned ----
@@ -183,8 +174,7 @@ iba_status iba_floam_extract(iba_handle* h, const int32_t* frames, int32_t n, co
     }
     HIP_TRY(h, hipStreamSynchronize(st));
     for (int32_t i = 0; i <= n; ++i) { res->efirst[(size_t)i] = (int64_t)eoff[task_first[(size_t)i]]; res->sfirst[(size_t)i] = (int64_t)soff[task_first[(size_t)i]]; }
-    guard.p = nullptr;
-    *out = res;
+    *out = res.release();
     return IBA_OK;
 }
 

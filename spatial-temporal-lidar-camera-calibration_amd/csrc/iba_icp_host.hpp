@@ -12,13 +12,6 @@ iba_status icp_check_target(iba_handle* h, int32_t fb, int32_t fe) {
     return IBA_OK;
 }
 
-template <class T>
-hipError_t icp_grow(DevBuf<T>& b, size_t count) {
-    if (b.p && b.n >= count) return hipSuccess;
-    b.release();
-    return b.alloc(count + count / 4);
-}
-
 // threads per block of the pass kernel for this target (the rule of DESIGN.md 5b) and the bytes of its node table
 void icp_shape(const iba_handle* h, int fb, int fe, int& threads, size_t& lds) {
     uint32_t nodes = 1;
@@ -30,18 +23,16 @@ void icp_shape(const iba_handle* h, int fb, int fe, int& threads, size_t& lds) {
 iba_status icp_reserve(iba_handle* h, int n, int B, int threads, bool pairs) {
     auto& w = h->icp;
     const size_t nw = ((size_t)n + (size_t)threads - 1) / (size_t)threads * (size_t)(threads / 64);
-    HIP_TRY(h, icp_grow(w.d_src, 3 * (size_t)n));
-    HIP_TRY(h, icp_grow(w.d_part, (size_t)B * nw * kIcpSums));
-    HIP_TRY(h, icp_grow(w.d_mom, (size_t)B * kIcpMom));
-    HIP_TRY(h, icp_grow(w.d_xf, (size_t)B));
-    if (pairs) HIP_TRY(h, icp_grow(w.d_pair, 2 * (size_t)B * (size_t)n));
+    HIP_TRY(h, w.d_src.grow(3 * (size_t)n));
+    HIP_TRY(h, w.d_part.grow((size_t)B * nw * kIcpSums));
+    HIP_TRY(h, w.d_mom.grow((size_t)B * kIcpMom));
+    HIP_TRY(h, w.d_xf.grow((size_t)B));
+    if (pairs) HIP_TRY(h, w.d_pair.grow(2 * (size_t)B * (size_t)n));
     if (w.pinned_B < B) {
-        if (w.h_xf) (void)hipHostFree(w.h_xf);
-        if (w.h_mom) (void)hipHostFree(w.h_mom);
-        w.h_xf = nullptr; w.h_mom = nullptr; w.pinned_B = 0;
+        w.pinned_B = 0;
         const int cap = std::max(64, B);
-        HIP_TRY(h, hipHostMalloc((void**)&w.h_xf, sizeof(IcpXf) * (size_t)cap, hipHostMallocDefault));
-        HIP_TRY(h, hipHostMalloc((void**)&w.h_mom, sizeof(double) * kIcpMom * (size_t)cap, hipHostMallocDefault));
+        HIP_TRY(h, w.h_xf.alloc((size_t)cap));
+        HIP_TRY(h, w.h_mom.alloc(kIcpMom * (size_t)cap));
         w.pinned_B = cap;
     }
     return IBA_OK;
@@ -64,7 +55,7 @@ void icp_make_xf(const double* T16, const double c[3], double gate, IcpXf& x) {
 iba_status icp_pass(iba_handle* h, int fb, int fe, int n, int nb, int threads, size_t lds, bool pairs) {
     auto& w = h->icp;
     const hipStream_t st = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(w.d_xf.p, w.h_xf, sizeof(IcpXf) * (size_t)nb, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(w.d_xf.p, w.h_xf.p, sizeof(IcpXf) * (size_t)nb, hipMemcpyHostToDevice, st));
     const dim3 grid((unsigned)(((size_t)n + (size_t)threads - 1) / (size_t)threads), (unsigned)nb);
     uint32_t* pf = pairs ? w.d_pair.p : nullptr; uint32_t* pi = pairs ? w.d_pair.p + (size_t)nb * (size_t)n : nullptr;
     if (threads == 64) hipLaunchKernelGGL(iba_icp_pass_kernel<64>, grid, dim3(64), lds, st, h->dev_problem(), h->d_frame_box.p, fb, fe, w.d_src.p, n, w.d_xf.p, w.d_part.p, pf, pi);
@@ -72,7 +63,7 @@ iba_status icp_pass(iba_handle* h, int fb, int fe, int n, int nb, int threads, s
     HIP_TRY(h, hipGetLastError());
     hipLaunchKernelGGL(iba_icp_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, w.d_part.p, (int)(grid.x * (unsigned)(threads / 64)), w.d_xf.p, w.d_mom.p);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(w.h_mom, w.d_mom.p, sizeof(double) * kIcpMom * (size_t)nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(w.h_mom.p, w.d_mom.p, sizeof(double) * kIcpMom * (size_t)nb, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     return IBA_OK;
 }
@@ -166,9 +157,9 @@ iba_status iba_icp_step(iba_handle* h, int32_t frame_begin, int32_t frame_end, c
     auto& w = h->icp;
     HIP_TRY(h, hipMemcpyAsync(w.d_src.p, src_xyz, sizeof(double) * 3 * (size_t)n_src, hipMemcpyHostToDevice, h->stream));
     double c[3]; icp_centroid(src_xyz, n_src, c);
-    for (int b = 0; b < B; ++b) icp_make_xf(T + 16 * (size_t)b, c, max_corr_dist, w.h_xf[b]);
+    for (int b = 0; b < B; ++b) icp_make_xf(T + 16 * (size_t)b, c, max_corr_dist, w.h_xf.p[b]);
     if (const iba_status s = icp_pass(h, frame_begin, frame_end, n_src, B, threads, lds, pairs)) return s;
-    std::memcpy(moments, w.h_mom, sizeof(double) * IBA_ICP_NMOM * (size_t)B);
+    std::memcpy(moments, w.h_mom.p, sizeof(double) * IBA_ICP_NMOM * (size_t)B);
     if (pairs) {
         HIP_TRY(h, hipMemcpy(pair_frame, w.d_pair.p, sizeof(uint32_t) * (size_t)B * (size_t)n_src, hipMemcpyDeviceToHost));
         HIP_TRY(h, hipMemcpy(pair_idx, w.d_pair.p + (size_t)B * (size_t)n_src, sizeof(uint32_t) * (size_t)B * (size_t)n_src, hipMemcpyDeviceToHost));
@@ -199,8 +190,8 @@ iba_status iba_icp_register(iba_handle* h, int32_t frame_begin, int32_t frame_en
     std::vector<int> live((size_t)B);   // the starts of the current pass, in ascending order
     for (int b = 0; b < B; ++b) { std::memcpy(st[(size_t)b].T, T_init + 16 * (size_t)b, sizeof(double) * 16); st[(size_t)b].n_src = n_src; live[(size_t)b] = b; }
     const auto pass = [&](const std::vector<int>& lv, const double* Ts, const double*& mom) -> iba_status {
-        for (size_t k = 0; k < lv.size(); ++k) icp_make_xf(Ts + 16 * k, c, opt->max_corr_dist, w.h_xf[k]);
-        mom = w.h_mom;
+        for (size_t k = 0; k < lv.size(); ++k) icp_make_xf(Ts + 16 * k, c, opt->max_corr_dist, w.h_xf.p[k]);
+        mom = w.h_mom.p;
         return icp_pass(h, frame_begin, frame_end, n_src, (int)lv.size(), threads, lds, false);
     };
     const auto update = [&](const IcpItem& s, double* U4) { return iba::icp::umeyama_from_moments(s.m, opt->with_scaling != 0, U4); };

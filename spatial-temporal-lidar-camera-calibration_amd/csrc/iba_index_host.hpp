@@ -4,14 +4,13 @@
 // by index_build_device: one launch chain on the SOURCE handle's stream for all frames of the new handle (iba_index_kernels.hpp) — per tree
 // level a segment kernel, rocPRIM's segmented radix sort and a split kernel (at most kMaxTreeDepth = 11 levels), then the sort inside the
 // leaves, the gather and the boxes. Down go 32 B per frame, up come a flag word and 32 B of frame box per frame. The work buffers are of
-// the size of the clouds, live for the call only, and are released before it returns.
+// the size of the clouds and live for the call only (IdxScratch).
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 namespace {
 
 struct IdxScratch {
     DevBuf<IdxFrame> fr; DevBuf<float4> src4; DevBuf<uint32_t> order, order2, val, seg_begin, seg_end, seg_dim, flag; DevBuf<uint64_t> key, key_out; DevBuf<unsigned char> tmp;
-    ~IdxScratch() { fr.release(); src4.release(); order.release(); order2.release(); val.release(); seg_begin.release(); seg_end.release(); seg_dim.release(); flag.release(); key.release(); key_out.release(); tmp.release(); }
 };
 
 #define IDX_TRY(expr)                                                                                      \
@@ -109,9 +108,9 @@ iba_status iba_submap_handle(iba_handle* src, const iba_submap_desc* subs, int32
     *out = nullptr;
     if (!params) return fail(src, IBA_ERR_INVALID_ARG, who + "the parameters are NULL");
     if (const iba_status s = check_params(src, *params)) return s;
-    iba_submap_clouds* c = nullptr;
-    if (const iba_status s = vox_build(src, subs, M, who, false, &c)) return s;
-    struct Guard { iba_submap_clouds* p; ~Guard() { delete p; } } guard{c};
+    iba_submap_clouds* built = nullptr;
+    if (const iba_status s = vox_build(src, subs, M, who, false, &built)) return s;
+    const std::unique_ptr<iba_submap_clouds> c(built);
     // a scans-only problem of M frames: no keypoints, no covisibility, identity poses, the intrinsics of a KITTI camera (none of them is read by the scan-side entry points)
     std::vector<uint64_t> pt_off((size_t)M + 1), zeros((size_t)M + 1, 0ull);
     std::vector<uint32_t> first((size_t)M + 1);

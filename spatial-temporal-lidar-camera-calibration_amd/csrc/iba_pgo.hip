@@ -13,6 +13,7 @@
 
 #include "../../include/iba_mi355x.h"
 #include "../../include/iba_mi355x_debug.h"
+#include "iba_device_buf.hpp"
 #include "iba_internal.hpp"
 #include "iba_pgo_host.hpp"
 #include "iba_pgo_kernels.hpp"
@@ -20,18 +21,7 @@
 namespace {
 
 using namespace iba::pgo;
-
-template <class T>
-struct DBuf {
-    T* p = nullptr;
-    hipError_t alloc(size_t count) { release(); return hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T)); }
-    hipError_t upload(const std::vector<T>& v) {
-        hipError_t e = alloc(v.size());
-        if (e != hipSuccess || v.empty()) return e;
-        return hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-};
+using iba::DevBuf;
 
 thread_local std::string t_err;
 
@@ -55,9 +45,9 @@ struct iba_pgo {
     int cur = 0;                 // poses[cur] are the poses, poses[1 - cur] the trial
     bool linearized = false;
     int nbE = 0, nbN = 0;
-    DBuf<double> poses[2], Xinv, info, weight, zeta, A, g, epart, D, b, npart, G, F, y, delta, upart, run_S, run_b, S, rhs, xs, scal;
-    DBuf<int32_t> d_src, d_tgt, inc_off, inc_edge, chain, run_first, run_last, sep_node, sep_of_node, brow, bcol, boff, kind, idx;
-    DBuf<uint8_t> d_flags;
+    DevBuf<double> poses[2], Xinv, info, weight, zeta, A, g, epart, D, b, npart, G, F, y, delta, upart, run_S, run_b, S, rhs, xs, scal;
+    DevBuf<int32_t> d_src, d_tgt, inc_off, inc_edge, chain, run_first, run_last, sep_node, sep_of_node, brow, bcol, boff, kind, idx;
+    DevBuf<uint8_t> d_flags;
     std::vector<uint8_t> trace;
     std::string err;
     hipStream_t stream = nullptr;
@@ -231,11 +221,6 @@ const char* iba_pgo_last_error(const iba_pgo* pg) { return pg ? pg->err.c_str() 
 void iba_pgo_destroy(iba_pgo* pg) {
     if (!pg) return;
     (void)hipSetDevice(pg->device);
-    for (DBuf<double>* d : {&pg->poses[0], &pg->poses[1], &pg->Xinv, &pg->info, &pg->weight, &pg->zeta, &pg->A, &pg->g, &pg->epart, &pg->D, &pg->b, &pg->npart, &pg->G, &pg->F, &pg->y,
-                            &pg->delta, &pg->upart, &pg->run_S, &pg->run_b, &pg->S, &pg->rhs, &pg->xs, &pg->scal}) d->release();
-    for (DBuf<int32_t>* d : {&pg->d_src, &pg->d_tgt, &pg->inc_off, &pg->inc_edge, &pg->chain, &pg->run_first, &pg->run_last, &pg->sep_node, &pg->sep_of_node, &pg->brow, &pg->bcol,
-                             &pg->boff, &pg->kind, &pg->idx}) d->release();
-    pg->d_flags.release();
     if (pg->stream) (void)hipStreamDestroy(pg->stream);
     delete pg;
 }

@@ -1,4 +1,4 @@
-// Host side of the Scan Context entry points (include/iba_mi355x.h; included at the end of iba_capi.hip, after iba_icp_host.hpp whose icp_grow it uses).
+// Host side of the Scan Context entry points (include/iba_mi355x.h; included at the end of iba_capi.hip, whose handle and HIP_TRY it uses).
 // iba_sc_describe: one launch chain on the handle's stream (memset of the bins, bins kernel, finalise kernel) and one synchronise; down go the node ->
 // frame list and the slice list (4 + 8 B per entry), nothing comes up. The database owns its device arrays and a stream of its own, so it outlives the
 // handle. iba_sc_detect: queries down (16 B each), search -> distances -> pick on the database's stream, one synchronise, the results up (240 B each).
@@ -14,11 +14,6 @@ struct iba_sc_db {
     // work buffers of the calls on this database, grown on demand
     DevBuf<iba_sc_query> d_q; DevBuf<int32_t> d_cand, d_pairs, d_shift; DevBuf<double> d_dist; DevBuf<iba_sc_result> d_res;
     std::string err;
-    ~iba_sc_db() {
-        desc.release(); ring_key.release(); sector_key.release(); col_norm.release(); ring_key_f.release(); skipped.release();
-        d_q.release(); d_cand.release(); d_pairs.release(); d_shift.release(); d_dist.release(); d_res.release();
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace {
@@ -28,15 +23,6 @@ constexpr int kScMaxQueries = 65536;
 constexpr int kScMaxPairs = 1 << 20;
 
 iba_status sc_fail(iba_sc_db* db, iba_status s, const std::string& msg) { if (db) db->err = msg; else g_create_error = msg; return s; }
-
-#define SC_HIP_TRY(db, expr)                                                                               \
-    do {                                                                                                   \
-        hipError_t _e = (expr);                                                                            \
-        if (_e != hipSuccess) {                                                                            \
-            (db)->err = std::string(#expr) + ": " + hipGetErrorString(_e);                                 \
-            return (_e == hipErrorNoDevice || _e == hipErrorInvalidDevice) ? IBA_ERR_NO_DEVICE : IBA_ERR_HIP; \
-        }                                                                                                  \
-    } while (0)
 
 // "" when the options are inside the supported range
 std::string sc_check_options(const iba_sc_options* o) {
@@ -78,7 +64,7 @@ iba_status sc_launch_distance(iba_sc_db* db, const ScShape& sh, const int32_t* d
     const size_t lds = sc_distance_lds(sh.R, sh.S, staged);
     if (staged) hipLaunchKernelGGL(iba_sc_distance_kernel<true>, dim3(n_blocks), dim3(64), lds, db->stream, db->desc.p, db->sector_key.p, db->col_norm.p, d_pairs, d_q, d_cand, sh, d_dist, d_shift);
     else hipLaunchKernelGGL(iba_sc_distance_kernel<false>, dim3(n_blocks), dim3(64), lds, db->stream, db->desc.p, db->sector_key.p, db->col_norm.p, d_pairs, d_q, d_cand, sh, d_dist, d_shift);
-    SC_HIP_TRY(db, hipGetLastError());
+    HIP_TRY(db, hipGetLastError());
     return IBA_OK;
 }
 
@@ -98,6 +84,7 @@ int32_t iba_sc_db_size(const iba_sc_db* db) { return db ? db->n : 0; }
 void iba_sc_db_free(iba_sc_db* db) {
     if (!db) return;
     (void)hipSetDevice(db->device);
+    if (db->stream) (void)hipStreamDestroy(db->stream);
     delete db;
 }
 
@@ -142,14 +129,12 @@ iba_status iba_sc_describe(iba_handle* h, const int32_t* frames, int32_t n, cons
     const size_t nb = (size_t)sh.R * (size_t)sh.S;
 
     HIP_TRY(h, hipSetDevice(h->device));
-    iba_sc_db* db = new iba_sc_db;
-    struct Guard { iba_sc_db* p; ~Guard() { delete p; } } guard{db};   // (released on every error path below)
+    std::unique_ptr<iba_sc_db, decltype(&iba_sc_db_free)> db(new iba_sc_db, iba_sc_db_free);   // (freed on every error path below)
     db->device = h->device; db->n = n; db->R = sh.R; db->S = sh.S; db->max_radius = sh.max_radius; db->lidar_height = sh.lidar_height;
     HIP_TRY(h, hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking));
     HIP_TRY(h, db->desc.alloc((size_t)n * nb)); HIP_TRY(h, db->ring_key.alloc((size_t)n * sh.R)); HIP_TRY(h, db->ring_key_f.alloc((size_t)n * sh.R));
     HIP_TRY(h, db->sector_key.alloc((size_t)n * sh.S)); HIP_TRY(h, db->col_norm.alloc((size_t)n * sh.S)); HIP_TRY(h, db->skipped.alloc((size_t)n));
     DevBuf<uint32_t> d_bins; DevBuf<int32_t> d_frames; DevBuf<ScBlock> d_blocks;
-    struct Work { DevBuf<uint32_t>& a; DevBuf<int32_t>& b; DevBuf<ScBlock>& c; ~Work() { a.release(); b.release(); c.release(); } } work{d_bins, d_frames, d_blocks};
     HIP_TRY(h, d_bins.alloc((size_t)n * nb)); HIP_TRY(h, d_frames.alloc((size_t)n)); HIP_TRY(h, d_blocks.alloc(blocks.size()));
     const hipStream_t st = h->stream;
     HIP_TRY(h, hipMemcpyAsync(d_frames.p, frames, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
@@ -164,8 +149,7 @@ iba_status iba_sc_describe(iba_handle* h, const int32_t* frames, int32_t n, cons
     hipLaunchKernelGGL(iba_sc_finalize_kernel, dim3((unsigned)n), dim3(64), 0, st, d_bins.p, sh, db->desc.p, db->ring_key.p, db->ring_key_f.p, db->sector_key.p, db->col_norm.p);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(st));
-    guard.p = nullptr;
-    *out = db;
+    *out = db.release();
     return IBA_OK;
 }
 
@@ -174,15 +158,15 @@ iba_status iba_sc_db_read(iba_sc_db* db, int32_t first, int32_t count, double* d
     if (first < 0 || count < 0 || (int64_t)first + count > db->n)
         return sc_fail(db, IBA_ERR_INVALID_ARG, "iba_sc_db_read: nodes [" + std::to_string(first) + ", " + std::to_string((int64_t)first + count) + ") are outside the database's " + std::to_string(db->n));
     if (count == 0) return IBA_OK;
-    SC_HIP_TRY(db, hipSetDevice(db->device));
+    HIP_TRY(db, hipSetDevice(db->device));
     const size_t nb = (size_t)db->R * (size_t)db->S, f = (size_t)first, c = (size_t)count;
     std::vector<uint32_t> sk;
-    if (desc) SC_HIP_TRY(db, hipMemcpyAsync(desc, db->desc.p + f * nb, sizeof(double) * c * nb, hipMemcpyDeviceToHost, db->stream));
-    if (ring_key) SC_HIP_TRY(db, hipMemcpyAsync(ring_key, db->ring_key.p + f * db->R, sizeof(double) * c * db->R, hipMemcpyDeviceToHost, db->stream));
-    if (ring_key_f) SC_HIP_TRY(db, hipMemcpyAsync(ring_key_f, db->ring_key_f.p + f * db->R, sizeof(float) * c * db->R, hipMemcpyDeviceToHost, db->stream));
-    if (sector_key) SC_HIP_TRY(db, hipMemcpyAsync(sector_key, db->sector_key.p + f * db->S, sizeof(double) * c * db->S, hipMemcpyDeviceToHost, db->stream));
-    if (n_skipped) { sk.resize(c); SC_HIP_TRY(db, hipMemcpyAsync(sk.data(), db->skipped.p + f, sizeof(uint32_t) * c, hipMemcpyDeviceToHost, db->stream)); }
-    SC_HIP_TRY(db, hipStreamSynchronize(db->stream));
+    if (desc) HIP_TRY(db, hipMemcpyAsync(desc, db->desc.p + f * nb, sizeof(double) * c * nb, hipMemcpyDeviceToHost, db->stream));
+    if (ring_key) HIP_TRY(db, hipMemcpyAsync(ring_key, db->ring_key.p + f * db->R, sizeof(double) * c * db->R, hipMemcpyDeviceToHost, db->stream));
+    if (ring_key_f) HIP_TRY(db, hipMemcpyAsync(ring_key_f, db->ring_key_f.p + f * db->R, sizeof(float) * c * db->R, hipMemcpyDeviceToHost, db->stream));
+    if (sector_key) HIP_TRY(db, hipMemcpyAsync(sector_key, db->sector_key.p + f * db->S, sizeof(double) * c * db->S, hipMemcpyDeviceToHost, db->stream));
+    if (n_skipped) { sk.resize(c); HIP_TRY(db, hipMemcpyAsync(sk.data(), db->skipped.p + f, sizeof(uint32_t) * c, hipMemcpyDeviceToHost, db->stream)); }
+    HIP_TRY(db, hipStreamSynchronize(db->stream));
     if (n_skipped) for (size_t i = 0; i < c; ++i) n_skipped[i] = (int64_t)sk[i];
     return IBA_OK;
 }
@@ -197,13 +181,13 @@ iba_status iba_sc_distance(iba_sc_db* db, const int32_t* pairs, int32_t P, const
         if (pairs[p] < 0 || pairs[p] >= db->n)
             return sc_fail(db, IBA_ERR_INVALID_ARG, who + "pair " + std::to_string(p / 2) + " names node " + std::to_string(pairs[p]) + " outside the database's " + std::to_string(db->n) + " nodes");
     const ScShape sh = sc_shape(*opt);
-    SC_HIP_TRY(db, hipSetDevice(db->device));
-    SC_HIP_TRY(db, icp_grow(db->d_pairs, 2 * (size_t)P)); SC_HIP_TRY(db, icp_grow(db->d_dist, (size_t)P)); SC_HIP_TRY(db, icp_grow(db->d_shift, (size_t)P));
-    SC_HIP_TRY(db, hipMemcpyAsync(db->d_pairs.p, pairs, sizeof(int32_t) * 2 * (size_t)P, hipMemcpyHostToDevice, db->stream));
+    HIP_TRY(db, hipSetDevice(db->device));
+    HIP_TRY(db, db->d_pairs.grow(2 * (size_t)P)); HIP_TRY(db, db->d_dist.grow((size_t)P)); HIP_TRY(db, db->d_shift.grow((size_t)P));
+    HIP_TRY(db, hipMemcpyAsync(db->d_pairs.p, pairs, sizeof(int32_t) * 2 * (size_t)P, hipMemcpyHostToDevice, db->stream));
     if (const iba_status s = sc_launch_distance(db, sh, db->d_pairs.p, nullptr, nullptr, (unsigned)P, db->d_dist.p, db->d_shift.p)) return s;
-    SC_HIP_TRY(db, hipMemcpyAsync(dist, db->d_dist.p, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, db->stream));
-    SC_HIP_TRY(db, hipMemcpyAsync(shift, db->d_shift.p, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, db->stream));
-    SC_HIP_TRY(db, hipStreamSynchronize(db->stream));
+    HIP_TRY(db, hipMemcpyAsync(dist, db->d_dist.p, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, db->stream));
+    HIP_TRY(db, hipMemcpyAsync(shift, db->d_shift.p, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, db->stream));
+    HIP_TRY(db, hipStreamSynchronize(db->stream));
     return IBA_OK;
 }
 
@@ -221,16 +205,16 @@ iba_status iba_sc_detect(iba_sc_db* db, const iba_sc_query* queries, int32_t Q, 
     }
     const ScShape sh = sc_shape(*opt);
     const size_t QK = (size_t)Q * (size_t)sh.k;
-    SC_HIP_TRY(db, hipSetDevice(db->device));
-    SC_HIP_TRY(db, icp_grow(db->d_q, (size_t)Q)); SC_HIP_TRY(db, icp_grow(db->d_cand, QK)); SC_HIP_TRY(db, icp_grow(db->d_dist, QK)); SC_HIP_TRY(db, icp_grow(db->d_shift, QK));
-    SC_HIP_TRY(db, icp_grow(db->d_res, (size_t)Q));
-    SC_HIP_TRY(db, hipMemcpyAsync(db->d_q.p, queries, sizeof(iba_sc_query) * (size_t)Q, hipMemcpyHostToDevice, db->stream));
+    HIP_TRY(db, hipSetDevice(db->device));
+    HIP_TRY(db, db->d_q.grow((size_t)Q)); HIP_TRY(db, db->d_cand.grow(QK)); HIP_TRY(db, db->d_dist.grow(QK)); HIP_TRY(db, db->d_shift.grow(QK));
+    HIP_TRY(db, db->d_res.grow((size_t)Q));
+    HIP_TRY(db, hipMemcpyAsync(db->d_q.p, queries, sizeof(iba_sc_query) * (size_t)Q, hipMemcpyHostToDevice, db->stream));
     hipLaunchKernelGGL(iba_sc_knn_kernel, dim3((unsigned)Q), dim3(64), 0, db->stream, db->ring_key_f.p, db->d_q.p, sh, db->d_cand.p);
-    SC_HIP_TRY(db, hipGetLastError());
+    HIP_TRY(db, hipGetLastError());
     if (const iba_status s = sc_launch_distance(db, sh, nullptr, db->d_q.p, db->d_cand.p, (unsigned)QK, db->d_dist.p, db->d_shift.p)) return s;
     hipLaunchKernelGGL(iba_sc_pick_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, db->stream, db->d_q.p, db->d_cand.p, db->d_dist.p, db->d_shift.p, sh, (int)Q, db->d_res.p);
-    SC_HIP_TRY(db, hipGetLastError());
-    SC_HIP_TRY(db, hipMemcpyAsync(out, db->d_res.p, sizeof(iba_sc_result) * (size_t)Q, hipMemcpyDeviceToHost, db->stream));
-    SC_HIP_TRY(db, hipStreamSynchronize(db->stream));
+    HIP_TRY(db, hipGetLastError());
+    HIP_TRY(db, hipMemcpyAsync(out, db->d_res.p, sizeof(iba_sc_result) * (size_t)Q, hipMemcpyDeviceToHost, db->stream));
+    HIP_TRY(db, hipStreamSynchronize(db->stream));
     return IBA_OK;
 }

@@ -1,7 +1,7 @@
 // Host side of iba_scan_step / iba_scan_register / iba_scan_information (include/iba_mi355x.h; included at the end of iba_capi.hip, after
 // iba_icp_host.hpp whose loop and helpers it uses). A pass = the transforms of the edges still running copied to the device from pinned
 // memory, iba_scan_pass_kernel, iba_scan_sum_kernel, the sums copied back to pinned memory, ONE stream synchronise for all edges: 160 B down
-// and 256 B up per edge and iteration, nothing of scan size. The buffers live in the handle, only grow, and are released in iba_destroy.
+// and 256 B up per edge and iteration, nothing of scan size. The buffers live in the handle and only grow.
 
 namespace {
 
@@ -32,15 +32,13 @@ bool scan_dist_ok(double d) { return d > 0.0 && std::isfinite(d); }
 
 iba_status scan_reserve_edges(iba_handle* h, int nb) {
     auto& w = h->scan;
-    HIP_TRY(h, icp_grow(w.d_xf, (size_t)nb));
-    HIP_TRY(h, icp_grow(w.d_mom, (size_t)nb * kScanMom));
+    HIP_TRY(h, w.d_xf.grow((size_t)nb));
+    HIP_TRY(h, w.d_mom.grow((size_t)nb * kScanMom));
     if (w.pinned_E < nb) {
-        if (w.h_xf) (void)hipHostFree(w.h_xf);
-        if (w.h_mom) (void)hipHostFree(w.h_mom);
-        w.h_xf = nullptr; w.h_mom = nullptr; w.pinned_E = 0;
+        w.pinned_E = 0;
         const int cap = std::max(64, nb + nb / 4);
-        HIP_TRY(h, hipHostMalloc((void**)&w.h_xf, sizeof(ScanXf) * (size_t)cap, hipHostMallocDefault));
-        HIP_TRY(h, hipHostMalloc((void**)&w.h_mom, sizeof(double) * kScanMom * (size_t)cap, hipHostMallocDefault));
+        HIP_TRY(h, w.h_xf.alloc((size_t)cap));
+        HIP_TRY(h, w.h_mom.alloc(kScanMom * (size_t)cap));
         w.pinned_E = cap;
     }
     return IBA_OK;
@@ -67,18 +65,18 @@ iba_status scan_pass(iba_handle* h, int nb, int mode, int threads, bool pairs) {
     auto& w = h->scan;
     const hipStream_t st = h->stream;
     uint32_t nodes = 1;
-    for (int k = 0; k < nb; ++k) nodes = std::max(nodes, (1u << h->h_frames[(size_t)w.h_xf[k].tgt].depth) - 1u);
+    for (int k = 0; k < nb; ++k) nodes = std::max(nodes, (1u << h->h_frames[(size_t)w.h_xf.p[k].tgt].depth) - 1u);
     const size_t lds = 8u * (size_t)nodes;
     if (threads != 64 && threads != 256) threads = h->scan_threads ? h->scan_threads : (lds <= 6144u ? 64 : 256);
     uint64_t blocks = 0, chunks = 0;
     for (int k = 0; k < nb; ++k) {
-        const uint32_t P = h->h_frames[(size_t)w.h_xf[k].src].P;
-        w.h_xf[k].blk0 = (uint32_t)blocks; w.h_xf[k].part0 = (uint32_t)chunks;
+        const uint32_t P = h->h_frames[(size_t)w.h_xf.p[k].src].P;
+        w.h_xf.p[k].blk0 = (uint32_t)blocks; w.h_xf.p[k].part0 = (uint32_t)chunks;
         blocks += (P + (uint32_t)threads - 1u) / (uint32_t)threads; chunks += (P + 63u) / 64u;
     }
     if (blocks > 0x7FFFFFFFull) return fail(h, IBA_ERR_UNSUPPORTED, "iba_scan: the batch needs more blocks than one launch takes");
-    HIP_TRY(h, icp_grow(w.d_part, (size_t)chunks * 31u));
-    HIP_TRY(h, hipMemcpyAsync(w.d_xf.p, w.h_xf, sizeof(ScanXf) * (size_t)nb, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, w.d_part.grow((size_t)chunks * 31u));
+    HIP_TRY(h, hipMemcpyAsync(w.d_xf.p, w.h_xf.p, sizeof(ScanXf) * (size_t)nb, hipMemcpyHostToDevice, st));
     uint32_t* pp = pairs ? w.d_pair.p : nullptr;
     const unsigned nblk = (unsigned)blocks;
     if (threads == 64) {
@@ -91,7 +89,7 @@ iba_status scan_pass(iba_handle* h, int nb, int mode, int threads, bool pairs) {
     else if (mode == kScanP2L) hipLaunchKernelGGL(iba_scan_sum_kernel<kScanP2L>, dim3((unsigned)nb), dim3(256), 0, st, h->dev_problem(), w.d_part.p, w.d_xf.p, w.d_mom.p);
     else hipLaunchKernelGGL(iba_scan_sum_kernel<kScanInfo>, dim3((unsigned)nb), dim3(256), 0, st, h->dev_problem(), w.d_part.p, w.d_xf.p, w.d_mom.p);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(w.h_mom, w.d_mom.p, sizeof(double) * kScanMom * (size_t)nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(w.h_mom.p, w.d_mom.p, sizeof(double) * kScanMom * (size_t)nb, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     h->scan_last_threads = threads;
     return IBA_OK;
@@ -102,8 +100,8 @@ iba_status scan_stage(iba_handle* h, const iba_scan_edge* edges, const std::vect
     auto& w = h->scan;
     for (int e : run) { st[(size_t)e].iterations = 0; st[(size_t)e].status = IBA_ICP_MAX_ITER; }
     const auto pass = [&](const std::vector<int>& lv, const double* Ts, const double*& mom) -> iba_status {
-        for (size_t k = 0; k < lv.size(); ++k) scan_make_xf(h, edges[lv[k]].src_frame, edges[lv[k]].tgt_frame, Ts + 16 * k, dist, w.h_xf[k]);
-        mom = w.h_mom;
+        for (size_t k = 0; k < lv.size(); ++k) scan_make_xf(h, edges[lv[k]].src_frame, edges[lv[k]].tgt_frame, Ts + 16 * k, dist, w.h_xf.p[k]);
+        mom = w.h_mom.p;
         return scan_pass(h, (int)lv.size(), estimation, 0, false);
     };
     const auto update = [&](const IcpItem& s, double* U4) {
@@ -142,16 +140,16 @@ iba_status iba_scan_step(iba_handle* h, const iba_scan_edge* edges, int32_t E, d
     if (const iba_status s = scan_reserve_edges(h, (int)run.size())) return s;
     auto& w = h->scan;
     if (pair_idx) {
-        HIP_TRY(h, icp_grow(w.d_pair, (size_t)n_pair));
+        HIP_TRY(h, w.d_pair.grow((size_t)n_pair));
         HIP_TRY(h, hipMemsetAsync(w.d_pair.p, 0xFF, sizeof(uint32_t) * n_pair, h->stream));
     }
     for (size_t k = 0; k < run.size(); ++k) {
         const iba_scan_edge& g = edges[run[k]];
-        scan_make_xf(h, g.src_frame, g.tgt_frame, g.T, max_corr_dist, w.h_xf[k]);
-        w.h_xf[k].pair0 = pair0[(size_t)run[k]];
+        scan_make_xf(h, g.src_frame, g.tgt_frame, g.T, max_corr_dist, w.h_xf.p[k]);
+        w.h_xf.p[k].pair0 = pair0[(size_t)run[k]];
     }
     if (const iba_status s = scan_pass(h, (int)run.size(), estimation, 0, pair_idx != nullptr)) return s;
-    for (size_t k = 0; k < run.size(); ++k) std::memcpy(moments + (size_t)IBA_SCAN_NMOM * (size_t)run[k], w.h_mom + (size_t)kScanMom * k, sizeof(double) * kScanMom);
+    for (size_t k = 0; k < run.size(); ++k) std::memcpy(moments + (size_t)IBA_SCAN_NMOM * (size_t)run[k], w.h_mom.p + (size_t)kScanMom * k, sizeof(double) * kScanMom);
     if (pair_idx) HIP_TRY(h, hipMemcpy(pair_idx, w.d_pair.p, sizeof(uint32_t) * n_pair, hipMemcpyDeviceToHost));
     return IBA_OK;
 }
@@ -169,10 +167,10 @@ iba_status iba_scan_information(iba_handle* h, const iba_scan_edge* edges, int32
     HIP_TRY(h, hipSetDevice(h->device));
     if (const iba_status s = scan_reserve_edges(h, (int)run.size())) return s;
     auto& w = h->scan;
-    for (size_t k = 0; k < run.size(); ++k) scan_make_xf(h, edges[run[k]].src_frame, edges[run[k]].tgt_frame, edges[run[k]].T, max_dist, w.h_xf[k]);
+    for (size_t k = 0; k < run.size(); ++k) scan_make_xf(h, edges[run[k]].src_frame, edges[run[k]].tgt_frame, edges[run[k]].T, max_dist, w.h_xf.p[k]);
     if (const iba_status s = scan_pass(h, (int)run.size(), kScanInfo, 0, false)) return s;
     for (size_t k = 0; k < run.size(); ++k) {
-        const double* m = w.h_mom + (size_t)kScanMom * k;
+        const double* m = w.h_mom.p + (size_t)kScanMom * k;
         iba::icp::information_from_sums(m, info + 36 * (size_t)run[k]);
         n_pairs[run[k]] = (int32_t)m[0];
     }
@@ -212,10 +210,10 @@ iba_status iba_scan_register(iba_handle* h, const iba_scan_edge* edges, int32_t 
     }
     if (o->info_dist > 0.0 && !run.empty()) {   // GetInformationMatrixFromPointClouds at the final transforms, all edges in one pass
         auto& w = h->scan;
-        for (size_t k = 0; k < run.size(); ++k) scan_make_xf(h, edges[run[k]].src_frame, edges[run[k]].tgt_frame, st[(size_t)run[k]].T, o->info_dist, w.h_xf[k]);
+        for (size_t k = 0; k < run.size(); ++k) scan_make_xf(h, edges[run[k]].src_frame, edges[run[k]].tgt_frame, st[(size_t)run[k]].T, o->info_dist, w.h_xf.p[k]);
         if (const iba_status s = scan_pass(h, (int)run.size(), kScanInfo, 0, false)) return s;
         for (size_t k = 0; k < run.size(); ++k) {
-            const double* m = w.h_mom + (size_t)kScanMom * k;
+            const double* m = w.h_mom.p + (size_t)kScanMom * k;
             iba::icp::information_from_sums(m, out[run[k]].info);
             out[run[k]].n_info = (int32_t)m[0];
         }

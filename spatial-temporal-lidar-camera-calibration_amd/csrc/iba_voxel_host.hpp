@@ -1,8 +1,8 @@
-// Host side of iba_submap_build (include/iba_mi355x.h; included at the end of iba_capi.hip, after iba_icp_host.hpp whose icp_grow it uses).
+// Host side of iba_submap_build (include/iba_mi355x.h; included at the end of iba_capi.hip, whose handle it uses).
 // One call = one launch chain for the whole batch of sub-maps (iba_voxel_kernels.hpp) with three synchronisations: after the bounds (the
 // extent is checked and the key fields are sized on the host), after the count of the voxels (the outputs are sized) and at the end. Down go
 // the member and sub-map blocks (128 B per member, 152 B per sub-map), up come the bounds (56 B per sub-map) and the voxel clouds: nothing of
-// input-scan size crosses PCIe. The work buffers live in the handle (h->vox), only grow, and are released in iba_destroy.
+// input-scan size crosses PCIe. The work buffers live in the handle (h->vox) and only grow.
 #include <rocprim/device/device_radix_sort.hpp>
 
 struct iba_submap_clouds {
@@ -75,19 +75,18 @@ iba_status vox_build(iba_handle* h, const iba_submap_desc* subs, int32_t M, cons
         }
         S.blk1 = (uint32_t)blocks;
     }
-    iba_submap_clouds* res = new iba_submap_clouds;
+    std::unique_ptr<iba_submap_clouds> res(new iba_submap_clouds);   // (freed on every error path below)
     res->M = M; res->first.assign((size_t)M + 1, 0); res->dropped.assign((size_t)M, 0);
-    if (N == 0) { *out = res; return IBA_OK; }   // every member is an empty scan: zero voxels, no launch
+    if (N == 0) { *out = res.release(); return IBA_OK; }   // every member is an empty scan: zero voxels, no launch
 
-    struct Guard { iba_submap_clouds* p; ~Guard() { delete p; } } guard{res};   // (released on every error path below)
     HIP_TRY(h, hipSetDevice(h->device));
     auto& w = h->vox;
     const hipStream_t st = h->stream;
-    HIP_TRY(h, icp_grow(w.d_mem, mem.size()));
-    HIP_TRY(h, icp_grow(w.d_sub, (size_t)M));
-    HIP_TRY(h, icp_grow(w.d_part, (size_t)blocks));
-    HIP_TRY(h, icp_grow(w.d_bounds, (size_t)M));
-    HIP_TRY(h, icp_grow(w.d_q3, 3 * (size_t)N));
+    HIP_TRY(h, w.d_mem.grow(mem.size()));
+    HIP_TRY(h, w.d_sub.grow((size_t)M));
+    HIP_TRY(h, w.d_part.grow((size_t)blocks));
+    HIP_TRY(h, w.d_bounds.grow((size_t)M));
+    HIP_TRY(h, w.d_q3.grow(3 * (size_t)N));
     HIP_TRY(h, hipMemcpyAsync(w.d_mem.p, mem.data(), sizeof(VoxMember) * mem.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(h, hipMemcpyAsync(w.d_sub.p, sub.data(), sizeof(VoxSub) * (size_t)M, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(iba_vox_transform_kernel, dim3((unsigned)blocks), dim3(kVoxThreads), 0, st, h->frames.p, h->pts4.p, h->inv_perm.p, w.d_mem.p, (int)mem.size(), w.d_q3.p, w.d_part.p);
@@ -116,13 +115,13 @@ iba_status vox_build(iba_handle* h, const iba_submap_desc* subs, int32_t M, cons
             imax[a] = std::max(imax[a], (uint64_t)top);
         }
     }
-    if (n_kept == 0) { guard.p = nullptr; *out = res; return IBA_OK; }   // nothing but dropped points
+    if (n_kept == 0) { *out = res.release(); return IBA_OK; }   // nothing but dropped points
     VoxBits bits{};
     bits.y_shift = vox_bits(imax[2]); bits.x_shift = bits.y_shift + vox_bits(imax[1]); bits.sub_shift = bits.x_shift + vox_bits(imax[0]);
     const unsigned end_bit = (unsigned)(bits.sub_shift + vox_bits((uint64_t)M));   // (sub-map M is the key of the dropped points; at most 51 + 13 bits)
 
-    HIP_TRY(h, icp_grow(w.d_key[0], (size_t)N)); HIP_TRY(h, icp_grow(w.d_key[1], (size_t)N));
-    HIP_TRY(h, icp_grow(w.d_val[0], (size_t)N)); HIP_TRY(h, icp_grow(w.d_val[1], (size_t)N));
+    HIP_TRY(h, w.d_key[0].grow((size_t)N)); HIP_TRY(h, w.d_key[1].grow((size_t)N));
+    HIP_TRY(h, w.d_val[0].grow((size_t)N)); HIP_TRY(h, w.d_val[1].grow((size_t)N));
     HIP_TRY(h, hipMemcpyAsync(w.d_sub.p, sub.data(), sizeof(VoxSub) * (size_t)M, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(iba_vox_key_kernel, dim3((unsigned)blocks), dim3(kVoxThreads), 0, st, h->frames.p, w.d_mem.p, (int)mem.size(), w.d_sub.p, (int)M, bits, w.d_q3.p, w.d_key[0].p, w.d_val[0].p);
     HIP_TRY(h, hipGetLastError());
@@ -130,7 +129,7 @@ iba_status vox_build(iba_handle* h, const iba_submap_desc* subs, int32_t M, cons
     rocprim::double_buffer<uint32_t> vb(w.d_val[0].p, w.d_val[1].p);
     size_t tmp_bytes = 0;
     HIP_TRY(h, rocprim::radix_sort_pairs(nullptr, tmp_bytes, kb, vb, (size_t)N, 0u, end_bit, st));
-    HIP_TRY(h, icp_grow(w.d_tmp, tmp_bytes));
+    HIP_TRY(h, w.d_tmp.grow(tmp_bytes));
     tmp_bytes = w.d_tmp.n;
     HIP_TRY(h, rocprim::radix_sort_pairs((void*)w.d_tmp.p, tmp_bytes, kb, vb, (size_t)N, 0u, end_bit, st));
     const uint64_t* keys = kb.current();
@@ -138,8 +137,8 @@ iba_status vox_build(iba_handle* h, const iba_submap_desc* subs, int32_t M, cons
 
     // ---- heads, slots, averages ----
     const uint32_t nhb = (uint32_t)((n_kept + (uint64_t)kVoxHeadBlock - 1) / (uint64_t)kVoxHeadBlock);
-    HIP_TRY(h, icp_grow(w.d_blockc, (size_t)nhb + 1));
-    HIP_TRY(h, icp_grow(w.d_subfirst, (size_t)M + 1));
+    HIP_TRY(h, w.d_blockc.grow((size_t)nhb + 1));
+    HIP_TRY(h, w.d_subfirst.grow((size_t)M + 1));
     hipLaunchKernelGGL(iba_vox_count_heads_kernel, dim3(nhb), dim3(kVoxThreads), 0, st, keys, n_kept, w.d_blockc.p);
     HIP_TRY(h, hipGetLastError());
     hipLaunchKernelGGL(iba_vox_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, w.d_blockc.p, nhb, w.d_blockc.p + nhb);
@@ -148,9 +147,9 @@ iba_status vox_build(iba_handle* h, const iba_submap_desc* subs, int32_t M, cons
     HIP_TRY(h, hipMemcpyAsync(&V, w.d_blockc.p + nhb, sizeof(V), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     if (V == 0 || (uint64_t)V > n_kept) return fail(h, IBA_ERR_HIP, who + "the voxel count came back outside (0, kept points]");
-    HIP_TRY(h, icp_grow(w.d_seg, (size_t)V));
-    HIP_TRY(h, icp_grow(w.d_xyz, 3 * (size_t)V));
-    HIP_TRY(h, icp_grow(w.d_cnt, (size_t)V));
+    HIP_TRY(h, w.d_seg.grow((size_t)V));
+    HIP_TRY(h, w.d_xyz.grow(3 * (size_t)V));
+    HIP_TRY(h, w.d_cnt.grow((size_t)V));
     HIP_TRY(h, hipMemsetAsync(w.d_subfirst.p, 0xFF, sizeof(uint32_t) * ((size_t)M + 1), st));
     hipLaunchKernelGGL(iba_vox_heads_kernel, dim3(nhb), dim3(kVoxThreads), 0, st, keys, n_kept, w.d_blockc.p, (int)bits.sub_shift, w.d_seg.p, w.d_subfirst.p);
     HIP_TRY(h, hipGetLastError());
@@ -167,8 +166,7 @@ iba_status vox_build(iba_handle* h, const iba_submap_desc* subs, int32_t M, cons
     HIP_TRY(h, hipStreamSynchronize(st));
     res->first[(size_t)M] = (int64_t)V;
     for (int s = M - 1; s >= 0; --s) res->first[(size_t)s] = first[(size_t)s] == kVoxNoSlot ? res->first[(size_t)s + 1] : (int64_t)first[(size_t)s];   // (a sub-map without voxels owns an empty range)
-    guard.p = nullptr;
-    *out = res;
+    *out = res.release();
     return IBA_OK;
 }
 
