@@ -532,7 +532,7 @@ iba_status iba_sc_replay_plan(const int32_t* sizes_at_call, int32_t n, const iba
  * max_edges_per_sector outside [0, 64], neighbour_span != 5, thresholds not finite. On failure *out is NULL and iba_last_error(h) carries the message.
  * Limits: the clouds come back to the host. To register against them, build a handle from them with iba_create; keeping them on the device as frames
  * of a new handle (as iba_submap_handle does for voxel clouds) is not done. The ring of a point is always derived from its elevation (a per-point
- * ring field supplied by the caller is not read). The scan-to-map step that consumes the clouds (odomEstimationClass.cpp), PCL's VoxelGrid and crop
+ * ring field supplied by the caller is not read). The scan-to-map step that consumes the clouds is iba_floam_map_* (below); PCL's VoxelGrid and crop
  * box and the local map are not restated. One GPU.
  */
 #define IBA_FLOAM_MAX_RING_POINTS 8192
@@ -566,6 +566,103 @@ const int32_t* iba_floam_surf_index(const iba_floam_features* f, int32_t s);
 /* The skipped points of scan s by reason and the points of each of its num_lines rings (before rule 3); every output may be NULL. */
 iba_status iba_floam_stats(const iba_floam_features* f, int32_t s, int64_t* n_nonfinite, int64_t* n_out_of_range, int64_t* n_no_ring, int32_t* ring_points /* num_lines */);
 void iba_floam_free(iba_floam_features* f);
+
+/*
+ * ---- F-LOAM scan-to-map: edge / surf factors and registration against given map clouds [src/floam/src/odomEstimationClass.cpp: updatePointsToMap
+ * :32-110, addEdgeCostFactor :132-170, addSurfCostFactor :172-208; src/floam/src/lidarOptimization.cpp: EdgeAnalyticCostFunction,
+ * SurfNormAnalyticCostFunction, PoseSE3Parameterization::Plus, getTransformFromSe3] ----
+ * The stage that turns the edge and surf clouds of a scan into a LiDAR pose: every edge point is matched to the line through its 5 nearest map edge
+ * points, every surf point to the plane through its 5 nearest map surf points, and a robustified 6-parameter problem is solved for the pose, twice
+ * (optimization_count) with a new association each time. Here a BATCH OF PAIRS (scan clouds, map clouds, start pose) is evaluated together; all four
+ * clouds of a pair are local frames of one handle (a scans-only handle from iba_create is enough; a frame of iba_submap_handle's handle is a voxel
+ * cloud). A frame may appear in any number of pairs. The association leaves its factor records on the device; an LM trial re-reads them.
+ *
+ * Rules, fixed here so that the result is a function of the input alone (tests/floam_map_ref.py restates them in numpy). Every f64 operation is rounded
+ * on its own (no fused multiply-add) except the three fma rows of the query transform. Every sum runs in a fixed order, no floating-point atomics: two
+ * calls give the same bytes and a pair's result does not depend on the rest of the batch.
+ *   1 query       the source point's float32 coordinates widened to double, lp_r = fma(T[r][2], z, fma(T[r][1], y, fma(T[r][0], x, T[r][3]))) (the rows
+ *                 of iba_icp_* / iba_scan_*). KNOWN DEVIATION: the query is not narrowed back to float; PCL's kd tree searches the float point.
+ *   2 neighbours  the five map points of least d^2 = (dx dx + dy dy) + dz dz, f64 on the widened floats, ascending by (d^2, original index): ties go to the
+ *                 lowest index (KNOWN DEVIATION: FLANN keeps the first visited). A point yields a factor only if the map frame holds at least 5 points
+ *                 and the 5th d^2 < max_nn_dist2, strictly; only such a point has neighbours in nn_idx. If the map edge frame holds at most min_map_edge
+ *                 points or the map surf frame at most min_map_surf, the pair has NO factor of either kind (the reference's > 10 && > 50).
+ *   3 edge        c = ((((p0 + p1) + p2) + p3) + p4) / 5 per axis; C = sum over the neighbours in order of (p - c)(p - c)^T; eigenvalues l0 <= l1 <= l2
+ *                 of C, u the unit eigenvector of l2; kept iff l2 > edge_eig_ratio l1; a = c + edge_half_len u, b = c - edge_half_len u. With
+ *                 nu = (lp - a) x (lp - b), de = a - b: r = |nu| / |de|, g = (de x (nu / |nu|)) / |de| (g = 0 when |nu| = 0), J = [lp x g, g] — the
+ *                 1x6 of EdgeAnalyticCostFunction, -(nu^T / |nu|) skew(de) [-skew(lp), I] / |de|. r and J do not change under u -> -u: no sign rule.
+ *   4 surf        n0 = the least-squares solution of A n0 = -1, A the 5x3 matrix of the neighbours in order (Householder QR, as the reference's
+ *                 colPivHouseholderQr up to pivoting); d = 1 / |n0|, n = n0 / |n0|; kept iff all of these are finite and |(n . p_j) + d| <=
+ *                 plane_max_resid for the five neighbours. r = (n . lp) + d, J = [lp x n, n] = n^T [-skew(lp), I].
+ *   5 kernel      Huber IRLS as elsewhere in this library: w = 1 for |r| <= huber_delta, else huber_delta / |r|; rho = r^2, else 2 huber_delta |r| -
+ *                 huber_delta^2; H += (w J)^T J, b += (w J)^T r, chi^2 += rho. KNOWN DEVIATION: Ceres's corrector also uses rho''.
+ *   6 moments     IBA_FLOAM_NMOM doubles per pair: [0] edge points that passed rule 2, [1] edge factors kept, [2] surf points that passed rule 2,
+ *                 [3] surf factors kept, [4..24] H, upper triangle by rows, [25..30] b, [31] chi^2, [32] sum r^2 of the edge factors, [33] of the surf
+ *                 factors. The order of iba_scan_step: one partial per 64 positions of the source cloud in kd-leaf order, a wave's lanes by DPP, the
+ *                 partials of a cloud by position, then edge cloud + surf cloud.
+ *   7 records     per pair the points of the edge cloud, then of the surf cloud, each in its ORIGINAL order: an iba_floam_record with kind 0 none / 1 edge /
+ *                 2 surf and v = a, b, 0 or n, d, 0, 0, 0; and, in nn_idx, 5 original map indices (0xFFFFFFFF x 5 for a point that failed rule 2). Pair
+ *                 after pair.
+ *   8 register    outer_passes times: associate at the current T (rules 1-4), then up to inner_iterations LM iterations on the FROZEN records — r, J
+ *                 and w are re-evaluated at each trial pose, the search is not repeated. LM is the trust-region loop of csrc/iba_lm.hpp (its
+ *                 LmOptions defaults; restated from Ceres's published algorithm, NOT Ceres) on 6 parameters, cost = chi^2 / 2: Jacobi scaling
+ *                 1 / (1 + sqrt(H_ii)) fixed per pass; (Hs + clamp(diag Hs, 1e-6, 1e32) / radius) ds = -gs by the 6x6 LDL^T of the scan-to-scan
+ *                 update; a trial pose T' = Exp(delta) T with delta = scale ds = [omega, upsilon] (the reference's Plus: the quaternion of
+ *                 getTransformFromSe3, translation J(omega) upsilon, the small-angle branch below 1e-10 rad); gradient tolerance 1e-10 at the top
+ *                 of an iteration, parameter tolerance 1e-8 against sqrt(1 + |t|^2) and function tolerance 1e-6 after the trial's evaluation,
+ *                 acceptance at a relative decrease above 1e-3, radius /= max(1/3, 1 - (2 rho - 1)^3) or halved, quartered, .. on rejection; the
+ *                 radius starts at 1e4 in every pass (the reference builds a new problem). A step whose model decrease is not positive shrinks
+ *                 the radius without an evaluation. A pair ends IBA_FLOAM_MAP_DEGENERATE with its last valid T when a map is too small (rule 2),
+ *                 an association keeps fewer than 6 factors, or a pivot is not positive and finite. The pairs of a batch advance together, one
+ *                 launch chain and one synchronise per evaluation for all pairs still running.
+ * Answers IBA_ERR_INVALID_ARG with a message in iba_last_error(h), before any launch: a NULL argument, a struct_size of another library, k != 5, a frame
+ * outside the handle, a non-finite T, a threshold that is not finite or negative, a negative count, B outside [1, 4096].
+ * Limits: NO local-map maintenance — addPointsToMap, PCL's VoxelGrid and CropBox and laserMappingClass are not restated: the map clouds are given
+ * (iba_submap_handle builds voxel clouds on the device). A map cloud is always ONE frame and a frame of this library is one kd tree (one tile): the
+ * search walks a single tree, its only box test is the frame's box against max_nn_dist2, and no bound is carried from tile to tile; a map spread over
+ * several frames has to be merged into one first. The constant-velocity prediction of the start pose is the caller's. Parity with Ceres and PCL is
+ * unpinned (neither can be built beside this library). One GPU.
+ */
+#define IBA_FLOAM_NMOM 34
+#define IBA_FLOAM_MAP_OK 0
+#define IBA_FLOAM_MAP_DEGENERATE 1
+typedef struct iba_floam_pair {             /* one registration problem */
+    int32_t src_edge_frame, src_surf_frame; /* the scan's edge / surf cloud */
+    int32_t map_edge_frame, map_surf_frame; /* the map's edge / surf cloud */
+    double  T[16];                          /* row-major 4x4, scan frame -> map frame */
+} iba_floam_pair;
+typedef struct iba_floam_map_options {
+    int32_t struct_size;          /* sizeof(iba_floam_map_options) */
+    int32_t k;                    /* 5, the only supported neighbour count */
+    double  max_nn_dist2;         /* 1.0 */
+    double  edge_eig_ratio;       /* 3.0 */
+    double  edge_half_len;        /* 0.1 */
+    double  plane_max_resid;      /* 0.2 */
+    double  huber_delta;          /* 0.1 */
+    int32_t outer_passes;         /* 2: the reference's steady-state optimization_count (12 after initMapWithPoints) */
+    int32_t inner_iterations;     /* 4 */
+    int32_t min_map_edge;         /* 10 */
+    int32_t min_map_surf;         /* 50 */
+} iba_floam_map_options;
+typedef struct iba_floam_record {
+    int32_t kind;                 /* 0 none, 1 edge, 2 surf */
+    int32_t tried;                /* 1: the point passed rule 2 */
+    double  v[7];                 /* edge: a, b, 0; surf: n, d, 0, 0, 0 */
+} iba_floam_record;
+typedef struct iba_floam_map_result {
+    double  T[16];                /* the final pose (the start pose for a pair that never ran) */
+    double  initial_cost, final_cost;   /* chi^2 / 2 at the first association, after the last accepted step */
+    int32_t passes, iterations, evaluations;
+    int32_t n_edge, n_surf;       /* factors kept by the last association */
+    int32_t status;               /* IBA_FLOAM_MAP_OK / IBA_FLOAM_MAP_DEGENERATE */
+} iba_floam_map_result;
+/* the reference's constants */
+iba_status iba_default_floam_map_options(iba_floam_map_options* opt);
+/* One association and evaluation per pair at pairs[b].T: search, fit, sums. nn_idx: NULL, or 5 entries per source point; records: NULL, or one per
+ * source point (rule 7: sum over the pairs of P(src_edge_frame) + P(src_surf_frame) points). */
+iba_status iba_floam_map_step(iba_handle* h, const iba_floam_pair* pairs, int32_t B, const iba_floam_map_options* opt,
+                              double* moments /* B x IBA_FLOAM_NMOM */, uint32_t* nn_idx, iba_floam_record* records);
+/* Rule 8 per pair from pairs[b].T, all pairs together. */
+iba_status iba_floam_map_register(iba_handle* h, const iba_floam_pair* pairs, int32_t B, const iba_floam_map_options* opt, iba_floam_map_result* out /* B */);
 
 /*
  * ---- Pose-graph optimisation: Levenberg-Marquardt with line process [backend_opt.cpp:433-528 MultiRegistration: nodes pose[i]^-1 :441, odometry

@@ -533,6 +533,18 @@ class IbaHandle:
         from . import floam
         return floam.extract(self, frames, opt, **fields)
 
+    # --- F-LOAM scan-to-map (iba_floam_map_*): edge / surf factors and registration against map clouds that are frames of this handle ---
+    def floam_map_step(self, pairs, opt=None, nn=False, records=False, **fields):
+        """iba_floam_map_step: [(src_edge_frame, src_surf_frame, map_edge_frame, map_surf_frame, T)] -> moments [B, floam_map.NMOM] (+ nn_idx / records
+        per pair when asked; floam_map.py)"""
+        from . import floam_map
+        return floam_map.step(self, pairs, opt, nn, records, **fields)
+
+    def floam_map_register(self, pairs, opt=None, **fields):
+        """iba_floam_map_register: the same pairs -> list of dict(T, initial_cost, final_cost, passes, iterations, evaluations, n_edge, n_surf, status)"""
+        from . import floam_map
+        return floam_map.register(self, pairs, opt, **fields)
+
     def debug_scan_threads(self, threads):
         """force the block shape of the scan pass kernel (64 / 256; 0: the rule)"""
         self.lib.iba_debug_scan_threads.argtypes = [C.c_void_p, C.c_int32]

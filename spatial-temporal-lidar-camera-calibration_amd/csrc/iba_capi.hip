@@ -41,6 +41,7 @@ const char* debug_env(const char* name) {   // (read at every handle creation: a
 #include "iba_sc_kernels.hpp"
 #include "iba_index_kernels.hpp"
 #include "iba_floam_kernels.hpp"
+#include "iba_floam_map_kernels.hpp"
 #include "iba_icp_math.hpp"
 #include "iba_types.hpp"
 
@@ -219,6 +220,11 @@ struct iba_handle {
         PinnedBuf<ScanXf> h_xf; PinnedBuf<double> h_mom; int pinned_E = 0;      // pinned staging of the edges and their sums
     } scan;
     int scan_threads = 0, scan_last_threads = 0;   // iba_debug_scan_threads: a forced block shape (0: the rule); the shape of the last pass
+    // iba_floam_map_* (iba_floam_map_host.hpp): the work buffers of a call, grown on demand
+    struct FloamMapWork {
+        DevBuf<FloamJob> d_job; DevBuf<FloamRec> d_rec; DevBuf<uint32_t> d_nn; DevBuf<double> d_part, d_mom;   // jobs, records and neighbour indices per source point, chunk partials, moments per pair
+        PinnedBuf<FloamJob> h_job; PinnedBuf<double> h_mom; int pinned_B = 0;                                // pinned staging of the jobs and the moments
+    } fmap;
     // iba_submap_build (iba_voxel_host.hpp): the work buffers of a call, grown on demand
     struct VoxWork {
         DevBuf<VoxMember> d_mem; DevBuf<VoxSub> d_sub; DevBuf<VoxPartial> d_part, d_bounds;   // members, sub-maps, block partials of the bounds, bounds per sub-map
@@ -2162,3 +2168,4 @@ iba_status reserve_batch(iba_handle* h, int B) {
 #include "iba_sc_host.hpp"    // iba_sc_describe / iba_sc_distance / iba_sc_detect / iba_sc_replay_plan
 #include "iba_index_host.hpp" // iba_submap_handle (the device index build) / iba_debug_scan_index
 #include "iba_floam_host.hpp" // iba_floam_extract and the accessors of its result
+#include "iba_floam_map_host.hpp" // iba_floam_map_step / iba_floam_map_register
