@@ -207,24 +207,15 @@ struct iba_handle {
     std::vector<uint64_t> h_kp_off;       // local frame -> kp offset (K+1)
     std::vector<uint32_t> h_kp_ext;       // internal (Morton) keypoint id -> reference keypoint id
     std::vector<float> h_kp_uv;           // (u, v) of every keypoint in internal order: the reject bitmap is rebuilt from it when max_pixel_dist changes
-    // iba_icp_* (iba_icp_host.hpp): the bounding box of every local frame's scan ([frame][8]: min xyz, -, max xyz, -) and the work buffers of a pass, grown on demand
+    // iba_icp_* (iba_icp_host.hpp): the bounding box of every local frame's scan ([frame][8]: min xyz, -, max xyz, -) and the work buffers of a pass (PassWork, iba_flat_pass.hpp)
     DevBuf<float> d_frame_box;
-    struct IcpWork {
-        DevBuf<double> d_src, d_part, d_mom; DevBuf<IcpXf> d_xf; DevBuf<uint32_t> d_pair;   // source cloud, wave partials, moment blocks, transforms, (frame, index) pairs
-        PinnedBuf<IcpXf> h_xf; PinnedBuf<double> h_mom; int pinned_B = 0;               // pinned staging of the transforms and the moment blocks
-    } icp;
+    struct IcpWork : PassWork<IcpXf> { DevBuf<double> d_src; DevBuf<uint32_t> d_pair; } icp;   // + source cloud, (frame, index) pairs
     // iba_scan_* (iba_scan_host.hpp): the frame boxes again on the host (the pivot of an edge's point-to-point sums) and the work buffers of a pass
     std::vector<float> h_frame_box;
-    struct ScanWork {
-        DevBuf<double> d_part, d_mom; DevBuf<ScanXf> d_xf; DevBuf<uint32_t> d_pair;   // chunk partials, sums per edge, edges, target index per source point
-        PinnedBuf<ScanXf> h_xf; PinnedBuf<double> h_mom; int pinned_E = 0;      // pinned staging of the edges and their sums
-    } scan;
+    struct ScanWork : PassWork<ScanXf> { DevBuf<uint32_t> d_pair; } scan;   // + target index per source point
     int scan_threads = 0, scan_last_threads = 0;   // iba_debug_scan_threads: a forced block shape (0: the rule); the shape of the last pass
     // iba_floam_map_* (iba_floam_map_host.hpp): the work buffers of a call, grown on demand
-    struct FloamMapWork {
-        DevBuf<FloamJob> d_job; DevBuf<FloamRec> d_rec; DevBuf<uint32_t> d_nn; DevBuf<double> d_part, d_mom;   // jobs, records and neighbour indices per source point, chunk partials, moments per pair
-        PinnedBuf<FloamJob> h_job; PinnedBuf<double> h_mom; int pinned_B = 0;                                // pinned staging of the jobs and the moments
-    } fmap;
+    struct FloamMapWork : PassWork<FloamJob> { DevBuf<FloamRec> d_rec; DevBuf<uint32_t> d_nn; } fmap;   // + records and neighbour indices per source point
     // iba_submap_build (iba_voxel_host.hpp): the work buffers of a call, grown on demand
     struct VoxWork {
         DevBuf<VoxMember> d_mem; DevBuf<VoxSub> d_sub; DevBuf<VoxPartial> d_part, d_bounds;   // members, sub-maps, block partials of the bounds, bounds per sub-map
@@ -1366,7 +1357,7 @@ iba_status create_impl(const iba_problem_desc* d, const iba_params* params, int 
     // blocks return at once.
     h->nn_ns = (int)((h->lstride + kSliceW - 1u) / kSliceW) | 1;
     // one-wave search blocks while a block's LDS plan (the tree's nodes + ~3 KB) lets a CU hold 16 of them (see kNNThreadsSmall)
-    h->nn_small = 8u * std::max(h->maxNodes, 1u) <= 6144u;
+    h->nn_small = 8u * std::max(h->maxNodes, 1u) <= kOneWaveLdsMax;
     if (const char* e = dbg_env("IBA_NN_SMALL")) h->nn_small = std::atoi(e) != 0;
     if (const char* e = dbg_env("IBA_NN_SMALL_MIN_B")) h->nn_small_min_b = std::max(1, std::atoi(e));
 

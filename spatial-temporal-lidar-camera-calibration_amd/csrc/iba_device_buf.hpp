@@ -55,6 +55,8 @@ struct PinnedBuf {
         if (e != hipSuccess) p = nullptr; else n = count;
         return e;
     }
+    // staging that only grows: at least 64 elements, a quarter of headroom, nothing kept of the old contents
+    hipError_t grow(size_t count) { return (p && n >= count) ? hipSuccess : alloc(std::max<size_t>(64, count + count / 4)); }
 };
 
 static_assert(!std::is_copy_constructible<DevBuf<int>>::value && std::is_nothrow_move_constructible<DevBuf<int>>::value, "DevBuf is move-only");

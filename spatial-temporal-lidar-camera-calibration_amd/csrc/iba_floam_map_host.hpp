@@ -1,16 +1,17 @@
 // Host side of iba_floam_map_step / iba_floam_map_register (include/iba_mi355x.h; included at the end of iba_capi.hip, after iba_icp_host.hpp
 // and iba_scan_host.hpp whose checks it shares). A pair is two jobs (edge, surf) of the flat grids of iba_floam_map_kernels.hpp. An association =
 // the jobs copied to the device from pinned memory, iba_floam_nn5_kernel, iba_floam_eval_kernel, iba_floam_sum_kernel, the moments copied back, ONE
-// stream synchronise for all pairs; an LM trial = the same without the search, on the records the association left on the device. 272 B down
-// and 272 B up per pair and evaluation, nothing of cloud size unless the caller asks for nn_idx / records. The buffers live in the handle and grow.
+// stream synchronise for all pairs (PassWork, iba_flat_pass.hpp); an LM trial = the same without the search, on the records the association left on
+// the device. 272 B down and 272 B up per pair and evaluation, nothing of cloud size unless the caller asks for nn_idx / records.
 
 namespace {
 
 constexpr int kFloamMapMaxB = 4096;
 
 struct FloamMapState {   // one pair of iba_floam_map_register
-    double T[16], H[36], g[6], scale[6], cost = 0.0, radius = 0.0, decrease = 2.0;
-    double Tn[16], model = 0.0, step2 = 0.0, xn2 = 0.0;   // the trial in flight
+    double T[16], H[36], g[6], cost = 0.0;
+    iba::LmStep<6> lm;                // the trust-region solve of the current association
+    double Tn[16], xn2 = 0.0;         // the trial in flight
     bool enabled = false, finished = false, inner = false;
 };
 
@@ -40,16 +41,7 @@ bool fmap_enabled(const iba_handle* h, const iba_floam_pair& p, const iba_floam_
 }
 
 iba_status fmap_reserve(iba_handle* h, int nb) {
-    auto& w = h->fmap;
-    HIP_TRY(h, w.d_job.grow(2 * (size_t)nb));
-    HIP_TRY(h, w.d_mom.grow((size_t)nb * kFloamMom));
-    if (w.pinned_B < nb) {
-        w.pinned_B = 0;
-        const int cap = std::max(64, nb + nb / 4);
-        HIP_TRY(h, w.h_job.alloc(2 * (size_t)cap));
-        HIP_TRY(h, w.h_mom.alloc(kFloamMom * (size_t)cap));
-        w.pinned_B = cap;
-    }
+    HIP_TRY(h, h->fmap.reserve(2 * (size_t)nb, (size_t)nb * kFloamMom));
     return IBA_OK;
 }
 
@@ -60,7 +52,7 @@ void fmap_stage(iba_handle* h, const iba_floam_pair* pairs, const iba_floam_map_
         const iba_floam_pair& p = pairs[lv[k]];
         const bool en = fmap_enabled(h, p, o);
         for (int s = 0; s < 2; ++s) {
-            FloamJob& j = w.h_job.p[2 * k + (size_t)s];
+            FloamJob& j = w.h_item.p[2 * k + (size_t)s];
             std::memcpy(j.T, Ts + 16 * k, 12 * sizeof(double));
             j.src = s ? p.src_surf_frame : p.src_edge_frame; j.map = s ? p.map_surf_frame : p.map_edge_frame;
             j.kind = s + 1; j.enabled = en ? 1 : 0; j.pad = 0;
@@ -69,42 +61,37 @@ void fmap_stage(iba_handle* h, const iba_floam_pair* pairs, const iba_floam_map_
     }
 }
 
-// One evaluation of the nb pairs staged in h->fmap.h_job: search (the records are rewritten) when `search`, then the sums at the staged poses
+// One evaluation of the nb pairs staged in h->fmap.h_item: search (the records are rewritten) when `search`, then the sums at the staged poses
 // on the records in place; the moments land in h->fmap.h_mom.
 iba_status fmap_pass(iba_handle* h, int nb, const iba_floam_map_options& o, bool search, bool want_nn) {
     auto& w = h->fmap;
     const hipStream_t st = h->stream;
     const int nj = 2 * nb;
     uint32_t nodes = 1;
-    for (int k = 0; k < nj; ++k) nodes = std::max(nodes, (1u << h->h_frames[(size_t)w.h_job.p[k].map].depth) - 1u);
-    const size_t lds = 8u * (size_t)nodes;
-    const int threads = lds <= 6144u ? 64 : 256;
+    for (int k = 0; k < nj; ++k) nodes = std::max(nodes, tree_nodes(h->h_frames[(size_t)w.h_item.p[k].map]));
+    const PassShape sh = pass_shape(nodes);
     constexpr int kEvThreads = 256;
     uint64_t bn = 0, be = 0, chunks = 0;
     for (int k = 0; k < nj; ++k) {
-        FloamJob& j = w.h_job.p[k];
+        FloamJob& j = w.h_item.p[k];
         const uint32_t P = h->h_frames[(size_t)j.src].P;
-        j.blk_nn = (uint32_t)bn; j.blk_ev = (uint32_t)be; j.part0 = (uint32_t)chunks;
-        bn += (P + (uint32_t)threads - 1u) / (uint32_t)threads; be += (P + (uint32_t)kEvThreads - 1u) / (uint32_t)kEvThreads; chunks += (P + 63u) / 64u;
+        j.blk_nn = flat_take(bn, P, sh.threads); j.blk_ev = flat_take(be, P, kEvThreads); j.part0 = flat_take(chunks, P, 64);
     }
     if (bn > 0x7FFFFFFFull || chunks > 0x7FFFFFFFull) return fail(h, IBA_ERR_UNSUPPORTED, "iba_floam_map: the batch needs more blocks than one launch takes");
     HIP_TRY(h, w.d_part.grow((size_t)chunks * kFloamSums));
-    HIP_TRY(h, hipMemcpyAsync(w.d_job.p, w.h_job.p, sizeof(FloamJob) * (size_t)nj, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, w.upload((size_t)nj, st));
     const FloamFit fit{o.max_nn_dist2, o.edge_eig_ratio, o.edge_half_len, o.plane_max_resid, o.huber_delta};
     if (search && bn > 0) {
-        uint32_t* nn = want_nn ? w.d_nn.p : nullptr;
-        if (threads == 64) hipLaunchKernelGGL(iba_floam_nn5_kernel<64>, dim3((unsigned)bn), dim3(64), lds, st, h->dev_problem(), h->d_frame_box.p, w.d_job.p, nj, fit, w.d_rec.p, nn);
-        else hipLaunchKernelGGL(iba_floam_nn5_kernel<256>, dim3((unsigned)bn), dim3(256), lds, st, h->dev_problem(), h->d_frame_box.p, w.d_job.p, nj, fit, w.d_rec.p, nn);
+        const auto kernel = sh.threads == 64 ? iba_floam_nn5_kernel<64> : iba_floam_nn5_kernel<256>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)bn), dim3((unsigned)sh.threads), sh.lds, st, h->dev_problem(), h->d_frame_box.p, w.d_item.p, nj, fit, w.d_rec.p, want_nn ? w.d_nn.p : nullptr);
         HIP_TRY(h, hipGetLastError());
     }
     if (be > 0) {
-        hipLaunchKernelGGL(iba_floam_eval_kernel<kEvThreads>, dim3((unsigned)be), dim3(kEvThreads), 0, st, h->dev_problem(), w.d_job.p, nj, o.huber_delta, w.d_rec.p, w.d_part.p);
+        hipLaunchKernelGGL(iba_floam_eval_kernel<kEvThreads>, dim3((unsigned)be), dim3(kEvThreads), 0, st, h->dev_problem(), w.d_item.p, nj, o.huber_delta, w.d_rec.p, w.d_part.p);
         HIP_TRY(h, hipGetLastError());
     }
-    hipLaunchKernelGGL(iba_floam_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, h->dev_problem(), w.d_part.p, w.d_job.p, w.d_mom.p);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(w.h_mom.p, w.d_mom.p, sizeof(double) * kFloamMom * (size_t)nb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
+    hipLaunchKernelGGL(iba_floam_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, h->dev_problem(), w.d_part.p, w.d_item.p, w.d_mom.p);
+    HIP_TRY(h, w.finish(kFloamMom * (size_t)nb, st));
     return IBA_OK;
 }
 
@@ -189,6 +176,12 @@ iba_status iba_floam_map_register(iba_handle* h, const iba_floam_pair* pairs, in
     if (!out) return fail(h, IBA_ERR_INVALID_ARG, "iba_floam_map_register: results are NULL");
     if (const iba_status s = fmap_check(h, pairs, B, o, "iba_floam_map_register")) return s;
     const iba::LmOptions lm;   // the trust-region rules of iba_lm.hpp
+    const auto ldlt = [](const double* A, const double* rhs, double* x) {   // false: a pivot or a step that is not positive and finite (the pair is degenerate)
+        double L[36] = {0.0}, dd[6];
+        bool ok = iba::icp::ldlt6_factor(A, L, dd);
+        if (ok) { iba::icp::ldlt6_apply(L, dd, rhs, x); for (int i = 0; i < 6; ++i) ok = ok && std::isfinite(x[i]); }
+        return ok;
+    };
     std::vector<uint64_t> rec0;
     const uint64_t n_rec = fmap_offsets(h, pairs, B, rec0);
     std::vector<FloamMapState> st((size_t)B);
@@ -227,8 +220,7 @@ iba_status iba_floam_map_register(iba_handle* h, const iba_floam_pair* pairs, in
             r.final_cost = s.cost;
             s.inner = true;
             if (m[1] + m[3] < 6.0) { s.finished = true; s.inner = false; r.status = IBA_FLOAM_MAP_DEGENERATE; continue; }
-            s.radius = lm.initial_trust_region_radius; s.decrease = 2.0;
-            for (int i = 0; i < 6; ++i) s.scale[i] = 1.0 / (1.0 + std::sqrt(std::max(s.H[i * 6 + i], 0.0)));
+            s.lm.begin(lm, s.H);
         }
         for (int it = 0; it < o->inner_iterations; ++it) {
             std::vector<int> tv; std::vector<double> Tt;
@@ -238,29 +230,13 @@ iba_status iba_floam_map_register(iba_handle* h, const iba_floam_pair* pairs, in
                 if (!s.inner) continue;
                 any = true;
                 ++out[b].iterations;
-                double gmax = 0.0; for (int i = 0; i < 6; ++i) gmax = std::max(gmax, std::fabs(s.g[i]));
-                if (gmax <= lm.gradient_tolerance) { s.inner = false; continue; }
-                double Hs[36], gs[6], A[36], ngs[6], ds[6];
-                for (int i = 0; i < 6; ++i) { gs[i] = s.scale[i] * s.g[i]; for (int j = 0; j < 6; ++j) Hs[i * 6 + j] = s.scale[i] * s.H[i * 6 + j] * s.scale[j]; }
-                std::memcpy(A, Hs, sizeof(A));
-                for (int i = 0; i < 6; ++i) { A[i * 6 + i] += std::min(std::max(Hs[i * 6 + i], lm.min_lm_diagonal), lm.max_lm_diagonal) / s.radius; ngs[i] = -gs[i]; }
-                double L[36] = {0.0}, dd[6];
-                bool ok = iba::icp::ldlt6_factor(A, L, dd);
-                if (ok) { iba::icp::ldlt6_apply(L, dd, ngs, ds); for (int i = 0; i < 6; ++i) ok = ok && std::isfinite(ds[i]); }
-                if (!ok) { s.inner = false; s.finished = true; out[b].status = IBA_FLOAM_MAP_DEGENERATE; continue; }   // a pivot that is not positive and finite
-                double model = 0.0;
-                for (int i = 0; i < 6; ++i) { double hd = 0.0; for (int j = 0; j < 6; ++j) hd += Hs[i * 6 + j] * ds[j]; model -= ds[i] * (gs[i] + 0.5 * hd); }
-                if (!(model > 0.0)) {
-                    s.radius = std::max(lm.min_trust_region_radius, s.radius / s.decrease); s.decrease *= 2.0;
-                    if (s.radius <= lm.min_trust_region_radius) s.inner = false;
-                    continue;
-                }
-                double delta[6], E[16];
-                s.step2 = 0.0;
-                for (int i = 0; i < 6; ++i) { delta[i] = s.scale[i] * ds[i]; s.step2 += delta[i] * delta[i]; }
+                const iba::LmProposal next = s.lm.propose(lm, s.H, s.g, ldlt);
+                if (next == iba::LmProposal::kNoSolve) { s.inner = false; s.finished = true; out[b].status = IBA_FLOAM_MAP_DEGENERATE; continue; }
+                if (next == iba::LmProposal::kStop) s.inner = false;
+                if (next != iba::LmProposal::kTrial) continue;
                 s.xn2 = 1.0 + ((s.T[3] * s.T[3] + s.T[7] * s.T[7]) + s.T[11] * s.T[11]);   // |(unit quaternion, translation)|^2 of the current pose
-                s.model = model;
-                fmap_exp(delta, E);
+                double E[16];
+                fmap_exp(s.lm.delta, E);
                 iba::icp::mat4_mul(E, s.T, s.Tn);
                 s.Tn[12] = 0.0; s.Tn[13] = 0.0; s.Tn[14] = 0.0; s.Tn[15] = 1.0;
                 tv.push_back(b); Tt.insert(Tt.end(), s.Tn, s.Tn + 16);
@@ -274,18 +250,9 @@ iba_status iba_floam_map_register(iba_handle* h, const iba_floam_pair* pairs, in
                 double Hn[36], gn[6], cn;
                 fmap_unpack(w.h_mom.p + (size_t)kFloamMom * k, Hn, gn, cn);
                 ++out[tv[k]].evaluations;
-                if (std::sqrt(s.step2) <= lm.parameter_tolerance * (std::sqrt(s.xn2) + lm.parameter_tolerance)) { s.inner = false; continue; }
-                if (std::fabs(s.cost - cn) <= lm.function_tolerance * s.cost) { s.inner = false; continue; }
-                const double rho = (s.cost - cn) / s.model;
-                if (rho > lm.min_relative_decrease) {
-                    std::memcpy(s.T, s.Tn, sizeof(s.T)); std::memcpy(s.H, Hn, sizeof(Hn)); std::memcpy(s.g, gn, sizeof(gn));
-                    s.cost = cn;
-                    const double t = 2.0 * rho - 1.0;
-                    s.radius = std::min(lm.max_trust_region_radius, s.radius / std::max(1.0 / 3.0, 1.0 - t * t * t)); s.decrease = 2.0;
-                } else {
-                    s.radius = std::max(lm.min_trust_region_radius, s.radius / s.decrease); s.decrease *= 2.0;
-                    if (s.radius <= lm.min_trust_region_radius) s.inner = false;
-                }
+                const iba::LmVerdict verdict = s.lm.judge(lm, s.cost, cn, s.xn2);
+                if (verdict == iba::LmVerdict::kStop) s.inner = false;
+                if (verdict == iba::LmVerdict::kAccept) { std::memcpy(s.T, s.Tn, sizeof(s.T)); std::memcpy(s.H, Hn, sizeof(Hn)); std::memcpy(s.g, gn, sizeof(gn)); s.cost = cn; }
             }
         }
         for (int b : lv) { st[(size_t)b].inner = false; out[b].final_cost = st[(size_t)b].cost; }

@@ -1,15 +1,13 @@
 // Device side of iba_floam_map_step / iba_floam_map_register (include/iba_mi355x.h): the scan-to-map stage of F-LOAM for a BATCH OF PAIRS
 // (edge / surf cloud of a scan -> edge / surf cloud of a map, all four resident frames of the handle).
 //
-// A pair is two JOBS, (pair, edge) and (pair, surf): a job's source cloud is searched against the job's map cloud. The grid of both kernels is
-// flat over the blocks of every job of the launch, as iba_scan_pass_kernel's is over its edges: a job with P source points owns
-// ceil(P / THREADS) consecutive blocks (blk0, ascending: a block finds its job by bisection) and ceil(P / 64) partials, one per 64-position
-// chunk of the SOURCE cloud in kd-leaf order.
+// A pair is two JOBS, (pair, edge) and (pair, surf): a job's source cloud is searched against the job's map cloud. Both kernels run on the
+// flat grid of iba_flat_pass.hpp (the search at the pass's block shape from blk_nn, the evaluation at 256 threads from blk_ev).
 //
 //  iba_floam_nn5_kernel<THREADS>   a lane owns one source point: widened, transformed in f64 (icp_transform), then an exact 5-NN search of
 //      the map frame's implicit kd tree, its node table staged in LDS by the block. A frame of this library IS one kd tile (what
-//      iba_icp_pass_kernel walks tile by tile are frames): the tile's box test is the exact one of that kernel, against the bound the search
-//      starts from, max_nn_dist2 — a query no closer than that to the map's box searches nothing. The walk is plain f64 and keeps NO path:
+//      iba_icp_pass_kernel walks tile by tile are frames): the tile's box test (box_dist2) is against the bound the search starts from,
+//      max_nn_dist2 — a query no closer than that to the map's box searches nothing. The walk is plain f64 and keeps NO path:
 //      the plane distance of level L is re-read from the LDS node of the leaf's ancestor, the visited far sides are one bit per level. The
 //      best list is five (d^2, original index, position) triples in named registers, kept ascending by (d^2, index) with four compare-and-
 //      swap steps per insertion; the pruning bound is min(5th best, max_nn_dist2). A far child is entered iff its plane distance^2 is <= the
@@ -19,10 +17,9 @@
 //      writes ONE record; nn_idx only when asked. No scratch: nothing is indexed dynamically.
 //  iba_floam_eval_kernel           a lane reads its source point, its record and the job's pose: r, J, the Huber weight and its 31 terms
 //      (tried, kept, 21 of H, 6 of b, chi^2, sum r^2). A wave adds its lanes' terms by DPP (wave_sum_f64) and its last lane writes one partial.
-//  iba_floam_sum_kernel            grid (pairs), 256 threads, the shape of iba_icp_sum_kernel: the partials of the edge job, then of the surf
-//      job, each in an order fixed by position; the pair's IBA_FLOAM_NMOM moments are composed from the two.
-// No atomics. A job's records and partials depend on the job alone: the same bytes whatever else is in the batch and whichever block shape
-// the batch's largest map tree selects.
+//  iba_floam_sum_kernel            grid (pairs): the partials of the edge job, then of the surf job; the pair's IBA_FLOAM_NMOM moments are
+//      composed from the two.
+// No scratch, no atomics.
 #pragma once
 #include "iba_icp_kernels.hpp"
 
@@ -74,15 +71,13 @@ __global__ __launch_bounds__(THREADS) void iba_floam_nn5_kernel(DevProblem dp, c
                                                                 FloamRec* __restrict__ recs, uint32_t* __restrict__ nn_idx) {
     extern __shared__ __align__(16) unsigned char smem[];
     TreeNode* s_nodes = (TreeNode*)smem;
-    int lo_j = 0, hi_j = nj - 1;   // the last job whose first block is not beyond this one (uniform over the block)
-    while (lo_j < hi_j) { const int mid = (lo_j + hi_j + 1) >> 1; if (jobs[mid].blk_nn <= blockIdx.x) lo_j = mid; else hi_j = mid - 1; }
-    const FloamJob& X = jobs[lo_j];
+    const FloamJob& X = jobs[flat_job<&FloamJob::blk_nn>(jobs, nj, blockIdx.x)];
     const FrameHdr& hs = dp.frames[X.src];
     const FrameHdr& hm = dp.frames[X.map];
     const uint32_t pos = (blockIdx.x - X.blk_nn) * (uint32_t)THREADS + threadIdx.x;   // position in the source cloud's tree order
     const bool act = pos < hs.P;
     const uint32_t P = hm.P, D = hm.depth;
-    for (uint32_t i = threadIdx.x; i < (1u << D) - 1u; i += THREADS) s_nodes[i] = dp.nodes[hm.node_base + i];
+    stage_nodes<THREADS>(dp, hm, s_nodes);
     __syncthreads();
     if (!act) return;   // (no barrier and no wave operation below)
     const float4 sv = dp.pts4[hs.pt_base + pos];
@@ -94,12 +89,7 @@ __global__ __launch_bounds__(THREADS) void iba_floam_nn5_kernel(DevProblem dp, c
     double d0 = INFINITY, d1 = INFINITY, d2 = INFINITY, d3 = INFINITY, d4 = INFINITY;
     uint32_t i0 = kNone, i1 = kNone, i2 = kNone, i3 = kNone, i4 = kNone, p0 = 0u, p1 = 0u, p2 = 0u, p3 = 0u, p4i = 0u;
     bool look = X.enabled != 0 && P >= 5u;
-    if (look) {   // the tile's box against the bound the search starts from
-        const float* bx = frame_box + 8 * (size_t)X.map;
-        const double lx = (double)bx[0], ly = (double)bx[1], lz = (double)bx[2], hx = (double)bx[4], hy = (double)bx[5], hz = (double)bx[6];
-        const double dx = q0 < lx ? q0 - lx : (q0 > hx ? q0 - hx : 0.0), dy = q1 < ly ? q1 - ly : (q1 > hy ? q1 - hy : 0.0), dz = q2 < lz ? q2 - lz : (q2 > hz ? q2 - hz : 0.0);
-        look = (dx * dx + dy * dy) + dz * dz < fit.max_nn_dist2;
-    }
+    if (look) look = box_dist2(frame_box + 8 * (size_t)X.map, q0, q1, q2) < fit.max_nn_dist2;   // the tile's box against the bound the search starts from
     if (look) {
         const uint32_t first_leaf = (1u << D) - 1u;
         uint32_t node = 0u, done = 0u;   // done bit L: the far child at level L of the current path needs no (further) visit
@@ -257,9 +247,7 @@ __device__ __forceinline__ bool floam_residual(const FloamRec& rec, double l0, d
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void iba_floam_eval_kernel(DevProblem dp, const FloamJob* __restrict__ jobs, int nj, double huber_delta, const FloamRec* __restrict__ recs,
                                                                  double* __restrict__ partials) {
-    int lo_j = 0, hi_j = nj - 1;
-    while (lo_j < hi_j) { const int mid = (lo_j + hi_j + 1) >> 1; if (jobs[mid].blk_ev <= blockIdx.x) lo_j = mid; else hi_j = mid - 1; }
-    const FloamJob& X = jobs[lo_j];
+    const FloamJob& X = jobs[flat_job<&FloamJob::blk_ev>(jobs, nj, blockIdx.x)];
     const FrameHdr& hs = dp.frames[X.src];
     const uint32_t pos = (blockIdx.x - X.blk_ev) * (uint32_t)THREADS + threadIdx.x;
     double v[kFloamSums];
@@ -290,14 +278,8 @@ __global__ __launch_bounds__(THREADS) void iba_floam_eval_kernel(DevProblem dp, 
             v[30] = r * r;
         }
     }
-#pragma unroll
-    for (int k = 0; k < kFloamSums; ++k) v[k] = wave_sum_f64(v[k]);   // (the total in lane 63)
     const uint32_t chunk = (blockIdx.x - X.blk_ev) * (uint32_t)(THREADS / 64) + (threadIdx.x >> 6);
-    if ((threadIdx.x & 63u) == 63u && chunk * 64u < hs.P) {
-        double* o = partials + ((size_t)X.part0 + (size_t)chunk) * kFloamSums;
-#pragma unroll
-        for (int k = 0; k < kFloamSums; ++k) o[k] = v[k];
-    }
+    wave_sum_store<kFloamSums>(v, chunk * 64u < hs.P, partials + ((size_t)X.part0 + (size_t)chunk) * kFloamSums);
 }
 
 // jobs 2 b (edge) and 2 b + 1 (surf) are pair b of the launch
@@ -307,24 +289,11 @@ __global__ __launch_bounds__(256) void iba_floam_sum_kernel(DevProblem dp, const
     for (int side = 0; side < 2; ++side) {
         const FloamJob& X = jobs[2 * b + side];
         const int nw = (int)((dp.frames[X.src].P + 63u) / 64u);
-        double a[kFloamSums];
-#pragma unroll
-        for (int k = 0; k < kFloamSums; ++k) a[k] = 0.0;
-        for (int w = t; w < nw; w += 256) {
-            const double* p = partials + ((size_t)X.part0 + (size_t)w) * kFloamSums;
-#pragma unroll
-            for (int k = 0; k < kFloamSums; ++k) a[k] += p[k];
-        }
-#pragma unroll
-        for (int k = 0; k < kFloamSums; ++k) a[k] = wave_sum_f64(a[k]);
-        if ((t & 63) == 63) {
-#pragma unroll
-            for (int k = 0; k < kFloamSums; ++k) s_w[side][t >> 6][k] = a[k];
-        }
+        block_sum_partials<kFloamSums>(partials + (size_t)X.part0 * kFloamSums, nw, s_w[side]);
     }
     __syncthreads();
     if (t < kFloamMom) {
-        const auto tot = [&](int side, int k) { return ((s_w[side][0][k] + s_w[side][1][k]) + s_w[side][2][k]) + s_w[side][3][k]; };
+        const auto tot = [&](int side, int k) { return wave_totals(s_w[side], k); };
         double r;
         if (t < 4) r = tot(t >> 1, t & 1);               // edge tried, edge kept, surf tried, surf kept
         else if (t < 32) r = tot(0, t - 2) + tot(1, t - 2);   // H (21), b (6), chi^2: the edge job's sum + the surf job's

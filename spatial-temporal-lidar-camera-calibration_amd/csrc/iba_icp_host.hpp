@@ -1,7 +1,7 @@
 // Host side of iba_icp_step / iba_icp_register / iba_icp_calib (include/iba_mi355x.h; included at the end of iba_capi.hip, whose handle it uses).
 // A pass = the transforms of the starts still running copied to the device from pinned memory, iba_icp_pass_kernel, iba_icp_sum_kernel, the
-// moment blocks copied back to pinned memory, one stream synchronise: 128 B down and 168 B up per start and iteration. The source cloud is
-// uploaded once per call. The buffers live in the handle and only grow.
+// moment blocks copied back to pinned memory, one stream synchronise (PassWork, iba_flat_pass.hpp): 128 B down and 168 B up per start and
+// iteration. The source cloud is uploaded once per call.
 
 namespace {
 
@@ -12,29 +12,20 @@ iba_status icp_check_target(iba_handle* h, int32_t fb, int32_t fe) {
     return IBA_OK;
 }
 
-// threads per block of the pass kernel for this target (the rule of DESIGN.md 5b) and the bytes of its node table
-void icp_shape(const iba_handle* h, int fb, int fe, int& threads, size_t& lds) {
+// block shape of the pass kernel for this target (the largest node table among its tiles that hold points)
+PassShape icp_shape(const iba_handle* h, int fb, int fe) {
     uint32_t nodes = 1;
-    for (int f = fb; f < fe; ++f) if (h->h_frames[(size_t)f].P > 0) nodes = std::max(nodes, (1u << h->h_frames[(size_t)f].depth) - 1u);
-    lds = 8u * (size_t)nodes;
-    threads = lds <= 6144u ? 64 : 256;
+    for (int f = fb; f < fe; ++f) if (h->h_frames[(size_t)f].P > 0) nodes = std::max(nodes, tree_nodes(h->h_frames[(size_t)f]));
+    return pass_shape(nodes);
 }
 
 iba_status icp_reserve(iba_handle* h, int n, int B, int threads, bool pairs) {
     auto& w = h->icp;
     const size_t nw = ((size_t)n + (size_t)threads - 1) / (size_t)threads * (size_t)(threads / 64);
+    HIP_TRY(h, w.reserve((size_t)B, (size_t)B * kIcpMom));
     HIP_TRY(h, w.d_src.grow(3 * (size_t)n));
     HIP_TRY(h, w.d_part.grow((size_t)B * nw * kIcpSums));
-    HIP_TRY(h, w.d_mom.grow((size_t)B * kIcpMom));
-    HIP_TRY(h, w.d_xf.grow((size_t)B));
     if (pairs) HIP_TRY(h, w.d_pair.grow(2 * (size_t)B * (size_t)n));
-    if (w.pinned_B < B) {
-        w.pinned_B = 0;
-        const int cap = std::max(64, B);
-        HIP_TRY(h, w.h_xf.alloc((size_t)cap));
-        HIP_TRY(h, w.h_mom.alloc(kIcpMom * (size_t)cap));
-        w.pinned_B = cap;
-    }
     return IBA_OK;
 }
 
@@ -44,27 +35,29 @@ void icp_centroid(const double* src, int n, double c[3]) {
     for (int i = 0; i < n; ++i) { s0 += src[3 * (size_t)i]; s1 += src[3 * (size_t)i + 1]; s2 += src[3 * (size_t)i + 2]; }
     c[0] = s0 / (double)n; c[1] = s1 / (double)n; c[2] = s2 / (double)n;
 }
-// the transform as the kernel takes it; the pivot by the kernel's own expression (icp_transform)
+// piv = T c by the kernel's own expression (icp_transform)
+void icp_pivot(const double* T16, const double c[3], double piv[3]) {
+    for (int r = 0; r < 3; ++r) piv[r] = std::fma(T16[r * 4 + 2], c[2], std::fma(T16[r * 4 + 1], c[1], std::fma(T16[r * 4], c[0], T16[r * 4 + 3])));
+}
+// the transform as the kernel takes it
 void icp_make_xf(const double* T16, const double c[3], double gate, IcpXf& x) {
     std::memcpy(x.T, T16, 12 * sizeof(double));
-    for (int r = 0; r < 3; ++r) x.piv[r] = std::fma(T16[r * 4 + 2], c[2], std::fma(T16[r * 4 + 1], c[1], std::fma(T16[r * 4], c[0], T16[r * 4 + 3])));
+    icp_pivot(T16, c, x.piv);
     x.gate2 = gate * gate;
 }
 
-// one pass over the nb transforms staged in h->icp.h_xf[0 .. nb): their moment blocks land in h->icp.h_mom (the source is on the device)
-iba_status icp_pass(iba_handle* h, int fb, int fe, int n, int nb, int threads, size_t lds, bool pairs) {
+// one pass over the nb transforms staged in h->icp.h_item[0 .. nb): their moment blocks land in h->icp.h_mom (the source is on the device)
+iba_status icp_pass(iba_handle* h, int fb, int fe, int n, int nb, PassShape sh, bool pairs) {
     auto& w = h->icp;
     const hipStream_t st = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(w.d_xf.p, w.h_xf.p, sizeof(IcpXf) * (size_t)nb, hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)(((size_t)n + (size_t)threads - 1) / (size_t)threads), (unsigned)nb);
+    HIP_TRY(h, w.upload((size_t)nb, st));
+    const dim3 grid((unsigned)(((size_t)n + (size_t)sh.threads - 1) / (size_t)sh.threads), (unsigned)nb);
     uint32_t* pf = pairs ? w.d_pair.p : nullptr; uint32_t* pi = pairs ? w.d_pair.p + (size_t)nb * (size_t)n : nullptr;
-    if (threads == 64) hipLaunchKernelGGL(iba_icp_pass_kernel<64>, grid, dim3(64), lds, st, h->dev_problem(), h->d_frame_box.p, fb, fe, w.d_src.p, n, w.d_xf.p, w.d_part.p, pf, pi);
-    else hipLaunchKernelGGL(iba_icp_pass_kernel<256>, grid, dim3(256), lds, st, h->dev_problem(), h->d_frame_box.p, fb, fe, w.d_src.p, n, w.d_xf.p, w.d_part.p, pf, pi);
+    const auto kernel = sh.threads == 64 ? iba_icp_pass_kernel<64> : iba_icp_pass_kernel<256>;
+    hipLaunchKernelGGL(kernel, grid, dim3((unsigned)sh.threads), sh.lds, st, h->dev_problem(), h->d_frame_box.p, fb, fe, w.d_src.p, n, w.d_item.p, w.d_part.p, pf, pi);
     HIP_TRY(h, hipGetLastError());
-    hipLaunchKernelGGL(iba_icp_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, w.d_part.p, (int)(grid.x * (unsigned)(threads / 64)), w.d_xf.p, w.d_mom.p);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(w.h_mom.p, w.d_mom.p, sizeof(double) * kIcpMom * (size_t)nb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
+    hipLaunchKernelGGL(iba_icp_sum_kernel, dim3((unsigned)nb), dim3(256), 0, st, w.d_part.p, (int)(grid.x * (unsigned)(sh.threads / 64)), w.d_item.p, w.d_mom.p);
+    HIP_TRY(h, w.finish(kIcpMom * (size_t)nb, st));
     return IBA_OK;
 }
 
@@ -152,13 +145,13 @@ iba_status iba_icp_step(iba_handle* h, int32_t frame_begin, int32_t frame_end, c
     if (n_src == 0) return IBA_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     const bool pairs = pair_idx != nullptr;
-    int threads; size_t lds; icp_shape(h, frame_begin, frame_end, threads, lds);
-    if (const iba_status s = icp_reserve(h, n_src, B, threads, pairs)) return s;
+    const PassShape sh = icp_shape(h, frame_begin, frame_end);
+    if (const iba_status s = icp_reserve(h, n_src, B, sh.threads, pairs)) return s;
     auto& w = h->icp;
     HIP_TRY(h, hipMemcpyAsync(w.d_src.p, src_xyz, sizeof(double) * 3 * (size_t)n_src, hipMemcpyHostToDevice, h->stream));
     double c[3]; icp_centroid(src_xyz, n_src, c);
-    for (int b = 0; b < B; ++b) icp_make_xf(T + 16 * (size_t)b, c, max_corr_dist, w.h_xf.p[b]);
-    if (const iba_status s = icp_pass(h, frame_begin, frame_end, n_src, B, threads, lds, pairs)) return s;
+    for (int b = 0; b < B; ++b) icp_make_xf(T + 16 * (size_t)b, c, max_corr_dist, w.h_item.p[b]);
+    if (const iba_status s = icp_pass(h, frame_begin, frame_end, n_src, B, sh, pairs)) return s;
     std::memcpy(moments, w.h_mom.p, sizeof(double) * IBA_ICP_NMOM * (size_t)B);
     if (pairs) {
         HIP_TRY(h, hipMemcpy(pair_frame, w.d_pair.p, sizeof(uint32_t) * (size_t)B * (size_t)n_src, hipMemcpyDeviceToHost));
@@ -181,8 +174,8 @@ iba_status iba_icp_register(iba_handle* h, int32_t frame_begin, int32_t frame_en
         return IBA_OK;
     }
     HIP_TRY(h, hipSetDevice(h->device));
-    int threads; size_t lds; icp_shape(h, frame_begin, frame_end, threads, lds);
-    if (const iba_status s = icp_reserve(h, n_src, B, threads, false)) return s;
+    const PassShape sh = icp_shape(h, frame_begin, frame_end);
+    if (const iba_status s = icp_reserve(h, n_src, B, sh.threads, false)) return s;
     auto& w = h->icp;
     HIP_TRY(h, hipMemcpyAsync(w.d_src.p, src_xyz, sizeof(double) * 3 * (size_t)n_src, hipMemcpyHostToDevice, h->stream));
     double c[3]; icp_centroid(src_xyz, n_src, c);
@@ -190,9 +183,9 @@ iba_status iba_icp_register(iba_handle* h, int32_t frame_begin, int32_t frame_en
     std::vector<int> live((size_t)B);   // the starts of the current pass, in ascending order
     for (int b = 0; b < B; ++b) { std::memcpy(st[(size_t)b].T, T_init + 16 * (size_t)b, sizeof(double) * 16); st[(size_t)b].n_src = n_src; live[(size_t)b] = b; }
     const auto pass = [&](const std::vector<int>& lv, const double* Ts, const double*& mom) -> iba_status {
-        for (size_t k = 0; k < lv.size(); ++k) icp_make_xf(Ts + 16 * k, c, opt->max_corr_dist, w.h_xf.p[k]);
+        for (size_t k = 0; k < lv.size(); ++k) icp_make_xf(Ts + 16 * k, c, opt->max_corr_dist, w.h_item.p[k]);
         mom = w.h_mom.p;
-        return icp_pass(h, frame_begin, frame_end, n_src, (int)lv.size(), threads, lds, false);
+        return icp_pass(h, frame_begin, frame_end, n_src, (int)lv.size(), sh, false);
     };
     const auto update = [&](const IcpItem& s, double* U4) { return iba::icp::umeyama_from_moments(s.m, opt->with_scaling != 0, U4); };
     if (const iba_status s = icp_run_loop(st, live, kIcpMom, opt->max_iter, opt->relative_fitness, opt->relative_rmse, pass, update)) return s;

@@ -1,23 +1,14 @@
 // Device side of iba_icp_step / iba_icp_register (include/iba_mi355x.h): one correspondence pass of point-to-point ICP per (transform, source
-// chunk), the sums of the kept pairs formed where the search runs.
+// chunk), the sums of the kept pairs formed where the search runs. The shared rules (sums, ties, block shape) are iba_flat_pass.hpp's.
 //
-//  iba_icp_pass_kernel<THREADS>   grid (ceil(n / THREADS), B). A lane owns one source point: it transforms the point in f64 (three fused
-//      multiply-adds per row, icp_transform), runs the evaluation path's own exact 1-NN lane search (lane_nn_begin / lane_nn_visit<1>, what
-//      iba_nn_probe_kernel drives) against every tile of the target — the tile's kd nodes staged in LDS by the block, the lane's best distance
-//      carried into the next tile's search as its pruning bound, a tile whose bounding box is further away than that skipped by the lane —,
-//      applies the gate d^2 < r^2 and forms its 18 terms in registers. A wave adds its lanes' terms by DPP (wave_sum_f64: fixed order) and its
-//      last lane writes ONE partial of kIcpSums doubles. No atomics, no scratch outside the tree search.
-//  iba_icp_sum_kernel             grid (B), 256 threads: the partials of a transform added in an order fixed by position (thread t takes the
-//      waves t, t + 256, ..; the 64 threads of a wave by DPP; the four waves in order), the pivot appended: IBA_ICP_NMOM doubles per transform.
-//      A launch of its own: folded into the pass kernel's last block it would wait on a completion counter (that serialises).
-//
-// Ties: nn_merge keeps the lowest original index inside a tile; across tiles a later tile replaces the best only when STRICTLY closer, and the
-// tiles are searched in ascending order: the lowest (frame, index) wins. The box test is exact: a box distance is formed with the operations of
-// the point distance, each monotone in its operand after rounding, so it never exceeds the computed distance of a point inside the box.
-// Block shape (the rule of DESIGN.md 5b): one-wave blocks while the largest tile's node table is at most 6 KB, else four waves per block.
+//  iba_icp_pass_kernel<THREADS>   grid (ceil(n / THREADS), B): not a flat grid, every transform walks the same uploaded source. A lane owns
+//      one source point: it transforms the point in f64 (three fused multiply-adds per row, icp_transform), runs the evaluation path's own
+//      exact 1-NN lane search (lane_nn_begin / lane_nn_visit<1>, what iba_nn_probe_kernel drives) against every tile of the target — the lane's
+//      best distance carried into the next tile's search as its pruning bound, a tile whose box is further away than that skipped by the
+//      lane —, applies the gate d^2 < r^2 and forms its 18 terms in registers. Every wave writes a partial of kIcpSums doubles.
+//  iba_icp_sum_kernel             grid (B): the partials of a transform added, the pivot appended: IBA_ICP_NMOM doubles per transform.
 #pragma once
-#include "iba_kernels.hpp"
-#include "iba_split_kernels.hpp"
+#include "iba_flat_pass.hpp"
 
 namespace iba {
 
@@ -56,15 +47,10 @@ __global__ __launch_bounds__(THREADS) void iba_icp_pass_kernel(DevProblem dp, co
         const FrameHdr& h = dp.frames[f];
         const uint32_t P = h.P, D = h.depth;
         if (P == 0) continue;
-        for (uint32_t i = threadIdx.x; i < (1u << D) - 1u; i += THREADS) s_nodes[i] = dp.nodes[h.node_base + i];
+        stage_nodes<THREADS>(dp, h, s_nodes);
         __syncthreads();
         bool look = act;
-        if (look && gfr != kNone) {   // a later tile: is its box within reach at all?
-            const float* bx = frame_box + 8 * (size_t)f;
-            const double lx = (double)bx[0], ly = (double)bx[1], lz = (double)bx[2], hx = (double)bx[4], hy = (double)bx[5], hz = (double)bx[6];
-            const double dx = q0 < lx ? q0 - lx : (q0 > hx ? q0 - hx : 0.0), dy = q1 < ly ? q1 - ly : (q1 > hy ? q1 - hy : 0.0), dz = q2 < lz ? q2 - lz : (q2 > hz ? q2 - hz : 0.0);
-            look = !((dx * dx + dy * dy) + dz * dz > gbest);
-        }
+        if (look && gfr != kNone) look = !(box_dist2(frame_box + 8 * (size_t)f, q0, q1, q2) > gbest);   // a later tile: is its box within reach at all?
         if (look) {
             const float4* p4 = dp.pts4 + h.pt_base;
             const uint32_t* perm = dp.perm + h.pt_base;
@@ -84,51 +70,23 @@ __global__ __launch_bounds__(THREADS) void iba_icp_pass_kernel(DevProblem dp, co
     if (keep) {
         const float4 pv = dp.pts4[gpt];
         gidx = dp.perm[gpt];
-        const double dq[3] = {q0 - X.piv[0], q1 - X.piv[1], q2 - X.piv[2]};
-        const double dp_[3] = {(double)pv.x - X.piv[0], (double)pv.y - X.piv[1], (double)pv.z - X.piv[2]};
-        v[0] = 1.0; v[1] = gbest;
-        v[2] = dq[0]; v[3] = dq[1]; v[4] = dq[2];
-        v[5] = dp_[0]; v[6] = dp_[1]; v[7] = dp_[2];
-        v[8] = (dq[0] * dq[0] + dq[1] * dq[1]) + dq[2] * dq[2];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) v[9 + 3 * i + j] = dp_[i] * dq[j];
+        p2p_terms(v, gbest, q0, q1, q2, (double)pv.x, (double)pv.y, (double)pv.z, X.piv);
     }
     if (pair_idx && act) {
         const size_t o = (size_t)blockIdx.y * (size_t)n + (size_t)e;
         pair_frame[o] = keep ? gfr : kNone; pair_idx[o] = gidx;
     }
-#pragma unroll
-    for (int k = 0; k < kIcpSums; ++k) v[k] = wave_sum_f64(v[k]);   // (the total in lane 63)
-    if ((threadIdx.x & 63u) == 63u) {
-        const size_t nw = (size_t)gridDim.x * (THREADS / 64);
-        double* o = partials + ((size_t)blockIdx.y * nw + (size_t)blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6)) * kIcpSums;
-#pragma unroll
-        for (int k = 0; k < kIcpSums; ++k) o[k] = v[k];
-    }
+    const size_t nw = (size_t)gridDim.x * (THREADS / 64);   // (every wave writes: the sum kernel reads nw partials per transform)
+    wave_sum_store<kIcpSums>(v, true, partials + ((size_t)blockIdx.y * nw + (size_t)blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6)) * kIcpSums);
 }
 
 // nw: partials (waves) per transform
 __global__ __launch_bounds__(256) void iba_icp_sum_kernel(const double* __restrict__ partials, int nw, const IcpXf* __restrict__ xf, double* __restrict__ out) {
     __shared__ double s_w[4][kIcpSums];
     const int b = (int)blockIdx.x, t = (int)threadIdx.x;
-    double a[kIcpSums];
-#pragma unroll
-    for (int k = 0; k < kIcpSums; ++k) a[k] = 0.0;
-    for (int w = t; w < nw; w += 256) {
-        const double* p = partials + ((size_t)b * (size_t)nw + (size_t)w) * kIcpSums;
-#pragma unroll
-        for (int k = 0; k < kIcpSums; ++k) a[k] += p[k];
-    }
-#pragma unroll
-    for (int k = 0; k < kIcpSums; ++k) a[k] = wave_sum_f64(a[k]);
-    if ((t & 63) == 63) {
-#pragma unroll
-        for (int k = 0; k < kIcpSums; ++k) s_w[t >> 6][k] = a[k];
-    }
+    block_sum_partials<kIcpSums>(partials + (size_t)b * (size_t)nw * kIcpSums, nw, s_w);
     __syncthreads();
-    if (t < kIcpSums) out[(size_t)b * kIcpMom + t] = ((s_w[0][t] + s_w[1][t]) + s_w[2][t]) + s_w[3][t];
+    if (t < kIcpSums) out[(size_t)b * kIcpMom + t] = wave_totals(s_w, t);
     else if (t < kIcpMom) out[(size_t)b * kIcpMom + t] = xf[b].piv[t - kIcpSums];
 }
 

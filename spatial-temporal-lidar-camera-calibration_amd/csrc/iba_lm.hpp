@@ -42,6 +42,53 @@ inline bool chol_solve7(const double* A, const double* b, double* x) {
     return true;
 }
 
+// One trust-region solve on N parameters, in the two halves a caller whose trials share one evaluation pass needs apart (iba_floam_map_register:
+// many pairs, one device pass per trial round); calibrate_lm runs them back to back. The solver, what a failed solve means, |x|^2 and the
+// Plus operation are the caller's.
+enum class LmProposal { kTrial, kRetry, kStop, kNoSolve };   // what propose returns
+enum class LmVerdict { kAccept, kReject, kStop };            // what judge returns
+template <int N>
+struct LmStep {
+    double radius = 0.0, decrease = 2.0, scale[N];
+    double delta[N], model = 0.0, step2 = 0.0;   // the trial in flight: the step in the caller's parameters, its model decrease, |step|^2
+    void begin(const LmOptions& o, const double* H) {   // Jacobi scaling, fixed at the first Jacobian of the solve (Ceres)
+        radius = o.initial_trust_region_radius; decrease = 2.0;
+        for (int i = 0; i < N; ++i) scale[i] = 1.0 / (1.0 + std::sqrt(std::max(H[i * N + i], 0.0)));
+    }
+    // the radius after a step that is not taken; false: it has reached its floor
+    bool shrink(const LmOptions& o) { radius = std::max(o.min_trust_region_radius, radius / decrease); decrease *= 2.0; return !(radius <= o.min_trust_region_radius); }
+    // Propose: the gradient test (kStop), the scaled damped system through solve(A, rhs, x) (false: kNoSolve, nothing changed), the model
+    // decrease; a model that is not positive shrinks the radius (kRetry, or kStop at its floor). kTrial: delta, model and step2 are set.
+    template <class Solve>
+    LmProposal propose(const LmOptions& o, const double* H, const double* g, Solve solve) {
+        double gmax = 0.0; for (int i = 0; i < N; ++i) gmax = std::max(gmax, std::fabs(g[i]));
+        if (gmax <= o.gradient_tolerance) return LmProposal::kStop;
+        double Hs[N * N], gs[N], A[N * N], ngs[N], ds[N];
+        for (int i = 0; i < N; ++i) { gs[i] = scale[i] * g[i]; for (int j = 0; j < N; ++j) Hs[i * N + j] = scale[i] * H[i * N + j] * scale[j]; }
+        std::memcpy(A, Hs, sizeof(A));
+        for (int i = 0; i < N; ++i) { A[i * N + i] += std::min(std::max(Hs[i * N + i], o.min_lm_diagonal), o.max_lm_diagonal) / radius; ngs[i] = -gs[i]; }
+        if (!solve(A, ngs, ds)) return LmProposal::kNoSolve;
+        model = 0.0;
+        for (int i = 0; i < N; ++i) { double hd = 0.0; for (int j = 0; j < N; ++j) hd += Hs[i * N + j] * ds[j]; model -= ds[i] * (gs[i] + 0.5 * hd); }
+        if (!(model > 0.0)) return shrink(o) ? LmProposal::kRetry : LmProposal::kStop;
+        step2 = 0.0;
+        for (int i = 0; i < N; ++i) { delta[i] = scale[i] * ds[i]; step2 += delta[i] * delta[i]; }
+        return LmProposal::kTrial;
+    }
+    // Judge the evaluated trial, in TrustRegionMinimizer::Minimize's order: the parameter- and the function-tolerance tests against the
+    // CURRENT point's cost — a run that stops on either keeps x (the candidate is not committed, and the stop can come on a step that would
+    // have been rejected) — and only then accept (kAccept: the caller commits the trial) or reject (kReject, or kStop at the radius' floor).
+    LmVerdict judge(const LmOptions& o, double cost, double trial_cost, double xn2) {
+        if (std::sqrt(step2) <= o.parameter_tolerance * (std::sqrt(xn2) + o.parameter_tolerance)) return LmVerdict::kStop;
+        if (std::fabs(cost - trial_cost) <= o.function_tolerance * cost) return LmVerdict::kStop;
+        const double rho = (cost - trial_cost) / model;
+        if (!(rho > o.min_relative_decrease)) return shrink(o) ? LmVerdict::kReject : LmVerdict::kStop;
+        const double t = 2.0 * rho - 1.0;
+        radius = std::min(o.max_trust_region_radius, radius / std::max(1.0 / 3.0, 1.0 - t * t * t)); decrease = 2.0;
+        return LmVerdict::kAccept;
+    }
+};
+
 // Build(x): freeze the association at x. Eval(x, H, g, cost): residual blocks of the frozen association at x.
 template <class Build, class Eval>
 inline bool calibrate_lm(const double* x0, const LmOptions& o, Build build, Eval eval, LmResult& r) {
@@ -54,42 +101,22 @@ inline bool calibrate_lm(const double* x0, const LmOptions& o, Build build, Eval
         if (!eval(x, H, g, cost)) return false;
         ++r.evaluations;
         if (outer == 0) r.initial_cost = cost;
-        double radius = o.initial_trust_region_radius, decrease_factor = 2.0;
-        double scale[7];   // Jacobi scaling, fixed at the first Jacobian of the solve (Ceres)
-        for (int i = 0; i < 7; ++i) scale[i] = 1.0 / (1.0 + std::sqrt(std::max(H[i * 7 + i], 0.0)));
+        LmStep<7> step;
+        step.begin(o, H);
         for (int it = 0; it < o.max_inner_iterations; ++it) {
             ++r.inner_iterations;
-            double gmax = 0; for (int i = 0; i < 7; ++i) gmax = std::max(gmax, std::fabs(g[i]));
-            if (gmax <= o.gradient_tolerance) break;
-            double Hs[49], gs[7];
-            for (int i = 0; i < 7; ++i) { gs[i] = scale[i] * g[i]; for (int j = 0; j < 7; ++j) Hs[i * 7 + j] = scale[i] * H[i * 7 + j] * scale[j]; }
-            double A[49]; std::memcpy(A, Hs, sizeof(A));
-            for (int i = 0; i < 7; ++i) A[i * 7 + i] += std::min(std::max(Hs[i * 7 + i], o.min_lm_diagonal), o.max_lm_diagonal) / radius;
-            double ngs[7], ds[7]; for (int i = 0; i < 7; ++i) ngs[i] = -gs[i];
-            bool ok = chol_solve7(A, ngs, ds);
-            double model = 0;
-            if (ok) { for (int i = 0; i < 7; ++i) { double hd = 0; for (int j = 0; j < 7; ++j) hd += Hs[i * 7 + j] * ds[j]; model -= ds[i] * (gs[i] + 0.5 * hd); } }
-            if (!ok || !(model > 0)) { radius = std::max(o.min_trust_region_radius, radius / decrease_factor); decrease_factor *= 2; if (radius <= o.min_trust_region_radius) break; continue; }
-            double xn[7], step2 = 0, xn2 = 0;
-            for (int i = 0; i < 7; ++i) { const double d = scale[i] * ds[i]; xn[i] = x[i] + d; step2 += d * d; xn2 += x[i] * x[i]; }
-            // TrustRegionMinimizer::Minimize order: evaluate the candidate, then the parameter- and the function-tolerance
-            // tests against the CURRENT point's cost — a run that stops on either keeps x (the candidate is not committed,
-            // and the stop can come on a step that would have been rejected) — and only then accept or reject.
+            LmProposal next = step.propose(o, H, g, chol_solve7);
+            if (next == LmProposal::kNoSolve) next = step.shrink(o) ? LmProposal::kRetry : LmProposal::kStop;   // not SPD: damp harder
+            if (next == LmProposal::kStop) break;
+            if (next == LmProposal::kRetry) continue;
+            double xn[7], xn2 = 0;
+            for (int i = 0; i < 7; ++i) { xn[i] = x[i] + step.delta[i]; xn2 += x[i] * x[i]; }
             double Hn[49], gn[7], cn;
             if (!eval(xn, Hn, gn, cn)) return false;
             ++r.evaluations;
-            if (std::sqrt(step2) <= o.parameter_tolerance * (std::sqrt(xn2) + o.parameter_tolerance)) break;
-            if (std::fabs(cost - cn) <= o.function_tolerance * cost) break;
-            const double rho = (cost - cn) / model;
-            if (rho > o.min_relative_decrease) {
-                std::memcpy(x, xn, sizeof(x)); std::memcpy(H, Hn, sizeof(H)); std::memcpy(g, gn, sizeof(g));
-                cost = cn;
-                const double t = 2.0 * rho - 1.0;
-                radius = std::min(o.max_trust_region_radius, radius / std::max(1.0 / 3.0, 1.0 - t * t * t)); decrease_factor = 2.0;
-            } else {
-                radius = std::max(o.min_trust_region_radius, radius / decrease_factor); decrease_factor *= 2;
-                if (radius <= o.min_trust_region_radius) break;
-            }
+            const LmVerdict verdict = step.judge(o, cost, cn, xn2);
+            if (verdict == LmVerdict::kStop) break;
+            if (verdict == LmVerdict::kAccept) { std::memcpy(x, xn, sizeof(x)); std::memcpy(H, Hn, sizeof(H)); std::memcpy(g, gn, sizeof(g)); cost = cn; }
         }
         r.final_cost = cost; r.outer_iterations = outer + 1;
         bool close = true;   // allClose (IBACalib2.hpp:9-18)

@@ -1,7 +1,7 @@
 // Host side of iba_scan_step / iba_scan_register / iba_scan_information (include/iba_mi355x.h; included at the end of iba_capi.hip, after
 // iba_icp_host.hpp whose loop and helpers it uses). A pass = the transforms of the edges still running copied to the device from pinned
-// memory, iba_scan_pass_kernel, iba_scan_sum_kernel, the sums copied back to pinned memory, ONE stream synchronise for all edges: 160 B down
-// and 256 B up per edge and iteration, nothing of scan size. The buffers live in the handle and only grow.
+// memory, iba_scan_pass_kernel, iba_scan_sum_kernel, the sums copied back to pinned memory, ONE stream synchronise for all edges (PassWork,
+// iba_flat_pass.hpp): 160 B down and 256 B up per edge and iteration, nothing of scan size.
 
 namespace {
 
@@ -31,67 +31,62 @@ iba_status scan_check_estimation(iba_handle* h, int32_t estimation, bool step, c
 bool scan_dist_ok(double d) { return d > 0.0 && std::isfinite(d); }
 
 iba_status scan_reserve_edges(iba_handle* h, int nb) {
-    auto& w = h->scan;
-    HIP_TRY(h, w.d_xf.grow((size_t)nb));
-    HIP_TRY(h, w.d_mom.grow((size_t)nb * kScanMom));
-    if (w.pinned_E < nb) {
-        w.pinned_E = 0;
-        const int cap = std::max(64, nb + nb / 4);
-        HIP_TRY(h, w.h_xf.alloc((size_t)cap));
-        HIP_TRY(h, w.h_mom.alloc(kScanMom * (size_t)cap));
-        w.pinned_E = cap;
-    }
+    HIP_TRY(h, h->scan.reserve((size_t)nb, (size_t)nb * kScanMom));
     return IBA_OK;
 }
 
-// the edge as the kernel takes it (its place in the grid is set by scan_pass); the pivot by the kernel's own expression (icp_transform)
+// the edge as the kernel takes it (its place in the grid is set by scan_pass); the pivot = T * centre of the source scan's box
 void scan_make_xf(const iba_handle* h, int src, int tgt, const double* T16, double dist, ScanXf& x) {
     std::memcpy(x.T, T16, 12 * sizeof(double));
     const float* bx = &h->h_frame_box[8 * (size_t)src];
     const double c[3] = {0.5 * ((double)bx[0] + (double)bx[4]), 0.5 * ((double)bx[1] + (double)bx[5]), 0.5 * ((double)bx[2] + (double)bx[6])};
-    for (int r = 0; r < 3; ++r) x.piv[r] = std::fma(T16[r * 4 + 2], c[2], std::fma(T16[r * 4 + 1], c[1], std::fma(T16[r * 4], c[0], T16[r * 4 + 3])));
+    icp_pivot(T16, c, x.piv);
     x.gate2 = dist * dist; x.src = src; x.tgt = tgt; x.blk0 = 0; x.part0 = 0; x.pair0 = 0;
 }
 
-template <int THREADS, int MODE>
-void scan_launch(iba_handle* h, unsigned blocks, int nb, size_t lds, uint32_t* pairs) {
+// launches the pass kernel at the given shape, then the sum kernel of the mode; the status returned is the pass launch's, the sum launch's
+// is read by the caller's PassWork::finish
+template <int MODE>
+hipError_t scan_launch_pass_and_sum(iba_handle* h, PassShape sh, unsigned blocks, int nb, uint32_t* pairs) {
     auto& w = h->scan;
-    hipLaunchKernelGGL((iba_scan_pass_kernel<THREADS, MODE>), dim3(blocks), dim3(THREADS), lds, h->stream, h->dev_problem(), w.d_xf.p, nb, std::max(3, (int)h->params.norm_min_pts), w.d_part.p, pairs);
+    const auto kernel = sh.threads == 64 ? iba_scan_pass_kernel<64, MODE> : iba_scan_pass_kernel<256, MODE>;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3((unsigned)sh.threads), sh.lds, h->stream, h->dev_problem(), w.d_item.p, nb, std::max(3, (int)h->params.norm_min_pts), w.d_part.p, pairs);
+    if (const hipError_t e = hipGetLastError()) return e;
+    hipLaunchKernelGGL(iba_scan_sum_kernel<MODE>, dim3((unsigned)nb), dim3(256), 0, h->stream, h->dev_problem(), w.d_part.p, w.d_item.p, w.d_mom.p);
+    return hipSuccess;
 }
 
-// One pass over the nb edges staged in h->scan.h_xf[0 .. nb) (every one runs): their sums land in h->scan.h_mom. threads: 0 = the rule of
+// One pass over the nb edges staged in h->scan.h_item[0 .. nb) (every one runs): their sums land in h->scan.h_mom. threads: 0 = the rule of
 // DESIGN.md 5b applied to the largest target tree of the pass, 64 / 256 forces a shape (the sums do not depend on it). pairs: the edges' pair0 are set by the caller.
 iba_status scan_pass(iba_handle* h, int nb, int mode, int threads, bool pairs) {
     auto& w = h->scan;
-    const hipStream_t st = h->stream;
     uint32_t nodes = 1;
-    for (int k = 0; k < nb; ++k) nodes = std::max(nodes, (1u << h->h_frames[(size_t)w.h_xf.p[k].tgt].depth) - 1u);
-    const size_t lds = 8u * (size_t)nodes;
-    if (threads != 64 && threads != 256) threads = h->scan_threads ? h->scan_threads : (lds <= 6144u ? 64 : 256);
+    for (int k = 0; k < nb; ++k) nodes = std::max(nodes, tree_nodes(h->h_frames[(size_t)w.h_item.p[k].tgt]));
+    PassShape sh = pass_shape(nodes);
+    if (threads == 64 || threads == 256) sh.threads = threads; else if (h->scan_threads) sh.threads = h->scan_threads;
     uint64_t blocks = 0, chunks = 0;
     for (int k = 0; k < nb; ++k) {
-        const uint32_t P = h->h_frames[(size_t)w.h_xf.p[k].src].P;
-        w.h_xf.p[k].blk0 = (uint32_t)blocks; w.h_xf.p[k].part0 = (uint32_t)chunks;
-        blocks += (P + (uint32_t)threads - 1u) / (uint32_t)threads; chunks += (P + 63u) / 64u;
+        const uint32_t P = h->h_frames[(size_t)w.h_item.p[k].src].P;
+        w.h_item.p[k].blk0 = flat_take(blocks, P, sh.threads); w.h_item.p[k].part0 = flat_take(chunks, P, 64);
     }
     if (blocks > 0x7FFFFFFFull) return fail(h, IBA_ERR_UNSUPPORTED, "iba_scan: the batch needs more blocks than one launch takes");
     HIP_TRY(h, w.d_part.grow((size_t)chunks * 31u));
-    HIP_TRY(h, hipMemcpyAsync(w.d_xf.p, w.h_xf.p, sizeof(ScanXf) * (size_t)nb, hipMemcpyHostToDevice, st));
-    uint32_t* pp = pairs ? w.d_pair.p : nullptr;
-    const unsigned nblk = (unsigned)blocks;
-    if (threads == 64) {
-        if (mode == kScanP2P) scan_launch<64, kScanP2P>(h, nblk, nb, lds, pp); else if (mode == kScanP2L) scan_launch<64, kScanP2L>(h, nblk, nb, lds, pp); else scan_launch<64, kScanInfo>(h, nblk, nb, lds, pp);
-    } else {
-        if (mode == kScanP2P) scan_launch<256, kScanP2P>(h, nblk, nb, lds, pp); else if (mode == kScanP2L) scan_launch<256, kScanP2L>(h, nblk, nb, lds, pp); else scan_launch<256, kScanInfo>(h, nblk, nb, lds, pp);
-    }
-    HIP_TRY(h, hipGetLastError());
-    if (mode == kScanP2P) hipLaunchKernelGGL(iba_scan_sum_kernel<kScanP2P>, dim3((unsigned)nb), dim3(256), 0, st, h->dev_problem(), w.d_part.p, w.d_xf.p, w.d_mom.p);
-    else if (mode == kScanP2L) hipLaunchKernelGGL(iba_scan_sum_kernel<kScanP2L>, dim3((unsigned)nb), dim3(256), 0, st, h->dev_problem(), w.d_part.p, w.d_xf.p, w.d_mom.p);
-    else hipLaunchKernelGGL(iba_scan_sum_kernel<kScanInfo>, dim3((unsigned)nb), dim3(256), 0, st, h->dev_problem(), w.d_part.p, w.d_xf.p, w.d_mom.p);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(w.h_mom.p, w.d_mom.p, sizeof(double) * kScanMom * (size_t)nb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    h->scan_last_threads = threads;
+    HIP_TRY(h, w.upload((size_t)nb, h->stream));
+    const auto launch = mode == kScanP2P ? scan_launch_pass_and_sum<kScanP2P> : (mode == kScanP2L ? scan_launch_pass_and_sum<kScanP2L> : scan_launch_pass_and_sum<kScanInfo>);
+    HIP_TRY(h, launch(h, sh, (unsigned)blocks, nb, pairs ? w.d_pair.p : nullptr));
+    HIP_TRY(h, w.finish(kScanMom * (size_t)nb, h->stream));
+    h->scan_last_threads = sh.threads;
+    return IBA_OK;
+}
+
+// the information pass (GetInformationMatrixFromPointClouds) over the edges `run` at the transforms T_of(e), all edges in one pass:
+// take(e, m) receives the sums of edge e
+template <class TOf, class Take>
+iba_status scan_info_pass(iba_handle* h, const iba_scan_edge* edges, const std::vector<int>& run, double dist, TOf T_of, Take take) {
+    auto& w = h->scan;
+    for (size_t k = 0; k < run.size(); ++k) scan_make_xf(h, edges[run[k]].src_frame, edges[run[k]].tgt_frame, T_of(run[k]), dist, w.h_item.p[k]);
+    if (const iba_status s = scan_pass(h, (int)run.size(), kScanInfo, 0, false)) return s;
+    for (size_t k = 0; k < run.size(); ++k) take(run[k], w.h_mom.p + (size_t)kScanMom * k);
     return IBA_OK;
 }
 
@@ -100,7 +95,7 @@ iba_status scan_stage(iba_handle* h, const iba_scan_edge* edges, const std::vect
     auto& w = h->scan;
     for (int e : run) { st[(size_t)e].iterations = 0; st[(size_t)e].status = IBA_ICP_MAX_ITER; }
     const auto pass = [&](const std::vector<int>& lv, const double* Ts, const double*& mom) -> iba_status {
-        for (size_t k = 0; k < lv.size(); ++k) scan_make_xf(h, edges[lv[k]].src_frame, edges[lv[k]].tgt_frame, Ts + 16 * k, dist, w.h_xf.p[k]);
+        for (size_t k = 0; k < lv.size(); ++k) scan_make_xf(h, edges[lv[k]].src_frame, edges[lv[k]].tgt_frame, Ts + 16 * k, dist, w.h_item.p[k]);
         mom = w.h_mom.p;
         return scan_pass(h, (int)lv.size(), estimation, 0, false);
     };
@@ -145,8 +140,8 @@ iba_status iba_scan_step(iba_handle* h, const iba_scan_edge* edges, int32_t E, d
     }
     for (size_t k = 0; k < run.size(); ++k) {
         const iba_scan_edge& g = edges[run[k]];
-        scan_make_xf(h, g.src_frame, g.tgt_frame, g.T, max_corr_dist, w.h_xf.p[k]);
-        w.h_xf.p[k].pair0 = pair0[(size_t)run[k]];
+        scan_make_xf(h, g.src_frame, g.tgt_frame, g.T, max_corr_dist, w.h_item.p[k]);
+        w.h_item.p[k].pair0 = pair0[(size_t)run[k]];
     }
     if (const iba_status s = scan_pass(h, (int)run.size(), estimation, 0, pair_idx != nullptr)) return s;
     for (size_t k = 0; k < run.size(); ++k) std::memcpy(moments + (size_t)IBA_SCAN_NMOM * (size_t)run[k], w.h_mom.p + (size_t)kScanMom * k, sizeof(double) * kScanMom);
@@ -166,15 +161,8 @@ iba_status iba_scan_information(iba_handle* h, const iba_scan_edge* edges, int32
     if (run.empty()) return IBA_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     if (const iba_status s = scan_reserve_edges(h, (int)run.size())) return s;
-    auto& w = h->scan;
-    for (size_t k = 0; k < run.size(); ++k) scan_make_xf(h, edges[run[k]].src_frame, edges[run[k]].tgt_frame, edges[run[k]].T, max_dist, w.h_xf.p[k]);
-    if (const iba_status s = scan_pass(h, (int)run.size(), kScanInfo, 0, false)) return s;
-    for (size_t k = 0; k < run.size(); ++k) {
-        const double* m = w.h_mom.p + (size_t)kScanMom * k;
-        iba::icp::information_from_sums(m, info + 36 * (size_t)run[k]);
-        n_pairs[run[k]] = (int32_t)m[0];
-    }
-    return IBA_OK;
+    return scan_info_pass(h, edges, run, max_dist, [&](int e) { return edges[e].T; },
+                          [&](int e, const double* m) { iba::icp::information_from_sums(m, info + 36 * (size_t)e); n_pairs[e] = (int32_t)m[0]; });
 }
 
 iba_status iba_scan_register(iba_handle* h, const iba_scan_edge* edges, int32_t E, const iba_scan_options* o, iba_scan_result* out) {
@@ -208,16 +196,9 @@ iba_status iba_scan_register(iba_handle* h, const iba_scan_edge* edges, int32_t 
         icp_fill_result(s.T, s.m, s.n_src, s.iterations, s.status, out[e].reg);
         out[e].n_planar = o->estimation == IBA_SCAN_POINT_TO_PLANE ? (int32_t)s.m[2] : 0;
     }
-    if (o->info_dist > 0.0 && !run.empty()) {   // GetInformationMatrixFromPointClouds at the final transforms, all edges in one pass
-        auto& w = h->scan;
-        for (size_t k = 0; k < run.size(); ++k) scan_make_xf(h, edges[run[k]].src_frame, edges[run[k]].tgt_frame, st[(size_t)run[k]].T, o->info_dist, w.h_xf.p[k]);
-        if (const iba_status s = scan_pass(h, (int)run.size(), kScanInfo, 0, false)) return s;
-        for (size_t k = 0; k < run.size(); ++k) {
-            const double* m = w.h_mom.p + (size_t)kScanMom * k;
-            iba::icp::information_from_sums(m, out[run[k]].info);
-            out[run[k]].n_info = (int32_t)m[0];
-        }
-    }
+    if (o->info_dist > 0.0 && !run.empty())   // at the final transforms
+        return scan_info_pass(h, edges, run, o->info_dist, [&](int e) { return (const double*)st[(size_t)e].T; },
+                              [&](int e, const double* m) { iba::icp::information_from_sums(m, out[e].info); out[e].n_info = (int32_t)m[0]; });
     return IBA_OK;
 }
 

@@ -1,24 +1,16 @@
 // Device side of iba_scan_step / iba_scan_register / iba_scan_information (include/iba_mi355x.h): one correspondence pass of scan-to-scan ICP
-// for a BATCH OF EDGES (source scan -> target scan, both resident in the handle), the sums of the kept pairs formed where the search runs.
+// for a BATCH OF EDGES (source scan -> target scan, both resident in the handle) on the flat grid of iba_flat_pass.hpp, a job = an edge.
 //
-//  iba_scan_pass_kernel<THREADS, MODE>   flat grid over the blocks of every edge of the pass. An edge with P source points owns
-//      ceil(P / THREADS) consecutive blocks (ScanXf::blk0, ascending over the edges: a block finds its edge by bisection) and ceil(P / 64)
-//      partials, one per 64-position chunk of the SOURCE scan in kd-leaf order. A lane reads its source point from the resident pts4 (float32,
-//      widened), transforms it in f64 (icp_transform), runs the evaluation path's exact 1-NN lane search (lane_nn_begin / lane_nn_visit<1>)
-//      against the edge's target tree — its kd nodes staged in LDS by the block —, applies the gate d^2 < r^2 and forms its terms in registers:
-//        MODE 0  point-to-point: the 18 pivoted sums of iba_icp_pass_kernel (same expressions), the pivot = T * centre of the source scan's box
+//  iba_scan_pass_kernel<THREADS, MODE>   a lane reads its source point from the resident pts4 (float32, widened), transforms it in f64
+//      (icp_transform), runs the evaluation path's exact 1-NN lane search (lane_nn_begin / lane_nn_visit<1>) against the edge's target tree,
+//      applies the gate d^2 < r^2 and forms its terms in registers:
+//        MODE 0  point-to-point: the 18 pivoted sums (p2p_terms), the pivot = T * centre of the source scan's box
 //        MODE 1  point-to-plane: kept pairs, sum d^2, pairs that carry a normal, JtJ (21, upper triangle by rows), Jtr (6), sum r^2 — 31 sums,
 //                about the origin of the target frame. The normal is the cost path's memoised plane of the target point (plane_cost); a record
 //                with fewer than max(norm_min_pts, 3) kept neighbours or a non-finite normal carries none: such a pair counts in [0], [1] only
 //        MODE 2  information: kept pairs, sum t (3), sum t t^T (6, upper triangle by rows), t the TARGET point — 10 sums about the origin
-//      A wave adds its lanes' terms by DPP (wave_sum_f64: fixed order) and its last lane writes ONE partial. No atomics. The terms are formed
-//      after the search has ended: none of them is live across it.
-//  iba_scan_sum_kernel                   grid (edges), 256 threads: the partials of an edge added in an order fixed by position (thread t takes
-//      the chunks t, t + 256, ..; the 64 threads of a wave by DPP; the four waves in order): IBA_SCAN_NMOM doubles per edge.
-//
-// What an edge's block computes depends on the edge alone: the chunk -> partial map is the same for both block shapes (a 256-thread block is
-// four chunks of ONE edge), so an edge's moments are the same bytes whatever else is in the batch and whichever shape the batch's largest
-// target tree selects. Ties: the lowest original index (nn_merge).
+//      The terms are formed after the search has ended: none of them is live across it.
+//  iba_scan_sum_kernel<MODE>             grid (edges): IBA_SCAN_NMOM doubles per edge.
 #pragma once
 #include "iba_icp_kernels.hpp"
 
@@ -43,15 +35,13 @@ __global__ __launch_bounds__(THREADS) void iba_scan_pass_kernel(DevProblem dp, c
     constexpr int NS = ScanSums<MODE>::n;
     extern __shared__ __align__(16) unsigned char smem[];
     TreeNode* s_nodes = (TreeNode*)smem;
-    int lo = 0, hi = nb - 1;   // the last edge whose first block is not beyond this one (uniform over the block)
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (xf[mid].blk0 <= blockIdx.x) lo = mid; else hi = mid - 1; }
-    const ScanXf& X = xf[lo];
+    const ScanXf& X = xf[flat_job<&ScanXf::blk0>(xf, nb, blockIdx.x)];
     const FrameHdr& hs = dp.frames[X.src];
     const FrameHdr& ht = dp.frames[X.tgt];
     const uint32_t pos = (blockIdx.x - X.blk0) * (uint32_t)THREADS + threadIdx.x;   // position in the source scan's tree order
     const bool act = pos < hs.P;
     const uint32_t P = ht.P, D = ht.depth;
-    for (uint32_t i = threadIdx.x; i < (1u << D) - 1u; i += THREADS) s_nodes[i] = dp.nodes[ht.node_base + i];
+    stage_nodes<THREADS>(dp, ht, s_nodes);
     __syncthreads();
     double q0 = 0.0, q1 = 0.0, q2 = 0.0;
     uint32_t sidx = 0u;
@@ -77,16 +67,7 @@ __global__ __launch_bounds__(THREADS) void iba_scan_pass_kernel(DevProblem dp, c
         const double t[3] = {(double)pv.x, (double)pv.y, (double)pv.z};
         v[0] = 1.0;
         if (MODE == kScanP2P) {
-            const double dq[3] = {q0 - X.piv[0], q1 - X.piv[1], q2 - X.piv[2]};
-            const double dp_[3] = {t[0] - X.piv[0], t[1] - X.piv[1], t[2] - X.piv[2]};
-            v[1] = bestA;
-            v[2] = dq[0]; v[3] = dq[1]; v[4] = dq[2];
-            v[5] = dp_[0]; v[6] = dp_[1]; v[7] = dp_[2];
-            v[8] = (dq[0] * dq[0] + dq[1] * dq[1]) + dq[2] * dq[2];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) v[9 + 3 * i + j] = dp_[i] * dq[j];
+            p2p_terms(v, bestA, q0, q1, q2, t[0], t[1], t[2], X.piv);
         } else if (MODE == kScanP2L) {
             v[1] = bestA;
             const PlaneRec& rec = dp.plane_cost[ht.pt_base + bposA];
@@ -112,14 +93,8 @@ __global__ __launch_bounds__(THREADS) void iba_scan_pass_kernel(DevProblem dp, c
         }
     }
     if (pair_idx && act) pair_idx[X.pair0 + sidx] = keep ? gidx : kNone;   // ORIGINAL order of the source scan
-#pragma unroll
-    for (int k = 0; k < NS; ++k) v[k] = wave_sum_f64(v[k]);   // (the total in lane 63)
     const uint32_t chunk = (blockIdx.x - X.blk0) * (uint32_t)(THREADS / 64) + (threadIdx.x >> 6);
-    if ((threadIdx.x & 63u) == 63u && chunk * 64u < hs.P) {   // (a wave of a 256-thread block beyond the scan's last chunk has no partial)
-        double* o = partials + ((size_t)X.part0 + (size_t)chunk) * NS;
-#pragma unroll
-        for (int k = 0; k < NS; ++k) o[k] = v[k];
-    }
+    wave_sum_store<NS>(v, chunk * 64u < hs.P, partials + ((size_t)X.part0 + (size_t)chunk) * NS);
 }
 
 template <int MODE>
@@ -128,23 +103,10 @@ __global__ __launch_bounds__(256) void iba_scan_sum_kernel(DevProblem dp, const 
     __shared__ double s_w[4][NS];
     const int b = (int)blockIdx.x, t = (int)threadIdx.x;
     const int nw = (int)((dp.frames[xf[b].src].P + 63u) / 64u);
-    double a[NS];
-#pragma unroll
-    for (int k = 0; k < NS; ++k) a[k] = 0.0;
-    for (int w = t; w < nw; w += 256) {
-        const double* p = partials + ((size_t)xf[b].part0 + (size_t)w) * NS;
-#pragma unroll
-        for (int k = 0; k < NS; ++k) a[k] += p[k];
-    }
-#pragma unroll
-    for (int k = 0; k < NS; ++k) a[k] = wave_sum_f64(a[k]);
-    if ((t & 63) == 63) {
-#pragma unroll
-        for (int k = 0; k < NS; ++k) s_w[t >> 6][k] = a[k];
-    }
+    block_sum_partials<NS>(partials + (size_t)xf[b].part0 * NS, nw, s_w);
     __syncthreads();
     double* o = out + (size_t)b * kScanMom;
-    if (t < NS) o[t] = ((s_w[0][t] + s_w[1][t]) + s_w[2][t]) + s_w[3][t];
+    if (t < NS) o[t] = wave_totals(s_w, t);
     else if (MODE == kScanP2P && t < kIcpMom) o[t] = xf[b].piv[t - kIcpSums];
     else if (t < kScanMom) o[t] = 0.0;
 }

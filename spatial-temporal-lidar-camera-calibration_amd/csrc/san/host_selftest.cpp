@@ -18,6 +18,8 @@
 
 #include "../../../include/iba_mi355x.h"
 #include "../../../include/iba_mi355x_debug.h"
+#include "../iba_icp_math.hpp"
+#include "../iba_lm.hpp"
 
 static int failures = 0;
 #define CHECK(c) do { if (!(c)) { std::fprintf(stderr, "host_selftest: %s failed at line %d\n", #c, __LINE__); ++failures; } } while (0)
@@ -52,6 +54,44 @@ static void mads_and_whitening() {
     std::vector<double> part((size_t)3 * iba_partial_stride(), 0.0);
     iba_cost_out co[3]; iba_normal_out no[3];
     CHECK(iba_finalize_cost(&p, part.data(), 3, co) == IBA_OK && iba_finalize_normal(&p, part.data(), 3, no) == IBA_OK);
+}
+
+// the split trust-region step (iba_lm.hpp) on f(x) = 1/2 (x - m)^T Q (x - m), Q symmetric positive definite: propose / judge through the
+// LDL^T solver must reach the known minimiser m and stop on a tolerance, never on a failed solve
+static void lm_step_quadratic() {
+    const double m[6] = {0.5, -1.25, 2.0, 0.125, -0.75, 3.0};
+    double Q[36];
+    for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) Q[i * 6 + j] = i == j ? 2.0 + 3.0 * i : 0.3 / (1.0 + std::abs(i - j));
+    const auto eval = [&](const double* x, double* g) {
+        double c = 0.0;
+        for (int i = 0; i < 6; ++i) { g[i] = 0.0; for (int j = 0; j < 6; ++j) g[i] += Q[i * 6 + j] * (x[j] - m[j]); c += 0.5 * (x[i] - m[i]) * g[i]; }
+        return c;
+    };
+    const auto ldlt = [](const double* A, const double* rhs, double* x) { double L[36] = {0.0}, d[6]; if (!iba::icp::ldlt6_factor(A, L, d)) return false; iba::icp::ldlt6_apply(L, d, rhs, x); return true; };
+    const iba::LmOptions o;
+    double x[6] = {0, 0, 0, 0, 0, 0}, g[6], cost = eval(x, g);
+    const double cost0 = cost;
+    iba::LmStep<6> step;
+    step.begin(o, Q);
+    int trials = 0, accepted = 0;
+    bool stopped = false;
+    for (int it = 0; it < 50 && !stopped; ++it) {
+        const iba::LmProposal next = step.propose(o, Q, g, ldlt);
+        CHECK(next != iba::LmProposal::kNoSolve);
+        if (next == iba::LmProposal::kStop || next == iba::LmProposal::kNoSolve) { stopped = true; break; }
+        if (next == iba::LmProposal::kRetry) continue;
+        double xn[6], gn[6], xn2 = 0.0;
+        for (int i = 0; i < 6; ++i) { xn[i] = x[i] + step.delta[i]; xn2 += x[i] * x[i]; }
+        const double cn = eval(xn, gn);
+        ++trials;
+        CHECK(step.model > 0.0);
+        const iba::LmVerdict verdict = step.judge(o, cost, cn, xn2);
+        if (verdict == iba::LmVerdict::kStop) stopped = true;
+        if (verdict == iba::LmVerdict::kAccept) { CHECK(cn < cost); std::memcpy(x, xn, sizeof(x)); std::memcpy(g, gn, sizeof(g)); cost = cn; ++accepted; }
+    }
+    CHECK(stopped && trials > 0 && accepted > 0 && step.radius > o.initial_trust_region_radius);   // every step of a quadratic is a good one: the radius only grew
+    CHECK(cost <= 1e-9 * cost0);
+    for (int i = 0; i < 6; ++i) CHECK(std::fabs(x[i] - m[i]) < 1e-4);
 }
 
 static void handeye() {
@@ -179,6 +219,7 @@ int main(int argc, char** argv) {
     const char* scratch = mkdtemp(tmpl);
     if (!scratch) { std::perror("mkdtemp"); return 2; }
     mads_and_whitening();
+    lm_step_quadratic();
     handeye();
     small_files(scratch);
     if (argc > 1) dataset(argv[1], scratch);
