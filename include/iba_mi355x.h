@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define IBA_ABI_VERSION 4 /* 2: iba_params.factor_3d2d_kind; 3: iba_icp_*; 4: iba_scan_*. An ADDED entry point (iba_submap_*, iba_sc_*, iba_floam_*) changes no existing struct and does not bump it: callers detect it by symbol */
+#define IBA_ABI_VERSION 4 /* 2: iba_params.factor_3d2d_kind; 3: iba_icp_*; 4: iba_scan_*. An ADDED entry point (iba_submap_*, iba_lattice_*, iba_sc_*, iba_floam_*) changes no existing struct and does not bump it: callers detect it by symbol */
 #define IBA_MAX_BATCH 64 /* the batch unit of the callers in this library (one MADS poll block, the planner's diagnostics); NOT a limit of the evaluators */
 #define IBA_MAX_CHAIN 512 /* most candidates ONE launch chain takes (iba_create_options.max_chain_batch <= this); a call with more runs as consecutive chains */
 
@@ -377,6 +377,47 @@ void iba_submap_free(iba_submap_clouds* c);
 iba_status iba_submap_handle(iba_handle* src, const iba_submap_desc* subs, int32_t M, const iba_params* params, iba_handle** out);
 
 /*
+ * ---- The lattice voxel filter with a crop box: PCL's VoxelGrid and CropBox as F-LOAM's local map uses them [src/floam/src/odomEstimationClass.cpp:
+ * downSamplingToMap :94-99, addPointsToMap :210-250] ----
+ * iba_submap_build's grid is Open3D's: it hangs on the cloud's own minimum, so the cells move whenever the cloud's extent does. A local map that is
+ * filtered again after every scan needs PCL's rule — cells anchored at the ORIGIN, the same cells on every step — and a box that cuts the map to the
+ * neighbourhood of the sensor. iba_lattice_build is that filter on the same inputs (resident scans + poses, a BATCH OF SUB-MAPS per launch chain) with
+ * the same result object and accessors. The result is a function of the input alone (tests/floam_odom_ref.py restates the rules in numpy; the device
+ * result equals it byte for byte):
+ *   L1 point     rule 1 of iba_submap_build, unchanged: float32 widened to f64, four separately rounded operations, no fused multiply-add; members in
+ *                list order, a member's points in original index order; a non-finite point is dropped and counted in n_dropped.
+ *   L2 crop      with has_crop, a point is kept iff crop_lo[a] <= q[a] <= crop_hi[a] on all three axes, BOTH ends inclusive as PCL's CropBox is; the
+ *                others are counted in n_cropped (a dropped point is never counted as cropped). KNOWN DEVIATION: PCL compares in float. The crop
+ *                takes effect in the first kernel: a cropped point takes part in no bound and costs no sort key beyond the drop bucket.
+ *   L3 cell      i[a] = floor(q[a] / leaf): IEEE f64 division, then floor; the origin is the anchor, there is no minb (floor(-0.1 / 0.4) = -1, and
+ *                -0 lies in cell 0). KNOWN DEVIATION: PCL forms floor(float(q) * inv_leaf) in float. A sub-map whose kept points span more than
+ *                2^17 cells along an axis (max i - min i + 1) answers IBA_ERR_UNSUPPORTED, with the wording of iba_submap_build's check.
+ *   L4 centroid  rules 3-5 of iba_submap_build, unchanged: sequential f64 sums in concatenation order divided by double(count), out12 applied after,
+ *                voxels ascending (ix, iy, iz), every occupied cell gives a point (PCL's min_points_per_voxel = 0). KNOWN DEVIATIONS: PCL
+ *                accumulates in float after an unstable sort and orders by (iz, iy, ix).
+ * Arguments: iba_submap_build's rules and messages, headed by this function's name (the cell size is named leaf); in addition crop_lo and crop_hi must
+ * be finite with lo <= hi, whether or not has_crop is set. A sub-map emptied by the crop answers zero voxels.
+ * Limits: the clouds come back to the host, as iba_submap_build's do; iba_floam_odom_run (further below) runs the same chain on the device without
+ * the download to keep F-LOAM's local map. One GPU.
+ */
+typedef struct iba_lattice_desc {
+    int32_t struct_size;      /* sizeof(iba_lattice_desc) */
+    int32_t n_members;
+    const int32_t* frames;    /* [n_members] local frames of the handle */
+    const double*  poses12;   /* [n_members x 12] row-major 3x4, scan frame -> common frame */
+    const double*  out12;     /* row-major 3x4 applied to the centroids, or NULL */
+    double  leaf;             /* cell size (odomEstimationClass: map_resolution for edges, 2 x map_resolution for surfs) */
+    int32_t has_crop;         /* 0: no crop (crop_lo / crop_hi must still be finite, lo <= hi: zeros do) */
+    int32_t reserved;         /* 0 */
+    double  crop_lo[3];       /* the box in the common frame, before out12 */
+    double  crop_hi[3];
+} iba_lattice_desc;
+/* The result is read through the iba_submap_* accessors and released with iba_submap_free. *out is NULL on failure. */
+iba_status iba_lattice_build(iba_handle* h, const iba_lattice_desc* subs, int32_t M, iba_submap_clouds** out);
+/* Points of sub-map s that the crop box removed (rule L2); 0 for a result of iba_submap_build, -1 for NULL or s out of range. */
+int64_t iba_submap_n_cropped(const iba_submap_clouds* c, int32_t s);
+
+/*
  * ---- Scan Context: descriptors, ring keys, batched loop search [src/scancontext/Scancontext.cpp: makeScancontext(vector<Vector3d>) :198-240, ring / sector
  * keys :242-271, distDirectSC :70-91, fastAlignUsingVkey :94-114, distanceBtnScanContext :117-149, detectLoopClosureID :393-486; called per keyframe from
  * backend_opt.cpp:325,361 and :305] ----
@@ -530,10 +571,10 @@ iba_status iba_sc_replay_plan(const int32_t* sizes_at_call, int32_t n, const iba
  * Answers IBA_ERR_INVALID_ARG with a message, before any launch: a NULL argument, a struct_size of another library, num_lines not 16, 32 or 64, n outside
  * [1, 2^20], a frame outside the handle, distances not finite or min_distance > max_distance, min_ring_points < 11, num_sectors outside [1, 64],
  * max_edges_per_sector outside [0, 64], neighbour_span != 5, thresholds not finite. On failure *out is NULL and iba_last_error(h) carries the message.
- * Limits: the clouds come back to the host. To register against them, build a handle from them with iba_create; keeping them on the device as frames
- * of a new handle (as iba_submap_handle does for voxel clouds) is not done. The ring of a point is always derived from its elevation (a per-point
+ * Limits: iba_floam_extract brings the clouds back to the host; to register against them yourself, build a handle from them with iba_create.
+ * iba_floam_odom_run (below) keeps them on the device as frames of a handle it builds there. The ring of a point is always derived from its elevation (a per-point
  * ring field supplied by the caller is not read). The scan-to-map step that consumes the clouds is iba_floam_map_* (below); PCL's VoxelGrid and crop
- * box and the local map are not restated. One GPU.
+ * box are iba_lattice_build and the local map is kept by iba_floam_odom_run. One GPU.
  */
 #define IBA_FLOAM_MAX_RING_POINTS 8192
 typedef struct iba_floam_options {
@@ -616,10 +657,10 @@ void iba_floam_free(iba_floam_features* f);
  *                 launch chain and one synchronise per evaluation for all pairs still running.
  * Answers IBA_ERR_INVALID_ARG with a message in iba_last_error(h), before any launch: a NULL argument, a struct_size of another library, k != 5, a frame
  * outside the handle, a non-finite T, a threshold that is not finite or negative, a negative count, B outside [1, 4096].
- * Limits: NO local-map maintenance — addPointsToMap, PCL's VoxelGrid and CropBox and laserMappingClass are not restated: the map clouds are given
- * (iba_submap_handle builds voxel clouds on the device). A map cloud is always ONE frame and a frame of this library is one kd tree (one tile): the
+ * Limits: the map clouds of these two calls are GIVEN (iba_submap_handle builds voxel clouds on the device); the loop that keeps a local map —
+ * addPointsToMap with PCL's VoxelGrid and CropBox — is iba_floam_odom_run (below). laserMappingClass is not restated. A map cloud is always ONE frame and a frame of this library is one kd tree (one tile): the
  * search walks a single tree, its only box test is the frame's box against max_nn_dist2, and no bound is carried from tile to tile; a map spread over
- * several frames has to be merged into one first. The constant-velocity prediction of the start pose is the caller's. Parity with Ceres and PCL is
+ * several frames has to be merged into one first. The constant-velocity prediction of the start pose is the caller's here (iba_floam_odom_run forms it). Parity with Ceres and PCL is
  * unpinned (neither can be built beside this library). One GPU.
  */
 #define IBA_FLOAM_NMOM 34
@@ -663,6 +704,75 @@ iba_status iba_floam_map_step(iba_handle* h, const iba_floam_pair* pairs, int32_
                               double* moments /* B x IBA_FLOAM_NMOM */, uint32_t* nn_idx, iba_floam_record* records);
 /* Rule 8 per pair from pairs[b].T, all pairs together. */
 iba_status iba_floam_map_register(iba_handle* h, const iba_floam_pair* pairs, int32_t B, const iba_floam_map_options* opt, iba_floam_map_result* out /* B */);
+
+/*
+ * ---- F-LOAM odometry: local map upkeep and the track loop [src/floam/src/floamClass.cpp System::Track; src/floam/src/odomEstimationClass.cpp:
+ * initMapWithPoints :25-29, updatePointsToMap :32-81, downSamplingToMap :94-99, addPointsToMap :210-250] ----
+ * The loop that joins iba_floam_extract and iba_floam_map_register into what the reference's floam_kitti produces: a pose per scan. A BATCH OF
+ * TRACKS (lists of resident scans of one handle) goes in, a pose per scan comes out, and nothing of cloud size crosses PCIe in between: the
+ * feature clouds, the down-sampled clouds and the local maps become frames of handles that are built on the device (csrc/iba_index_kernels.hpp).
+ * Rules, per track (tests/floam_odom_ref.py restates the filter and the host-side rules in numpy):
+ *   O1 features     iba_floam_extract's rules on every scan of every track: ONE chain for the whole call (it depends on no pose).
+ *   O2 down-sample  downSamplingToMap: the lattice filter (iba_lattice_build, rules L1-L4) without crop on each scan's clouds in the scan's own
+ *                   frame, edge cloud leaf = map_resolution, surf cloud leaf = 2 map_resolution, centroids narrowed to float32 (round to nearest
+ *                   even): ONE chain for the whole call.
+ *   O3 first scan   initMapWithPoints: pose T0; the map is the RAW, un-down-sampled edge and surf features moved by T0 (rule L1's expression,
+ *                   narrowed to float32), no crop, no filter. The step record has passes = 0 and T_pred = T = T0.
+ *   O4 prediction   for k >= 1, T_pred = T[k-1] (inv(T[k-2]) T[k-1]) with T[-1] := T0; inv = [R^T, -R^T t]; f64 on the host.
+ *   O5 solve        rule 8 of iba_floam_map_* from T_pred on (down-sampled scan clouds, map of step k - 1) with max(map.outer_passes,
+ *                   init_passes - k) passes: the reference's optimization_count, 12 after init, one less on every scan, down to 2. A DEGENERATE
+ *                   pair keeps the pose the solve returns (the reference keeps its prediction when the map is too small) and the track goes on.
+ *   O6 map update   addPointsToMap, per kind: members [map of step k - 1, identity; down-sampled scan cloud, T[k]], crop t[k] +- crop_half per axis
+ *                   (f64), the lattice filter with leaf map_resolution (edge) / 2 map_resolution (surf), narrowed to float32. Map points therefore
+ *                   stay in (ix, iy, iz) order, old map first within a cell.
+ *   O7 batch        the tracks of a call advance in lock-step: one extract chain, one down-sampling chain, then per step one solve and one map
+ *                   update for all tracks still running. Tracks may differ in length and a frame may appear in several tracks. A track's result
+ *                   does not depend on the rest of the batch, and two calls give the same bytes.
+ * Answers IBA_ERR_INVALID_ARG with a message, before any launch: a NULL argument, B outside [1, 256], n_scans outside [1, 2^16], a frame outside
+ * the handle, a non-finite T0, map_resolution or crop_half not positive and finite, init_passes < 0, a wrong struct_size (nested ones included);
+ * the checks of the two nested option blocks run too and are reported under this function's name. IBA_ERR_UNSUPPORTED: more than 2048 scans in
+ * one call (the down-sampling chain takes two sub-maps per scan), a cloud of 2^22 points or more, a map that spans more than 2^17 cells along an
+ * axis, a coordinate that is not finite after narrowing to float32.
+ * Limits: a first version — every step builds a small handle (the four clouds of every running track) on the device and releases the one
+ * before; csrc/iba_floam_odom_host.hpp and DESIGN.md say what a step allocates. laserMappingClass (the global map for display) is not restated.
+ * Parity with Ceres and PCL is unpinned, as for iba_floam_map_*. One GPU.
+ */
+typedef struct iba_floam_track {
+    int32_t n_scans;
+    const int32_t* frames;        /* [n_scans] local frames of the handle, in time order */
+    double  T0[16];               /* row-major 4x4, the pose of the first scan */
+} iba_floam_track;
+typedef struct iba_floam_odom_options {
+    int32_t struct_size;          /* sizeof(iba_floam_odom_options) */
+    int32_t init_passes;          /* 12 */
+    int32_t keep_maps;            /* 0; 1: the map after every step stays readable (tests) */
+    int32_t reserved;             /* 0 */
+    double  map_resolution;       /* 0.4 (HDL_64; 0.2 for 16 / 32 lines) */
+    double  crop_half;            /* 100.0 */
+    iba_floam_options     extract;
+    iba_floam_map_options map;    /* outer_passes is the floor of the pass count (2) */
+} iba_floam_odom_options;
+typedef struct iba_floam_odom_step {
+    double  T_pred[16], T[16];
+    double  initial_cost, final_cost;
+    int32_t passes, iterations, evaluations, n_edge, n_surf, status;
+    int64_t n_src_edge, n_src_surf;   /* the down-sampled scan clouds */
+    int64_t n_map_edge, n_map_surf;   /* the map AFTER this step */
+} iba_floam_odom_step;
+typedef struct iba_floam_odom iba_floam_odom;
+/* the reference's constants, the nested blocks included */
+iba_status iba_default_floam_odom_options(iba_floam_odom_options* opt);
+/* B tracks in lock-step. The result is allocated by the library; release it with iba_floam_odom_free. *out is NULL on failure. */
+iba_status iba_floam_odom_run(iba_handle* h, const iba_floam_track* tracks, int32_t B, const iba_floam_odom_options* opt, iba_floam_odom** out);
+/* Tracks of a result (0 for NULL); scans of track b (-1 out of range); its n_scans step records (NULL out of range); the down-sampled cloud of
+ * scan k and the map after step k (kind 0 edge / 1 surf; 3 floats per point, *n points; the map of the last step always, of any step with
+ * keep_maps; NULL with *n = -1 otherwise). Valid until iba_floam_odom_free. */
+int32_t iba_floam_odom_num(const iba_floam_odom* o);
+int32_t iba_floam_odom_n_scans(const iba_floam_odom* o, int32_t b);
+const iba_floam_odom_step* iba_floam_odom_steps(const iba_floam_odom* o, int32_t b);
+const float* iba_floam_odom_src(const iba_floam_odom* o, int32_t b, int32_t k, int32_t kind, int64_t* n);
+const float* iba_floam_odom_map(const iba_floam_odom* o, int32_t b, int32_t k, int32_t kind, int64_t* n);
+void iba_floam_odom_free(iba_floam_odom* o);
 
 /*
  * ---- Pose-graph optimisation: Levenberg-Marquardt with line process [backend_opt.cpp:433-528 MultiRegistration: nodes pose[i]^-1 :441, odometry

@@ -545,6 +545,20 @@ class IbaHandle:
         from . import floam_map
         return floam_map.register(self, pairs, opt, **fields)
 
+    # --- the lattice voxel filter with a crop box (iba_lattice_build): PCL's VoxelGrid + CropBox of F-LOAM's local map ---
+    def lattice_build(self, subs):
+        """iba_lattice_build: subs = iterable of (frames, poses, out, leaf, crop) — as for submap_build, crop = None or (lo [3], hi [3]) in the common
+        frame -> list of dict(xyz [V, 3] float64 in ascending (ix, iy, iz), count [V] int32, n_dropped, n_cropped) per sub-map (floam_odom.py)"""
+        from . import floam_odom
+        return floam_odom.lattice_build(self, subs)
+
+    # --- F-LOAM odometry (iba_floam_odom_run): extract, down-sample, solve against the local map and update it, a batch of tracks in lock-step ---
+    def floam_odom(self, tracks, opt=None, **fields):
+        """iba_floam_odom_run: tracks = [(frames [n] in time order, T0 4x4)] -> per track a list of dict per scan (floam_odom.odom). opt = an
+        IbaFloamOdomOptions, or fields of one (extract = {...}, map = {...} for the nested blocks) over the reference's defaults."""
+        from . import floam_odom
+        return floam_odom.odom(self, tracks, opt, **fields)
+
     def debug_scan_threads(self, threads):
         """force the block shape of the scan pass kernel (64 / 256; 0: the rule)"""
         self.lib.iba_debug_scan_threads.argtypes = [C.c_void_p, C.c_int32]

@@ -42,6 +42,7 @@ const char* debug_env(const char* name) {   // (read at every handle creation: a
 #include "iba_index_kernels.hpp"
 #include "iba_floam_kernels.hpp"
 #include "iba_floam_map_kernels.hpp"
+#include "iba_floam_odom_kernels.hpp"
 #include "iba_icp_math.hpp"
 #include "iba_types.hpp"
 
@@ -221,6 +222,7 @@ struct iba_handle {
         DevBuf<VoxMember> d_mem; DevBuf<VoxSub> d_sub; DevBuf<VoxPartial> d_part, d_bounds;   // members, sub-maps, block partials of the bounds, bounds per sub-map
         DevBuf<double> d_q3; DevBuf<uint64_t> d_key[2]; DevBuf<uint32_t> d_val[2]; DevBuf<unsigned char> d_tmp;   // staged q, the sort's double buffers and its temporary storage
         DevBuf<uint32_t> d_blockc, d_subfirst, d_seg; DevBuf<double> d_xyz; DevBuf<int32_t> d_cnt;   // head counts per block (+ total), first voxel per sub-map, segment starts, the clouds
+        DevBuf<VoxLatPartial> d_lpart, d_lbounds; DevBuf<VoxCrop> d_crop;   // iba_lattice_build: its partials and bounds (with the cropped counts), the crop boxes
     } vox;
 
     DevProblem dev_problem() const {
@@ -1063,7 +1065,7 @@ iba_status eval_cost_partial_impl(iba_handle* h, const double* x, int B, double*
 
 namespace {
 // iba_submap_handle (iba_index_host.hpp): where the scans of a new handle come from when they are already on the device
-struct ScanSource { iba_handle* src; const uint32_t* first; };   // the handle whose voxel chain holds the clouds (src->vox), first voxel of every frame (n_frames + 1)
+struct ScanSource { iba_handle* src; const uint32_t* first; const double* xyz = nullptr; };   // the handle whose stream the build runs on, first point of every frame (n_frames + 1) in xyz (3 doubles per point, on src's device; NULL: the clouds of src's voxel chain, src->vox.d_xyz)
 iba_status index_build_device(iba_handle* dst, const ScanSource& from, std::string& why);
 iba_status create_impl(const iba_problem_desc* d, const iba_params* params, int device, int32_t frame_begin, int32_t frame_end, const iba_create_options* user_opt, const ScanSource* pre, iba_handle** out);
 }  // namespace
@@ -2160,3 +2162,4 @@ iba_status reserve_batch(iba_handle* h, int B) {
 #include "iba_index_host.hpp" // iba_submap_handle (the device index build) / iba_debug_scan_index
 #include "iba_floam_host.hpp" // iba_floam_extract and the accessors of its result
 #include "iba_floam_map_host.hpp" // iba_floam_map_step / iba_floam_map_register
+#include "iba_floam_odom_host.hpp" // iba_floam_odom_run and the accessors of its result

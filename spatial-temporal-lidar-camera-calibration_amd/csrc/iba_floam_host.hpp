@@ -2,7 +2,8 @@
 // vox_bits it shares). One call = one launch chain for the whole batch of scans (iba_floam_kernels.hpp) with three synchronisations: after the
 // classification and the partition (the ring sizes come up, 272 B per scan: rule 3 is checked and the sectors are listed on the host), after the
 // scans of the sector counts (the outputs are sized) and at the end. Down go the scan, block and sector lists (16 + 8 B per 256 points, 16 B per
-// sector); up come the ring sizes, the offsets per sector and the two clouds. The work buffers belong to the call.
+// sector); up come the ring sizes, the offsets per sector and the two clouds. The work buffers belong to the call. floam_extract_impl is the
+// same chain with the clouds left on the device for iba_floam_odom_run (iba_floam_odom_host.hpp).
 #include <rocprim/device/device_radix_sort.hpp>
 
 struct iba_floam_features {
@@ -45,8 +46,13 @@ iba_status iba_default_floam_options(iba_floam_options* o) {
     return IBA_OK;
 }
 
-iba_status iba_floam_extract(iba_handle* h, const int32_t* frames, int32_t n, const iba_floam_options* opt, iba_floam_features** out) {
-    const std::string who = "iba_floam_extract: ";
+namespace {
+
+struct FloamDevClouds { DevBuf<float> exyz, sxyz; };   // the gathered clouds of a call, left on the device (efirst / sfirst of the result index them)
+
+// iba_floam_extract. keep != NULL (iba_floam_odom_run): the two clouds stay on the device in *keep and are NOT downloaded — the result then holds
+// the counts, first positions and statistics only, its xyz / index arrays are empty. `who` heads the messages.
+iba_status floam_extract_impl(iba_handle* h, const int32_t* frames, int32_t n, const iba_floam_options* opt, const std::string& who, FloamDevClouds* keep, iba_floam_features** out) {
     if (!h) return fail(nullptr, IBA_ERR_INVALID_ARG, who + "the handle is NULL");
     if (!out) return fail(h, IBA_ERR_INVALID_ARG, who + "the result pointer is NULL");
     *out = nullptr;
@@ -163,19 +169,26 @@ iba_status iba_floam_extract(iba_handle* h, const int32_t* frames, int32_t n, co
     hipLaunchKernelGGL(iba_floam_gather_kernel, dim3((unsigned)T), dim3(kFloamThreads), 0, st, d_tasks.p, d_rp.p, opt->max_edges_per_sector, d_epos.p, d_spos.p, d_ne.p, d_ns.p, d_exyz.p, d_eidx.p, d_sxyz.p,
                        d_sidx.p);
     HIP_TRY(h, hipGetLastError());
-    res->exyz.resize(3 * NE); res->eidx.resize(NE); res->sxyz.resize(3 * NS); res->sidx.resize(NS);
-    if (NE) {
+    if (!keep) { res->exyz.resize(3 * NE); res->eidx.resize(NE); res->sxyz.resize(3 * NS); res->sidx.resize(NS); }
+    if (NE && !keep) {
         HIP_TRY(h, hipMemcpyAsync(res->exyz.data(), d_exyz.p, sizeof(float) * 3 * NE, hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipMemcpyAsync(res->eidx.data(), d_eidx.p, sizeof(int32_t) * NE, hipMemcpyDeviceToHost, st));
     }
-    if (NS) {
+    if (NS && !keep) {
         HIP_TRY(h, hipMemcpyAsync(res->sxyz.data(), d_sxyz.p, sizeof(float) * 3 * NS, hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipMemcpyAsync(res->sidx.data(), d_sidx.p, sizeof(int32_t) * NS, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(h, hipStreamSynchronize(st));
     for (int32_t i = 0; i <= n; ++i) { res->efirst[(size_t)i] = (int64_t)eoff[task_first[(size_t)i]]; res->sfirst[(size_t)i] = (int64_t)soff[task_first[(size_t)i]]; }
+    if (keep) { keep->exyz = std::move(d_exyz); keep->sxyz = std::move(d_sxyz); }
     *out = res.release();
     return IBA_OK;
+}
+
+}  // namespace
+
+iba_status iba_floam_extract(iba_handle* h, const int32_t* frames, int32_t n, const iba_floam_options* opt, iba_floam_features** out) {
+    return floam_extract_impl(h, frames, n, opt, "iba_floam_extract: ", nullptr, out);
 }
 
 int32_t iba_floam_num(const iba_floam_features* f) { return f ? f->n : 0; }

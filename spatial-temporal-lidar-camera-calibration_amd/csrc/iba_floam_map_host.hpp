@@ -15,17 +15,25 @@ struct FloamMapState {   // one pair of iba_floam_map_register
     bool enabled = false, finished = false, inner = false;
 };
 
+// "" when the options are inside the supported range; otherwise the message, as iba_floam_map_* word it under the name `w`
+std::string fmap_options_error(const iba_floam_map_options* o, const std::string& w) {
+    if (!o) return w + ": options are NULL (iba_default_floam_map_options fills them)";
+    if (o->struct_size != (int32_t)sizeof(iba_floam_map_options)) return "iba_floam_map_options.struct_size does not match this library";
+    if (o->k != 5) return w + ": k = " + std::to_string(o->k) + " neighbours are not supported (5 is the only value)";
+    const double th[5] = {o->max_nn_dist2, o->edge_eig_ratio, o->edge_half_len, o->plane_max_resid, o->huber_delta};
+    for (double v : th) if (!std::isfinite(v) || v < 0.0) return "iba_floam_map_options: max_nn_dist2, edge_eig_ratio, edge_half_len, plane_max_resid and huber_delta must be finite and not negative";
+    if (o->outer_passes < 0 || o->inner_iterations < 0 || o->min_map_edge < 0 || o->min_map_surf < 0)
+        return "iba_floam_map_options: outer_passes, inner_iterations, min_map_edge and min_map_surf must not be negative";
+    return "";
+}
+
 iba_status fmap_check(iba_handle* h, const iba_floam_pair* pairs, int32_t B, const iba_floam_map_options* o, const char* who) {
     const std::string w(who);
     if (!pairs) return fail(h, IBA_ERR_INVALID_ARG, w + ": pairs are NULL");
-    if (!o) return fail(h, IBA_ERR_INVALID_ARG, w + ": options are NULL (iba_default_floam_map_options fills them)");
-    if (o->struct_size != (int32_t)sizeof(iba_floam_map_options)) return fail(h, IBA_ERR_INVALID_ARG, "iba_floam_map_options.struct_size does not match this library");
+    const std::string bad = fmap_options_error(o, w);
+    if (!bad.empty() && (!o || o->struct_size != (int32_t)sizeof(iba_floam_map_options))) return fail(h, IBA_ERR_INVALID_ARG, bad);
     if (B < 1 || B > kFloamMapMaxB) return fail(h, IBA_ERR_INVALID_ARG, w + ": B must be in [1, 4096]");
-    if (o->k != 5) return fail(h, IBA_ERR_INVALID_ARG, w + ": k = " + std::to_string(o->k) + " neighbours are not supported (5 is the only value)");
-    const double th[5] = {o->max_nn_dist2, o->edge_eig_ratio, o->edge_half_len, o->plane_max_resid, o->huber_delta};
-    for (double v : th) if (!std::isfinite(v) || v < 0.0) return fail(h, IBA_ERR_INVALID_ARG, "iba_floam_map_options: max_nn_dist2, edge_eig_ratio, edge_half_len, plane_max_resid and huber_delta must be finite and not negative");
-    if (o->outer_passes < 0 || o->inner_iterations < 0 || o->min_map_edge < 0 || o->min_map_surf < 0)
-        return fail(h, IBA_ERR_INVALID_ARG, "iba_floam_map_options: outer_passes, inner_iterations, min_map_edge and min_map_surf must not be negative");
+    if (!bad.empty()) return fail(h, IBA_ERR_INVALID_ARG, bad);
     for (int b = 0; b < B; ++b) {
         const iba_floam_pair& p = pairs[b];
         const int32_t fr[4] = {p.src_edge_frame, p.src_surf_frame, p.map_edge_frame, p.map_surf_frame};

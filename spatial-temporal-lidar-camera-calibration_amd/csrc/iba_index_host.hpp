@@ -4,7 +4,8 @@
 // by index_build_device: one launch chain on the SOURCE handle's stream for all frames of the new handle (iba_index_kernels.hpp) — per tree
 // level a segment kernel, rocPRIM's segmented radix sort and a split kernel (at most kMaxTreeDepth = 11 levels), then the sort inside the
 // leaves, the gather and the boxes. Down go 32 B per frame, up come a flag word and 32 B of frame box per frame. The work buffers are of
-// the size of the clouds and live for the call only (IdxScratch).
+// the size of the clouds and live for the call only (IdxScratch). The source of the build is any buffer of f64 triples on the device
+// (ScanSource::xyz; NULL = the voxel chain's clouds): iba_floam_odom_run (iba_floam_odom_host.hpp) builds its handles through the same chain.
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 namespace {
@@ -50,7 +51,7 @@ iba_status index_build_device(iba_handle* dst, const ScanSource& from, std::stri
     IDX_TRY(w.src4.alloc((size_t)total)); IDX_TRY(w.order.alloc((size_t)total)); IDX_TRY(w.flag.alloc(1));
     IDX_TRY(hipMemsetAsync(w.flag.p, 0, sizeof(uint32_t), st));
     auto blocks = [](uint64_t n, uint32_t per) { return dim3((unsigned)((n + per - 1) / per)); };
-    hipLaunchKernelGGL(iba_idx_stage_kernel, blocks(n_quads, kIdxThreads), dim3(kIdxThreads), 0, st, w.fr.p, M, n_quads, src->vox.d_xyz.p, w.src4.p, w.order.p, w.flag.p);
+    hipLaunchKernelGGL(iba_idx_stage_kernel, blocks(n_quads, kIdxThreads), dim3(kIdxThreads), 0, st, w.fr.p, M, n_quads, from.xyz ? from.xyz : src->vox.d_xyz.p, w.src4.p, w.order.p, w.flag.p);
     IDX_TRY(hipGetLastError());
     const uint32_t* final_order = w.order.p;
     if (dmax > 0) {
@@ -101,23 +102,22 @@ iba_status index_build_device(iba_handle* dst, const ScanSource& from, std::stri
 
 }  // namespace
 
-iba_status iba_submap_handle(iba_handle* src, const iba_submap_desc* subs, int32_t M, const iba_params* params, iba_handle** out) {
-    if (!src) return IBA_ERR_INVALID_ARG;
-    const std::string who = "iba_submap_handle: ";
-    if (!out) return fail(src, IBA_ERR_INVALID_ARG, who + "the result pointer is NULL");
-    *out = nullptr;
-    if (!params) return fail(src, IBA_ERR_INVALID_ARG, who + "the parameters are NULL");
-    if (const iba_status s = check_params(src, *params)) return s;
-    iba_submap_clouds* built = nullptr;
-    if (const iba_status s = vox_build(src, subs, M, who, false, &built)) return s;
-    const std::unique_ptr<iba_submap_clouds> c(built);
-    // a scans-only problem of M frames: no keypoints, no covisibility, identity poses, the intrinsics of a KITTI camera (none of them is read by the scan-side entry points)
-    std::vector<uint64_t> pt_off((size_t)M + 1), zeros((size_t)M + 1, 0ull);
-    std::vector<uint32_t> first((size_t)M + 1);
-    for (int s = 0; s <= M; ++s) { pt_off[(size_t)s] = (uint64_t)c->first[(size_t)s]; first[(size_t)s] = (uint32_t)c->first[(size_t)s]; }
+// A scans-only handle of M frames whose points are on src's device already, in xyz (3 doubles per point, narrowed to float32 by the stage kernel;
+// NULL: src->vox.d_xyz). counts == NULL: the frames lie one after the other, frame s = the points first64[s] .. first64[s + 1] (M + 1 entries);
+// otherwise frame s has counts[s] points from first64[s] on (iba_floam_odom_run: frames anywhere in a staging buffer). No keypoints, no covisibility,
+// identity poses, the intrinsics of a KITTI camera (none of them is read by the scan-side entry points). The message is left in
+// iba_last_error(src), headed by `who`; `what` names a frame in it.
+iba_status scan_handle_from_device(iba_handle* src, const double* xyz, const std::vector<int64_t>& first64, const std::vector<int64_t>* counts, int32_t M, const iba_params* params, const std::string& who, const char* what,
+                                   iba_handle** out) {
+    std::vector<uint64_t> pt_off((size_t)M + 1, 0ull), zeros((size_t)M + 1, 0ull);
+    std::vector<uint32_t> first((size_t)M + 1, 0u);
+    for (int s = 0; s < M; ++s) {
+        first[(size_t)s] = (uint32_t)first64[(size_t)s];
+        pt_off[(size_t)s + 1] = pt_off[(size_t)s] + (uint64_t)(counts ? (*counts)[(size_t)s] : first64[(size_t)s + 1] - first64[(size_t)s]);
+    }
     for (int s = 0; s < M; ++s)
         if (pt_off[(size_t)s + 1] - pt_off[(size_t)s] >= (1ull << 22))
-            return fail(src, IBA_ERR_UNSUPPORTED, who + "sub-map " + std::to_string(s) + " has " + std::to_string(pt_off[(size_t)s + 1] - pt_off[(size_t)s]) + " voxels; a frame holds fewer than 2^22 points (choose a larger voxel)");
+            return fail(src, IBA_ERR_UNSUPPORTED, who + what + " " + std::to_string(s) + " has " + std::to_string(pt_off[(size_t)s + 1] - pt_off[(size_t)s]) + " voxels; a frame holds fewer than 2^22 points (choose a larger voxel)");
     const double intr[6] = {718.856, 718.856, 607.1928, 185.2157, 1241.0, 376.0};
     std::vector<double> intrinsics(6 * (size_t)M), Tl(12 * (size_t)M, 0.0);
     std::vector<float> T34(12 * (size_t)M, 0.f);
@@ -130,12 +130,25 @@ iba_status iba_submap_handle(iba_handle* src, const iba_submap_desc* subs, int32
     std::memset(&d, 0, sizeof(d));
     d.n_frames = M; d.pt_offset = pt_off.data(); d.pts_xyz = nullptr; d.intrinsics = intrinsics.data(); d.kp_offset = zeros.data(); d.covis_offset = zeros.data();
     d.match_offset = match_off; d.Tcw = T34.data(); d.Tc_next = T34.data(); d.Tl_next = Tl.data();
-    const ScanSource from{src, first.data()};
+    const ScanSource from{src, first.data(), xyz};
     iba_handle* h = nullptr;
     const iba_status s = create_impl(&d, params, src->device, 0, M, nullptr, &from, &h);
     if (s != IBA_OK) return fail(src, s, g_create_error.rfind(who, 0) == 0 ? g_create_error : who + g_create_error);
     *out = h;
     return IBA_OK;
+}
+
+iba_status iba_submap_handle(iba_handle* src, const iba_submap_desc* subs, int32_t M, const iba_params* params, iba_handle** out) {
+    if (!src) return IBA_ERR_INVALID_ARG;
+    const std::string who = "iba_submap_handle: ";
+    if (!out) return fail(src, IBA_ERR_INVALID_ARG, who + "the result pointer is NULL");
+    *out = nullptr;
+    if (!params) return fail(src, IBA_ERR_INVALID_ARG, who + "the parameters are NULL");
+    if (const iba_status s = check_params(src, *params)) return s;
+    iba_submap_clouds* built = nullptr;
+    if (const iba_status s = vox_build(src, subs, M, who, false, &built)) return s;
+    const std::unique_ptr<iba_submap_clouds> c(built);
+    return scan_handle_from_device(src, nullptr, c->first, nullptr, M, params, who, "sub-map", out);
 }
 
 int64_t iba_frame_num_points(const iba_handle* h, int32_t frame) { return (h && frame >= 0 && frame < h->n_frames) ? (int64_t)h->h_frames[(size_t)frame].P : -1; }

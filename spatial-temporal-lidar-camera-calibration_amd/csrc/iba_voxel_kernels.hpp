@@ -48,11 +48,15 @@ struct VoxMember {       // one member of one sub-map (host -> device)
 struct VoxSub {          // one sub-map
     double out[12];      // output transform (has_out)
     double voxel;
-    double minb[3];      // min over kept q - 0.5 voxel (written by the host between the bounds and the key kernel)
+    double minb[3];      // min over kept q - 0.5 voxel (written by the host between the bounds and the key kernel); iba_lattice_build: the least cell index per axis
     uint32_t blk0, blk1; // its blocks in the flat grid
     int32_t has_out, pad;
 };
 struct VoxPartial { double mn[3], mx[3]; uint64_t dropped; };   // of one block / one sub-map
+struct VoxLatPartial { double mn[3], mx[3]; uint64_t dropped, cropped; };   // the same of iba_lattice_build: points outside the crop box counted on their own
+struct VoxCrop { double lo[3], hi[3]; int32_t has_crop, pad; };             // one sub-map's crop box (iba_lattice_build)
+template <bool kLattice> struct VoxPartialOf { using type = VoxPartial; };
+template <> struct VoxPartialOf<true> { using type = VoxLatPartial; };
 struct VoxBits { int32_t sub_shift, x_shift, y_shift, pad; };   // iz sits at bit 0
 
 // row r of T * (x, y, z, 1): ((T0 x + T1 y) + T2 z) + T3, every operation rounded on its own (tests/submap_ref.py restates it in numpy, which has no fma)
@@ -75,6 +79,12 @@ __host__ __device__ __forceinline__ double vox_index(double q, double minb, doub
     return floor(d / voxel);
 }
 
+// PCL's cell of one axis with the origin as the anchor: floor(q / leaf) (iba_lattice_build, rule L3)
+__host__ __device__ __forceinline__ double vox_lattice_index(double q, double leaf) {
+#pragma clang fp contract(off)
+    return floor(q / leaf);
+}
+
 __device__ __forceinline__ int vox_member_of_block(const VoxMember* __restrict__ mem, int n_mem, uint32_t blk) {
     int lo = 0, hi = n_mem - 1;   // the last member whose first block is not beyond this one (the host lists no member without points: every blk0 is distinct)
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (mem[mid].blk0 <= blk) lo = mid; else hi = mid - 1; }
@@ -83,32 +93,41 @@ __device__ __forceinline__ int vox_member_of_block(const VoxMember* __restrict__
 
 __device__ __forceinline__ double vox_shfl_xor(double v, int m) { return __shfl_xor(v, m, 64); }
 
+// kLattice (iba_lattice_build): a finite q outside its sub-map's crop box (both ends inclusive) is staged as NaN like a dropped point and counted
+// on its own; it takes part in no bound and, in the key kernel, costs no key beyond the drop bucket. crops is read by that variant only.
+template <bool kLattice>
 __global__ __launch_bounds__(kVoxThreads) void iba_vox_transform_kernel(const FrameHdr* __restrict__ frames, const float4* __restrict__ pts4, const uint32_t* __restrict__ inv_perm,
-                                                                       const VoxMember* __restrict__ mem, int n_mem, double* __restrict__ q3, VoxPartial* __restrict__ partials) {
+                                                                       const VoxMember* __restrict__ mem, int n_mem, const VoxCrop* __restrict__ crops, double* __restrict__ q3,
+                                                                       typename VoxPartialOf<kLattice>::type* __restrict__ partials) {
     __shared__ double s_mn[4][3], s_mx[4][3];
-    __shared__ uint32_t s_dr[4];
+    __shared__ uint32_t s_dr[4], s_cr[4];
     const VoxMember& X = mem[vox_member_of_block(mem, n_mem, blockIdx.x)];
     const FrameHdr& fh = frames[X.frame];
     const uint32_t o = (blockIdx.x - X.blk0) * (uint32_t)kVoxThreads + threadIdx.x;   // original index in the member's scan
     const bool act = o < fh.P;
     const double inf = __builtin_huge_val();
     double mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
-    uint32_t dropped = 0u;
+    uint32_t dropped = 0u, cropped = 0u;
     if (act) {
         const float4 p = pts4[fh.pt_base + inv_perm[fh.pt_base + o]];
         const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
         double q[3];
         vox_apply(X.T, x, y, z, q[0], q[1], q[2]);
         const bool keep = isfinite(x) && isfinite(y) && isfinite(z) && isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]);
+        bool inside = true;
+        if constexpr (kLattice) {
+            const VoxCrop& C = crops[X.sub];
+            if (C.has_crop) inside = C.lo[0] <= q[0] && q[0] <= C.hi[0] && C.lo[1] <= q[1] && q[1] <= C.hi[1] && C.lo[2] <= q[2] && q[2] <= C.hi[2];
+        }
         double* dst = q3 + 3 * (X.pos0 + o);
-        if (keep) {
+        if (keep && inside) {
             dst[0] = q[0]; dst[1] = q[1]; dst[2] = q[2];
 #pragma unroll
             for (int a = 0; a < 3; ++a) { mn[a] = q[a]; mx[a] = q[a]; }
         } else {
             const double nan = __builtin_nan("");
             dst[0] = nan; dst[1] = nan; dst[2] = nan;
-            dropped = 1u;
+            if (keep) cropped = 1u; else dropped = 1u;
         }
     }
 #pragma unroll
@@ -119,16 +138,18 @@ __global__ __launch_bounds__(kVoxThreads) void iba_vox_transform_kernel(const Fr
             mn[a] = lo < mn[a] ? lo : mn[a]; mx[a] = hi > mx[a] ? hi : mx[a];
         }
         dropped += (uint32_t)__shfl_xor((int)dropped, m, 64);
+        if constexpr (kLattice) cropped += (uint32_t)__shfl_xor((int)cropped, m, 64);
     }
     const int w = (int)(threadIdx.x >> 6);
     if ((threadIdx.x & 63u) == 0u) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) { s_mn[w][a] = mn[a]; s_mx[w][a] = mx[a]; }
         s_dr[w] = dropped;
+        if constexpr (kLattice) s_cr[w] = cropped;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        VoxPartial r;
+        typename VoxPartialOf<kLattice>::type r;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             double lo = s_mn[0][a], hi = s_mx[0][a];
@@ -137,22 +158,27 @@ __global__ __launch_bounds__(kVoxThreads) void iba_vox_transform_kernel(const Fr
             r.mn[a] = lo; r.mx[a] = hi;
         }
         r.dropped = (uint64_t)((s_dr[0] + s_dr[1]) + (s_dr[2] + s_dr[3]));
+        if constexpr (kLattice) r.cropped = (uint64_t)((s_cr[0] + s_cr[1]) + (s_cr[2] + s_cr[3]));
         partials[blockIdx.x] = r;
     }
 }
 
-__global__ __launch_bounds__(kVoxThreads) void iba_vox_bounds_kernel(const VoxSub* __restrict__ subs, const VoxPartial* __restrict__ partials, VoxPartial* __restrict__ out) {
+template <bool kLattice>
+__global__ __launch_bounds__(kVoxThreads) void iba_vox_bounds_kernel(const VoxSub* __restrict__ subs, const typename VoxPartialOf<kLattice>::type* __restrict__ partials,
+                                                                    typename VoxPartialOf<kLattice>::type* __restrict__ out) {
+    using Partial = typename VoxPartialOf<kLattice>::type;
     __shared__ double s_mn[4][3], s_mx[4][3];
-    __shared__ unsigned long long s_dr[4];
+    __shared__ unsigned long long s_dr[4], s_cr[4];
     const VoxSub& S = subs[blockIdx.x];
     const double inf = __builtin_huge_val();
     double mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
-    unsigned long long dropped = 0ull;
+    unsigned long long dropped = 0ull, cropped = 0ull;
     for (uint32_t b = S.blk0 + threadIdx.x; b < S.blk1; b += (uint32_t)kVoxThreads) {
-        const VoxPartial p = partials[b];
+        const Partial p = partials[b];
 #pragma unroll
         for (int a = 0; a < 3; ++a) { mn[a] = p.mn[a] < mn[a] ? p.mn[a] : mn[a]; mx[a] = p.mx[a] > mx[a] ? p.mx[a] : mx[a]; }
         dropped += p.dropped;
+        if constexpr (kLattice) cropped += p.cropped;
     }
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) {
@@ -162,16 +188,18 @@ __global__ __launch_bounds__(kVoxThreads) void iba_vox_bounds_kernel(const VoxSu
             mn[a] = lo < mn[a] ? lo : mn[a]; mx[a] = hi > mx[a] ? hi : mx[a];
         }
         dropped += (unsigned long long)__shfl_xor((long long)dropped, m, 64);
+        if constexpr (kLattice) cropped += (unsigned long long)__shfl_xor((long long)cropped, m, 64);
     }
     const int w = (int)(threadIdx.x >> 6);
     if ((threadIdx.x & 63u) == 0u) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) { s_mn[w][a] = mn[a]; s_mx[w][a] = mx[a]; }
         s_dr[w] = dropped;
+        if constexpr (kLattice) s_cr[w] = cropped;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        VoxPartial r;
+        Partial r;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             double lo = s_mn[0][a], hi = s_mx[0][a];
@@ -180,10 +208,13 @@ __global__ __launch_bounds__(kVoxThreads) void iba_vox_bounds_kernel(const VoxSu
             r.mn[a] = lo; r.mx[a] = hi;
         }
         r.dropped = (uint64_t)((s_dr[0] + s_dr[1]) + (s_dr[2] + s_dr[3]));
+        if constexpr (kLattice) r.cropped = (uint64_t)((s_cr[0] + s_cr[1]) + (s_cr[2] + s_cr[3]));
         out[blockIdx.x] = r;
     }
 }
 
+// kLattice: the cell is floor(q / leaf) and the key field holds it minus the sub-map's least cell of that axis (VoxSub::minb, two exact integers)
+template <bool kLattice>
 __global__ __launch_bounds__(kVoxThreads) void iba_vox_key_kernel(const FrameHdr* __restrict__ frames, const VoxMember* __restrict__ mem, int n_mem, const VoxSub* __restrict__ subs, int n_sub,
                                                                  VoxBits bits, const double* __restrict__ q3, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
     const VoxMember& X = mem[vox_member_of_block(mem, n_mem, blockIdx.x)];
@@ -193,10 +224,17 @@ __global__ __launch_bounds__(kVoxThreads) void iba_vox_key_kernel(const FrameHdr
     const uint64_t g = X.pos0 + o;
     const double q0 = q3[3 * g], q1 = q3[3 * g + 1], q2 = q3[3 * g + 2];
     uint64_t key;
-    if (q0 == q0) {   // (a dropped point was staged as NaN)
-        const uint64_t ix = (uint64_t)(long long)vox_index(q0, S.minb[0], S.voxel);
-        const uint64_t iy = (uint64_t)(long long)vox_index(q1, S.minb[1], S.voxel);
-        const uint64_t iz = (uint64_t)(long long)vox_index(q2, S.minb[2], S.voxel);
+    if (q0 == q0) {   // (a dropped or cropped point was staged as NaN)
+        uint64_t ix, iy, iz;
+        if constexpr (kLattice) {
+            ix = (uint64_t)(long long)(vox_lattice_index(q0, S.voxel) - S.minb[0]);
+            iy = (uint64_t)(long long)(vox_lattice_index(q1, S.voxel) - S.minb[1]);
+            iz = (uint64_t)(long long)(vox_lattice_index(q2, S.voxel) - S.minb[2]);
+        } else {
+            ix = (uint64_t)(long long)vox_index(q0, S.minb[0], S.voxel);
+            iy = (uint64_t)(long long)vox_index(q1, S.minb[1], S.voxel);
+            iz = (uint64_t)(long long)vox_index(q2, S.minb[2], S.voxel);
+        }
         key = ((uint64_t)X.sub << bits.sub_shift) | (ix << bits.x_shift) | (iy << bits.y_shift) | iz;
     } else {
         key = (uint64_t)n_sub << bits.sub_shift;
