@@ -25,6 +25,7 @@
  *   IBA_NN_CG, IBA_PAIRS_DENSE_MIN, IBA_PAIRS_WAVE (the pair search's form: iba_debug_last_pairs_threads), IBA_COMMON_MIN_BATCH, IBA_PAIR_BOUND, IBA_ASSOC2_FLREG, IBA_ASSOC2_THREADS (256 / 512 threads per
  *   block of the shared-pair association, else chosen per launch), IBA_ASSOC2_SMALL_MIN, IBA_ASSOC_BLOCKS, IBA_CAND_BYTES,
  *   IBA_PAIR_BYTES                                        launch-shape / LDS-plan knobs of single kernels (A/B timing)
+ *   IBA_PAIRS_VISIBLE                                     0: the pair search always runs its full (chunks, keyframes) grid, never the visible-chunk list (iba_debug_pairs_visible)
  *   IBA_NN_ROUNDS                                         0: the entries the anchored lists leave over are searched leaf by leaf (rounds 3-4) instead of
  *                                                         in rounds of leaves (same results; A/B timing)
  *   IBA_DONE_FLAG                                         0: a blocking call polls its stream (rounds 3-4) instead of the sequence number the summing
@@ -100,6 +101,27 @@ int32_t iba_debug_last_pairs_threads(const iba_handle* h);
  * slot -1: the slot of the last call's first group. Returns the length of the list (capped at the list capacity), -1 on a bad argument.
  * The list is a superset of the pairs any candidate of the batch can accept (see iba_pairs_kernel). */
 int32_t iba_debug_pair_list(iba_handle* h, int32_t slot, int32_t frame, uint32_t* out_pairs, int32_t cap);
+/* debug: the visible-chunk list of the shared pair search (one wave per listed 64-position chunk — one block per listed run of eight chunks in the
+ * 512-thread form — instead of one per chunk of every scan; built around an anchor transform with an entrywise bound, rebuilt when a batch leaves
+ * the bound. A rebuild is launched behind the call that found the batch outside and waits for nothing: that call runs the full grid, the next
+ * search walks the new list. IBA_PAIRS_VISIBLE=0 forces the full grid.
+ * out4 = {items in the list (0: none ready), rebuilds so far, 1 if the last pair search walked the list, items a full grid has}. Same results
+ * with or without the list: every wave still tests its chunk against the call's own bound. */
+iba_status iba_debug_pairs_visible(const iba_handle* h, int32_t out4[4]);
+/* debug: the bound a rebuild of that list is given — the batch's own bound times infl (>= 1) plus the floors (rotation entries >= 1e-3, metres
+ * >= 1e-2) — and the least number of pair searches between two rebuilds (defaults 4, 1e-3, 1e-2, 4; tools/vis_sweep.py) */
+iba_status iba_debug_set_pairs_visible_bound(iba_handle* h, double infl, double rho_floor, double tau_floor, int32_t gap);
+/* debug (host arithmetic, no GPU): the chunk test of the pair kernels and of the list builder, the same function compiled for the host. g24: R[9],
+ * t[3], rho[9], tau[3]; box8: min xyz, -, max xyz, -; cam5: fx, cx, cy, W, H. 1: no transform within the bound sees the box, 0: kept */
+int32_t iba_debug_chunk_box_culled(const double g24[24], const float box8[8], const double cam5[5]);
+/* debug: how many chunks pass the pair search's chunk test under the bound of group `group` of the LAST pair search (the first chunk of a
+ * keyframe always counts: it clears counters); waits for the stream. -1 on a bad argument or when no pair search has run. */
+int64_t iba_debug_pairs_chunks_passing(iba_handle* h, int32_t group);
+/* debug (host only): the composition rule of that list — the entrywise bound (out12: rho[9], tau[3]) around the anchor (Ra, ta) of every
+ * transform within (rho_g, tau_g) of the group reference (Rg, tg) */
+iba_status iba_debug_vis_compose(const double Ra[9], const double ta[3], const double Rg[9], const double tg[3], const double rho_g[9], const double tau_g[3], double out12[12]);
+/* debug (host only): the check a call makes before it walks the list: 1 when the group (Rg, tg, rho_g, tau_g) lies inside (rho_a, tau_a) around the anchor */
+int32_t iba_debug_vis_covers(const double Ra[9], const double ta[3], const double rho_a[9], const double tau_a[3], const double Rg[9], const double tg[3], const double rho_g[9], const double tau_g[3]);
 /* diagnostic: list entries of the last evaluation (all candidates) that the anchored neighbour lists could not settle and the
  * tree search took over; -1 when no search ran */
 double iba_debug_nn_left_to_tree(iba_handle* h);

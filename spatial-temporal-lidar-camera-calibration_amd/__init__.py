@@ -610,6 +610,20 @@ class IbaHandle:
         self.lib.iba_debug_pairs_builds.argtypes = [C.c_void_p]
         return int(self.lib.iba_debug_pairs_builds(self.h))
 
+    @property
+    def pairs_visible(self):
+        """(items in the pair search's visible-chunk list — 0: none ready —, rebuilds so far, 1 if the last pair search walked the list, items a full grid has)"""
+        out = (C.c_int32 * 4)()
+        self.lib.iba_debug_pairs_visible.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        self._chk(self.lib.iba_debug_pairs_visible(self.h, out))
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    def pairs_chunks_passing(self, group=0):
+        """chunks that pass the pair search's chunk test under the bound of a group of the last pair search (-1: none ran)"""
+        self.lib.iba_debug_pairs_chunks_passing.restype = C.c_int64
+        self.lib.iba_debug_pairs_chunks_passing.argtypes = [C.c_void_p, C.c_int32]
+        return int(self.lib.iba_debug_pairs_chunks_passing(self.h, int(group)))
+
     def rescans(self, reset=True):
         """association blocks since the last reset that took the rescan-every-point fallback (speed only)"""
         self.lib.iba_debug_rescans.restype = C.c_int64

@@ -60,6 +60,9 @@ constexpr int kRing = 4;
 
 }  // namespace
 
+// the visible-chunk list's rebuild bound (plan_visible): defaults, the smallest floors and the caps the superset argument there allows
+constexpr double kVisInflDefault = 4.0, kVisRhoFloorMin = 1e-3, kVisTauFloorMin = 1e-2, kVisRhoCap = 0.2, kVisTauCap = 2.0;
+constexpr int kVisGapDefault = 4;
 struct iba_handle {
     int device = 0;
     int n_frames = 0;          // owned frames
@@ -142,6 +145,18 @@ struct iba_handle {
                                           // -1 (default): 64 while the keyframes' scans are below pairs_dense_min points, else 0 (IBA_PAIRS_WAVE forces a form)
     int last_pairs_threads = -1;          // the form of the last pair-search launch (iba_debug_last_pairs_threads)
     uint32_t pairs_dense_min = 32768u;    // scans of at least this many points: the pair search tests a block's boxes before it loads the block's points and the keypoint grid (IBA_PAIRS_DENSE_MIN)
+    // the visible-chunk list of the pair search (iba_vis_list_kernel): items (keyframe << 16 | chunk; | block of eight chunks on handles whose searches run
+    // iba_pairs_kernel), per-keyframe counts and offsets; at most 4 bytes per chunk
+    DevBuf<uint32_t> d_vis_items, d_vis_counts, d_vis_off; PinnedBuf<uint32_t> h_vis_total; uint32_t* h_vis_total_dev = nullptr;
+    bool vis_on = true;                   // IBA_PAIRS_VISIBLE=0: always the full grid; also off for handles the item format or the margin rule below cannot serve
+    bool vis_valid = false; GroupRef vis_ref{};   // the list's anchor and the bound a call's groups must lie in (vis_covers); the list itself was built with that bound times 1 + vis_kappa
+    bool vis_pending = false; hipEvent_t vis_ev = nullptr;   // a rebuild is in flight: the list becomes valid once the event behind it has fired (no host wait anywhere)
+    bool vis_use = false, vis_rebuild = false;    // this call (plan_visible): walk the list / launch a rebuild behind this call's kernels
+    uint32_t vis_n = 0, vis_full = 0; int vis_rebuilds = 0, vis_last_used = 0, vis_since_build = 0;   // vis_full: items of a full grid (all chunks / all blocks)
+    double vis_kappa = 1e-3;
+    // the rebuild bound: the call's composed bound times vis_infl plus a floor; pair searches between two rebuilds at least. Chosen by the sweep of
+    // tools/vis_sweep.py (profiles/r08a_rocprof_summary.md); iba_debug_set_pairs_visible_bound is that tool's knob
+    double vis_infl = kVisInflDefault, vis_rho_floor = kVisRhoFloorMin, vis_tau_floor = kVisTauFloorMin; int vis_gap = kVisGapDefault;
     int common_mode = 1;                  // IBA_COMMON_PAIRS: 0 = never, 1 = when the batch is tight (default), 2 = whenever the bound allows
     bool spin_wait = true;                // IBA_SPIN_WAIT=0: blocking waits only
     bool nn_sets = true;                  // IBA_NN_SETS=0: no anchored neighbour lists, every lane searches the tree (diagnostic)
@@ -474,6 +489,50 @@ inline bool plan_pairs(iba_handle* h, const Cand* hc, int B) {
     return true;
 }
 
+// the form of the pair search (run_split): 64 / 256 / 512 = iba_pairs_wave_kernel in blocks of that many threads, 0 = iba_pairs_kernel
+inline int pairs_form(const iba_handle* h) { return kChunk != 64 ? 0 : h->pairs_threads >= 0 ? h->pairs_threads : (h->maxP >= h->pairs_dense_min ? 0 : 64); }
+// The visible-chunk list and this call's pair search (after plan_pairs, host only): walk the list when every group the launch builds lies
+// inside the list's bound (vis_covers); otherwise run the full grid and have run_split launch a rebuild around the first group's reference
+// behind this call's kernels — with the groups' composed bound times vis_infl plus a floor, not beyond the caps (a batch that wide culls little; a NaN
+// has no bound), and not more often than every vis_gap pair searches (a poll that alternates between two far incumbents would otherwise rebuild
+// on every call: 11 us of kernels for the 5 us a listed search saves). The rebuild waits for nothing: the list counts as built when the event
+// behind it has fired, which a later call finds out by a query.
+// WHY A LISTED TEST IS A SUPERSET OF THE CALL'S: chunk_box_culled compares interval ends qc -/+ m against thresholds of
+// 1e-6 of the interval's scale. Inside the bound the group's interval lies within the anchor's (vis_composed_bound); the list is built
+// with the bound times 1 + vis_kappa, kappa = 1e-3 max(1, W / min(cx, W - cx), H / min(cy, H - cy)): the extra kappa d_i (d = rho a3 + tau,
+// at least floor-sized: 1e-3 |q|_1 + 1e-2) outweighs what the two evaluations differ by — thresholds (1e-6 d), the 1e-9 slops of m
+// (d_j <= 200 d_i by the floors and caps), f64 rounding (1e-15 |q|) — so whatever the anchor's test culls, the call's own test culls too.
+// Being outside the bound costs speed, never results.
+inline void plan_visible(iba_handle* h) {
+    h->vis_use = h->vis_rebuild = false;
+    if (!h->vis_on || h->n_build <= 0 || !h->d_vis_items.p) return;
+    ++h->vis_since_build;   // (pair searches since the last rebuild: a call that runs no search does not come here)
+    if (h->vis_pending) {
+        if (hipEventQuery(h->vis_ev) != hipSuccess) { (void)hipGetLastError(); return; }
+        h->vis_pending = false;
+        h->vis_n = *h->h_vis_total.p;
+        h->vis_valid = h->vis_n >= (uint32_t)h->n_frames && h->vis_n <= h->vis_full;   // (every keyframe lists its first item)
+    }
+    if (h->vis_valid) {
+        bool in = true;
+        for (int k = 0; k < h->n_build && in; ++k) in = vis_covers(h->vis_ref, h->pplan.g[k]);
+        if (in) { h->vis_use = true; return; }
+        if (h->vis_since_build <= h->vis_gap) return;
+    }
+    GroupRef a = h->pplan.g[0];
+    for (int i = 0; i < 9; ++i) a.rho[i] = 0;
+    for (int i = 0; i < 3; ++i) a.tau[i] = 0;
+    for (int k = 0; k < h->n_build; ++k) {
+        double rho[9], tau[3];
+        if (!vis_composed_bound(a.R, a.t, h->pplan.g[k], rho, tau)) return;
+        for (int i = 0; i < 9; ++i) a.rho[i] = std::max(a.rho[i], rho[i]);
+        for (int i = 0; i < 3; ++i) a.tau[i] = std::max(a.tau[i], tau[i]);
+    }
+    for (int i = 0; i < 9; ++i) { a.rho[i] = a.rho[i] * h->vis_infl + h->vis_rho_floor; if (!(a.rho[i] <= kVisRhoCap)) return; }
+    for (int i = 0; i < 3; ++i) { a.tau[i] = a.tau[i] * h->vis_infl + h->vis_tau_floor; if (!(a.tau[i] <= kVisTauCap)) return; }
+    h->vis_ref = a; h->vis_valid = false; h->vis_rebuild = true;   // (this call: the full grid)
+}
+
 iba_status ensure_scratch(iba_handle* h);
 iba_status compute_plane_cache(iba_handle* h) {
     const iba_params& p = h->params;
@@ -562,6 +621,8 @@ iba_status stage_cands(iba_handle* h, const double* x, int B, hipStream_t st, Ca
     else for (int b = 0; b < B; ++b) make_cand_values(x + 7 * b, hc[b]);
     const bool planned = plan && h->common_mode > 0 && B >= h->common_min_batch && h->d_pairs.p;
     h->cref_ok = planned && plan_pairs(h, hc, B);
+    h->vis_use = h->vis_rebuild = false; h->vis_last_used = 0;
+    if (h->cref_ok) plan_visible(h);
     h->plan_wide = planned && !h->cref_ok;   // the planner looked at this batch and found it wide everywhere
     h->head_pending = false; h->head_slot = slot; h->head_B = B;
     if (plan && h->chain_fold) h->head_pending = true;   // run_split's first kernel carries the block (and records the slot's event at the end of the chain)
@@ -804,20 +865,44 @@ iba_status run_split(iba_handle* h, const Cand* dc, int B, int want, bool frozen
         const dim3 pgrid_z(1, nf, h->n_build + (head_open ? 1 : 0));
         // The form (r07): one wave per 64-position culling chunk at the bench shape (200 KF x 10 k points: 46 -> 39 us, same bits), the
         // 512-thread blocks on dense scans (200 KF x 120 k points: 322 us vs 386 us in one-wave blocks — tools/experiments/README.md)
-        const int pt = kChunk != 64 ? 0 : h->pairs_threads >= 0 ? h->pairs_threads : (h->maxP >= h->pairs_dense_min ? 0 : 64);
+        const int pt = pairs_form(h);
         h->last_pairs_threads = pt;
+        const bool listed = h->vis_use && h->vis_valid;
+        h->vis_last_used = listed ? 1 : 0;
         auto wave_form = [&](auto kern, int threads) {   // one wave per culling chunk (its LDS is static: 5.5 KB per wave)
             const uint32_t per_block = (uint32_t)threads;   // tree positions per block: kChunk per wave
-            hipLaunchKernelGGL(kern, dim3(std::max(1u, (h->maxP + per_block - 1u) / per_block), pgrid_z.y, pgrid_z.z), dim3(threads), 0, st, PairsArgs{pp, h->pplan}, h->params.max_pixel_dist,
-                               nf, h->d_pairs.p, h->d_hard.p, h->d_pcounts.p, h->pair_cap, h->hard_cap, head_open ? head_src : nullptr, (uint4*)dc, head_open ? head_n16 : 0u, h->pairs_dense_min);
+            const uint32_t waves = per_block / (uint32_t)kChunk;
+            const dim3 grid = listed ? dim3((h->vis_n + waves - 1u) / waves, 1, pgrid_z.z) : dim3(std::max(1u, (h->maxP + per_block - 1u) / per_block), pgrid_z.y, pgrid_z.z);
+            hipLaunchKernelGGL(kern, grid, dim3(threads), 0, st, PairsArgs{pp, h->pplan}, h->params.max_pixel_dist,
+                               nf, h->d_pairs.p, h->d_hard.p, h->d_pcounts.p, h->pair_cap, h->hard_cap, head_open ? head_src : nullptr, (uint4*)dc, head_open ? head_n16 : 0u, h->pairs_dense_min,
+                               listed ? (const uint32_t*)h->d_vis_items.p : (const uint32_t*)nullptr, listed ? h->vis_n : 0u);
         };
         if (pt == 64) wave_form(iba_pairs_wave_kernel<64>, 64);
         else if (pt == 256) wave_form(iba_pairs_wave_kernel<256>, 256);
         else if (pt == 512) wave_form(iba_pairs_wave_kernel<512>, 512);
         else
-        hipLaunchKernelGGL(iba_pairs_kernel, dim3(std::max(1u, (h->maxP + (uint32_t)kPairsThreads - 1u) / (uint32_t)kPairsThreads), nf, h->n_build + (head_open ? 1 : 0)), dim3(kPairsThreads), lds, st, PairsArgs{pp, h->pplan}, h->params.max_pixel_dist, kuv_off,
-                           nf, h->d_pairs.p, h->d_hard.p, h->d_pcounts.p, h->pair_cap, h->hard_cap, head_open ? head_src : nullptr, (uint4*)dc, head_open ? head_n16 : 0u, h->pairs_dense_min);
+        hipLaunchKernelGGL(iba_pairs_kernel, listed ? dim3(h->vis_n, 1, pgrid_z.z) : dim3(std::max(1u, (h->maxP + (uint32_t)kPairsThreads - 1u) / (uint32_t)kPairsThreads), nf, pgrid_z.z), dim3(kPairsThreads), lds, st, PairsArgs{pp, h->pplan}, h->params.max_pixel_dist, kuv_off,
+                           nf, h->d_pairs.p, h->d_hard.p, h->d_pcounts.p, h->pair_cap, h->hard_cap, head_open ? head_src : nullptr, (uint4*)dc, head_open ? head_n16 : 0u, h->pairs_dense_min,
+                           listed ? (const uint32_t*)h->d_vis_items.p : (const uint32_t*)nullptr);
         HIP_TRY(h, hipGetLastError());
+        // a rebuild of the visible-chunk list (plan_visible): two small launches behind the search that just ran on the full grid, and an event
+        // (they overwrite the list, its counts and the pinned total in THIS call's stream: like d_pairs and d_pcounts, the list assumes that the calls
+        //  on a handle are serialised — one stream, or a caller who orders the streams it passes to the *_partial entry points)
+        if (h->vis_rebuild) {
+            GroupRef wide = h->vis_ref;
+            for (double& r : wide.rho) r *= 1.0 + h->vis_kappa;
+            for (double& t : wide.tau) t *= 1.0 + h->vis_kappa;
+            if (pt != 0) {
+                hipLaunchKernelGGL((iba_vis_list_kernel<false, 1>), dim3(nf), dim3(kVisThreads), 0, st, wide, dp.frames, dp.chunk_box, nf, h->d_vis_counts.p, h->d_vis_off.p, h->d_vis_items.p, h->h_vis_total_dev);
+                hipLaunchKernelGGL((iba_vis_list_kernel<true, 1>), dim3(nf), dim3(kVisThreads), 0, st, wide, dp.frames, dp.chunk_box, nf, h->d_vis_counts.p, h->d_vis_off.p, h->d_vis_items.p, h->h_vis_total_dev);
+            } else {
+                hipLaunchKernelGGL((iba_vis_list_kernel<false, kPairsThreads / kChunk>), dim3(nf), dim3(kVisThreads), 0, st, wide, dp.frames, dp.chunk_box, nf, h->d_vis_counts.p, h->d_vis_off.p, h->d_vis_items.p, h->h_vis_total_dev);
+                hipLaunchKernelGGL((iba_vis_list_kernel<true, kPairsThreads / kChunk>), dim3(nf), dim3(kVisThreads), 0, st, wide, dp.frames, dp.chunk_box, nf, h->d_vis_counts.p, h->d_vis_off.p, h->d_vis_items.p, h->h_vis_total_dev);
+            }
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipEventRecord(h->vis_ev, st));
+            h->vis_rebuild = false; h->vis_pending = true; h->vis_since_build = 0; ++h->vis_rebuilds;
+        }
         h->pairs_builds += h->n_build;
         head_open = false;
     }
@@ -1082,6 +1167,7 @@ void iba_destroy(iba_handle* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->ev_mid) (void)hipEventDestroy(h->ev_mid);
+    if (h->vis_ev) (void)hipEventDestroy(h->vis_ev);
     for (int i = 0; i < kRing; ++i) if (h->ring_ev[i]) (void)hipEventDestroy(h->ring_ev[i]);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1469,6 +1555,28 @@ iba_status create_impl(const iba_problem_desc* d, const iba_params* params, int 
         if ((er = h->d_hard.alloc((size_t)kMaxPairGroups * std::max(nf, 1) * h->hard_cap)) != hipSuccess) return bail("alloc hard list", er);
         if ((er = h->d_pcounts.alloc(2 * (size_t)kMaxPairGroups * std::max(nf, 1) * kCountStride)) != hipSuccess) return bail("alloc pair counts", er);
         if ((er = hipMemset(h->d_pcounts.p, 0, sizeof(uint32_t) * 2 * (size_t)kMaxPairGroups * std::max(nf, 1) * kCountStride)) != hipSuccess) return bail("clear pair counts", er);
+        // the visible-chunk list of the pair search: sized for every chunk (4 bytes each). An optional memo: without it the full grid runs.
+        {
+            size_t chunks = 0; uint32_t most = 0; double ratio = 1.0;
+            for (int lf = 0; lf < nf; ++lf) {
+                const FrameHdr& x = h->h_frames[lf];
+                const uint32_t nc = std::max(1u, (x.P + (uint32_t)kChunk - 1u) / (uint32_t)kChunk);
+                chunks += nc; most = std::max(most, nc);
+                const double mu = std::min(x.cx, x.W - x.cx), mv = std::min(x.cy, x.H - x.cy);
+                ratio = (mu > 0 && mv > 0) ? std::max(ratio, std::max(x.W / mu, x.H / mv)) : INFINITY;   // (a principal point outside the image: no margin rule, no list)
+            }
+            h->vis_kappa = 1e-3 * ratio;
+            size_t full = chunks;   // items of a full grid: chunks, or iba_pairs_kernel's blocks of eight
+            if (pairs_form(h) == 0) { full = 0; for (int lf = 0; lf < nf; ++lf) full += std::max<size_t>(1, (h->h_frames[lf].P + (size_t)kPairsThreads - 1) / (size_t)kPairsThreads); }
+            h->vis_full = (uint32_t)std::min<size_t>(full, 0x7fffffffu);
+            if (const char* e = dbg_env("IBA_PAIRS_VISIBLE")) h->vis_on = std::atoi(e) != 0;
+            if (nf < 1 || nf > (int)(kVisChunkMask + 1u) - 1 || most > kVisChunkMask + 1u || chunks > 0x7fffffffu || !(h->vis_kappa <= 0.1)) h->vis_on = false;
+            if (h->vis_on && (h->d_vis_items.alloc(chunks) != hipSuccess || h->d_vis_counts.alloc((size_t)nf) != hipSuccess || h->d_vis_off.alloc((size_t)nf + 1) != hipSuccess ||
+                              h->h_vis_total.alloc(1) != hipSuccess || hipHostGetDevicePointer((void**)&h->h_vis_total_dev, h->h_vis_total.p, 0) != hipSuccess ||
+                              hipEventCreateWithFlags(&h->vis_ev, hipEventDisableTiming) != hipSuccess)) {
+                (void)hipGetLastError(); h->d_vis_items.release(); h->vis_on = false;
+            }
+        }
     }
     if ((er = h->d_partials.alloc((size_t)h->chain_cap * kPartialStride)) != hipSuccess) return bail("alloc partials", er);
     if ((er = h->d_corr.alloc((size_t)std::max<int64_t>(h->n_keypoints, 1))) != hipSuccess) return bail("alloc corr", er);
@@ -1552,6 +1660,7 @@ iba_status iba_set_params(iba_handle* h, const iba_params* p) {
     h->params = *p; to_dev_params(*p, h->dprm); h->frozen_valid = false;
     for (bool& v : h->anchor_valid) v = false;   // the lists carry the planes' verdicts under the old parameters
     for (auto& ps : h->pslot) ps.valid = false;    // the pair lists were cut for the old max_pixel_dist
+    h->vis_valid = false; h->vis_pending = false;  // (the chunk test reads no parameter today; a new parameter set starts a new list all the same)
     return compute_plane_cache(h);
 }
 
@@ -1781,6 +1890,39 @@ int32_t iba_debug_pair_list(iba_handle* h, int32_t slot, int32_t frame, uint32_t
     return n;
 }
 int32_t iba_debug_anchor_builds(const iba_handle* h) { return h ? h->anchor_builds : -1; }
+// debug: the visible-chunk list {items, rebuilds, the last pair search walked it, chunks of all keyframes}
+iba_status iba_debug_pairs_visible(const iba_handle* h, int32_t out4[4]) {
+    if (!h || !out4) return IBA_ERR_INVALID_ARG;
+    out4[0] = h->vis_valid ? (int32_t)h->vis_n : 0; out4[1] = h->vis_rebuilds; out4[2] = h->vis_last_used; out4[3] = (int32_t)h->vis_full;
+    return IBA_OK;
+}
+// debug: the rebuild bound of the visible-chunk list (tools/vis_sweep.py): factor, floors (not below the smallest the superset argument allows), gap
+iba_status iba_debug_set_pairs_visible_bound(iba_handle* h, double infl, double rho_floor, double tau_floor, int32_t gap) {
+    if (!h || !(infl >= 1.0) || !(rho_floor >= kVisRhoFloorMin && rho_floor <= kVisRhoCap) || !(tau_floor >= kVisTauFloorMin && tau_floor <= kVisTauCap) || gap < 0) return IBA_ERR_INVALID_ARG;
+    // (the argument bounds d_j / d_i by cap / floor <= 200: a larger floor only lowers that ratio)
+    h->vis_infl = infl; h->vis_rho_floor = rho_floor; h->vis_tau_floor = tau_floor; h->vis_gap = gap;
+    return IBA_OK;
+}
+// debug (host arithmetic only): chunk_box_culled — the one function the pair kernels and the list builder call — on the host. g24: R[9], t[3], rho[9], tau[3];
+// box8: min xyz, -, max xyz, - as floats; cam5: fx, cx, cy, W, H. 1: culled, 0: kept
+int32_t iba_debug_chunk_box_culled(const double g24[24], const float box8[8], const double cam5[5]) {
+    if (!g24 || !box8 || !cam5) return -1;
+    GroupRef g;
+    std::memcpy(g.R, g24, sizeof(g.R)); std::memcpy(g.t, g24 + 9, sizeof(g.t)); std::memcpy(g.rho, g24 + 12, sizeof(g.rho)); std::memcpy(g.tau, g24 + 21, sizeof(g.tau));
+    return chunk_box_culled(g, make_float4(box8[0], box8[1], box8[2], box8[3]), make_float4(box8[4], box8[5], box8[6], box8[7]), cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]) ? 1 : 0;
+}
+// debug: chunks that pass chunk_box_culled under the bound of a group of the last pair search (the list builder's counting pass with that bound)
+int64_t iba_debug_pairs_chunks_passing(iba_handle* h, int32_t group) {
+    if (!h || group < 0 || group >= h->n_build || !h->d_vis_counts.p || h->n_frames < 1) return -1;
+    if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -1;   // (a rebuild in flight uses the same counts)
+    hipLaunchKernelGGL((iba_vis_list_kernel<false, 1>), dim3(h->n_frames), dim3(kVisThreads), 0, h->stream, h->pplan.g[group], h->frames.p, h->chunk_box.p, h->n_frames, h->d_vis_counts.p, h->d_vis_off.p,
+                       (uint32_t*)nullptr, (uint32_t*)nullptr);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return -1;
+    std::vector<uint32_t> c((size_t)h->n_frames);
+    if (hipMemcpy(c.data(), h->d_vis_counts.p, sizeof(uint32_t) * c.size(), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    int64_t n = 0; for (uint32_t v : c) n += v;
+    return n;
+}
 
 // debug: exact 1-NN of n LiDAR-frame queries in the scan of a local frame, through the frame kernels' own search
 iba_status iba_debug_nn(iba_handle* h, int32_t frame, const double* q, int32_t n, int32_t mode, uint32_t* out_idx, double* out_d2) {

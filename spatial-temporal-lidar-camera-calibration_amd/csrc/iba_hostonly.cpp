@@ -196,4 +196,22 @@ iba_status iba_debug_plan_groups(const double* x, int32_t B, double max_fx, doub
     return IBA_OK;
 }
 
+// The composition rule of the visible-chunk list (vis_composed_bound, iba_pair_plan.hpp; host only): the entrywise bound around the anchor
+// (Ra, ta) of every transform within (rho_g, tau_g) of the group reference (Rg, tg). out12: rho (9), tau (3).
+iba_status iba_debug_vis_compose(const double Ra[9], const double ta[3], const double Rg[9], const double tg[3], const double rho_g[9], const double tau_g[3], double out12[12]) {
+    if (!Ra || !ta || !Rg || !tg || !rho_g || !tau_g || !out12) return IBA_ERR_INVALID_ARG;
+    GroupRef g;
+    std::memcpy(g.R, Rg, sizeof(g.R)); std::memcpy(g.t, tg, sizeof(g.t)); std::memcpy(g.rho, rho_g, sizeof(g.rho)); std::memcpy(g.tau, tau_g, sizeof(g.tau));
+    return vis_composed_bound(Ra, ta, g, out12, out12 + 9) ? IBA_OK : IBA_ERR_INVALID_ARG;
+}
+
+// ... and the host check built on it (vis_covers): 1 when the group lies inside the bound (rho_a, tau_a) around the anchor, 0 when not (or no bound), -1: bad argument
+int32_t iba_debug_vis_covers(const double Ra[9], const double ta[3], const double rho_a[9], const double tau_a[3], const double Rg[9], const double tg[3], const double rho_g[9], const double tau_g[3]) {
+    if (!Ra || !ta || !rho_a || !tau_a || !Rg || !tg || !rho_g || !tau_g) return -1;
+    GroupRef a, g;
+    std::memcpy(a.R, Ra, sizeof(a.R)); std::memcpy(a.t, ta, sizeof(a.t)); std::memcpy(a.rho, rho_a, sizeof(a.rho)); std::memcpy(a.tau, tau_a, sizeof(a.tau));
+    std::memcpy(g.R, Rg, sizeof(g.R)); std::memcpy(g.t, tg, sizeof(g.t)); std::memcpy(g.rho, rho_g, sizeof(g.rho)); std::memcpy(g.tau, tau_g, sizeof(g.tau));
+    return vis_covers(a, g) ? 1 : 0;
+}
+
 }  // extern "C"

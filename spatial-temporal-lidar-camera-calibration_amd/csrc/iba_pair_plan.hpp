@@ -22,24 +22,33 @@ struct GroupRef { double R[9], t[3], rho[9], tau[3]; };   // reference candidate
 // rho_ij = max_b |R_b R_0^T - I|_ij, tau_i = max_b |t_b - R_b R_0^T t_0|_i of a batch around a reference (R_0, t_0), inflated for their own
 // rounding; rel (optional): the candidates' own (M_b, a_b) as floats. false: a NaN / absurd candidate, no bound.
 // (idx: the members of the group among hc[], nullptr = hc[0 .. B))
+// one transform (R, t) against the reference (R0, t0): |R R_0^T - I| and |t - R R_0^T t_0| folded into the running maxima rho / tau (not
+// yet inflated); rel_row (optional): the motion itself as 12 floats. false: NaN / absurd.
+inline bool spread_accumulate(const double* R, const double* t, const double* R0, const double* t0, double* rho, double* tau, float* rel_row) {
+    double A[9];
+    for (int r = 0; r < 3; ++r)
+        for (int q = 0; q < 3; ++q) A[r * 3 + q] = (R[r * 3] * R0[q * 3] + R[r * 3 + 1] * R0[q * 3 + 1]) + R[r * 3 + 2] * R0[q * 3 + 2];   // R R_0^T
+    for (int r = 0; r < 3; ++r) {
+        const double a = t[r] - ((A[r * 3] * t0[0] + A[r * 3 + 1] * t0[1]) + A[r * 3 + 2] * t0[2]);
+        if (!(std::fabs(a) <= 1e30)) return false;
+        tau[r] = std::max(tau[r], std::fabs(a));
+        if (rel_row) rel_row[9 + r] = (float)a;
+        for (int q = 0; q < 3; ++q) { const double m = A[r * 3 + q] - (r == q ? 1.0 : 0.0), e = std::fabs(m); if (!(e <= 4.0)) return false; rho[r * 3 + q] = std::max(rho[r * 3 + q], e); if (rel_row) rel_row[r * 3 + q] = (float)m; }
+    }
+    return true;
+}
+inline void spread_inflate(double* rho, double* tau) {
+    for (int i = 0; i < 9; ++i) rho[i] = rho[i] * (1.0 + 1e-9) + 1e-15;
+    for (int i = 0; i < 3; ++i) tau[i] = tau[i] * (1.0 + 1e-9) + 1e-15;
+}
 inline bool batch_spread(const Cand* hc_all, int B, const double* R0, const double* t0, double* rho, double* tau, float (*rel)[12], const int* idx = nullptr) {
     for (int i = 0; i < 9; ++i) rho[i] = 0;
     for (int i = 0; i < 3; ++i) tau[i] = 0;
     for (int b = 0; b < B; ++b) {
         const Cand& c = hc_all[idx ? idx[b] : b];
-        double A[9];
-        for (int r = 0; r < 3; ++r)
-            for (int q = 0; q < 3; ++q) A[r * 3 + q] = (c.R[r * 3] * R0[q * 3] + c.R[r * 3 + 1] * R0[q * 3 + 1]) + c.R[r * 3 + 2] * R0[q * 3 + 2];   // R_b R_0^T
-        for (int r = 0; r < 3; ++r) {
-            const double a = c.t[r] - ((A[r * 3] * t0[0] + A[r * 3 + 1] * t0[1]) + A[r * 3 + 2] * t0[2]);
-            if (!(std::fabs(a) <= 1e30)) return false;
-            tau[r] = std::max(tau[r], std::fabs(a));
-            if (rel) rel[b][9 + r] = (float)a;
-            for (int q = 0; q < 3; ++q) { const double m = A[r * 3 + q] - (r == q ? 1.0 : 0.0), e = std::fabs(m); if (!(e <= 4.0)) return false; rho[r * 3 + q] = std::max(rho[r * 3 + q], e); if (rel) rel[b][r * 3 + q] = (float)m; }
-        }
+        if (!spread_accumulate(c.R, c.t, R0, t0, rho, tau, rel ? rel[b] : nullptr)) return false;
     }
-    for (int i = 0; i < 9; ++i) rho[i] = rho[i] * (1.0 + 1e-9) + 1e-15;
-    for (int i = 0; i < 3; ++i) tau[i] = tau[i] * (1.0 + 1e-9) + 1e-15;
+    spread_inflate(rho, tau);
     return true;
 }
 
@@ -99,6 +108,41 @@ inline int cluster_batch(double max_fx, const Cand* hc, int B, double max_px, in
         for (int g = 0; g < ng && ok; ++g) ok = gp[g].n > 0 && pick_group(max_fx, hc, gp[g]) && gp[g].px <= max_px;
         if (ok) return ng;
     }
+}
+
+// The visible-chunk list of a handle (iba_vis_list_kernel) is built for an ANCHOR transform (Ra, ta) with an entrywise bound. A pair search
+// may walk the list instead of every chunk when each of its groups lies inside that bound — reference AND bound, because the search's own
+// chunk test runs on the group's entrywise hull (g.rho, g.tau), not on its members. With M = R_g R_a^T - I, a = t_g - R_g R_a^T t_a (spread_accumulate:
+// the measure of batch_spread, for the group's reference alone) a transform within the group's hull moves a point q_a of the
+// anchor's frame by at most (|M| + rho_g (I + |M|)) |q_a| + (|a| + rho_g |a| + tau_g): the composed bound, entrywise, rounded up.
+// The same inequality bounds the chunk test's interval of the group inside the anchor's (qc_g = (I + M) qc_a + a, |R_g| e <= (I + |M|) |R_a| e).
+// false: no bound (NaN, an absurd transform).
+inline bool vis_composed_bound(const double* Ra, const double* ta, const GroupRef& g, double* rho, double* tau) {
+    double m[9] = {0}, a[3] = {0};
+    if (!spread_accumulate(g.R, g.t, Ra, ta, m, a, nullptr)) return false;
+    spread_inflate(m, a);
+    for (int i = 0; i < 3; ++i) {
+        double ti = a[i] + g.tau[i];
+        for (int k = 0; k < 3; ++k) ti += g.rho[i * 3 + k] * a[k];
+        if (!(ti <= 1e30)) return false;
+        tau[i] = ti * (1.0 + 1e-12);
+        for (int j = 0; j < 3; ++j) {
+            double r = m[i * 3 + j] + g.rho[i * 3 + j];
+            for (int k = 0; k < 3; ++k) r += g.rho[i * 3 + k] * m[k * 3 + j];
+            if (!(r <= 1e30)) return false;
+            rho[i * 3 + j] = r * (1.0 + 1e-12);
+        }
+    }
+    return true;
+}
+// ... and is the group inside (rho_a, tau_a) around the anchor?
+inline bool vis_covers(const GroupRef& anchor, const GroupRef& g) {
+    double rho[9], tau[3];
+    if (!vis_composed_bound(anchor.R, anchor.t, g, rho, tau)) return false;
+    bool fits = true;
+    for (int i = 0; i < 9; ++i) fits = fits && rho[i] <= anchor.rho[i];
+    for (int i = 0; i < 3; ++i) fits = fits && tau[i] <= anchor.tau[i];
+    return fits;
 }
 
 }  // namespace iba

@@ -770,13 +770,41 @@ constexpr int kPairsThreads = 512;    // measured at the bench shape: 1024 threa
 constexpr int kCountStride = 32;   // u32 per frame (one 128-byte line: the frames' counters do not share a line): pairs, hard points, overflow flag
 constexpr int kPairStage = 2048;   // (point, keypoint) hits a block parks in LDS before ONE global reservation writes them out
 
+// The chunk test of the pair search, step 1 of both pair kernels and the test of the visible-chunk list (iba_vis_list_kernel): is the static
+// AABB [lo, hi] of kChunk consecutive tree positions invisible to every transform within the entrywise bound (cr.rho, cr.tau) of the
+// reference (cr.R, cr.t)? For a point p of a box with centre c and half extent e: q_b(p)_i lies within m_i = (|R_0| e)_i + delta_i of
+// q_0(c)_i, delta from the bound at |q_0(c)| + |R_0| e. The piece is invisible when it is behind the camera (z + m_z <= 0) or wholly
+// beyond one image border: u >= W <=> fx x + (cx - W) z >= 0 (z > 0), u < 0 <=> fx x + cx z < 0, v alike. A NaN box (an empty chunk)
+// compares false everywhere: kept, harmless. ONE copy: the list is a superset of what a call's own test keeps only because it is this test
+// (also compiled for the host: iba_debug_chunk_box_culled lets a CPU test pin that implication without a GPU).
+__host__ __device__ __forceinline__ bool chunk_box_culled(const GroupRef& cr, const float4 lo, const float4 hi, const double fx, const double cx, const double cy, const double W, const double H) {
+    const double c3[3] = {0.5 * ((double)lo.x + (double)hi.x), 0.5 * ((double)lo.y + (double)hi.y), 0.5 * ((double)lo.z + (double)hi.z)};
+    const double e3[3] = {0.5 * ((double)hi.x - (double)lo.x), 0.5 * ((double)hi.y - (double)lo.y), 0.5 * ((double)hi.z - (double)lo.z)};
+    double qc[3], ex[3], m[3];
+    for (int i = 0; i < 3; ++i) {
+        qc[i] = ((cr.R[i * 3] * c3[0] + cr.R[i * 3 + 1] * c3[1]) + cr.R[i * 3 + 2] * c3[2]) + cr.t[i];
+        ex[i] = (fabs(cr.R[i * 3]) * e3[0] + fabs(cr.R[i * 3 + 1]) * e3[1]) + fabs(cr.R[i * 3 + 2]) * e3[2];
+    }
+    const double a3[3] = {fabs(qc[0]) + ex[0], fabs(qc[1]) + ex[1], fabs(qc[2]) + ex[2]};
+    for (int i = 0; i < 3; ++i)
+        m[i] = (ex[i] + ((cr.rho[i * 3] * a3[0] + cr.rho[i * 3 + 1] * a3[1]) + cr.rho[i * 3 + 2] * a3[2]) + cr.tau[i]) * (1.0 + 1e-9) + 1e-9 * ((a3[0] + a3[1]) + a3[2]) + 1e-9;
+    const double zhi = qc[2] + m[2];
+    const bool behind = zhi <= 0.0;
+    const bool right = fx * (qc[0] - m[0]) + (cx - W) * zhi >= 1e-6 * (fx * a3[0] + W * a3[2]);
+    const bool left = fx * (qc[0] + m[0]) + cx * zhi < -1e-6 * (fx * a3[0] + W * a3[2]);
+    const bool below = fx * (qc[1] - m[1]) + (cy - H) * zhi >= 1e-6 * (fx * a3[1] + H * a3[2]);
+    const bool above = fx * (qc[1] + m[1]) + cy * zhi < -1e-6 * (fx * a3[1] + H * a3[2]);
+    return behind || right || left || below || above;
+}
+
 // grid: (ceil(max P / kPairsThreads), frames); one scan point per thread. The keypoint grid of the frame (coarse CSR + the
 // keypoints' (u, v)) sits in LDS, so a thread's walk costs LDS round trips, not L2 ones; the hits of a block are parked in LDS
 // and written out behind one atomic reservation per block.
 __global__ __launch_bounds__(kPairsThreads) void iba_pairs_kernel(PairsArgs pa_by_value, double max_pixel_dist, uint32_t lds_kuv_off, int n_frames,
                                                                   PairRec* __restrict__ pairs_all, uint32_t* __restrict__ hard_all,
                                                                   uint32_t* __restrict__ counts_all, int pair_cap, int hard_cap,
-                                                                  const uint4* __restrict__ head_src, uint4* __restrict__ head_dst, uint32_t head_n16, uint32_t dense_min_pts) {
+                                                                  const uint4* __restrict__ head_src, uint4* __restrict__ head_dst, uint32_t head_n16, uint32_t dense_min_pts,
+                                                                  const uint32_t* __restrict__ vis_items) {
     extern __shared__ __align__(16) unsigned char smem[];
     if (head_n16 != 0u && blockIdx.z + 1u == gridDim.z) {   // the chain's head: one more z-plane of the grid carries the candidates to the device (see chain_head_copy)
         chain_head_copy(head_src, head_dst, head_n16, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, (uint32_t)kPairsThreads);
@@ -797,12 +825,16 @@ __global__ __launch_bounds__(kPairsThreads) void iba_pairs_kernel(PairsArgs pa_b
     PairRec* pairs = pairs_all + slot * (size_t)n_frames * (size_t)pair_cap;
     uint32_t* hard = hard_all + slot * (size_t)n_frames * (size_t)hard_cap;
     uint32_t* counts = counts_all + pa->pl.cnt_off[grp]; uint32_t* counts_next = counts_all + pa->pl.next_off[grp];
-    const int f = blockIdx.y;
+    // which block of kPairsThreads consecutive tree positions: the block's place in the (blocks, keyframes) grid, or — vis_items != nullptr —
+    // its item of the handle's visible list (keyframe << 16 | block; the grid is then exactly the items: iba_vis_list_kernel with G = 8)
+    uint32_t blk = blockIdx.x;
+    int f = blockIdx.y;
+    if (vis_items != nullptr) { const uint32_t item = vis_items[blockIdx.x]; f = (int)(item >> 16); blk = item & 0xffffu; }
     const FrameHdr& h = dp.frames[f];
     const uint32_t P = h.P, K = h.K;
-    const uint32_t begin = blockIdx.x * (uint32_t)kPairsThreads;
+    const uint32_t begin = blk * (uint32_t)kPairsThreads;
     // the counters of the NEXT call's lists are cleared here (two sets, used in turn: no memset between the kernels of a call)
-    if (blockIdx.x == 0 && threadIdx.x < 4) counts_next[(size_t)f * kCountStride + threadIdx.x] = 0u;
+    if (blk == 0 && threadIdx.x < 4) counts_next[(size_t)f * kCountStride + threadIdx.x] = 0u;
     if (begin >= P) return;
     uint2* s_hit = (uint2*)smem;                                   // [kPairStage] (tree position, keypoint)
     uint32_t* s_n = (uint32_t*)(smem + 8u * kPairStage);            // [0] hits parked, [1] base of the block's global reservation, [4..] one flag per wave
@@ -816,11 +848,9 @@ __global__ __launch_bounds__(kPairsThreads) void iba_pairs_kernel(PairsArgs pa_b
     const int gw = (int)h.gw, gh = (int)h.gh, gwc = (int)h.gwc;
     const double fx = h.fx, cx = h.cx, cy = h.cy, W = h.W, H = h.H;
     const uint32_t pos = begin + threadIdx.x;
-    // ---- the block's culling chunks (static AABBs of kChunk consecutive tree positions) against every candidate's frustum: a
-    //      block of kPairsThreads consecutive tree positions is a compact piece of the scene, and most pieces are seen by no candidate.
-    //      For a point p of a box with centre c and half extent e: q_b(p)_i lies within m_i = (|R_0| e)_i + delta_i of q_0(c)_i,
-    //      delta from the batch bound at |q_0(c)| + |R_0| e. The piece is invisible when it is behind the camera (z + m_z <= 0) or
-    //      wholly beyond one image border: u >= W <=> fx x + (cx - W) z >= 0 (z > 0), u < 0 <=> fx x + cx z < 0, v alike. ----
+    // ---- the block's culling chunks (static AABBs of kChunk consecutive tree positions) against every candidate's frustum
+    //      (chunk_box_culled): a block of kPairsThreads consecutive tree positions is a compact piece of the scene, and most pieces
+    //      are seen by no candidate. ----
     constexpr uint32_t kBlkChunks = (uint32_t)kPairsThreads / (uint32_t)kChunk;
     bool chunk_vis = false;
     float4 blo = make_float4(INFINITY, INFINITY, INFINITY, 0.f), bhi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.f);   // this lane's chunk box (lanes < kBlkChunks)
@@ -830,23 +860,7 @@ __global__ __launch_bounds__(kPairsThreads) void iba_pairs_kernel(PairsArgs pa_b
             const float4* bx = (const float4*)(dp.chunk_box + 8 * (h.box_base + ch));
             const float4 lo = bx[0], hi = bx[1];
             blo = lo; bhi = hi;
-            const double c3[3] = {0.5 * ((double)lo.x + (double)hi.x), 0.5 * ((double)lo.y + (double)hi.y), 0.5 * ((double)lo.z + (double)hi.z)};
-            const double e3[3] = {0.5 * ((double)hi.x - (double)lo.x), 0.5 * ((double)hi.y - (double)lo.y), 0.5 * ((double)hi.z - (double)lo.z)};
-            double qc[3], ex[3], m[3];
-            for (int i = 0; i < 3; ++i) {
-                qc[i] = ((cr.R[i * 3] * c3[0] + cr.R[i * 3 + 1] * c3[1]) + cr.R[i * 3 + 2] * c3[2]) + cr.t[i];
-                ex[i] = (fabs(cr.R[i * 3]) * e3[0] + fabs(cr.R[i * 3 + 1]) * e3[1]) + fabs(cr.R[i * 3 + 2]) * e3[2];
-            }
-            const double a3[3] = {fabs(qc[0]) + ex[0], fabs(qc[1]) + ex[1], fabs(qc[2]) + ex[2]};
-            for (int i = 0; i < 3; ++i)
-                m[i] = (ex[i] + ((cr.rho[i * 3] * a3[0] + cr.rho[i * 3 + 1] * a3[1]) + cr.rho[i * 3 + 2] * a3[2]) + cr.tau[i]) * (1.0 + 1e-9) + 1e-9 * ((a3[0] + a3[1]) + a3[2]) + 1e-9;
-            const double zhi = qc[2] + m[2];
-            const bool behind = zhi <= 0.0;
-            const bool right = fx * (qc[0] - m[0]) + (cx - W) * zhi >= 1e-6 * (fx * a3[0] + W * a3[2]);
-            const bool left = fx * (qc[0] + m[0]) + cx * zhi < -1e-6 * (fx * a3[0] + W * a3[2]);
-            const bool below = fx * (qc[1] - m[1]) + (cy - H) * zhi >= 1e-6 * (fx * a3[1] + H * a3[2]);
-            const bool above = fx * (qc[1] + m[1]) + cy * zhi < -1e-6 * (fx * a3[1] + H * a3[2]);
-            chunk_vis = !(behind || right || left || below || above);   // a NaN box (empty chunk) compares false everywhere: kept, harmless
+            chunk_vis = !chunk_box_culled(cr, lo, hi, fx, cx, cy, W, H);   // a NaN box (empty chunk) compares false everywhere: kept, harmless
         }
     }
     // A DENSE scan (the reference's own: 120 k points, 235 blocks per keyframe, three in four of them behind or beside every candidate's
@@ -1084,11 +1098,72 @@ __device__ __forceinline__ int wave_max_i(int x) {
     return x;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The VISIBLE-CHUNK LIST of a handle (r08). Which chunks of a scan a camera can see hardly depends on the candidate: candidates move by
+// milliradians and millimetres, the image covers tens of degrees. The list holds, keyframe by keyframe, every chunk that passes
+// chunk_box_culled for an ANCHOR transform with an entrywise bound (rho_a, tau_a); a pair search whose groups all lie inside that bound
+// (vis_composed_bound, iba_pair_plan.hpp) starts one wave per ITEM instead of one per chunk. The wave still runs its own test with the
+// call's tighter bound, so the pairs it finds are those of the full grid. Chunk 0 of every keyframe is always listed: it clears the
+// counters of the slot's next build. Item: keyframe << 16 | chunk (the host keeps handles beyond either range on the full grid).
+// For iba_pairs_kernel (dense scans) an item is a BLOCK of eight consecutive chunks, listed when any of them passes: the block's batch bound is
+// taken over the union of its eight boxes, so its chunks must stay the full grid's (item: keyframe << 16 | block).
+// iba_vis_list_kernel<false>: one block per keyframe counts its items; <true>: the block sums the counts of the keyframes before it (its
+// offset), tests again and writes its items in chunk order; the last keyframe's block hands the total to the host through pinned memory.
+// ------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kVisFrameShift = 16u, kVisChunkMask = 0xffffu;
+constexpr int kVisThreads = 256;
+template <bool FILL, int G>   // G: chunks per item — 1 for the one-wave form, kPairsThreads / kChunk for iba_pairs_kernel's blocks of consecutive chunks
+__global__ __launch_bounds__(kVisThreads) void iba_vis_list_kernel(GroupRef cr, const FrameHdr* __restrict__ frames, const float* __restrict__ chunk_box, int n_frames,
+                                                                   uint32_t* __restrict__ counts, uint32_t* __restrict__ offsets, uint32_t* __restrict__ items, uint32_t* __restrict__ total_out) {
+    __shared__ uint32_t s_w[kVisThreads / 64];
+    const int f = blockIdx.x;
+    const FrameHdr& h = frames[f];
+    const uint32_t nch = max(1u, (h.P + (uint32_t)kChunk - 1u) / (uint32_t)kChunk);
+    const uint32_t nc = (nch + (uint32_t)G - 1u) / (uint32_t)G;   // items the keyframe can have
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t base = 0u;
+    if (FILL) {
+        uint32_t part = 0u;
+        for (int i = (int)threadIdx.x; i < f; i += kVisThreads) part += counts[i];
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) part += (uint32_t)__shfl_xor((int)part, o);
+        if (lane == 0u) s_w[wave] = part;
+        __syncthreads();
+        for (int w = 0; w < kVisThreads / 64; ++w) base += s_w[w];
+        __syncthreads();
+    }
+    uint32_t run = 0u;
+    for (uint32_t c0 = 0u; c0 < nc; c0 += (uint32_t)kVisThreads) {
+        const uint32_t c = c0 + threadIdx.x;
+        bool keep = false;
+        if (c == 0u) keep = true;   // (also a keyframe without points: its counters are cleared all the same)
+        else if (c < nc) {
+            for (uint32_t ch = c * (uint32_t)G; ch < min(nch, (c + 1u) * (uint32_t)G) && !keep; ++ch) {   // an item stays when any of its chunks does
+                const float4* bx = (const float4*)(chunk_box + 8 * (h.box_base + ch));
+                keep = !chunk_box_culled(cr, bx[0], bx[1], h.fx, h.cx, h.cy, h.W, h.H);
+            }
+        }
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0u) s_w[wave] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t before = 0u, all = 0u;
+        for (uint32_t w = 0; w < (uint32_t)(kVisThreads / 64); ++w) { const uint32_t n = s_w[w]; if (w < wave) before += n; all += n; }
+        if (FILL && keep) items[base + run + before + lane_prefix(m)] = ((uint32_t)f << kVisFrameShift) | c;
+        run += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (!FILL) counts[f] = run;
+        else { offsets[f] = base; if (f + 1 == n_frames) { offsets[n_frames] = base + run; *total_out = base + run; } }
+    }
+}
+
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void iba_pairs_wave_kernel(PairsArgs pa_by_value, double max_pixel_dist, int n_frames,
                                                                  PairRec* __restrict__ pairs_all, uint32_t* __restrict__ hard_all,
                                                                  uint32_t* __restrict__ counts_all, int pair_cap, int hard_cap,
-                                                                 const uint4* __restrict__ head_src, uint4* __restrict__ head_dst, uint32_t head_n16, uint32_t dense_min_pts) {
+                                                                 const uint4* __restrict__ head_src, uint4* __restrict__ head_dst, uint32_t head_n16, uint32_t dense_min_pts,
+                                                                 const uint32_t* __restrict__ vis_items, uint32_t vis_n) {
     constexpr int kWaves = THREADS / 64;
     __shared__ __align__(16) unsigned char smem[kWaves * kPwWaveLds];
     if (head_n16 != 0u && blockIdx.z + 1u == gridDim.z) {   // the chain's head (see iba_pairs_kernel)
@@ -1100,10 +1175,17 @@ __global__ __launch_bounds__(THREADS) void iba_pairs_wave_kernel(PairsArgs pa_by
     (void)pa_by_value;
     const uint32_t lane = threadIdx.x & 63u, wave = kWaves == 1 ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = blockIdx.z;
-    const FrameHdr& h = pa->dp.frames[blockIdx.y];
+    // which chunk: the wave's place in the (chunks, keyframes) grid, or — vis_items != nullptr — its item of the handle's visible-chunk
+    // list (keyframe << 16 | chunk, wave-uniform: a scalar load), on a grid of about vis_n waves (iba_vis_list_kernel)
+    uint32_t chunk = blockIdx.x * (uint32_t)kWaves + wave;
+    int f = blockIdx.y;
+    if (vis_items != nullptr) {
+        if (chunk >= vis_n) return;
+        const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane((int)vis_items[chunk]);
+        f = (int)(item >> kVisFrameShift); chunk = item & kVisChunkMask;
+    }
+    const FrameHdr& h = pa->dp.frames[f];
     const uint32_t P = h.P;
-    const uint32_t chunk = blockIdx.x * (uint32_t)kWaves + wave;
-    const int f = blockIdx.y;
     uint32_t* cnt = counts_all + pa->pl.cnt_off[grp] + (size_t)f * kCountStride;
     // the counters of the NEXT call's lists: cleared by the first chunk of the (frame, group), before any return
     if (chunk == 0u && lane < 4u) counts_all[pa->pl.next_off[grp] + (size_t)f * kCountStride + lane] = 0u;
@@ -1128,26 +1210,8 @@ __global__ __launch_bounds__(THREADS) void iba_pairs_wave_kernel(PairsArgs pa_by
     const float4 lo = bx[0], hi = bx[1];
     float4 pv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (!dense && pos < P) pv = p4[pos];
-    // ---- 1. the chunk's box against every candidate's frustum (iba_pairs_kernel's test, wave-uniform) ----
-    {
-        const double c3[3] = {0.5 * ((double)lo.x + (double)hi.x), 0.5 * ((double)lo.y + (double)hi.y), 0.5 * ((double)lo.z + (double)hi.z)};
-        const double e3[3] = {0.5 * ((double)hi.x - (double)lo.x), 0.5 * ((double)hi.y - (double)lo.y), 0.5 * ((double)hi.z - (double)lo.z)};
-        double qc[3], ex[3], m[3];
-        for (int i = 0; i < 3; ++i) {
-            qc[i] = ((cr.R[i * 3] * c3[0] + cr.R[i * 3 + 1] * c3[1]) + cr.R[i * 3 + 2] * c3[2]) + cr.t[i];
-            ex[i] = (fabs(cr.R[i * 3]) * e3[0] + fabs(cr.R[i * 3 + 1]) * e3[1]) + fabs(cr.R[i * 3 + 2]) * e3[2];
-        }
-        const double a3[3] = {fabs(qc[0]) + ex[0], fabs(qc[1]) + ex[1], fabs(qc[2]) + ex[2]};
-        for (int i = 0; i < 3; ++i)
-            m[i] = (ex[i] + ((cr.rho[i * 3] * a3[0] + cr.rho[i * 3 + 1] * a3[1]) + cr.rho[i * 3 + 2] * a3[2]) + cr.tau[i]) * (1.0 + 1e-9) + 1e-9 * ((a3[0] + a3[1]) + a3[2]) + 1e-9;
-        const double zhi = qc[2] + m[2];
-        const bool behind = zhi <= 0.0;
-        const bool right = fx * (qc[0] - m[0]) + (cx - W) * zhi >= 1e-6 * (fx * a3[0] + W * a3[2]);
-        const bool left = fx * (qc[0] + m[0]) + cx * zhi < -1e-6 * (fx * a3[0] + W * a3[2]);
-        const bool below = fx * (qc[1] - m[1]) + (cy - H) * zhi >= 1e-6 * (fx * a3[1] + H * a3[2]);
-        const bool above = fx * (qc[1] + m[1]) + cy * zhi < -1e-6 * (fx * a3[1] + H * a3[2]);
-        if (behind || right || left || below || above) return;   // (a NaN box compares false everywhere: kept, harmless)
-    }
+    // ---- 1. the chunk's box against every candidate's frustum (chunk_box_culled, wave-uniform): the call's own bound, whatever list the chunk came from ----
+    if (chunk_box_culled(cr, lo, hi, fx, cx, cy, W, H)) return;
 #if IBA_PAIRS_CUT == 1
     return;
 #endif
