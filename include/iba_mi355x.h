@@ -241,7 +241,8 @@ iba_status iba_icp_calib(iba_handle* h, int32_t frame_begin, int32_t frame_end, 
  * source and target scans, the target's kd tree and its memoised normals are already resident. A scans-only handle is enough.
  * Voxel down-sampling and the merged sub-map target of a loop closure are iba_submap_build, and choosing WHICH keyframe pairs to close a loop between
  * (Scan Context) is iba_sc_describe / iba_sc_detect (both below); the pose-graph optimisation over the resulting edges is iba_pgo_* (below:
- * Open3D's GlobalOptimization; iSAM2 stays the caller's), and PCD IO stays the caller's.
+ * Open3D's GlobalOptimization), the smoothing stage that yields the isam poses is iba_smooth_* with the plan of iba_backend_plan (both below; GTSAM's
+ * iSAM2 is restated as its converged optimum, not linked), and PCD IO stays the caller's.
  *
  * Restated from Open3D's public sources (not part of the reference tree: parity with it is UNPINNED; the kd search stays pinned to nanoflann):
  *   RegistrationICP, GetRegistrationResultAndCorrespondences, SearchHybrid's strict gate    the loop of iba_icp_register (one implementation)
@@ -824,7 +825,7 @@ void iba_floam_odom_free(iba_floam_odom* o);
  * or source == target, a number that is not finite (poses, T, the upper triangle of info, the options), a pose or T whose last row is not exactly
  * 0 0 0 1, reference_node outside [-1, N), segment < 1, max_iteration / max_iteration_lm < 0. iba_pgo_last_error(pg) carries the message of a call
  * on pg; iba_pgo_last_error(NULL) of the calls without one (create, plan), on this thread.
- * Limits: one GPU; iSAM2 and the incremental path (UpdateISAM) are not here; a graph whose cross edges touch more than IBA_PGO_MAX_SEPARATORS nodes.
+ * Limits: one GPU; a graph whose cross edges touch more than IBA_PGO_MAX_SEPARATORS nodes. The incremental path (UpdateISAM) is iba_smooth_* (below).
  */
 #define IBA_PGO_MAX_SEPARATORS 1024
 #define IBA_PGO_STOP_NONE 0               /* the pass did not run */
@@ -874,9 +875,166 @@ iba_status iba_pgo_optimize(iba_pgo* pg, iba_pgo_result* result);
 /* The state: poses N x 16, weights E, dropped flags E bytes. Every output may be NULL. */
 iba_status iba_pgo_read(iba_pgo* pg, double* nodes16, double* weight, uint8_t* pruned);
 
+/*
+ * ---- Robust smoothing of a chain-with-loops pose graph [backend_opt.cpp:242-431 LoopClosureRun / LoopClosureRegThread / UpdateISAM: the noise
+ * models :108-113 (Cauchy::Create(1) over the loop variances), PriorFactor :198-200, the odometry BetweenFactor prevPose.between(currPose) :206, a robust
+ * BetweenFactor per verified loop :266, isam->update() and calculateBestEstimate() :375-381] ----
+ * The smoothing stage of the reference's LiDAR back end, the one that yields floam_isam_xx.txt. An iba_smooth is a stand-alone object on one device
+ * (no iba_handle needed) whose graph GROWS: nodes and factors are appended between updates, iba_smooth_update optimises every node present from the
+ * current estimates. Everything of size N or F stays on the device between LM trials.
+ *
+ * KNOWN DEVIATIONS (GTSAM is not part of the reference tree: parity with it is UNPINNED, as for iba_pgo_* and iba_scan_*):
+ *   - iSAM2's incremental Bayes-tree algorithm (a few Gauss-Newton steps of the affected cliques per update()) is NOT restated. iba_smooth_update
+ *     runs Levenberg-Marquardt to the CONVERGED robust optimum of the same factor graph over all nodes.
+ * THIS TEXT IS THE CONTRACT: tests/smooth_ref.py restates it in numpy and the tests hold the device to that. Transforms are row-major 4x4 with the
+ * last row 0 0 0 1; a rigid inverse is always formed as [R^T, -R^T t]; all arithmetic is IEEE f64 without contraction; no floating-point atomics,
+ * every sum in a fixed order: two calls give the same bytes.
+ *   S1 poses, tangents  P_i maps body to world (FramePoses, gtsam::Pose3). xi = [omega, upsilon], rotation first (GTSAM's order). Exp(xi) = [R, t]:
+ *                    R = I + a W + b W^2, t = (I + b W + c W^2) upsilon, W = [omega]x, theta = |omega|, a = sin(theta) / theta, b = (1 - cos(theta)) /
+ *                    theta^2, c = (theta - sin(theta)) / theta^3. Log([R, t]): the quaternion (w, v) of R by its largest component, w >= 0,
+ *                    omega = (2 atan2(|v|, w) / |v|) v — exact up to theta = pi — and upsilon = (I - W / 2 + e W^2) t, e = (1 - (theta / 2)
+ *                    cot(theta / 2)) / theta^2. SERIES: with theta^2 < 1e-2 each of a, b, c, e (and c2, k4 of S2) is its Taylor polynomial in theta^2
+ *                    through theta^10 (c2, k4: theta^8); with (|v| / w)^2 < 2.5e-3 the factor 2 atan2(|v|, w) / |v| is (2 / w) (1 - u / 3 + u^2 / 5 -
+ *                    u^3 / 7 + u^4 / 9 - u^5 / 11), u = (|v| / w)^2. r = 0 exactly (every odometry factor and the prior start there) is the normal case.
+ *   S2 residual      a prior (j, Z): r = Log(Z^-1 P_j); a between factor (i, j, Z): r = Log(Z^-1 P_i^-1 P_j). Perturbations on the left, in the world
+ *                    frame: P <- Exp(delta) P. J = dr / d delta_j = Jr^-1(r) Ad(P_j^-1); for a between factor dr / d delta_i = -J exactly.
+ *                    Ad([R, t]) = [[R, 0], [[t]x R, R]]. Jr^-1(r) = [[Ji, 0], [-Ji Q Ji, Ji]], Ji = I + W / 2 + e W^2 and, with U = [upsilon]x,
+ *                    d = omega . upsilon: Q = -U / 2 + c (W U + U W + d W) - c2 (W W U + U W W + 3 d W) - 2 k4 d W W (Barfoot's Q block at -r),
+ *                    c2 = (theta^2 / 2 + cos(theta) - 1) / theta^4, k4 = (c2 + 3 (c - 1/6) / theta^2) / 2. So a factor has ONE block
+ *                    A = w J^T S^-1 J and one vector g = w J^T S^-1 r, S = diag(var): a between factor H_ii += A, H_jj += A, H_ij = H_ji -= A,
+ *                    b_i += g, b_j -= g; a prior H_jj += A, b_j -= g.
+ *   S3 robust weight q = sum r_k^2 / var_k. A robust factor (Cauchy, k = 1): w = 1 / (1 + q), and it adds log1p(q) to F; any other factor w = 1 and
+ *                    adds q. F is twice the loss. Weights are recomputed at every linearisation.
+ *   S4 LM            rule 6 of iba_pgo_* with F in the place of r (a trial's F_new is F at the trial poses), the same option fields and stops
+ *                    (IBA_PGO_STOP_*; x of stop (b) the stacked vec6 of rule 1 there), the trial pose Exp(delta_i) P_i, and lambda_0 = 1e-5 * the
+ *                    largest diagonal entry of the BETWEEN-factor part of H (the priors are left out: at the reference's prior variance 1e-12 they
+ *                    would put lambda seven orders above the odometry information). One pass: no pruning, no reference-node compensation.
+ *   S5 solve         the block-arrowhead chain of iba_pgo_* (chain factor: the first between factor, in call order, on nodes i and i + 1; separators,
+ *                    runs, blocked Cholesky), the same kernels. The plan is rebuilt on the host whenever nodes or factors were added since the
+ *                    last one. Cross factors touching more than IBA_PGO_MAX_SEPARATORS nodes: IBA_ERR_INVALID_ARG from the call that plans.
+ * Answers IBA_ERR_INVALID_ARG with a message, BEFORE the device is touched: a NULL argument, struct_size, a number that is not finite, a pose or Z whose
+ * last row is not exactly 0 0 0 1, a node outside the graph or i == j, a variance that is not finite or not > 0, segment < 1, max_iteration /
+ * max_iteration_lm < 0, first / count outside the graph. iba_smooth_last_error(s) carries the message of a call on s; iba_smooth_last_error(NULL)
+ * that of iba_smooth_create, on this thread. A graph without a node: IBA_ERR_STATE from linearize / solve / update.
+ * A device failure while the graph is brought onto the device loses the estimates: the call answers IBA_ERR_HIP, every later one IBA_ERR_STATE.
+ * Limits: one GPU; factors cannot be removed; Gaussian or Cauchy(1) noise on a diagonal covariance only. LONG TRAJECTORIES: stop (b) compares |delta|
+ * with 1e-6 of the stacked pose vector, and lambda_0 follows the largest diagonal entry of H, whose rotation part carries |t|^2 / var lever arms of
+ * world-frame perturbations. On a trajectory of hundreds of metres (500 nodes and more in profiles/backend_bench.md) the first trial's step falls under
+ * that stop at the default options and iba_smooth_update applies nothing; convergence is shown at N <= 130. Lower min_relative_increment there.
+ */
+typedef struct iba_smooth_options {
+    int32_t struct_size;               /* sizeof(iba_smooth_options) */
+    int32_t max_iteration;             /* 100 */
+    int32_t max_iteration_lm;          /* 20 */
+    int32_t segment;                   /* separator spacing K of the solve, 128 */
+    double  min_relative_increment, min_relative_residual_increment, min_right_term, min_residual;   /* 1e-6 each */
+    double  upper_scale_factor, lower_scale_factor;   /* 2/3, 1/3 */
+} iba_smooth_options;
+typedef struct iba_smooth_result {
+    int32_t struct_size;               /* written by the library: sizeof(iba_smooth_result) */
+    int32_t n_nodes, n_factors;        /* the graph that was optimised */
+    int32_t iterations, trials, stop;  /* outer iterations, LM trials, IBA_PGO_STOP_* */
+    double  F_start, F, lambda_start, lambda, max_b;   /* F and lambda before and after; max |b| at the final poses */
+} iba_smooth_result;
+typedef struct iba_smooth iba_smooth;
+iba_status iba_default_smooth_options(iba_smooth_options* opt);
+iba_status iba_smooth_create(const iba_smooth_options* opt, int device, iba_smooth** out);   /* *out is NULL on failure */
+void iba_smooth_destroy(iba_smooth* s);
+const char* iba_smooth_last_error(const iba_smooth* s);   /* never NULL */
+/* Appends node n (0, 1, 2 ... in call order) with pose16 as its estimate. */
+iba_status iba_smooth_add_node(iba_smooth* s, const double* pose16);
+/* Factors are numbered 0, 1, 2 ... in call order, priors and between factors together. var6: the diagonal of S in [omega, upsilon] order. */
+iba_status iba_smooth_add_prior(iba_smooth* s, int32_t node, const double* Z16, const double* var6);
+iba_status iba_smooth_add_between(iba_smooth* s, int32_t i, int32_t j, const double* Z16, const double* var6, int32_t robust);
+/* Linearises at the current estimates (S2, S3). Every output may be NULL: r F x 6, w F, A F x 36 (row-major), D N x 36 (the diagonal blocks of H),
+ * b N x 6, *F. */
+iba_status iba_smooth_linearize(iba_smooth* s, double* r, double* w, double* A, double* D, double* b, double* F);
+/* (H + lambda I) delta = b at the last linearisation (IBA_ERR_STATE without one, or when the graph grew since); delta N x 6 */
+iba_status iba_smooth_solve(iba_smooth* s, double lambda, double* delta);
+/* S4 over every node present, from the current estimates */
+iba_status iba_smooth_update(iba_smooth* s, iba_smooth_result* result);
+/* The estimates of nodes first .. first + count - 1 (count x 16) and the weights of ALL factors at the last linearisation (F doubles; 1 before any).
+ * Either output may be NULL. */
+iba_status iba_smooth_read(iba_smooth* s, int32_t first, int32_t count, double* nodes16, double* weight);
+
+/*
+ * ---- The back end's loop-closure run: options and plan [backend_opt.cpp:322-370 SCManage, :304-314 PerformLoopClosure; config/loam/backend.yml,
+ * BackEndOption backend_opt.h:48-85] ----
+ * iba_backend_plan (host only, no device) is SCManage's bookkeeping as a pure function of the raw poses: which frames become keyframes, which
+ * frame's cloud is described for each, which keyframes call detectLoopClosureID, and the sizes_at_call sequence iba_sc_replay_plan takes. With it
+ * the run is a composition of what is above: iba_submap_handle over the described frames -> iba_sc_describe -> iba_sc_replay_plan + iba_sc_detect
+ * (Scan Context never depends on the optimised poses) -> per detection iba_submap_build / iba_scan_register -> iba_smooth_add_between +
+ * iba_smooth_update. iba_backend_run is that composition as one call on a handle whose frames 0 .. N - 1 are the raw scans (scans only is enough):
+ *   1 the plan; 2 the voxel clouds of all described frames as ONE iba_submap_handle batch; 3 one iba_sc_describe; 4 the whole detection sequence as one
+ *   iba_sc_detect; 5 a prior on node 0 at the raw pose; 6 per frame j the factor between(raw_(j-1), raw_j) = raw_(j-1)^-1 raw_j at odom_var and node j
+ *   at its raw pose; 7 at a detection with loop node k, history = keyframes[k]: the sub-map over frames [max(0, history - S), min(history + S, N)),
+ *   S = lc_submap_size, posed by the CURRENT poses (estimates for nodes already optimised, raw for the others), brought into the history frame by
+ *   out12 = pose[history]^-1 (formed as [R^T, -R^T t], as every rigid inverse of this library), is the target frame and the query keyframe's voxel cloud the source frame of a two-frame iba_submap_handle, and
+ *   iba_scan_register (opt->scan) runs from the identity; 8 the loop is accepted iff fitness > loop_overlap_thre && inlier_rmse <
+ *   loop_inlier_rmse_thre, both strict; 9 on accept between(history, j, T, loop_var, robust), iba_smooth_update, and the estimates of nodes 0 .. j
+ *   become the current poses; 10 after the last frame one more update.
+ * KNOWN DEVIATION: a loop is verified at the moment it is detected, with the poses current then; in the reference the timing of the loop-closure
+ * thread decides which poses a sub-map sees. The detection records hold every loop Scan Context found (accepted or not) in frame order. Errors of the
+ * composed calls come back with this function's name in front (iba_backend_last_error). Nothing of cloud size crosses PCIe. The smoother runs on the
+ * handle's device (iba_handle_device).
+ * Rules (poses12: N row-major 3x4, the KITTI layout; frame 0 is keyframe 0, describes itself and is never a query). For j = 1 .. N - 1:
+ * PoseDif(pose_(j-1), pose_j) = (|t_j - t_(j-1)|, the angle of R = R_j R_(j-1)^T taken as atan2(s, c), c = (trace(R) - 1) / 2, s = half the norm of
+ * (R21 - R12, R02 - R20, R10 - R01)) is added to four accumulators (sequential f64 sums). translation > keyframe_meter_gap || rotation >
+ * keyframe_rad_gap (both strict): both reset, j becomes a keyframe and describes frame j - cloud_lag; THEN, and only then, the loop-closure pair is
+ * tested against lc_keyframe_meter_gap / lc_keyframe_rad_gap (strict): both reset and the keyframe is a query, sizes_at_call = the keyframes so far.
+ * IBA_ERR_INVALID_ARG with a message (iba_backend_last_error, per thread): a NULL opt or poses12, struct_size, N < 1, a number that is not finite,
+ * a variance not > 0, voxel not > 0, lc_submap_size < 0, cloud_lag or keep_update_poses other than 0 or 1.
+ */
+typedef struct iba_backend_options {
+    int32_t struct_size;               /* sizeof(iba_backend_options) */
+    int32_t lc_submap_size;            /* LCSubmapSize 25 */
+    double  voxel;                     /* odom.voxel 0.2 */
+    double  keyframe_meter_gap, keyframe_rad_gap;         /* 1.5, 0.15 */
+    double  lc_keyframe_meter_gap, lc_keyframe_rad_gap;   /* 3, 1 */
+    double  loop_overlap_thre, loop_inlier_rmse_thre;     /* 0.5, 0.2: a loop is accepted iff fitness > and inlier_rmse <, both strict (:263) */
+    iba_sc_options sc;                 /* iba_default_sc_options; dist_thres = scDistThres 0.2, max_radius = scMaximumRadius 80 (backend_opt.h:60-61) */
+    iba_scan_options scan;             /* the loop registration as written (:262): point-to-point, coarse 1.0 m x 1 iteration (1e-4), refine
+                                          0.3 m x 0 iterations (1e-6), no information matrix */
+    double  prior_var[6], odom_var[6], loop_var[6];       /* backend_opt.h:81-83: 1e-12; 1e-6 x 3, 1e-4 x 3; 0.5 */
+    iba_smooth_options smooth;         /* iba_default_smooth_options */
+    int32_t cloud_lag;                 /* 1: a keyframe j describes LoadPCD(j - 1), as :360 does; 0: its own scan */
+    int32_t keep_update_poses;         /* 0; 1: the result keeps the estimates after every update (iba_backend_result_update_poses12), n_nodes x 12 doubles each */
+} iba_backend_options;
+iba_status iba_default_backend_options(iba_backend_options* opt);
+const char* iba_backend_last_error(void);   /* never NULL; of this thread's last iba_backend_* call that failed */
+/* Every output may be NULL; keyframes, described, detects and sizes_at_call hold up to N entries. keyframes[k]: the frame of keyframe k (KeyFrameQuery);
+ * described[k]: the frame whose cloud is node k of the Scan Context database; detects[k]: 1 when keyframe k is a query; sizes_at_call[c]: the
+ * descriptors held at call c (its query is node sizes_at_call[c] - 1). */
+iba_status iba_backend_plan(const double* poses12, int32_t N, const iba_backend_options* opt, int32_t* keyframes, int32_t* described, uint8_t* detects,
+                            int32_t* n_keyframes, int32_t* sizes_at_call, int32_t* n_calls);
+typedef struct iba_backend_detection {
+    int32_t query_frame, history_frame, accepted, reserved;
+    double  sc_dist, fitness, rmse;   /* Scan Context's min_dist; iba_scan_register's fitness and inlier_rmse */
+    double  T[16];                    /* row-major 4x4, query cloud -> history frame: the loop factor's measurement */
+} iba_backend_detection;
+typedef struct iba_backend_result iba_backend_result;
+/* *out is NULL on failure; release it with iba_backend_result_free. */
+iba_status iba_backend_run(iba_handle* h, const double* poses12, int32_t N, const iba_backend_options* opt, iba_backend_result** out);
+void iba_backend_result_free(iba_backend_result* r);
+/* Of a result (0 / NULL for NULL), valid until it is freed: the N final poses, 12 doubles per row in the KITTI layout writePoses writes; the keyframes;
+ * the detections; the iba_smooth_result of every update (one per accepted loop, then the final one). */
+int32_t iba_backend_result_n_frames(const iba_backend_result* r);
+const double* iba_backend_result_poses12(const iba_backend_result* r);
+int32_t iba_backend_result_n_keyframes(const iba_backend_result* r);
+const int32_t* iba_backend_result_keyframes(const iba_backend_result* r);
+int32_t iba_backend_result_n_detections(const iba_backend_result* r);
+const iba_backend_detection* iba_backend_result_detections(const iba_backend_result* r);
+int32_t iba_backend_result_n_updates(const iba_backend_result* r);
+const iba_smooth_result* iba_backend_result_updates(const iba_backend_result* r);
+/* With opt->keep_update_poses: the estimates after update u, updates[u].n_nodes rows of 12 doubles (the current poses of nodes 0 .. n_nodes - 1 that the
+ * next sub-map is posed by); NULL without the option or for u out of range. */
+const double* iba_backend_result_update_poses12(const iba_backend_result* r, int32_t u);
+
 /* The ABI version the LIBRARY was built with (IBA_ABI_VERSION of its header). iba_params carries no struct_size: a caller compiled against
  * an older header would pass a shorter struct. Callers compare iba_abi_version() with their own IBA_ABI_VERSION before iba_create(). */
 int32_t iba_abi_version(void);
+/* The HIP device a handle lives on (the `device` it was created with; a handle of iba_submap_handle: its source's); -1 for NULL. */
+int32_t iba_handle_device(const iba_handle* h);
 
 /* Output of one BAError() call. The first five fields are the reference's returned tuple
  * (iba_global.cpp:343); the rest are the counters it prints with verborse (:341-342). */

@@ -204,6 +204,10 @@ iba_status iba_debug_div2_selftest(int32_t device, const double* num0, const dou
  * set on the trials of pass 2. Up to cap bytes are written; *n = the number of trials. */
 iba_status iba_debug_pgo_trace(iba_pgo* pg, uint8_t* trials, int32_t cap, int32_t* n);
 
+/* debug: the LM trials of the last iba_smooth_update in order, one byte each: 1 accepted, 0 rejected, 2 the trial that stopped on the increment. Up to
+ * cap bytes are written; *n = the number of trials. */
+iba_status iba_debug_smooth_trace(iba_smooth* s, uint8_t* trials, int32_t cap, int32_t* n);
+
 #ifdef __cplusplus
 }
 #endif

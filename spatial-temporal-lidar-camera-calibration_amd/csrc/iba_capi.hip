@@ -1158,6 +1158,7 @@ iba_status create_impl(const iba_problem_desc* d, const iba_params* params, int 
 extern "C" {
 
 int32_t iba_abi_version(void) { return IBA_ABI_VERSION; }
+int32_t iba_handle_device(const iba_handle* h) { return h ? (int32_t)h->device : -1; }
 const char* iba_last_error(const iba_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 int64_t iba_num_points(const iba_handle* h) { return h ? h->n_points : 0; }
 int64_t iba_num_keypoints(const iba_handle* h) { return h ? h->n_keypoints : 0; }

@@ -17,6 +17,7 @@
 #include "iba_internal.hpp"
 #include "iba_pgo_host.hpp"
 #include "iba_pgo_kernels.hpp"
+#include "iba_pgo_solve.hpp"
 
 namespace {
 
@@ -41,12 +42,13 @@ struct iba_pgo {
     std::vector<uint8_t> flags;
     std::vector<double> info55;
     Plan plan;
+    Arrow ar;                    // the plan on the device and the solve (shared with iba_smooth)
     double mu = 0.0;
     int cur = 0;                 // poses[cur] are the poses, poses[1 - cur] the trial
     bool linearized = false;
     int nbE = 0, nbN = 0;
-    DevBuf<double> poses[2], Xinv, info, weight, zeta, A, g, epart, D, b, npart, G, F, y, delta, upart, run_S, run_b, S, rhs, xs, scal;
-    DevBuf<int32_t> d_src, d_tgt, inc_off, inc_edge, chain, run_first, run_last, sep_node, sep_of_node, brow, bcol, boff, kind, idx;
+    DevBuf<double> poses[2], Xinv, info, weight, zeta, A, g, epart, D, b, npart, delta, upart, scal;
+    DevBuf<int32_t> d_src, d_tgt;
     DevBuf<uint8_t> d_flags;
     std::vector<uint8_t> trace;
     std::string err;
@@ -58,7 +60,6 @@ namespace {
 iba_status fail(iba_pgo* pg, iba_status s, const std::string& m) { if (pg) pg->err = m; else t_err = m; return s; }
 
 EdgeDev edge_dev(const iba_pgo* pg) { return EdgeDev{pg->E, pg->d_src.p, pg->d_tgt.p, pg->Xinv.p, pg->info.p, pg->d_flags.p}; }
-RunDev run_dev(const iba_pgo* pg) { return RunDev{(int)pg->plan.run_first.size(), pg->run_first.p, pg->run_last.p, pg->chain.p, pg->N}; }
 
 // the plan of the active edges onto the device (create and prune time)
 iba_status upload_plan(iba_pgo* pg) {
@@ -67,17 +68,8 @@ iba_status upload_plan(iba_pgo* pg) {
     std::string why;
     if (!make_plan(pg->N, pg->src.data(), pg->tgt.data(), active.data(), pg->E, pg->opt.segment, sep_cap(), pg->plan, why)) return fail(pg, IBA_ERR_INVALID_ARG, "iba_pgo: " + why);
     pg->mu = line_process_mu(pg->opt, pg->info55.data(), pg->flags.data(), pg->E);
-    const Plan& p = pg->plan;
-    const size_t n = 6 * p.sep.size(), R = p.run_first.size();
-    hipError_t e = hipSuccess;
-    auto up = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    up(pg->d_flags.upload(pg->flags));
-    up(pg->inc_off.upload(p.inc_off)); up(pg->inc_edge.upload(p.inc_edge)); up(pg->chain.upload(p.chain));
-    up(pg->run_first.upload(p.run_first)); up(pg->run_last.upload(p.run_last));
-    up(pg->sep_node.upload(p.sep)); up(pg->sep_of_node.upload(p.sep_of_node));
-    up(pg->brow.upload(p.brow)); up(pg->bcol.upload(p.bcol)); up(pg->boff.upload(p.boff)); up(pg->kind.upload(p.kind)); up(pg->idx.upload(p.idx));
-    up(pg->run_S.alloc(108 * R)); up(pg->run_b.alloc(12 * R));
-    up(pg->S.alloc(n * n)); up(pg->rhs.alloc(n)); up(pg->xs.alloc(n));
+    hipError_t e = pg->d_flags.upload(pg->flags);
+    if (e == hipSuccess) e = pg->ar.upload(pg->plan, pg->N);
     if (e != hipSuccess) return fail(pg, IBA_ERR_HIP, std::string("iba_pgo: plan upload: ") + hipGetErrorString(e));
     pg->linearized = false;
     return IBA_OK;
@@ -90,7 +82,7 @@ iba_status linearize(iba_pgo* pg, bool recompute_w, double* scal_host) {
         hipLaunchKernelGGL(pgo_edge_kernel<true>, dim3(pg->nbE), dim3(kThreads), 0, st, edge_dev(pg), (const double*)pg->poses[pg->cur].p, pg->mu, recompute_w ? 1 : 0, pg->weight.p,
                            pg->zeta.p, pg->A.p, pg->g.p, pg->epart.p);
     hipLaunchKernelGGL(pgo_final_kernel, dim3(1), dim3(64), 0, st, (const double*)pg->epart.p, pg->nbE, 1, 0, pg->scal.p);
-    hipLaunchKernelGGL(pgo_node_kernel, dim3(pg->N), dim3(64), 0, st, (int)pg->N, (const int32_t*)pg->inc_off.p, (const int32_t*)pg->inc_edge.p, (const double*)pg->A.p,
+    hipLaunchKernelGGL(pgo_node_kernel, dim3(pg->N), dim3(64), 0, st, (int)pg->N, (const int32_t*)pg->ar.inc_off.p, (const int32_t*)pg->ar.inc_edge.p, (const double*)pg->A.p,
                        (const double*)pg->g.p, (const double*)pg->poses[pg->cur].p, pg->D.p, pg->b.p, pg->npart.p);
     hipLaunchKernelGGL(pgo_final_kernel, dim3(1), dim3(64), 0, st, (const double*)pg->npart.p, (int)pg->N, 1, 2, pg->scal.p + 1);
     if (hipMemcpyAsync(scal_host, pg->scal.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return fail(pg, IBA_ERR_HIP, "iba_pgo: download of the scalars");
@@ -101,28 +93,7 @@ iba_status linearize(iba_pgo* pg, bool recompute_w, double* scal_host) {
 }
 
 // the launch chain of (H + lambda I) delta = b; no synchronisation
-void solve_launch(iba_pgo* pg, double lambda) {
-    hipStream_t st = pg->stream;
-    const Plan& p = pg->plan;
-    const int R = (int)p.run_first.size(), ns = (int)p.sep.size(), n = 6 * ns, nblk = (int)p.brow.size();
-    (void)hipMemsetAsync(pg->scal.p + 7, 0, sizeof(double), st);
-    (void)hipMemsetAsync(pg->S.p, 0, (size_t)n * n * sizeof(double), st);
-    if (R > 0)
-        hipLaunchKernelGGL(pgo_run_forward_kernel, dim3((R + 3) / 4), dim3(64), 0, st, run_dev(pg), (const double*)pg->D.p, (const double*)pg->b.p, (const double*)pg->A.p, lambda,
-                           pg->G.p, pg->F.p, pg->y.p, pg->run_S.p, pg->run_b.p, pg->scal.p);
-    hipLaunchKernelGGL(pgo_sep_assemble_kernel, dim3(nblk), dim3(64), 0, st, (const int32_t*)pg->brow.p, (const int32_t*)pg->bcol.p, (const int32_t*)pg->boff.p,
-                       (const int32_t*)pg->kind.p, (const int32_t*)pg->idx.p, (const double*)pg->D.p, (const double*)pg->b.p, (const double*)pg->A.p,
-                       (const double*)pg->run_S.p, (const double*)pg->run_b.p, lambda, n, pg->S.p, pg->rhs.p);
-    for (int j0 = 0; j0 < n; j0 += kNB) {
-        const int w = std::min(kNB, n - j0);
-        hipLaunchKernelGGL(pgo_chol_panel_kernel, dim3(1), dim3(kThreads), 0, st, pg->S.p, n, j0, w, pg->scal.p);
-        const int rest = n - (j0 + w);
-        if (rest > 0) { const int nt = (rest + kTile - 1) / kTile; hipLaunchKernelGGL(pgo_chol_update_kernel, dim3(nt, nt), dim3(kThreads), 0, st, pg->S.p, n, j0, w); }
-    }
-    hipLaunchKernelGGL(pgo_sep_solve_kernel, dim3(1), dim3(kThreads), 0, st, (const double*)pg->S.p, n, (const double*)pg->rhs.p, pg->xs.p);
-    hipLaunchKernelGGL(pgo_run_back_kernel, dim3((std::max(R, ns) + 63) / 64), dim3(64), 0, st, run_dev(pg), ns, (const int32_t*)pg->sep_node.p, (const int32_t*)pg->sep_of_node.p,
-                       (const double*)pg->xs.p, (const double*)pg->G.p, (const double*)pg->F.p, (const double*)pg->y.p, pg->delta.p);
-}
+void solve_launch(iba_pgo* pg, double lambda) { pg->ar.launch(pg->stream, pg->D.p, pg->b.p, pg->A.p, lambda, pg->delta.p, pg->scal.p); }
 
 // trial poses into poses[1 - cur] from delta, the trial residual; scal[0..7] on the host afterwards
 iba_status trial(iba_pgo* pg, double lambda, double* scal_host) {
@@ -201,6 +172,35 @@ iba_status lm_pass(iba_pgo* pg, iba_pgo_pass* out, uint8_t trace_bit) {
 
 }  // namespace
 
+// iba_pgo_solve.hpp: the one place the solve's kernels are launched from
+namespace iba { namespace pgo {
+
+void Arrow::launch(hipStream_t st, const double* D, const double* b, const double* A, double lambda, double* delta, double* scal) {
+    const RunDev rd{R, run_first.p, run_last.p, chain.p, N};
+    const int n = 6 * ns;
+    (void)hipMemsetAsync(scal + 7, 0, sizeof(double), st);
+    (void)hipMemsetAsync(S.p, 0, (size_t)n * n * sizeof(double), st);
+    if (R > 0)
+        hipLaunchKernelGGL(pgo_run_forward_kernel, dim3((R + 3) / 4), dim3(64), 0, st, rd, D, b, A, lambda, G.p, F.p, y.p, run_S.p, run_b.p, scal);
+    hipLaunchKernelGGL(pgo_sep_assemble_kernel, dim3(nblk), dim3(64), 0, st, (const int32_t*)brow.p, (const int32_t*)bcol.p, (const int32_t*)boff.p,
+                       (const int32_t*)kind.p, (const int32_t*)idx.p, D, b, A, (const double*)run_S.p, (const double*)run_b.p, lambda, n, S.p, rhs.p);
+    for (int j0 = 0; j0 < n; j0 += kNB) {
+        const int w = std::min(kNB, n - j0);
+        hipLaunchKernelGGL(pgo_chol_panel_kernel, dim3(1), dim3(kThreads), 0, st, S.p, n, j0, w, scal);
+        const int rest = n - (j0 + w);
+        if (rest > 0) { const int nt = (rest + kTile - 1) / kTile; hipLaunchKernelGGL(pgo_chol_update_kernel, dim3(nt, nt), dim3(kThreads), 0, st, S.p, n, j0, w); }
+    }
+    hipLaunchKernelGGL(pgo_sep_solve_kernel, dim3(1), dim3(kThreads), 0, st, (const double*)S.p, n, (const double*)rhs.p, xs.p);
+    hipLaunchKernelGGL(pgo_run_back_kernel, dim3((std::max(R, ns) + 63) / 64), dim3(64), 0, st, rd, ns, (const int32_t*)sep_node.p, (const int32_t*)sep_of_node.p,
+                       (const double*)xs.p, (const double*)G.p, (const double*)F.p, (const double*)y.p, delta);
+}
+
+void final_launch(hipStream_t st, const double* partial, int nblocks, int nsum, int nmax, double* out) {
+    hipLaunchKernelGGL(pgo_final_kernel, dim3(1), dim3(64), 0, st, partial, nblocks, nsum, nmax, out);
+}
+
+} }  // namespace iba::pgo
+
 extern "C" {
 
 iba_status iba_default_pgo_options(iba_pgo_options* o) {
@@ -276,7 +276,7 @@ iba_status iba_pgo_create(const double* nodes16, int32_t N, const iba_pgo_edge* 
     if (e == hipSuccess) up(hipMemcpy(pg->poses[0].p, nodes16, 16 * n * sizeof(double), hipMemcpyHostToDevice));
     up(pg->d_src.upload(pg->src)); up(pg->d_tgt.upload(pg->tgt)); up(pg->Xinv.upload(xinv)); up(pg->info.upload(info)); up(pg->weight.upload(ones));
     up(pg->zeta.alloc(6 * m)); up(pg->A.alloc(36 * m)); up(pg->g.alloc(6 * m)); up(pg->epart.alloc(pg->nbE));
-    up(pg->D.alloc(36 * n)); up(pg->b.alloc(6 * n)); up(pg->npart.alloc(3 * n)); up(pg->G.alloc(36 * n)); up(pg->F.alloc(36 * n)); up(pg->y.alloc(6 * n));
+    up(pg->D.alloc(36 * n)); up(pg->b.alloc(6 * n)); up(pg->npart.alloc(3 * n));
     up(pg->delta.alloc(6 * n)); up(pg->upart.alloc(2 * (size_t)pg->nbN)); up(pg->scal.alloc(kScal));
     up(hipStreamCreate(&pg->stream));
     if (e != hipSuccess) { const std::string msg = hipGetErrorString(e); iba_pgo_destroy(pg); return fail(nullptr, IBA_ERR_HIP, "iba_pgo_create: " + msg); }

@@ -1,0 +1,202 @@
+"""Device tier of the robust pose-graph smoother (include/iba_mi355x.h, iba_smooth_*) against tests/smooth_ref.py.
+Gates:
+  linearise   per output, |device - long double| <= 4 x |float64 restatement - long double| + one ulp of the output's scale, on the same case (the gate
+              of tests/test_gpu_pgo.py). The scale is the sum of the absolute values of the terms of the output's largest sum (for r: its largest entry).
+  solve       |(H + lambda I) delta - b| / |b| of the device against the same figure of the dense float64 solve of the SAME H, b (read back from the
+              device), both evaluated in long double, margin 8 x.
+  optimise    decisions reproduced exactly on seeds where the float64 reference and its two long-double twins (linearise / solve in long double) share
+              one trial trace and no decision is a near-tie (asserted here, on the CPU side of the test); final poses within 4 x the larger distance
+              of the float64 reference from the twins; the reference's max |b| at the device's poses no larger than at the reference's own
+              last-but-one accepted iterate.
+Every figure is printed and, with IBA_SMOOTH_PARITY_OUT set, appended to that file as JSON lines (profiles/backend_parity.md is made from them)."""
+import importlib
+import json
+import os
+
+import numpy as np
+import pytest
+
+import smooth_ref as S
+
+pytestmark = pytest.mark.gpu
+PKG = "spatial-temporal-lidar-camera-calibration_amd"
+
+
+@pytest.fixture(scope="module")
+def sm(pkg):
+    return importlib.import_module(PKG + ".smooth")
+
+
+def _note(**kw):
+    print("smooth-figures", json.dumps(kw))
+    p = os.environ.get("IBA_SMOOTH_PARITY_OUT")
+    if p:
+        with open(p, "a") as f:
+            f.write(json.dumps(kw) + "\n")
+
+
+def _device(sm, g, nodes=None, **fields):
+    """the graph appended as the back end does: a node, then the factors that end at it"""
+    s = sm.Smoother(**fields)
+    nodes = g.nodes if nodes is None else nodes
+    for n in nodes:
+        s.add_node(n)
+    for f in range(g.F):
+        if g.fi[f] < 0:
+            s.add_prior(g.fj[f], g.Z[f], g.var[f])
+        else:
+            s.add_between(g.fi[f], g.fj[f], g.Z[f], g.var[f], g.robust[f])
+    return s
+
+
+def _lin_cases():
+    yield "E1", S.case_graph(2, seed=3)
+    for n in (64, 65, 66):
+        yield "E%d" % (n - 1), S.case_graph(n, seed=n, robust_chain=(5, 40))
+    yield "E129", S.case_graph(100, cross=[(i, i + 35 + (i % 5)) for i in range(0, 60, 2)], seed=9)
+    # factors against the chain (stored and cross), a duplicate of a chain factor and of a cross factor, a node of degree 6, the prior on node 5
+    yield "reversed_duplicate_prior5", S.case_graph(16, cross=((8, 1), (8, 12), (14, 8), (10, 11), (11, 10), (8, 12)), seed=4, reverse=(5, 9), prior_node=5)
+
+
+@pytest.mark.parametrize("name,g", list(_lin_cases()), ids=[n for n, _ in _lin_cases()])
+def test_linearise_against_long_double(sm, name, g):
+    s = _device(sm, g, segment=4)
+    a, b = s.linearize(), s.linearize()
+    s.close()
+    for k in ("r", "w", "A", "D", "b"):
+        assert a[k].tobytes() == b[k].tobytes(), k
+    assert a["F"] == b["F"]
+    assert sum(1 for i in g.fi if i >= 0) == {"E1": 1, "E63": 63, "E64": 64, "E65": 65, "E129": 129}.get(name, 21)
+    f64, ld = S.linearize(g.nodes, g), S.linearize(g.nodes, g, dtype=np.longdouble)
+    for k in ("r", "w", "A", "D", "b", "F"):
+        truth = np.asarray(ld[k])
+        dev = float(np.max(np.abs(np.asarray(a[k], np.longdouble) - truth)))
+        own = float(np.max(np.abs(np.asarray(f64[k], np.longdouble) - truth)))
+        ulp = S.EPS * ld["terms"][k]
+        _note(test="linearise", case=name, output=k, device=dev, f64=own, ulp_of_scale=ulp)
+        assert dev <= 4.0 * own + ulp, (name, k, dev, own, ulp)
+
+
+def _rel_residual(H, b, lam, delta):
+    Hl, bl, dl = H.astype(np.longdouble), b.astype(np.longdouble), np.asarray(delta, np.longdouble).reshape(-1)
+    r = Hl @ dl + np.longdouble(lam) * dl - bl
+    return float(np.sqrt(np.sum(r * r))) / float(np.sqrt(np.sum(bl * bl)))
+
+
+# N = 40 at segment 8: separators 0, 8, 16, 24, 32 and the runs between them
+SOLVE_CASES = [("chain", ()), ("cross_inside_one_run", ((10, 13),)), ("cross_between_separators", ((8, 24),)), ("cross_run_to_run_reversed", ((29, 3),))]
+
+
+@pytest.mark.parametrize("name,cross", SOLVE_CASES, ids=[c[0] for c in SOLVE_CASES])
+def test_solve_against_the_dense_solve_of_the_same_system(sm, name, cross):
+    g = S.case_graph(40, cross=cross, seed=1)
+    assert np.all(g.var[0] == 1e-12)          # the prior of the reference is in the system
+    s = _device(sm, g, segment=8)
+    lin = s.linearize()
+    H, b = S.dense_system(g.N, g, lin["A"], lin["b"])
+    assert np.array_equal(np.stack([H[6 * i:6 * i + 6, 6 * i:6 * i + 6] for i in range(g.N)]), lin["D"])     # D is the block diagonal of the same H
+    lam0 = 1e-5 * S.linearize(g.nodes, g)["max_diag_between"]
+    for lam in (lam0, 1.0, 1e6):
+        d1, d2 = s.solve(lam), s.solve(lam)
+        assert d1.tobytes() == d2.tobytes()
+        dev, dense = _rel_residual(H, b, lam, d1), _rel_residual(H, b, lam, S.dense_solve(H, b, lam))
+        _note(test="solve", case=name, lam=lam, device=dev, dense=dense)
+        assert dev <= 8.0 * dense, (name, lam, dev, dense)
+    s.close()
+
+
+# seeds on which the float64 reference and both twins share one trace with margins (found on the CPU; asserted below)
+OPT_CASES = [(40, 2, 43), (130, 3, 4)]
+
+
+def _reference(g):
+    a, lin, sol = S.optimize(g), S.optimize(g, ld="lin"), S.optimize(g, ld="solve")
+    for t in (lin, sol):
+        assert (t["trace"], t["iterations"], t["trials"], t["stop"]) == (a["trace"], a["iterations"], a["trials"], a["stop"])
+    for t in (a, lin, sol):
+        S.check_margins(t)
+    tol = 4.0 * max(float(np.max(np.abs(a["nodes"] - lin["nodes"]))), float(np.max(np.abs(a["nodes"] - sol["nodes"]))))
+    return a, tol
+
+
+@pytest.mark.parametrize("N,loops,seed", OPT_CASES)
+def test_optimise_reproduces_the_reference_run(sm, N, loops, seed):
+    g, loop_ids = S.make_graph(N, loops=loops, false_loops=1, seed=seed)          # the reference's variances
+    ref, tol = _reference(g)
+    assert ref["trace"].count(1) >= 2
+    s = _device(sm, g, segment=32)
+    res = s.update()
+    nodes, weight = s.read()
+    trace = s.trace()
+    s.close()
+    assert trace == ref["trace"]
+    assert (res.iterations, res.trials, res.stop, res.n_nodes, res.n_factors) == (ref["iterations"], ref["trials"], ref["stop"], g.N, g.F)
+    assert abs(res.F - ref["F"]) <= 1e-9 * ref["F"] and abs(res.lambda_ - ref["lam"]) <= 1e-6 * ref["lam"] and abs(res.lambda_start - ref["lam0"]) <= 1e-9 * ref["lam0"]
+    err = float(np.max(np.abs(nodes - ref["nodes"])))
+    werr = float(np.max(np.abs(weight - ref["weight"])))
+    mb_dev, mb_ref = S.max_b_at(nodes, g), ref["max_b"][-2]
+    _note(test="optimise", N=N, seed=seed, pose_error=err, tolerance=tol, weight_error=werr, false_loop_weight=float(weight[loop_ids[-1]]),
+          max_b_at_device_poses=mb_dev, max_b_reference_last_but_one=mb_ref, max_b_reference_final=ref["max_b"][-1], device_max_b=res.max_b,
+          run=(ref["iterations"], ref["trials"], ref["stop"]))
+    assert err <= tol
+    assert mb_dev <= mb_ref
+    assert weight[loop_ids[-1]] < 0.05 and werr <= 1e-9
+    assert np.all(weight[[f for f in range(g.F) if not g.robust[f]]] == 1.0)
+
+
+def test_growth_equals_a_fresh_object(sm):
+    """30 nodes and a loop, an update, 12 more nodes with their odometry and a second loop, an update: byte for byte what a fresh object answers
+    that is given all the factors in the same order and, as start values, the first object's estimates and the new nodes' poses"""
+    g, _ = S.make_graph(42, loops=0, false_loops=0, seed=5)
+    loop = lambda a, b: (a, b, S.rel(g.truth[a], g.truth[b]), S.LOOP_VAR, True)
+    first = S.Graph(g.nodes[:30])
+    for f in range(30):          # the prior and the odometry factors (0, 1) .. (28, 29)
+        first.add(g.fi[f], g.fj[f], g.Z[f], g.var[f], g.robust[f])
+    first.add(*loop(3, 27))
+    s = _device(sm, first, segment=8)
+    r1 = s.update()
+    mid, _ = s.read()
+    assert r1.n_nodes == 30 and r1.trials > 0 and np.max(np.abs(mid - g.nodes[:30])) > 1e-6
+    for n in range(30, 42):
+        s.add_node(g.nodes[n])
+        s.add_between(n - 1, n, g.Z[n], g.var[n])
+    s.add_between(*loop(10, 40))
+    both, _ = s.read()          # before the update: the estimates, then the poses as appended
+    assert np.array_equal(both[:30], mid) and np.array_equal(both[30:], g.nodes[30:])
+    r2 = s.update()
+    grown, w_grown = s.read()
+    t_grown = s.trace()
+    s.close()
+    whole = S.Graph(g.nodes)
+    for f in range(30):
+        whole.add(g.fi[f], g.fj[f], g.Z[f], g.var[f], g.robust[f])
+    whole.add(*loop(3, 27))
+    for n in range(30, 42):
+        whole.add(n - 1, n, g.Z[n], g.var[n])
+    whole.add(*loop(10, 40))
+    f = _device(sm, whole, nodes=both, segment=8)
+    r3 = f.update()
+    fresh, w_fresh = f.read()
+    t_fresh = f.trace()
+    f.close()
+    assert r2.n_nodes == 42 and r2.trials > 0 and t_grown == t_fresh
+    assert grown.tobytes() == fresh.tobytes() and w_grown.tobytes() == w_fresh.tobytes()
+    assert (r2.iterations, r2.trials, r2.stop, r2.F, r2.lambda_) == (r3.iterations, r3.trials, r3.stop, r3.F, r3.lambda_)
+
+
+def test_known_answer_and_optimum_on_the_device(sm):
+    """the linear 4-node chain of smooth_ref.chain4 (every odometry factor absorbs d so2 / (3 so2 + sl2)), and a graph built at its optimum"""
+    d, so2, sl2 = 0.3, 1e-4, 1e-4
+    s = _device(sm, S.chain4(d, so2, sl2), **S.NEVER)
+    s.update()
+    nodes, _ = s.read()
+    s.close()
+    assert np.max(np.abs(np.diff(nodes[:, 0, 3]) - 1.0 - d * so2 / (3 * so2 + sl2))) <= 1e-12 and abs(nodes[0, 0, 3]) <= 1e-12
+    g, _ = S.make_graph(30, loops=0, false_loops=0, seed=3)
+    for a, b in ((2, 20), (7, 28)):
+        g.add(a, b, S.rel(g.nodes[a], g.nodes[b]), S.LOOP_VAR, robust=True)
+    s = _device(sm, g)
+    res = s.update()
+    nodes, _ = s.read()
+    s.close()
+    assert (res.stop, res.trials, res.iterations) == (S.STOP_RIGHT_TERM, 0, 0) and np.array_equal(nodes, g.nodes)

@@ -1,0 +1,229 @@
+"""CPU tier of the robust pose-graph smoother (include/iba_mi355x.h, iba_smooth_*): the numpy restatement tests/smooth_ref.py against independent
+yardsticks (scipy's expm / logm, central differences, a linear known answer), and the argument checks of the C ABI, which need no device — a graph is
+built on the host and the device is opened by the first call that computes."""
+import importlib
+
+import numpy as np
+import pytest
+
+import pgo_ref as P
+import smooth_ref as S
+
+PKG = "spatial-temporal-lidar-camera-calibration_amd"
+THETAS = [0.0, 1e-9, 1e-4, 0.0999, 0.1, 0.1001, 0.5, 2.0, 3.0, 3.14, 3.14159]   # 0.1 = sqrt(SERIES_TH2): at and around the series threshold; near pi
+
+
+def _hat6(x):
+    M = np.zeros((4, 4))
+    M[:3, :3] = S.hat(x[None, :3])[0]
+    M[:3, 3] = x[3:]
+    return M
+
+
+def _xi(rng, theta):
+    d = rng.normal(size=3)
+    return np.concatenate([theta * d / np.linalg.norm(d), rng.normal(size=3)])
+
+
+@pytest.mark.parametrize("theta", THETAS)
+def test_exp_and_log_against_scipy(theta):
+    from scipy.linalg import expm, logm
+    rng = np.random.default_rng(int(theta * 1e6) % 1000)
+    xi = _xi(rng, theta)
+    T = S.exp_se3(xi[None])[0]
+    assert np.max(np.abs(T - expm(_hat6(xi)))) <= 1e-14 * (1.0 + np.max(np.abs(xi)))
+    r = S.log_se3(T[None])[0]
+    assert np.max(np.abs(r - xi)) <= 1e-13 if theta > 3.1 else np.max(np.abs(r - xi)) <= 4e-15
+    if 1e-6 < theta < 3.1:          # logm loses digits at both ends; the round trip above covers them
+        L = np.real(logm(T))
+        assert np.max(np.abs(np.array([L[2, 1], L[0, 2], L[1, 0], L[0, 3], L[1, 3], L[2, 3]]) - r)) <= 1e-12
+
+
+def test_series_and_closed_form_agree_at_the_threshold():
+    """Just below the threshold the float64 series is exact to rounding. At it the closed forms cancel: c = (t - s) / t^3 loses 6 eps / t^2, e and c2
+    12 eps / t^2, k4 — through 3 (c - 1/6) / t^2 — 9 eps c / (t^4 k4) = 4e-10. They enter r and J multiplied by t^2 |t| (c, e), t^2 and t^3 |upsilon|
+    (c2, k4): below eps of the result in every case."""
+    x, eps = S.SERIES_TH2, S.EPS
+    bound = dict(a=4 * eps, b=4 * eps, c=6 * eps / x, e=12 * eps / x, c2=12 * eps / x, k4=4e-10)
+    for at, tol in ((x * (1 - 1e-12), {k: 4 * eps for k in bound}), (x, bound)):
+        k64, k80 = S.coeffs(np.array([at])), S.coeffs(np.array([at], np.longdouble))
+        for name in k64:
+            assert abs(float(k64[name][0]) - float(k80[name][0])) <= tol[name] * abs(float(k80[name][0])), (at, name)
+    lo, hi = S.coeffs(np.array([x * (1 - 1e-12)], np.longdouble)), S.coeffs(np.array([x], np.longdouble))
+    for name in lo:          # the two branches meet: the polynomials' truncation is far below a 1e-12 step of theta^2
+        assert abs(float(lo[name][0] - hi[name][0])) <= 1e-13, name
+
+
+def _residual_ld(Pi, Pj, Z, di, dj, prior):
+    dt = np.longdouble
+    Pj2 = S.exp_se3(dj[None])[0] @ Pj.astype(dt)
+    if prior:
+        M = P.mul12(P.inv12(Z[None].astype(dt)), Pj2[None])
+    else:
+        Pi2 = S.exp_se3(di[None])[0] @ Pi.astype(dt)
+        M = P.mul12(P.mul12(P.inv12(Z[None].astype(dt)), P.inv12(Pi2[None])), Pj2[None])
+    return S.log_se3(M)[0]
+
+
+@pytest.mark.parametrize("prior", [False, True], ids=["between", "prior"])
+@pytest.mark.parametrize("theta", THETAS)
+def test_jacobian_against_central_differences(theta, prior):
+    """differences in long double with h = 1e-7: truncation 1e-14, rounding 1e-19 / 1e-7 — the yardstick is good to 1e-11"""
+    rng = np.random.default_rng(7 + int(theta * 1e6) % 1000)
+    xi = _xi(rng, theta)
+    Pi = S.exp_se3(rng.normal(size=(1, 6)))[0]
+    Pj = S.exp_se3(rng.normal(size=(1, 6)) * np.array([1, 1, 1, 5, 5, 5]))[0]
+    base = Pj if prior else S.rel(Pi, Pj)
+    Z = base.copy() if theta == 0.0 else base @ np.linalg.inv(S.exp_se3(xi[None])[0])    # Z^-1 [Pi^-1] Pj = Exp(xi); theta 0: r = 0
+    Z[3] = [0, 0, 0, 1]
+    g = S.Graph(np.stack([Pi, Pj]), [(-1 if prior else 0, 1, Z, np.ones(6), False)])
+    r, J, _, _ = S.factor_terms(g.nodes, g)
+    if theta == 0.0:
+        assert np.max(np.abs(r)) <= 1e-14
+    else:
+        assert np.max(np.abs(r[0] - xi)) <= (1e-12 if theta > 3.1 else 2e-14)
+    h = np.longdouble(1e-7)
+    Jj, Ji = np.zeros((6, 6)), np.zeros((6, 6))
+    z = np.zeros(6, np.longdouble)
+    for k in range(6):
+        e = z.copy(); e[k] = h
+        Jj[:, k] = ((_residual_ld(Pi, Pj, Z, z, e, prior) - _residual_ld(Pi, Pj, Z, z, -e, prior)) / (2 * h)).astype(np.float64)
+        if not prior:
+            Ji[:, k] = ((_residual_ld(Pi, Pj, Z, e, z, prior) - _residual_ld(Pi, Pj, Z, -e, z, prior)) / (2 * h)).astype(np.float64)
+    scale = np.max(np.abs(Jj))
+    assert np.max(np.abs(J[0] - Jj)) <= 1e-10 * scale
+    if not prior:
+        assert np.max(np.abs(Ji + Jj)) <= 2e-10 * scale          # dr / d delta_i = -J
+
+
+@pytest.mark.parametrize("d,so2,sl2", [(0.3, 1e-4, 1e-4), (-0.2, 1e-4, 0.5), (0.05, 1e-6, 1e-4)])
+def test_known_answer_of_the_linear_chain(d, so2, sl2):
+    """An LM step is accepted only when F decreases, and F near its minimum F* is flat: positions are resolved to sqrt(eps F* so2), 1e-13 and
+    below in these cases."""
+    res = S.optimize(S.chain4(d, so2, sl2), S.options(**S.NEVER))
+    x = res["nodes"][:, 0, 3]
+    want = d * so2 / (3 * so2 + sl2)
+    assert np.max(np.abs(np.diff(x) - 1.0 - want)) <= 1e-12
+    assert abs(x[0]) <= 1e-12 and np.max(np.abs(res["nodes"][:, :3, :3] - np.eye(3))) <= 1e-12 and np.max(np.abs(res["nodes"][:, 1:3, 3])) <= 1e-12
+
+
+def test_a_graph_at_its_optimum_stops_on_the_right_term_without_a_trial():
+    g, _ = S.make_graph(30, loops=0, false_loops=0, seed=3)
+    for a, b in ((2, 20), (7, 28)):          # loops that agree with the poses: nothing to do
+        g.add(a, b, S.rel(g.nodes[a], g.nodes[b]), S.LOOP_VAR, robust=True)
+    res = S.optimize(g)
+    assert (res["stop"], res["trials"], res["iterations"], res["trace"]) == (S.STOP_RIGHT_TERM, 0, 0, [])
+    assert np.array_equal(res["nodes"], g.nodes)
+
+
+def test_the_issues_prototype_shapes_converge_and_turn_the_false_loop_off():
+    for N in (40, 130):
+        g, loops = S.make_graph(N, loops=2, false_loops=1, seed=1)
+        res = S.optimize(g)
+        assert res["stop"] in (S.STOP_INCREMENT, S.STOP_RESIDUAL_INCREMENT, S.STOP_RIGHT_TERM) and 0 not in res["trace"]
+        assert res["weight"][loops[-1]] < 0.05 and np.all(res["weight"][loops[:-1]] > 0.9)
+        assert res["F"] < S.linearize(g.nodes, g)["F"]
+
+
+# ---- the C ABI without a device ----
+@pytest.fixture(scope="module")
+def sm(pkg):
+    return importlib.import_module(PKG + ".smooth")
+
+
+def test_abi_version_is_unchanged_and_the_symbols_are_exported(pkg):
+    lib = pkg.load_library()
+    assert lib.iba_abi_version() == 4
+    for name in ("iba_smooth_create", "iba_smooth_destroy", "iba_smooth_last_error", "iba_default_smooth_options", "iba_smooth_add_node", "iba_smooth_add_prior",
+                 "iba_smooth_add_between", "iba_smooth_linearize", "iba_smooth_solve", "iba_smooth_update", "iba_smooth_read"):
+        getattr(lib, name)
+
+
+def test_default_options(sm):
+    o = sm.smooth_options()
+    import ctypes as C
+    assert o.struct_size == C.sizeof(sm.IbaSmoothOptions)
+    assert (o.max_iteration, o.max_iteration_lm, o.segment) == (100, 20, 128)
+    assert (o.min_relative_increment, o.min_relative_residual_increment, o.min_right_term, o.min_residual) == (1e-6,) * 4
+    assert (o.upper_scale_factor, o.lower_scale_factor) == (2.0 / 3.0, 1.0 / 3.0)
+    assert sm._lib().iba_default_smooth_options(None) == 1
+
+
+def _bad(sm, fn, needle):
+    with pytest.raises(sm.IbaError) as e:
+        fn()
+    assert e.value.status == 1 and needle in str(e.value), str(e.value)
+
+
+def test_create_checks(sm):
+    import ctypes as C
+    L = sm._lib()
+    out = C.c_void_p(None)
+    assert L.iba_smooth_create(None, 0, C.byref(out)) == 1 and b"opt is NULL" in L.iba_smooth_last_error(None)
+    assert L.iba_smooth_create(C.byref(sm.smooth_options()), 0, None) == 1 and b"out is NULL" in L.iba_smooth_last_error(None)
+    _bad(sm, lambda: sm.Smoother(struct_size=8), "struct_size")
+    _bad(sm, lambda: sm.Smoother(segment=0), "segment")
+    _bad(sm, lambda: sm.Smoother(max_iteration=-1), "max_iteration")
+    _bad(sm, lambda: sm.Smoother(min_residual=float("nan")), "not finite")
+    _bad(sm, lambda: sm.Smoother(device=-1), "device")
+    assert L.iba_smooth_last_error(None) is not None
+    L.iba_smooth_destroy(None)
+
+
+def test_graph_building_checks(sm):
+    import ctypes as C
+    s = sm.Smoother()
+    L, I, v = s.lib, np.eye(4), np.ones(6)
+    assert L.iba_smooth_last_error(s.h) == b""
+    assert L.iba_smooth_add_node(None, sm._p(I.reshape(-1))) == 1 and L.iba_smooth_add_node(s.h, None) == 1
+    bad_row, nan = I.copy(), I.copy()
+    bad_row[3, 3] = 2.0
+    nan[0, 3] = np.nan
+    _bad(sm, lambda: s.add_node(bad_row), "last row")
+    _bad(sm, lambda: s.add_node(nan), "not finite")
+    _bad(sm, lambda: s.add_prior(0, I, v), "outside")            # no node yet
+    assert s.add_node(I) == 0 and s.add_node(I) == 1
+    for fn, who in ((lambda Z, var: s.add_prior(0, Z, var), "iba_smooth_add_prior"), (lambda Z, var: s.add_between(0, 1, Z, var), "iba_smooth_add_between")):
+        _bad(sm, lambda: fn(bad_row, v), "last row")
+        _bad(sm, lambda: fn(nan, v), "not finite")
+        for k, x in ((0, 0.0), (3, -1.0), (5, np.inf), (2, np.nan)):
+            var = v.copy()
+            var[k] = x
+            _bad(sm, lambda: fn(I, var), "var6[%d]" % k)
+        with pytest.raises(sm.IbaError) as e:
+            fn(nan, v)
+        assert who in str(e.value)
+    assert L.iba_smooth_add_prior(s.h, 0, None, sm._p(v)) == 1 and L.iba_smooth_add_prior(s.h, 0, sm._p(I.reshape(-1)), None) == 1
+    assert L.iba_smooth_add_between(s.h, 0, 1, None, sm._p(v), 0) == 1 and L.iba_smooth_add_between(None, 0, 1, sm._p(I.reshape(-1)), sm._p(v), 0) == 1
+    _bad(sm, lambda: s.add_prior(2, I, v), "outside")
+    _bad(sm, lambda: s.add_prior(-1, I, v), "outside")
+    _bad(sm, lambda: s.add_between(0, 2, I, v), "outside")
+    _bad(sm, lambda: s.add_between(-1, 1, I, v), "outside")
+    _bad(sm, lambda: s.add_between(-2, 1, I, v), "outside")
+    _bad(sm, lambda: s.add_between(1, 1, I, v), "i == j")
+    assert s.F == 0
+    s.add_prior(1, I, v)
+    s.add_between(1, 0, I, v, robust=True)
+    # what needs no device: the estimates as appended, weights of 1; the checks of read, solve, update, linearize
+    nodes, w = s.read()
+    assert np.array_equal(nodes, np.stack([I, I])) and np.array_equal(w, [1.0, 1.0])
+    _bad(sm, lambda: s.read(1, 2), "outside")
+    _bad(sm, lambda: s.read(-1, 1), "outside")
+    assert L.iba_smooth_read(None, 0, 0, None, None) == 1 and L.iba_smooth_read(s.h, 0, 2, None, None) == 0
+    assert L.iba_smooth_solve(s.h, C.c_double(1.0), None) == 1 and L.iba_smooth_solve(None, C.c_double(1.0), None) == 1
+    d = np.zeros((2, 6))
+    assert L.iba_smooth_solve(s.h, C.c_double(-1.0), sm._p(d)) == 1 and L.iba_smooth_solve(s.h, C.c_double(np.nan), sm._p(d)) == 1
+    assert L.iba_smooth_solve(s.h, C.c_double(1.0), sm._p(d)) == 5          # IBA_ERR_STATE: nothing was linearised
+    assert L.iba_smooth_update(s.h, None) == 1 and L.iba_smooth_update(None, None) == 1
+    assert L.iba_smooth_linearize(None, None, None, None, None, None, None) == 1
+    n = C.c_int32(-1)
+    buf = np.zeros(4, np.uint8)
+    for args in ((None, None, 0, C.byref(n)), (s.h, None, 0, None), (s.h, sm._p(buf), -1, C.byref(n)), (s.h, None, 2, C.byref(n))):
+        assert L.iba_debug_smooth_trace(*args) == 1
+    assert L.iba_debug_smooth_trace(s.h, None, 0, C.byref(n)) == 0 and n.value == 0          # no update yet: an empty trace
+    s.close()
+    empty = sm.Smoother()
+    with pytest.raises(sm.IbaError) as e:
+        empty.update()
+    assert e.value.status == 5 and "no node" in str(e.value)
+    empty.close()
