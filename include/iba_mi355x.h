@@ -1030,6 +1030,87 @@ const iba_smooth_result* iba_backend_result_updates(const iba_backend_result* r)
  * next sub-map is posed by); NULL without the option or for u out of range. */
 const double* iba_backend_result_update_poses12(const iba_backend_result* r, int32_t u);
 
+/*
+ * ---- Scan-to-image projection: z-buffered depth, visibility, colours [what a caller does with a calibrated extrinsic: the README pictures
+ * doc/proj_XX_gt.png / proj_XX_pred.png of the reference, a sparse depth image per camera frame, a colour per LiDAR point] ----
+ * A JOB is one (local frame of the handle, extrinsic x) pair; the J jobs of a call may repeat frames, so one frame can be rendered under the initial,
+ * the ground-truth and the optimised extrinsic. Everything is computed on the device and stays there until an accessor copies one job's product down.
+ * All arithmetic is IEEE f64 without contraction, all reductions are integer (minima and counts): no floating-point atomics, two calls give the same
+ * bytes, and tests/project_ref.py restates every rule in numpy and is compared byte for byte.
+ *
+ *   P1 pose.       R, t = Sim3Exp(x) on the host (csrc/iba_host_math.hpp), as the evaluator forms them. The scale entry x[6] does not enter: it scales
+ *                  camera translations, not LiDAR points. The 12 doubles (R | t, row-major 3 x 4) are kept per job: iba_projection_pose.
+ *   P2 transform.  The point's float32 coordinates are widened; q_k = ((R_k0 x + R_k1 y) + R_k2 z) + t_k. A point with a non-finite coordinate is
+ *                  skipped and counted (n_skipped).
+ *   P3 projection. IN_FRONT iff z_min < q_z < z_max, both strict. u = (fx q_x + cx q_z) / q_z, v = (f q_y + cy q_z) / q_z with f = fy, or fx under
+ *                  v_focal_is_fx (the evaluator's rule, iba_global.cpp:73). The quotients come from the evaluator's device helper (div2,
+ *                  csrc/iba_kernels.hpp), which tests/test_gpu_division.py pins as equal to plain division. INSIDE iff 0 <= u < W && 0 <= v < H. The
+ *                  pixel is (iu, iv) = (floor(u), floor(v)). The depth is z32 = q_z rounded to float32.
+ *   P4 z-buffer.   key = (bits of z32) << 32 | original point index — the point's position in the caller's scan, not its kd-leaf position. z32 is
+ *                  not negative, so keys order like depths and a tie goes to the lowest index. Every INSIDE point lowers, by a 64-bit integer atomic
+ *                  min, the key of every pixel of its footprint [iu - r, iu + r] x [iv - r, iv + r] clipped to the image (r = splat). Empty = all ones.
+ *   P5 images.     Depth = the winning key's z32, 0 for an empty pixel; index = its point, 0xFFFFFFFF for an empty pixel (row-major H x W).
+ *                  n_pixels = the pixels that hold a key.
+ *   P6 visibility. An INSIDE point is VISIBLE iff (double)z32 <= (double)zwin * (1.0 + occlusion_tol), zwin the depth of the final key at the point's
+ *                  own centre pixel (a point is always inside its own footprint, so zwin exists).
+ *   P7 colour.     For a VISIBLE point: bilinear at (u, v), pixel centres at integer coordinates. x0 = floor(u), x1 = min(x0 + 1, W - 1), a = u - x0,
+ *                  likewise y0, y1, b from v. Per channel c = ((1 - a) * ((1 - b) * c00 + b * c01)) + (a * ((1 - b) * c10 + b * c11)), the first
+ *                  index of c being x; the byte is floor(c + 0.5). A point that is not VISIBLE gets 0 0 0.
+ *   P8 overlay.    The output is the input image, or black for NULL; a pixel that holds a key takes iba_project_gradient(zn),
+ *                  zn = min(max((z - z_near) / (z_far - z_near), 0), 1), z the pixel's depth widened. The gradient is this five-stop piecewise-linear
+ *                  ramp: zn = 0 blue (0, 0, 255), 0.25 cyan (0, 255, 255), 0.5 green (0, 255, 0), 0.75 yellow (255, 255, 0), 1 red (255, 0, 0);
+ *                  s = 4 zn, k = min(floor(s), 3), f = s - k, c = (1 - f) * stop_k + f * stop_(k+1) per channel, the byte floor(c + 0.5).
+ *                  iba_project_gradient clamps zn to [0, 1] itself (NaN: 0).
+ *   P9 counts.     All counts are integers, so every reduction order gives the same value.
+ *
+ * A point's record (iba_projection_points): flags = IN_FRONT 1 | INSIDE 2 | VISIBLE 4; (u, v) and z32 are as computed for an IN_FRONT point and 0
+ * otherwise (skipped points included).
+ * MEMORY: the result keeps 8 bytes per pixel (depth, index) and 24 bytes per point of every job. The z-buffer's keys (8 bytes per pixel) live only
+ * while a CHUNK of consecutive jobs runs: the jobs of a call are cut so that a chunk's key, depth and index images (16 bytes per pixel and job) stay
+ * under IBA_PROJECT_BUDGET_BYTES, or under a quarter of the device memory free at the call where that is less; a chunk holds at least one job. A chunk
+ * boundary changes no byte. The result does not depend on the handle once iba_project_run has returned.
+ * ERRORS, all IBA_ERR_INVALID_ARG with a message (iba_project_last_error, per thread) BEFORE the device is touched: a NULL argument or a wrong
+ * struct_size; J < 1 or a frame outside the handle's local frames; a non-finite x or option, splat outside 0..4, occlusion_tol < 0, not
+ * 0 < z_min < z_max, not z_near < z_far, v_focal_is_fx not 0 / 1; a camera that is partly zero, not finite, with fx, fy <= 0 or W, H not whole, or
+ * W H outside [1, 2^26]; a frame without intrinsics (every frame of a scans-only handle of iba_submap_handle) while camera is all 0 — the message names the
+ * frame; a job index outside the result.
+ */
+#define IBA_PROJECT_BUDGET_BYTES (1ull << 30)
+#define IBA_PROJECT_IN_FRONT 1u
+#define IBA_PROJECT_INSIDE   2u
+#define IBA_PROJECT_VISIBLE  4u
+typedef struct iba_project_options {
+    int32_t struct_size;     /* sizeof(iba_project_options) */
+    int32_t splat;           /* 1: half-width r of the square footprint, 0..4 */
+    double  occlusion_tol;   /* 0.02: relative depth slack of P6, finite and >= 0 */
+    double  z_min, z_max;    /* 0.1, 120: depth range in metres, 0 < z_min < z_max */
+    int32_t v_focal_is_fx;   /* 0; 1 reproduces the evaluator's rule for v (fx for both, iba_global.cpp:73) */
+    int32_t reserved;
+    double  camera[6];       /* fx, fy, cx, cy, W, H. All 0: the frame's intrinsics; otherwise it overrides them for every job */
+    double  z_near, z_far;   /* 2, 60: range of the overlay's gradient */
+} iba_project_options;
+typedef struct iba_project_counts {
+    int64_t n_points, n_skipped, n_in_front, n_inside, n_visible, n_pixels;
+} iba_project_counts;
+typedef struct iba_projection iba_projection;
+iba_status iba_default_project_options(iba_project_options* opt);
+const char* iba_project_last_error(void);   /* never NULL; of this thread's last iba_project_* / iba_projection_* call that failed */
+/* x7: J x 7 (the evaluator's x), frames: J local frames. *out is NULL on failure; release it with iba_projection_free. The four kernels (splat,
+ * resolve, visible, and per accessor colourise / overlay) are csrc/iba_project_kernels.hpp; the run launches on the handle's stream and synchronises once. */
+iba_status iba_project_run(iba_handle* h, const double* x7, const int32_t* frames, int32_t J, const iba_project_options* opt, iba_projection** out);
+void iba_projection_free(iba_projection* p);
+int32_t iba_projection_n_jobs(const iba_projection* p);                                    /* 0 for NULL */
+iba_status iba_projection_size(const iba_projection* p, int32_t job, int32_t* W, int32_t* H);
+iba_status iba_projection_pose(const iba_projection* p, int32_t job, double Rt12[12]);     /* the R | t the device used (P1) */
+iba_status iba_projection_counts(const iba_projection* p, int32_t job, iba_project_counts* counts);
+iba_status iba_projection_depth(iba_projection* p, int32_t job, float* depth_HxW);
+iba_status iba_projection_index(iba_projection* p, int32_t job, uint32_t* index_HxW);
+/* per point in the ORIGINAL order of the frame's scan; any of the three may be NULL */
+iba_status iba_projection_points(iba_projection* p, int32_t job, double* uv_nx2, float* z_n, uint8_t* flags_n);
+iba_status iba_projection_colorize(iba_projection* p, int32_t job, const uint8_t* rgb_HxWx3, uint8_t* point_rgb_nx3);   /* P7: one launch */
+iba_status iba_projection_overlay(iba_projection* p, int32_t job, const uint8_t* rgb_HxWx3 /* may be NULL: black */, uint8_t* out_HxWx3);   /* P8: one launch */
+iba_status iba_project_gradient(double zn, uint8_t rgb[3]);                                /* host only: the overlay's palette */
+
 /* The ABI version the LIBRARY was built with (IBA_ABI_VERSION of its header). iba_params carries no struct_size: a caller compiled against
  * an older header would pass a shorter struct. Callers compare iba_abi_version() with their own IBA_ABI_VERSION before iba_create(). */
 int32_t iba_abi_version(void);

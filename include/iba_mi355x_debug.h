@@ -42,6 +42,11 @@
  *                                                         wait for its stream before the group is declared broken
  *   IBA_PGO_MAX_SEP                                       the separator cap of iba_pgo_create / iba_pgo_plan in place of IBA_PGO_MAX_SEPARATORS (1 .. 1024; tests reach
  *                                                         the doubling of K at a small graph)
+ *   IBA_PROJECT_BUDGET                                    bytes a chunk of iba_project_run's jobs may take (key, depth and index images: 16 per pixel and job) in
+ *                                                         place of IBA_PROJECT_BUDGET_BYTES and the free-memory rule, read at every call (tests reach the
+ *                                                         split of a call at small images; same results)
+ *   IBA_PROJECT_TIMING                                    set: iba_project_run and the colourise / overlay accessors record HIP events around their kernels
+ *                                                         (iba_debug_projection_kernel_ms; tools/project_bench.py); same results
  *   IBA_GROUP_REDUCE_HOST (flag of iba_group_create_ex, not a variable), IBA_DEBUG_FAIL_RANK / IBA_DEBUG_FAIL_PHASE: inject one
  *                                                         failure into a group's evaluation (tests of the fail-not-hang path)
  */
@@ -207,6 +212,17 @@ iba_status iba_debug_pgo_trace(iba_pgo* pg, uint8_t* trials, int32_t cap, int32_
 /* debug: the LM trials of the last iba_smooth_update in order, one byte each: 1 accepted, 0 rejected, 2 the trial that stopped on the increment. Up to
  * cap bytes are written; *n = the number of trials. */
 iba_status iba_debug_smooth_trace(iba_smooth* s, uint8_t* trials, int32_t cap, int32_t* n);
+
+/* debug, host only (no device): the argument checks of iba_project_run on a stand-in for the handle — n_frames local frames with intrinsics6
+ * (n_frames x 6: fx, fy, cx, cy, W, H), NULL for a scans-only handle. The status and message (iba_project_last_error) iba_project_run would give. */
+iba_status iba_debug_project_validate(int32_t n_frames, const double* intrinsics6, const double* x7, const int32_t* frames, int32_t J, const iba_project_options* opt);
+/* debug, host only: a result of n_jobs empty jobs without device buffers (the accessors' job-index checks); release it with iba_projection_free. */
+iba_status iba_debug_project_stub(int32_t n_jobs, iba_projection** out);
+/* debug: the chunks the jobs of the call behind p were cut into (IBA_PROJECT_BUDGET); 0 for NULL */
+int32_t iba_debug_projection_chunks(const iba_projection* p);
+/* debug: with IBA_PROJECT_TIMING set at the call, HIP-event times (ms) of the kernels behind p: [0] splat, [1] resolve, [2] visible, each summed over
+ * the chunks of iba_project_run; [3] the last iba_projection_colorize's launch, [4] the last iba_projection_overlay's. Zeros without the variable. */
+iba_status iba_debug_projection_kernel_ms(const iba_projection* p, float ms[5]);
 
 #ifdef __cplusplus
 }

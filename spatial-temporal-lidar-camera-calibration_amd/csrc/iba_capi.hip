@@ -43,6 +43,7 @@ const char* debug_env(const char* name) {   // (read at every handle creation: a
 #include "iba_floam_kernels.hpp"
 #include "iba_floam_map_kernels.hpp"
 #include "iba_floam_odom_kernels.hpp"
+#include "iba_project_kernels.hpp"
 #include "iba_icp_math.hpp"
 #include "iba_types.hpp"
 
@@ -220,7 +221,8 @@ struct iba_handle {
     bool ring_used[kRing] = {false, false, false, false};
     int ring_next = 0;
     std::vector<FrameHdr> h_frames;
-    std::vector<uint64_t> h_kp_off;       // local frame -> kp offset (K+1)
+    bool scans_only = false;              // built by scan_handle_from_device (iba_index_host.hpp): no keypoints, placeholder intrinsics (iba_project_run asks)
+    std::vector<uint64_t> h_kp_off;      // local frame -> kp offset (K+1)
     std::vector<uint32_t> h_kp_ext;       // internal (Morton) keypoint id -> reference keypoint id
     std::vector<float> h_kp_uv;           // (u, v) of every keypoint in internal order: the reject bitmap is rebuilt from it when max_pixel_dist changes
     // iba_icp_* (iba_icp_host.hpp): the bounding box of every local frame's scan ([frame][8]: min xyz, -, max xyz, -) and the work buffers of a pass (PassWork, iba_flat_pass.hpp)
@@ -1147,6 +1149,11 @@ iba_status eval_cost_partial_impl(iba_handle* h, const double* x, int B, double*
 }
 
 }  // namespace
+
+namespace iba {
+// what iba_project_run (iba_project.hip) reads of a handle
+ProjectView project_view(const iba_handle* h) { return ProjectView{h->device, h->stream, h->n_frames, h->h_frames.data(), h->pts4.p, h->scans_only}; }
+}  // namespace iba
 
 namespace {
 // iba_submap_handle (iba_index_host.hpp): where the scans of a new handle come from when they are already on the device

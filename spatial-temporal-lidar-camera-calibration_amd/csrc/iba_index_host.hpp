@@ -134,6 +134,7 @@ iba_status scan_handle_from_device(iba_handle* src, const double* xyz, const std
     iba_handle* h = nullptr;
     const iba_status s = create_impl(&d, params, src->device, 0, M, nullptr, &from, &h);
     if (s != IBA_OK) return fail(src, s, g_create_error.rfind(who, 0) == 0 ? g_create_error : who + g_create_error);
+    h->scans_only = true;
     *out = h;
     return IBA_OK;
 }

@@ -30,4 +30,21 @@ const char* debug_env(const char* name);
 // candidates one launch chain takes on this handle (iba_create_options.max_chain_batch; IBA_MAX_BATCH while the planes are refitted per evaluation)
 int chain_capacity(const iba_handle* h);
 
+// ---- the scan-to-image projection (iba_project.hip): what it reads of a handle, and the launches of iba_project_kernels.hpp ----
+namespace project { struct ProjJob; struct ProjRec; }
+struct ProjectView {
+    int device; hipStream_t stream;
+    int n_frames; const FrameHdr* frames;   // the host copy of the local frames' headers (points, offsets, intrinsics)
+    const float4* pts4;                     // (x, y, z, original index bits) per tree position, on the device
+    bool scans_only;                        // a handle of scans alone (iba_submap_handle and its kin): the intrinsics in its headers are placeholders
+};
+ProjectView project_view(const iba_handle* h);
+hipError_t project_splat(hipStream_t st, const float4* pts4, const project::ProjJob* d_jobs, int nj, uint32_t bias, uint32_t n_blocks, int r, double z_min, double z_max,
+                         unsigned long long* keys, project::ProjRec* recs, uint32_t* cnt);
+hipError_t project_resolve(hipStream_t st, const project::ProjJob* d_jobs, int nj, uint32_t bias, uint32_t n_blocks, const unsigned long long* keys, float* depth, uint32_t* index, uint32_t* cnt);
+// rgb == nullptr: P6 alone, n_visible counted; else one job's points coloured as well (cnt unused)
+hipError_t project_visible(hipStream_t st, const project::ProjJob* d_jobs, int nj, uint32_t bias, uint32_t n_blocks, double tol, project::ProjRec* recs, const float* depth, uint32_t* cnt,
+                           const uint8_t* rgb, uint8_t* point_rgb);
+hipError_t project_overlay(hipStream_t st, const project::ProjJob* d_job, uint32_t n_blocks, const float* depth, const uint32_t* index, const uint8_t* rgb, uint8_t* out, double z_near, double z_far);
+
 }  // namespace iba

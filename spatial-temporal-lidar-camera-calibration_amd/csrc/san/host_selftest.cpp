@@ -20,6 +20,7 @@
 #include "../../../include/iba_mi355x_debug.h"
 #include "../iba_icp_math.hpp"
 #include "../iba_lm.hpp"
+#include "../iba_project_host.hpp"
 
 static int failures = 0;
 #define CHECK(c) do { if (!(c)) { std::fprintf(stderr, "host_selftest: %s failed at line %d\n", #c, __LINE__); ++failures; } } while (0)
@@ -214,6 +215,35 @@ static void dataset(const std::string& root, const std::string& scratch) {
     }
 }
 
+// the host half of the scan-to-image projection (iba_project_host.hpp): every refusal of the validation, the cut into chunks, the palette
+static void projection_host() {
+    namespace prj = iba::project;
+    iba_project_options o;
+    prj::default_options(o);
+    const double intr[12] = {30, 24, 19.5, 11.5, 40, 24, 0, 0, 0, 0, 0, 0};
+    double x[14] = {0};
+    const int32_t fr[2] = {0, 0}, bad_fr[2] = {0, 2}, no_cam[2] = {0, 1};
+    CHECK(prj::validate(&o, x, fr, 2, 2, intr).empty());
+    CHECK(!prj::validate(nullptr, x, fr, 2, 2, intr).empty() && !prj::validate(&o, nullptr, fr, 2, 2, intr).empty() && !prj::validate(&o, x, nullptr, 2, 2, intr).empty());
+    CHECK(!prj::validate(&o, x, fr, 0, 2, intr).empty() && !prj::validate(&o, x, bad_fr, 2, 2, intr).empty());
+    CHECK(prj::validate(&o, x, no_cam, 2, 2, intr).find("frame 1 has no intrinsics") != std::string::npos);
+    CHECK(prj::validate(&o, x, fr, 2, 2, nullptr).find("frame 0 has no intrinsics") != std::string::npos);
+    x[11] = NAN; CHECK(prj::validate(&o, x, fr, 2, 2, intr).find("job 1: x[4]") != std::string::npos); x[11] = 0.0;
+    iba_project_options b = o; b.splat = 5; CHECK(!prj::validate(&b, x, fr, 2, 2, intr).empty());
+    b = o; b.z_min = 0.0; CHECK(!prj::validate(&b, x, fr, 2, 2, intr).empty());
+    b = o; b.camera[4] = 40.0; CHECK(prj::validate(&b, x, fr, 2, 2, intr).find("partly zero") != std::string::npos);
+    b = o; std::memcpy(b.camera, intr, sizeof(b.camera)); CHECK(prj::validate(&b, x, no_cam, 2, 2, nullptr).empty());
+    b.camera[4] = 8193.0; b.camera[5] = 8192.0; CHECK(!prj::validate(&b, x, fr, 2, 2, intr).empty());
+    const std::vector<uint64_t> px = {960, 960, 0, 960, 5000, 960};
+    CHECK((prj::cut_chunks(px, 2 * 16 * 960) == std::vector<int32_t>{0, 3, 4, 5, 6}));      // (an empty job costs nothing; a job beyond the budget runs alone)
+    CHECK((prj::cut_chunks(px, 1) == std::vector<int32_t>{0, 1, 2, 4, 5, 6}) && (prj::cut_chunks(px, ~0ull >> 1) == std::vector<int32_t>{0, 6}));
+    CHECK((prj::cut_chunks({}, 100) == std::vector<int32_t>{0, 0}));
+    uint8_t c[3];
+    const double zs[] = {-1.0, 0.0, 0.125, 0.25, 0.5, 0.75, 0.999999, 1.0, 2.0, NAN, INFINITY};
+    const int want[][3] = {{0, 0, 255}, {0, 0, 255}, {0, 128, 255}, {0, 255, 255}, {0, 255, 0}, {255, 255, 0}, {255, 0, 0}, {255, 0, 0}, {255, 0, 0}, {0, 0, 255}, {255, 0, 0}};
+    for (size_t i = 0; i < sizeof(zs) / sizeof(zs[0]); ++i) { prj::gradient(zs[i], c); CHECK(c[0] == want[i][0] && c[1] == want[i][1] && c[2] == want[i][2]); }
+}
+
 int main(int argc, char** argv) {
     char tmpl[] = "/tmp/iba_san_XXXXXX";
     const char* scratch = mkdtemp(tmpl);
@@ -221,6 +251,7 @@ int main(int argc, char** argv) {
     mads_and_whitening();
     lm_step_quadratic();
     handeye();
+    projection_host();
     small_files(scratch);
     if (argc > 1) dataset(argv[1], scratch);
     (void)!system((std::string("rm -rf '") + scratch + "'").c_str());
