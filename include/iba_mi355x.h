@@ -1111,6 +1111,109 @@ iba_status iba_projection_colorize(iba_projection* p, int32_t job, const uint8_t
 iba_status iba_projection_overlay(iba_projection* p, int32_t job, const uint8_t* rgb_HxWx3 /* may be NULL: black */, uint8_t* out_HxWx3);   /* P8: one launch */
 iba_status iba_project_gradient(double zn, uint8_t rgb[3]);                                /* host only: the overlay's palette */
 
+/*
+ * ---- ORB feature extraction: pyramid, FAST, oriented BRIEF [the camera side's first brick: ORBextractor::operator(), src/orb_slam/src/ORBextractor.cc
+ * of the reference, for a batch of 8-bit images that may differ in size] ----
+ * Nearly everything is per-pixel integer work; tests/orb_ref.py restates every rule in numpy and the device results are compared byte for byte. Unless
+ * stated otherwise float arithmetic is float32, every operation rounded, no contraction; rint = round half to even (cvRound).
+ *
+ *   O1 levels.     sf[0] = 1, sf[l] = sf[l-1] * scale_factor, inv[l] = 1 / sf[l]; Wl = rint((float)W * inv[l]), Hl likewise; a level with Wl < 1 or
+ *                  Hl < 1 is empty. Features per level as the constructor (:436-446): factor = 1 / scale_factor, d = n_features * (1 - factor) /
+ *                  (1 - (float)pow((double)factor, (double)n_levels)); level l < L - 1 takes rint(d), then d *= factor; the last takes what is left, at
+ *                  least 0. 2000 / 1.2 / 8 gives 434 362 302 251 209 175 145 122.
+ *   O2 resize.     Level l from level l - 1. Per axis: scale = (double)src / dst; f = (float)((d + 0.5) * scale - 0.5); s = floor(f); f -= s; s < 0:
+ *                  s = 0, f = 0; s >= src - 1: s = src - 1, f = 0; c1 = rint(f * 2048), c0 = 2048 - c1. The host builds these tables; the kernel is
+ *                  integer: S = p[s] * c0 + p[s + 1] * c1 per source row (p[s + 1] is not read where s = src - 1: its weight is 0),
+ *                  out = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2. The reference's 19-pixel reflected border around a level is
+ *                  not built: no output depends on it.
+ *   O3 cells.      minB = 16, maxBX = Wl - 16, maxBY = Hl - 16, width = maxBX - minB, height likewise; nCols = floor(width / 30), nRows =
+ *                  floor(height / 30); a level with nCols < 1 or nRows < 1 has no cells and no keypoints (the reference divides by zero there and
+ *                  ends with none). wCell = ceil(width / nCols), hCell = ceil(height / nRows). Cell (i, j) is the sub-image [iniX, maxX) x [iniY, maxY)
+ *                  of :789-806: iniX = minB + j wCell, maxX = min(iniX + wCell + 6, maxBX), likewise Y with i; FAST tests its pixels at distance >= 3
+ *                  from the sub-image's border: [iniX + 3, maxX - 3) x [iniY + 3, maxY - 3). A cell exists iff that region is not empty (the
+ *                  reference's skip tests drop exactly the empty columns, and FAST finds nothing in an empty row). The regions tile
+ *                  [19, Wl - 19) x [19, Hl - 19) without overlap.
+ *   O4 FAST score. The 16-pixel Bresenham circle of radius 3. Per polarity the arc value is the minimum over 9 consecutive circle pixels of v_k - p
+ *                  (bright) or p - v_k (dark); score = the maximum over the 16 arcs and both polarities, minus 1: the largest t for which 9 contiguous
+ *                  pixels are all > p + t or all < p - t. A pixel is a corner at t iff score >= t. One uint8 score map per level serves both
+ *                  thresholds: 0 where score < min_th_fast and at pixels nearer than 3 to the level's edge.
+ *   O5 per cell.   Among a cell's tested pixels with score >= ini_th_fast keep those whose score is strictly greater than all 8 neighbours'; a neighbour
+ *                  counts as 0 outside the cell's tested region or below the threshold, so two equal adjacent corners remove each other. None kept:
+ *                  repeat with min_th_fast and count a fallback cell. A level's candidates are ordered by cell (i, then j), inside a cell by row,
+ *                  then column; coordinates are relative to minB (what the reference hands to DistributeOctTree); response = score.
+ *   O6 distribution (host, iba_orb_distribute). DistributeOctTree and DivideNode (:481-763) restated exactly: n_ini = round(width / height) in float,
+ *                  hX = width / n_ini, the start nodes with truncated corners, a candidate's start node (int)(x / hX); the two phases, the list order
+ *                  (children pushed to the front, n1..n4), the stop tests, a result of >= N and up to N + 3 nodes (also for N = 0, as in the
+ *                  reference), the best response per node with the first winning a tie. ONE RULE IS THE LIBRARY'S OWN: the reference sorts
+ *                  (size, node address) pairs in its second phase, so equal sizes are ordered by heap address; here, among equal sizes, the node
+ *                  created later is divided first.
+ *   O7 orientation. Integer moments m10 = sum u I, m01 = sum v I over the 31-row circular patch at the keypoint's pixel in the UNBLURRED level, row v
+ *                  spanning |u| <= umax[|v|], umax = 15 15 15 15 14 14 14 13 13 12 11 10 9 8 6 3 (the constructor's rule). angle = the degree
+ *                  arctangent polynomial of ((float)m01, (float)m10): with ax = |x|, ay = |y|, c = min / (max + (float)DBL_EPSILON), c2 = c c,
+ *                  a = (((p7 c2 + p5) c2 + p3) c2 + p1) c, p1 p3 p5 p7 = 0.9997878412794807f, -0.3258083974640975f, 0.1555786518463281f,
+ *                  -0.04432655554792128f, each times (float)(180 / pi); ax < ay: a = 90 - a; x < 0: a = 180 - a; y < 0: a = 360 - a.
+ *   O8 blur.       Every level that has keypoints: separable 7 taps, integer weights 18 34 49 54 49 34 18 (256 exp(-k^2 / 8) / sum rounded, the centre
+ *                  taking the remainder), reflect-101 at the level's own border; horizontal sums are exact in 16 bits, vertical out =
+ *                  (sum + 32768) >> 16. A level without keypoints is not blurred: its blurred stage reads as zeros.
+ *   O9 descriptor. a_rad = angle * (float)(pi / 180); cos and sin of (double)a_rad from ONE fixed sequence of f64 operations (csrc/iba_orb_host.hpp,
+ *                  orb_sincos: q = floor(x * 2/pi + 0.5), r = (x - q pio2_hi) - q pio2_lo, the sine and the cosine polynomial in Horner form, the
+ *                  quadrant swap; the same function on host and device), each rounded to float: a = cos, b = sin. A pattern point (x, y) is read at
+ *                  row = rint(x * b + y * a), col = rint(x * a - y * b) from the keypoint in the BLURRED level: two products and one sum each. Bit k of
+ *                  byte i is t0 < t1 of test 8 i + k. Keypoints lie >= 19 pixels from the level's edge and pattern points within radius 18: no read
+ *                  can leave the level and there is no clamp.
+ *   O10 output.    Levels in ascending order, inside a level the order of O6's node list. xy = (level pixel, i.e. candidate + 16) * sf[l];
+ *                  size = (int)(31 * sf[l]); octave = l; response = score; angle in degrees.
+ *
+ * KNOWN DEVIATIONS / UNPINNED. The library does not link OpenCV: five rules are its own integer restatements, modelled on
+ * the reference's OpenCV calls and NOT pinned to recorded OpenCV outputs: O2 resize (cv::resize INTER_LINEAR), O8 blur (GaussianBlur 7 x 7, sigma 2),
+ * O4 FAST score (cv::FAST's corner score), O5 the per-cell non-maximum suppression (cv::FAST with nonmaxSuppression), O7 the polynomial arctangent
+ * (cv::fastAtan2). O6's tie rule is stated above. The BRIEF test-pair table is an INPUT (256 x 4 int8: x0 y0 x1 y1 per test); the library ships none.
+ * Masks, undistortion, ComputeKeyPointsOld and matching are not provided.
+ * DEVICE: one chain per chunk over flat tables (one row per image and level, per 64 x 16 tile, per cell, per keypoint): resize level by level, score,
+ * cell count, scan, ordered cell write, the candidates down, O6 on the host, the keypoints up, orientation, blur, descriptor (csrc/iba_orb_kernels.hpp).
+ * MEMORY: a chunk of consecutive images takes IBA_ORB_BYTES_PER_PIXEL bytes per pyramid pixel (pyramid, scores, blurred levels, the candidate
+ * bound); a call is cut so that a chunk stays under IBA_ORB_BUDGET_BYTES, or under a quarter of the device memory free at the call where that is less; a
+ * chunk holds at least one image and a chunk boundary changes no byte. Without keep_stages the planes live only for the call and the result is host
+ * memory; with it the result owns pyramid, scores and blurred levels on the device (3 bytes per pyramid pixel) and the candidates on the host.
+ * ERRORS, all IBA_ERR_INVALID_ARG with a message (iba_orb_last_error, per thread) BEFORE the device is touched: a NULL argument or a wrong struct_size;
+ * n < 1; an image with W, H < 1 or stride < W; options outside the stated ranges, a scale_factor that is not finite or <= 1; pattern == NULL or a
+ * pattern point outside the disc x^2 + y^2 <= 324; an image where some level has cells and n_ini == 0 (the reference would index out of bounds); an
+ * image or level index outside the result; a stage accessor on a result without keep_stages.
+ */
+#define IBA_ORB_BUDGET_BYTES (1ull << 30)
+#define IBA_ORB_BYTES_PER_PIXEL 6ull
+typedef struct iba_orb_image   { const uint8_t* gray; int32_t W, H; int64_t stride; } iba_orb_image;   /* 8-bit, row-major, stride >= W bytes */
+typedef struct iba_orb_options {
+    int32_t struct_size;     /* sizeof(iba_orb_options) */
+    int32_t n_features;      /* 2000, >= 1 */
+    float   scale_factor;    /* 1.2f, finite and > 1 */
+    int32_t n_levels;        /* 8, 1..16 */
+    int32_t ini_th_fast;     /* 20 */
+    int32_t min_th_fast;     /* 7, 1 <= min <= ini <= 254 */
+    int32_t keep_stages;     /* 0; 1 keeps pyramid, score maps, candidates and blurred levels for the stage accessors */
+    int32_t reserved;
+    const int8_t* pattern;   /* 256 x 4: x0 y0 x1 y1 per test, every point with x*x + y*y <= 324; read during iba_orb_extract only */
+} iba_orb_options;
+typedef struct iba_orb_features iba_orb_features;
+iba_status iba_default_orb_options(iba_orb_options* opt);            /* pattern = NULL: the caller must set it */
+const char* iba_orb_last_error(void);                                /* never NULL; of this thread's last iba_orb_* call that failed */
+/* *out is NULL on failure; release it with iba_orb_free */
+iba_status iba_orb_extract(const iba_orb_image* images, int32_t n, const iba_orb_options* opt, int device, iba_orb_features** out);
+void       iba_orb_free(iba_orb_features* f);
+int32_t    iba_orb_n_images(const iba_orb_features* f);              /* 0 for NULL */
+/* any output may be NULL; the three per-level arrays take n_levels entries */
+iba_status iba_orb_counts(const iba_orb_features* f, int32_t image, int32_t* n_keypoints, int32_t* per_level, int32_t* candidates_per_level, int32_t* fallback_cells_per_level);
+iba_status iba_orb_read(iba_orb_features* f, int32_t image, float* xy /* n x 2 */, float* angle, float* response, int32_t* octave, float* size, uint8_t* desc /* n x 32 */);   /* any may be NULL */
+/* stage accessors, keep_stages only; a level's size is iba_orb_plan's */
+iba_status iba_orb_level(iba_orb_features* f, int32_t image, int32_t level, int32_t blurred, uint8_t* out /* Hl x Wl */);
+iba_status iba_orb_scores(iba_orb_features* f, int32_t image, int32_t level, uint8_t* out /* Hl x Wl, 0 = no corner */);
+iba_status iba_orb_candidates(iba_orb_features* f, int32_t image, int32_t level, int32_t* xy /* n x 2, relative to minB */, int32_t* score);   /* n = candidates_per_level[level] */
+/* host only, pure functions (precedents: iba_pgo_plan, iba_backend_plan). iba_orb_plan ignores opt->pattern; every output may be NULL; level_wh is
+ * 0 0 for an empty level, cells 0 0 0 0 and n_ini 0 for a level without cells. */
+iba_status iba_orb_plan(int32_t W, int32_t H, const iba_orb_options* opt, int32_t* level_wh /* L x 2 */, int32_t* features_per_level, int32_t* cells /* L x 4: nCols nRows wCell hCell */, int32_t* n_ini /* L */, int32_t umax[16]);
+/* O6 on n candidates (0 <= x < width, 0 <= y < height): chosen receives *n_chosen <= n candidate indices in the order of the node list */
+iba_status iba_orb_distribute(const int32_t* xy, const int32_t* score, int32_t n, int32_t width, int32_t height, int32_t N, int32_t* chosen /* cap n */, int32_t* n_chosen);
+
 /* The ABI version the LIBRARY was built with (IBA_ABI_VERSION of its header). iba_params carries no struct_size: a caller compiled against
  * an older header would pass a shorter struct. Callers compare iba_abi_version() with their own IBA_ABI_VERSION before iba_create(). */
 int32_t iba_abi_version(void);

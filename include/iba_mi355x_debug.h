@@ -47,6 +47,8 @@
  *                                                         split of a call at small images; same results)
  *   IBA_PROJECT_TIMING                                    set: iba_project_run and the colourise / overlay accessors record HIP events around their kernels
  *                                                         (iba_debug_projection_kernel_ms; tools/project_bench.py); same results
+ *   IBA_ORB_BUDGET, IBA_ORB_TIMING                        the same two for iba_orb_extract (6 bytes per pyramid pixel and image; iba_debug_orb_chunks,
+ *                                                         iba_debug_orb_stage_ms; tools/orb_bench.py); same results
  *   IBA_GROUP_REDUCE_HOST (flag of iba_group_create_ex, not a variable), IBA_DEBUG_FAIL_RANK / IBA_DEBUG_FAIL_PHASE: inject one
  *                                                         failure into a group's evaluation (tests of the fail-not-hang path)
  */
@@ -223,6 +225,24 @@ int32_t iba_debug_projection_chunks(const iba_projection* p);
 /* debug: with IBA_PROJECT_TIMING set at the call, HIP-event times (ms) of the kernels behind p: [0] splat, [1] resolve, [2] visible, each summed over
  * the chunks of iba_project_run; [3] the last iba_projection_colorize's launch, [4] the last iba_projection_overlay's. Zeros without the variable. */
 iba_status iba_debug_projection_kernel_ms(const iba_projection* p, float ms[5]);
+
+/* debug, host only: O7's degree arctangent polynomial and O9's pair for one angle in degrees: ab = (a, b) = (cos, sin) rounded to float as the
+ * descriptor kernel uses them, cs = the f64 cosine and sine before the rounding (iba_orb_* of iba_mi355x.h; the functions are compiled once for host
+ * and device, csrc/iba_orb_host.hpp) */
+float iba_debug_orb_atan2(float y, float x);
+iba_status iba_debug_orb_sincos(float angle_deg, float ab[2], double cs[2]);
+/* debug, host only: a result of n_images empty images without device buffers (the accessors' index and keep_stages checks); release it with iba_orb_free */
+iba_status iba_debug_orb_stub(int32_t n_images, int32_t n_levels, int32_t keep_stages, iba_orb_features** out);
+/* debug: the chunks the images of the call behind f were cut into (IBA_ORB_BUDGET: bytes a chunk may take in place of IBA_ORB_BUDGET_BYTES and the
+ * free-memory rule, read at every call under IBA_DEBUG_ENV=1; same results); 0 for NULL */
+int32_t iba_debug_orb_chunks(const iba_orb_features* f);
+/* debug: with IBA_ORB_TIMING set at the call (under IBA_DEBUG_ENV=1), times in ms summed over the chunks: [0] resize, [1] score, [2] cell count + scan +
+ * write, [3] the host's share between them and the next launch (both candidate copies, O6, the keypoints up; steady clock), [4] orientation, [5] blur,
+ * [6] descriptor; the kernels' from HIP events. Zeros without the variable. Same results. */
+iba_status iba_debug_orb_stage_ms(const iba_orb_features* f, float ms[7]);
+/* debug: O8 and O9 alone on one image taken as a level: the blurred image (may be NULL) and the descriptors of n keypoints at given level pixels
+ * (>= 19 from every edge) and given angles in degrees. Tests reach the rint ties of O9 with it, which no image reaches on purpose. */
+iba_status iba_debug_orb_describe(const uint8_t* gray, int32_t W, int32_t H, const int32_t* xy, const float* angle, int32_t n, const int8_t* pattern, int device, uint8_t* blurred, uint8_t* desc);
 
 #ifdef __cplusplus
 }
