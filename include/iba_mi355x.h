@@ -1168,7 +1168,9 @@ iba_status iba_project_gradient(double zn, uint8_t rgb[3]);                     
  * the reference's OpenCV calls and NOT pinned to recorded OpenCV outputs: O2 resize (cv::resize INTER_LINEAR), O8 blur (GaussianBlur 7 x 7, sigma 2),
  * O4 FAST score (cv::FAST's corner score), O5 the per-cell non-maximum suppression (cv::FAST with nonmaxSuppression), O7 the polynomial arctangent
  * (cv::fastAtan2). O6's tie rule is stated above. The BRIEF test-pair table is an INPUT (256 x 4 int8: x0 y0 x1 y1 per test); the library ships none.
- * Masks, undistortion, ComputeKeyPointsOld and matching are not provided.
+ * Masks, undistortion and ComputeKeyPointsOld are not provided. Windowed matching is iba_orb_match below; the matchers that remain unprovided are
+ * SearchByBoW and SearchForTriangulation (they need the DBoW2 vocabulary), Fuse, SearchBySim3, and the SearchByProjection overloads that take map
+ * points or a key frame.
  * DEVICE: one chain per chunk over flat tables (one row per image and level, per 64 x 16 tile, per cell, per keypoint): resize level by level, score,
  * cell count, scan, ordered cell write, the candidates down, O6 on the host, the keypoints up, orientation, blur, descriptor (csrc/iba_orb_kernels.hpp).
  * MEMORY: a chunk of consecutive images takes IBA_ORB_BYTES_PER_PIXEL bytes per pyramid pixel (pyramid, scores, blurred levels, the candidate
@@ -1213,6 +1215,143 @@ iba_status iba_orb_candidates(iba_orb_features* f, int32_t image, int32_t level,
 iba_status iba_orb_plan(int32_t W, int32_t H, const iba_orb_options* opt, int32_t* level_wh /* L x 2 */, int32_t* features_per_level, int32_t* cells /* L x 4: nCols nRows wCell hCell */, int32_t* n_ini /* L */, int32_t umax[16]);
 /* O6 on n candidates (0 <= x < width, 0 <= y < height): chosen receives *n_chosen <= n candidate indices in the order of the node list */
 iba_status iba_orb_distribute(const int32_t* xy, const int32_t* score, int32_t n, int32_t width, int32_t height, int32_t N, int32_t* chosen /* cap n */, int32_t* n_chosen);
+
+/*
+ * ---- Windowed ORB descriptor matching [the camera side's second brick: the two call sites of the reference's ORBmatcher that need no vocabulary and
+ * no map, SearchForInitialization (src/orb_slam/src/ORBmatcher.cc:405-520) and SearchByProjection(Frame&, const Frame&, th, bMono) (:1328-1470), on
+ * Frame::AssignFeaturesToGrid, PosInGrid and GetFeaturesInArea (src/orb_slam/src/Frame.cc:230-245, :327-392)] ----
+ * A call takes F frames and J jobs; a job matches the queries it lists against the keypoints of one frame (its train frame) under one of two rules.
+ * All consecutive pairs of a sequence are one call. The work is integer work (cell indices, list order, popcounts, comparisons); tests/orb_match_ref.py
+ * restates every rule in numpy and the device results are compared byte for byte. Float arithmetic is float32, every operation rounded, evaluated left
+ * to right, no contraction; round = half away from zero (the C function the reference calls).
+ *
+ *   M1 frame.      n keypoints, each with xy (float32, the undistorted position), octave (int32), angle (float32 degrees), desc (32 bytes), and the four
+ *                  float32 bounds min_x, max_x, min_y, max_y (the reference's mnMinX ..). The grid is 64 columns by 48 rows;
+ *                  inv_w = 64.0f / (max_x - min_x), inv_h = 48.0f / (max_y - min_y).
+ *   M2 grid.       (PosInGrid, AssignFeaturesToGrid) px = (int)round((x - min_x) * inv_w), py likewise with min_y and inv_h. A keypoint with px outside
+ *                  [0, 64) or py outside [0, 48) is in no cell. It is round, not floor: the reference's rule, kept. A cell's list holds its keypoints
+ *                  in ascending index. (The comparison with the range is made on the rounded float, so no product is too large to convert.)
+ *   M3 area query. (GetFeaturesInArea(u, v, r, minLevel, maxLevel)) c0x = max(0, (int)floor((u - min_x - r) * inv_w)); c0x >= 64: the list is empty.
+ *                  c1x = min(63, (int)ceil((u - min_x + r) * inv_w)); c1x < 0: empty. The same for y with 48 and 47. check = minLevel > 0 ||
+ *                  maxLevel >= 0. Walk ix outer, iy inner, then the cell's list in its order; with check skip a keypoint whose octave < minLevel and,
+ *                  where maxLevel >= 0, one whose octave > maxLevel; keep the keypoint iff fabs(x - u) < r && fabs(y - v) < r, both strict. The
+ *                  list's order is part of the result: it decides ties.
+ *   M4 distance.   The number of set bits of the XOR of the two 32-byte descriptors.
+ *   M5 a query.    (u, v, r, minLevel, maxLevel, desc, angle, valid); desc and angle are those of keypoint query_index of the job's query frame. A
+ *                  query that is not valid is never looked at and stays unmatched.
+ *   M6 rule INIT.  (SearchForInitialization's loop, :418-487) Per train keypoint held_dist = INT_MAX and holder = -1. The queries in ascending index:
+ *                  walk the list, skipping a candidate c with held_dist[c] <= dist; over the rest best = the least distance, held by the FIRST
+ *                  candidate in list order that attains it (strict <); best2 = the second smallest value of the multiset (two candidates at the
+ *                  same least distance give best2 == best; fewer than two candidates: INT_MAX). Accept iff best <= th_low and
+ *                  (float)best < (float)best2 * nn_ratio. On accept: a candidate that has a holder takes that holder's match away (match[holder] =
+ *                  -1, n_matches--, n_displaced++); then match[q] = c, holder[c] = q, held_dist[c] = best, n_matches++, and the QUERY is entered
+ *                  into the rotation histogram (M8) with rot = angle_q - angle_c. A holder displaced later STAYS in the histogram's counts.
+ *   M7 rule CLAIM. (the loop of :1351-1445 for the monocular case) Per train keypoint a claimed bit. The queries in ascending index: skip claimed
+ *                  candidates; best starts at 256 and the first candidate with the strictly least distance wins (a candidate at distance 256 never
+ *                  does); accept iff a candidate was found and best <= th_high. On accept: claim the candidate, match[q] = c, n_matches++, and the
+ *                  TRAIN index is entered into the histogram with rot = angle_q - angle_c. As a claimed keypoint is claimed once, the entry names
+ *                  the query as well. KNOWN DEVIATION: the reference skips a candidate only if its map point also has Observations() > 0; here every
+ *                  claim counts.
+ *   M8 rotation.   (check_orientation != 0) rot < 0.0f: rot += 360.0f. bin = (int)round(rot * (1.0f / 30)); bin == 30 becomes 0. The factor is the
+ *                  reference's 1.0f / HISTO_LENGTH where 360.0f / HISTO_LENGTH would spread the bins, so the bins in use are 0..12: restated, not
+ *                  corrected. ComputeThreeMaxima (:1601-1642) exactly: strict > in bin order (a count above max1 moves 1 to 2 and 2 to 3, one above
+ *                  max2 moves 2 to 3); ind2 and ind3 are dropped when (float)max2 < 0.1f * (float)max1, else ind3 when (float)max3 < 0.1f *
+ *                  (float)max1. Every entry of a bin other than the three loses its match: INIT decrements n_matches only where the entry still
+ *                  holds a match, CLAIM always decrements (its entries all hold one). Without check_orientation hist is zeros and ind is -1 -1 -1.
+ *   M9 outputs per job. match[n_queries] (the train index or -1), dist[n_queries] (the accepted distance of a surviving match, else -1), n_matches,
+ *                  n_candidates (the sum of the list lengths), n_displaced (INIT), n_rot_removed (matches M8 took away), hist[30] (the counts at
+ *                  push time), ind[3].
+ *
+ * THE TWO QUERY BUILDERS (host only, pure) restate what the reference's call sites hand to GetFeaturesInArea:
+ *   iba_orb_match_init_queries: one query per keypoint of frame1, query_index = its index, valid iff octave == 0 (the reference skips level1 > 0; an
+ *                  octave below 0 is not valid either), centre = prev_matched_xy, r = (float)window_size, levels (0, 0).
+ *   iba_orb_match_motion_queries: (:1359-1390 for bMono) one query per keypoint i of the last frame; not valid where has_point[i] == 0 or outlier[i] != 0.
+ *                  xc = ((R00 X + R01 Y) + R02 Z) + t0, yc and zc likewise with rows 1 and 2 of the current frame's Tcw (3 x 4 row-major, float32);
+ *                  invzc = (float)(1.0 / (double)zc); not valid iff invzc < 0; u = fx * xc * invzc + cx, v = fy * yc * invzc + cy; not valid where
+ *                  u < min_x, u > max_x, v < min_y or v > max_y of the CURRENT frame's bounds (a centre exactly on a bound is kept), and - the
+ *                  library's own rule - where u or v is not finite; r = th * scale_factors[octave], levels (octave - 1, octave + 1). A query that is
+ *                  not valid gets centre 0 0, radius 0 and levels 0 0. UNPINNED: the reference forms Rcw * X + tcw with OpenCV's 3 x 3 float product,
+ *                  which may sum in another order than the one stated here.
+ *
+ * DEVICE (csrc/iba_orb_match_kernels.hpp): every frame goes up once, however many jobs name it. Grid: one thread per keypoint of any frame takes its
+ * cell and counts per (frame, cell); a scan; one wave per frame fills the lists in ascending index by ballot-free lane ranks (no order depends on atomic
+ * arrival). Lists: one thread per query counts its M3 list, the counts are scanned, and a second pass writes the candidate indices in M3's order
+ * together with their M4 distances (one uint16 each). Resolve: ONE wave per job walks the queries in order; the lanes stride over the query's
+ * segment, the wave combines (distance, list position) lexicographically and the second order statistic, lane 0 applies M6 or M7; the per-train
+ * state is in LDS up to IBA_ORB_MATCH_LDS_TRAIN train keypoints and in global memory above; M8 runs at the end of the same kernel. The resolve is
+ * sequential by the rule's definition: the parallelism is across jobs.
+ * MEMORY: the frames, the queries and the grid of the whole call stay on the device for the call (60 bytes per keypoint, 36 per query, 8 per grid cell; a chunk adds 13 bytes per query of its jobs). The candidate
+ * lists (IBA_ORB_MATCH_BYTES_PER_CANDIDATE bytes per entry, sized from the count pass) are cut into chunks of consecutive jobs under
+ * IBA_ORB_MATCH_BUDGET_BYTES, or under a quarter of the device memory free at the call where that is less; a chunk holds at least one job and a chunk
+ * boundary changes no byte. A chunk whose lists hold 2^31 entries or more answers IBA_ERR_UNSUPPORTED. The result is host memory.
+ * ERRORS, all IBA_ERR_INVALID_ARG with a message (iba_orb_match_last_error, per thread) BEFORE the device is touched: a NULL argument (a frame's
+ * arrays may be NULL only where n == 0, a job's where n_queries == 0; valid may always be NULL: all valid) or a wrong struct_size; F < 1, J < 1; a
+ * frame with n < 0 or n > IBA_ORB_MATCH_MAX_KEYPOINTS; bounds that are not finite or max <= min; a keypoint position that is not finite; an angle
+ * that is not finite or outside [0, 360] (the histogram's bins would leave the table); a job's frame or a query's query_index out of range; an unknown
+ * rule; n_queries < 0; a centre or radius that is not finite, r < 0, or a magnitude above 1e6 (the reference's (int) of such a float is undefined);
+ * nn_ratio not finite or <= 0; th_low or th_high outside [0, 256]; a job or frame index outside the result; a stage accessor on a result without
+ * keep_stages. A frame with n == 0 and a job with n_queries == 0 are legal.
+ */
+#define IBA_ORB_MATCH_BUDGET_BYTES (1ull << 30)
+#define IBA_ORB_MATCH_BYTES_PER_CANDIDATE 6ull
+#define IBA_ORB_MATCH_MAX_KEYPOINTS 32768
+#define IBA_ORB_MATCH_LDS_TRAIN 8192
+#define IBA_ORB_MATCH_GRID_COLS 64
+#define IBA_ORB_MATCH_GRID_ROWS 48
+#define IBA_ORB_MATCH_HISTO 30
+typedef enum iba_orb_match_rule { IBA_ORB_MATCH_INIT = 0, IBA_ORB_MATCH_CLAIM = 1 } iba_orb_match_rule;
+typedef struct iba_orb_frame {                /* host pointers, read during the call only */
+    const float*   xy;        /* n x 2 */
+    const int32_t* octave;    /* n */
+    const float*   angle;     /* n, degrees in [0, 360] */
+    const uint8_t* desc;      /* n x 32 */
+    int32_t n;
+    float min_x, max_x, min_y, max_y;
+} iba_orb_frame;
+typedef struct iba_orb_match_job {
+    int32_t query_frame, train_frame;   /* indices into the call's frame array; they may be equal */
+    int32_t rule;                       /* iba_orb_match_rule */
+    int32_t n_queries;
+    const float*   centre_xy;           /* n_queries x 2 */
+    const float*   radius;              /* n_queries */
+    const int32_t* level_range;         /* n_queries x 2: minLevel maxLevel */
+    const int32_t* query_index;         /* n_queries: the keypoint of query_frame that supplies descriptor and angle */
+    const uint8_t* valid;               /* n_queries, or NULL: all valid */
+} iba_orb_match_job;
+typedef struct iba_orb_match_options {
+    int32_t struct_size;        /* sizeof(iba_orb_match_options) */
+    int32_t th_low;             /* 50: INIT's bound on best */
+    int32_t th_high;            /* 100: CLAIM's bound on best */
+    float   nn_ratio;           /* 0.9f: INIT's ratio */
+    int32_t check_orientation;  /* 1 */
+    int32_t keep_stages;        /* 0; 1 keeps the grid and the candidate lists for the stage accessors */
+} iba_orb_match_options;
+typedef struct iba_orb_match_counts {
+    int32_t n_queries, n_matches, n_candidates, n_displaced, n_rot_removed;
+    int32_t hist[IBA_ORB_MATCH_HISTO];
+    int32_t ind[3];
+} iba_orb_match_counts;
+typedef struct iba_orb_matches iba_orb_matches;
+iba_status iba_default_orb_match_options(iba_orb_match_options* opt);
+const char* iba_orb_match_last_error(void);                          /* never NULL; of this thread's last iba_orb_match* call that failed */
+/* *out is NULL on failure; release it with iba_orb_matches_free */
+iba_status iba_orb_match(const iba_orb_frame* frames, int32_t F, const iba_orb_match_job* jobs, int32_t J, const iba_orb_match_options* opt, int device, iba_orb_matches** out);
+void       iba_orb_matches_free(iba_orb_matches* m);
+int32_t    iba_orb_matches_n_jobs(const iba_orb_matches* m);         /* 0 for NULL */
+iba_status iba_orb_matches_job(const iba_orb_matches* m, int32_t job, iba_orb_match_counts* counts);
+iba_status iba_orb_matches_read(const iba_orb_matches* m, int32_t job, int32_t* match /* n_queries */, int32_t* dist /* n_queries */);   /* either may be NULL */
+/* stage accessors, keep_stages only. Grid: cell_off[3073] with cell = px * 48 + py (the order M3 walks) and list[cell_off[3072]] = the frame's keypoints
+ * by cell, ascending inside a cell; *n_listed = cell_off[3072] (the keypoints that are in a cell). Lists: off[n_queries + 1] and, per entry, the train
+ * index and the distance in M3's order; their length is the job's n_candidates. Every output may be NULL. */
+iba_status iba_orb_matches_grid(const iba_orb_matches* m, int32_t frame, int32_t* cell_off /* 3073 */, int32_t* list /* cap n */, int32_t* n_listed);
+iba_status iba_orb_matches_lists(const iba_orb_matches* m, int32_t job, int32_t* off /* n_queries + 1 */, int32_t* index, uint16_t* dist);
+/* host only, pure functions: the per-query arrays of the reference's two call sites (rules above). The outputs take frame->n entries each. */
+iba_status iba_orb_match_init_queries(const iba_orb_frame* frame1, const float* prev_matched_xy /* n x 2 */, int32_t window_size,
+                                      float* centre_xy, float* radius, int32_t* level_range, int32_t* query_index, uint8_t* valid);
+iba_status iba_orb_match_motion_queries(const iba_orb_frame* last_frame, const uint8_t* has_point /* n */, const uint8_t* outlier /* n */, const float* world_xyz /* n x 3 */,
+                                        const float Tcw12[12] /* the current frame's */, float fx, float fy, float cx, float cy, const float bounds[4] /* the current frame's min_x max_x min_y max_y */,
+                                        const float* scale_factors, int32_t n_scale_factors, float th,
+                                        float* centre_xy, float* radius, int32_t* level_range, int32_t* query_index, uint8_t* valid);
 
 /* The ABI version the LIBRARY was built with (IBA_ABI_VERSION of its header). iba_params carries no struct_size: a caller compiled against
  * an older header would pass a shorter struct. Callers compare iba_abi_version() with their own IBA_ABI_VERSION before iba_create(). */

@@ -49,6 +49,8 @@
  *                                                         (iba_debug_projection_kernel_ms; tools/project_bench.py); same results
  *   IBA_ORB_BUDGET, IBA_ORB_TIMING                        the same two for iba_orb_extract (6 bytes per pyramid pixel and image; iba_debug_orb_chunks,
  *                                                         iba_debug_orb_stage_ms; tools/orb_bench.py); same results
+ *   IBA_ORB_MATCH_BUDGET, IBA_ORB_MATCH_TIMING            the same two for iba_orb_match (6 bytes per candidate-list entry; iba_debug_orb_match_chunks,
+ *                                                         iba_debug_orb_match_stage_ms; tools/orb_match_bench.py); same results
  *   IBA_GROUP_REDUCE_HOST (flag of iba_group_create_ex, not a variable), IBA_DEBUG_FAIL_RANK / IBA_DEBUG_FAIL_PHASE: inject one
  *                                                         failure into a group's evaluation (tests of the fail-not-hang path)
  */
@@ -243,6 +245,18 @@ iba_status iba_debug_orb_stage_ms(const iba_orb_features* f, float ms[7]);
 /* debug: O8 and O9 alone on one image taken as a level: the blurred image (may be NULL) and the descriptors of n keypoints at given level pixels
  * (>= 19 from every edge) and given angles in degrees. Tests reach the rint ties of O9 with it, which no image reaches on purpose. */
 iba_status iba_debug_orb_describe(const uint8_t* gray, int32_t W, int32_t H, const int32_t* xy, const float* angle, int32_t n, const int8_t* pattern, int device, uint8_t* blurred, uint8_t* desc);
+/* debug, host only: a result of n_jobs jobs without queries over n_frames frames without keypoints (the accessors' index and keep_stages checks);
+ * release it with iba_orb_matches_free */
+iba_status iba_debug_orb_match_stub(int32_t n_jobs, int32_t n_frames, int32_t keep_stages, iba_orb_matches** out);
+/* debug: the chunks the jobs of the call behind m were cut into (IBA_ORB_MATCH_BUDGET: bytes a chunk's candidate lists may take in place of
+ * IBA_ORB_MATCH_BUDGET_BYTES and the free-memory rule, read at every call under IBA_DEBUG_ENV=1; same results); 0 for NULL */
+int32_t iba_debug_orb_match_chunks(const iba_orb_matches* m);
+/* debug: with IBA_ORB_MATCH_TIMING set at the call (under IBA_DEBUG_ENV=1), times in ms from HIP events, summed over the chunks: [0] grid (cell, scan,
+ * fill), [1] list count, [2] scan + list write with the distances, [3] resolve. Zeros without the variable. Same results. */
+iba_status iba_debug_orb_match_stage_ms(const iba_orb_matches* m, float ms[4]);
+/* debug, host only: the chunk planner on its own: the cut of n_jobs jobs with the given candidate counts under budget bytes; cut receives *n_cut
+ * <= n_jobs + 1 ascending job indices, the first 0 and the last n_jobs */
+iba_status iba_debug_orb_match_plan(const int64_t* candidates, int32_t n_jobs, uint64_t budget, int32_t* cut, int32_t* n_cut);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,357 @@
+"""Windowed ORB matching, the host half (include/iba_mi355x.h, iba_orb_match*): the symbols and struct layouts, every argument check, the two query
+builders against tests/orb_match_ref.py, and the restatement's own known answers computed by hand — all without a device."""
+import ctypes as C
+import importlib
+import re
+
+import numpy as np
+import pytest
+
+import orb_match_ref as R
+
+PKG = "spatial-temporal-lidar-camera-calibration_amd"
+F = np.float32
+BOUNDS = (0.0, 640.0, 0.0, 480.0)          # ten pixels per cell on both axes
+
+
+@pytest.fixture(scope="module")
+def om():
+    importlib.import_module(PKG)
+    return importlib.import_module(PKG + ".orb_match")
+
+
+@pytest.fixture(scope="module")
+def err():
+    return importlib.import_module(PKG).IbaError
+
+
+def rand_frame(n, seed, bounds=BOUNDS, octaves=3):
+    rng = np.random.default_rng(seed)
+    xy = np.stack([rng.uniform(bounds[0], bounds[1], n), rng.uniform(bounds[2], bounds[3], n)], 1).astype(F)
+    return R.make_frame(xy, rng.integers(0, octaves, n), rng.uniform(0, 360, n).astype(F), rng.integers(0, 256, (n, 32)), bounds)
+
+
+def lib_frame(om, f):
+    return om.frame(f["xy"], f["octave"], f["angle"], f["desc"], f["bounds"])
+
+
+# ---- symbols, layouts, ABI ----
+
+def test_symbols_and_layouts(om):
+    L = om._lib()
+    names = ("iba_default_orb_match_options", "iba_orb_match_last_error", "iba_orb_match", "iba_orb_matches_free", "iba_orb_matches_n_jobs", "iba_orb_matches_job",
+             "iba_orb_matches_read", "iba_orb_matches_grid", "iba_orb_matches_lists", "iba_orb_match_init_queries", "iba_orb_match_motion_queries",
+             "iba_debug_orb_match_stub", "iba_debug_orb_match_chunks", "iba_debug_orb_match_stage_ms", "iba_debug_orb_match_plan")
+    pkg = importlib.import_module(PKG)
+    hdr = "".join(open(p).read() for p in pkg.HEADER_PATHS)
+    for name in names:
+        getattr(L, name)
+        assert re.search(r"\b%s\s*\(" % name, hdr), name + " is not declared"
+    assert L.iba_abi_version() == 4 and re.search(r"#define\s+IBA_ABI_VERSION\s+4\b", hdr)
+    o = om.match_options()
+    assert (o.struct_size, o.th_low, o.th_high, o.check_orientation, o.keep_stages) == (C.sizeof(om.IbaOrbMatchOptions), 50, 100, 1, 0) and o.nn_ratio == F(0.9)
+    assert C.sizeof(om.IbaOrbMatchOptions) == 24
+    assert C.sizeof(om.IbaOrbFrame) == 56 and om.IbaOrbFrame.n.offset == 32 and om.IbaOrbFrame.max_y.offset == 48
+    assert C.sizeof(om.IbaOrbMatchJob) == 56 and om.IbaOrbMatchJob.centre_xy.offset == 16 and om.IbaOrbMatchJob.valid.offset == 48
+    assert C.sizeof(om.IbaOrbMatchCounts) == 4 * (5 + 30 + 3) and om.IbaOrbMatchCounts.hist.offset == 20
+    assert L.iba_orb_match_last_error() is not None
+    assert L.iba_orb_matches_n_jobs(None) == 0 and L.iba_debug_orb_match_chunks(None) == 0
+    assert "matching are not provided" not in hdr and "SearchByBoW and SearchForTriangulation" in hdr
+
+
+# ---- argument checks: all before the device is touched (device -1 would fail otherwise with another status) ----
+
+def _call(om, frames, jobs, **fields):
+    return om.match(frames, jobs, device=-1, **fields)
+
+
+@pytest.fixture(scope="module")
+def good(om):
+    a, b = rand_frame(50, 1), rand_frame(40, 2)
+    q = R.init_queries(a, a["xy"], 30)
+    return a, b, q
+
+
+def _expect(err, fn, text):
+    with pytest.raises(err) as e:
+        fn()
+    assert e.value.status == 1, str(e.value)
+    assert text in str(e.value), str(e.value)
+
+
+def test_argument_checks(om, err, good):
+    a, b, q = good
+    fa, fb = lib_frame(om, a), lib_frame(om, b)
+    ok_job = lambda **kw: om.job(0, 1, om.INIT, **{**q, **kw})
+    L = om._lib()
+    o = om.match_options()
+    p = C.c_void_p(None)
+    fr = (om.IbaOrbFrame * 1)()
+    C.memmove(C.addressof(fr[0]), C.addressof(fa), C.sizeof(om.IbaOrbFrame))
+    jb = (om.IbaOrbMatchJob * 1)()
+    j0 = om.job(0, 0, om.INIT, **q)
+    C.memmove(C.addressof(jb[0]), C.addressof(j0), C.sizeof(om.IbaOrbMatchJob))
+    # NULL arguments and counts
+    assert L.iba_orb_match(C.addressof(fr), 1, C.addressof(jb), 1, C.addressof(o), -1, None) == 1 and b"out is NULL" in L.iba_orb_match_last_error()
+    assert L.iba_orb_match(None, 1, C.addressof(jb), 1, C.addressof(o), -1, C.addressof(p)) == 1 and b"frames is NULL" in L.iba_orb_match_last_error()
+    assert L.iba_orb_match(C.addressof(fr), 1, None, 1, C.addressof(o), -1, C.addressof(p)) == 1 and b"jobs is NULL" in L.iba_orb_match_last_error()
+    assert L.iba_orb_match(C.addressof(fr), 1, C.addressof(jb), 1, None, -1, C.addressof(p)) == 1 and b"opt is NULL" in L.iba_orb_match_last_error()
+    assert L.iba_orb_match(C.addressof(fr), 0, C.addressof(jb), 1, C.addressof(o), -1, C.addressof(p)) == 1 and b"F < 1" in L.iba_orb_match_last_error()
+    assert L.iba_orb_match(C.addressof(fr), 1, C.addressof(jb), 0, C.addressof(o), -1, C.addressof(p)) == 1 and b"J < 1" in L.iba_orb_match_last_error()
+    assert p.value is None
+    assert L.iba_default_orb_match_options(None) == 1
+    # options
+    _expect(err, lambda: _call(om, [fa, fb], [ok_job()], struct_size=20), "struct_size")
+    for kw in ({"th_low": -1}, {"th_low": 257}, {"th_high": -1}, {"th_high": 257}):
+        _expect(err, lambda: _call(om, [fa, fb], [ok_job()], **kw), "outside [0, 256]")
+    for v in (0.0, -0.5, float("nan"), float("inf")):
+        _expect(err, lambda: _call(om, [fa, fb], [ok_job()], nn_ratio=v), "nn_ratio")
+    # frames
+    big = om.frame(np.zeros((32769, 2), F), np.zeros(32769, np.int32), np.zeros(32769, F), np.zeros((32769, 32), np.uint8), BOUNDS)
+    _expect(err, lambda: _call(om, [fa, big], [ok_job()]), "frame 1: n outside")
+    for bad, text in (((0, 0, 0, 480), "max <= min"), ((0, 640, 5, 5), "max <= min"), ((0, float("inf"), 0, 480), "not finite"), ((float("nan"), 640, 0, 480), "not finite")):
+        _expect(err, lambda: _call(om, [fa, om.frame(b["xy"], b["octave"], b["angle"], b["desc"], bad)], [ok_job()]), text)
+    xy = b["xy"].copy(); xy[3, 1] = np.inf
+    _expect(err, lambda: _call(om, [fa, om.frame(xy, b["octave"], b["angle"], b["desc"], BOUNDS)], [ok_job()]), "keypoint 3: a position")
+    ang = b["angle"].copy(); ang[7] = 361.0
+    _expect(err, lambda: _call(om, [fa, om.frame(b["xy"], b["octave"], ang, b["desc"], BOUNDS)], [ok_job()]), "keypoint 7: an angle")
+    nul = lib_frame(om, b); nul.desc = None
+    _expect(err, lambda: _call(om, [fa, nul], [ok_job()]), "a NULL array")
+    # jobs
+    _expect(err, lambda: _call(om, [fa, fb], [om.job(0, 2, om.INIT, **q)]), "a frame index outside")
+    _expect(err, lambda: _call(om, [fa, fb], [om.job(-1, 1, om.INIT, **q)]), "a frame index outside")
+    _expect(err, lambda: _call(om, [fa, fb], [om.job(0, 1, 2, **q)]), "an unknown rule")
+    _expect(err, lambda: _call(om, [fa, fb], [om.job(1, 0, om.INIT, **q)]), "query_index outside")          # indices 40 .. 49 of a 40-keypoint frame
+    idx = q["query_index"].copy(); idx[2] = -1
+    _expect(err, lambda: _call(om, [fa, fb], [ok_job(query_index=idx)]), "query 2: query_index")
+    for k, v, text in ((4, np.nan, "not finite"), (4, np.inf, "not finite"), (4, -1.0, "r < 0"), (4, 2e6, "above 1e6")):
+        r = q["radius"].copy(); r[k] = v
+        _expect(err, lambda: _call(om, [fa, fb], [ok_job(radius=r)]), "query 4: ")
+        _expect(err, lambda: _call(om, [fa, fb], [ok_job(radius=r)]), text)
+    for v, text in ((np.nan, "not finite"), (-np.inf, "not finite"), (-1.5e6, "above 1e6")):
+        c = q["centre_xy"].copy(); c[9, 1] = v
+        _expect(err, lambda: _call(om, [fa, fb], [ok_job(), ok_job(centre_xy=c)]), "job 1: query 9")
+        _expect(err, lambda: _call(om, [fa, fb], [ok_job(), ok_job(centre_xy=c)]), text)
+    nj = ok_job(); nj.level_range = None
+    _expect(err, lambda: _call(om, [fa, fb], [nj]), "a NULL array")
+    nj = ok_job(); nj.n_queries = -1
+    _expect(err, lambda: _call(om, [fa, fb], [nj]), "n_queries < 0")
+    # the accessors on NULL
+    assert L.iba_orb_matches_job(None, 0, None) == 1 and L.iba_orb_matches_read(None, 0, None, None) == 1
+    assert L.iba_orb_matches_grid(None, 0, None, None, None) == 1 and L.iba_orb_matches_lists(None, 0, None, None, None) == 1
+    L.iba_orb_matches_free(None)
+
+
+def test_accessor_checks(om, err):
+    """the index and keep_stages checks of the accessors, on results without a device"""
+    m = om.OrbMatches.stub(2, 3, keep_stages=0)
+    assert len(m) == 2 and m.n_chunks == 0 and m.counts(1)["n_queries"] == 0 and m.read(0)[0].size == 0
+    for bad in (-1, 2):
+        _expect(err, lambda: m.counts(bad), "outside the result's 2 jobs")
+        _expect(err, lambda: m.read(bad), "outside the result's 2 jobs")
+    _expect(err, lambda: m.grid(0), "did not ask for keep_stages")
+    _expect(err, lambda: m.lists(0), "did not ask for keep_stages")
+    assert om._lib().iba_orb_matches_job(m.p, 0, None) == 1
+    m.close()
+    k = om.OrbMatches.stub(2, 3, keep_stages=1)
+    off, lst = k.grid(2)
+    assert off.tolist() == [0] * 3073 and lst.size == 0 and k.lists(1)[0].tolist() == [0]
+    for bad in (-1, 3):
+        _expect(err, lambda: k.grid(bad), "outside the result's 3 frames")
+    _expect(err, lambda: k.lists(2), "outside the result's 2 jobs")
+    k.close()
+
+
+def test_legal_empties_pass_the_checks(om, err, good):
+    """a frame with n == 0 and a job with n_queries == 0 are legal: the call gets as far as the device (which device -1 is not)"""
+    a, b, q = good
+    empty = om.frame(np.zeros((0, 2), F), np.zeros(0, np.int32), np.zeros(0, F), np.zeros((0, 32), np.uint8), BOUNDS)
+    none = om.job(1, 0, om.CLAIM, np.zeros((0, 2), F), np.zeros(0, F), np.zeros((0, 2), np.int32), np.zeros(0, np.int32))
+    with pytest.raises(err) as e:
+        _call(om, [lib_frame(om, a), empty], [none, om.job(0, 1, om.INIT, **q)])
+    assert e.value.status != 1, str(e.value)
+
+
+# ---- the restatement's known answers, by hand ----
+
+def test_m2_rounding_and_edges():
+    f = R.make_frame(np.zeros((0, 2)), [], [], np.zeros((0, 32)), BOUNDS)
+    # products exactly k + 0.5: half away from zero (floor would give k, half-to-even would give 2 for 2.5)
+    assert R.pos_in_grid(f, 25.0, 35.0) == (3, 4)
+    assert R.pos_in_grid(f, 5.0, 15.0) == (1, 2)
+    assert R.pos_in_grid(f, -5.0, 100.0) == (-1, 10)        # -0.5 -> -1: no cell
+    assert R.pos_in_grid(f, -4.0, 100.0)[0] == 0            # -0.4 -> -0: cell 0
+    assert R.pos_in_grid(f, 635.0, 475.0) == (-1, -1)       # 63.5 -> 64 and 47.5 -> 48: px == 64 is outside
+    assert R.pos_in_grid(f, 634.0, 474.0) == (63, 47)
+    assert float(R.roundf(F(2.5))) == 3.0 and float(R.roundf(F(-2.5))) == -3.0 and float(R.roundf(F(0.49999997))) == 0.0
+    g = R.make_frame([[25.0, 35.0], [900.0, 10.0], [25.0, 35.0], [24.0, 36.0]], [0] * 4, [0] * 4, np.zeros((4, 32)), BOUNDS)
+    off, lst = R.grid(g)
+    c = 3 * 48 + 4
+    assert off[c + 1] - off[c] == 2 and lst[off[c]:off[c + 1]].tolist() == [0, 2] and off[-1] == 3      # ascending index; keypoint 1 is in no cell
+    assert lst[off[2 * 48 + 4]:off[2 * 48 + 4 + 1]].tolist() == [3]
+
+
+def brute_area(frame, u, v, r, min_level, max_level):
+    """M3 read literally: ix outer, iy inner, the cell's list in ascending index"""
+    u, v, r = F(u), F(v), F(r)
+    iw, ih = R.inv_wh(frame)
+    wx, wy = R.window(u, frame["bounds"][0], r, iw, 64), R.window(v, frame["bounds"][2], r, ih, 48)
+    if wx is None or wy is None:
+        return []
+    cells = {}
+    for i, (x, y) in enumerate(frame["xy"]):
+        cells.setdefault(R.pos_in_grid(frame, x, y), []).append(i)
+    out = []
+    for ix in range(wx[0], wx[1] + 1):
+        for iy in range(wy[0], wy[1] + 1):
+            for i in cells.get((ix, iy), []):
+                if (min_level > 0 or max_level >= 0) and (frame["octave"][i] < min_level or (max_level >= 0 and frame["octave"][i] > max_level)):
+                    continue
+                if abs(F(frame["xy"][i, 0] - u)) < r and abs(F(frame["xy"][i, 1] - v)) < r:
+                    out.append(i)
+    return out
+
+
+def test_m3_known_answers():
+    f = rand_frame(400, 11, octaves=5)
+    g = R.grid(f)
+    # the four early returns
+    assert len(R.area(f, g, 700.0, 100.0, 15.0, -1, -1)) == 0      # c0x = 68 >= 64
+    assert len(R.area(f, g, -100.0, 100.0, 15.0, -1, -1)) == 0     # c1x = -8 < 0
+    assert len(R.area(f, g, 100.0, 600.0, 15.0, -1, -1)) == 0      # c0y = 58 >= 48
+    assert len(R.area(f, g, 100.0, -50.0, 15.0, -1, -1)) == 0      # c1y = -3 < 0
+    assert R.window(700.0, F(0), 15.0, F(0.1), 64) is None and R.window(100.0, F(0), 15.0, F(0.1), 64) == (8, 12) and R.window(5.0, F(0), 15.0, F(0.1), 64) == (0, 2)
+    # the check truth table
+    h = R.make_frame([[100.0, 100.0]] * 5, [0, 1, 2, 3, 4], [0] * 5, np.zeros((5, 32)), BOUNDS)
+    gh = R.grid(h)
+    assert R.area(h, gh, 100.0, 100.0, 5.0, -1, -1).tolist() == [0, 1, 2, 3, 4]     # no check
+    assert R.area(h, gh, 100.0, 100.0, 5.0, 0, 0).tolist() == [0]                   # maxLevel >= 0
+    assert R.area(h, gh, 100.0, 100.0, 5.0, 2, -1).tolist() == [2, 3, 4]            # minLevel > 0, no upper bound
+    assert R.area(h, gh, 100.0, 100.0, 5.0, -1, 3).tolist() == [0, 1, 2, 3]
+    # |dx| == r is excluded, both axes strict
+    e = R.make_frame([[105.0, 100.0], [104.5, 100.0], [100.0, 95.0], [100.0, 95.5]], [0] * 4, [0] * 4, np.zeros((4, 32)), BOUNDS)
+    assert R.area(e, R.grid(e), 100.0, 100.0, 5.0, -1, -1).tolist() == [1, 3]       # (both kept ones round into cell (10, 10): ascending index)
+    # the list's order against the literal walk, on windows of every kind
+    rng = np.random.default_rng(3)
+    for _ in range(60):
+        u, v, r = rng.uniform(-50, 700), rng.uniform(-50, 530), rng.uniform(0, 90)
+        lv = [(-1, -1), (0, 0), (2, -1), (-1, 3), (1, 3)][int(rng.integers(0, 5))]
+        assert R.area(f, g, u, v, r, *lv).tolist() == brute_area(f, u, v, r, *lv)
+
+
+def test_m8_known_answers():
+    # bins follow float32: rot * (1.0f / 30), half away from zero
+    assert R.rot_bin(15.0, 0.0) == 1        # 0.5 -> 1
+    assert R.rot_bin(45.0, 0.0) == 2        # 1.5 -> 2
+    assert R.rot_bin(345.0, 0.0) == 12      # 11.5 -> 12: the bins in use end at 12
+    assert R.rot_bin(10.0, 25.0) == 12      # -15 + 360 = 345
+    assert R.rot_bin(0.0, 360.0) == 0 and R.rot_bin(360.0, 0.0) == 12 and R.rot_bin(14.0, 0.0) == 0
+    for rot, want in ((15.0, 1), (45.0, 2), (345.0, 12)):
+        assert int(R.roundf(F(F(rot) * F(F(1.0) / F(30))))) == want
+    # ComputeThreeMaxima: max2 just under and just at 0.1f * max1
+    h = np.zeros(30, np.int32)
+    h[4], h[7], h[9] = 100, 9, 5
+    assert F(F(0.1) * F(100)) == F(10)                       # 0.1f * 100.0f = 10.00000015 rounds to exactly 10 in float32
+    assert R.three_maxima(h) == [4, -1, -1]                  # max2 = 9 < 10: ind2 and ind3 go
+    h[7] = 10
+    assert R.three_maxima(h) == [4, 7, -1]                   # max2 = 10 is not < 10: ind2 stays; max3 = 5 < 10: ind3 goes
+    h[9] = 10
+    assert R.three_maxima(h) == [4, 7, 9]                    # strict >: the first of two equal counts is ind2; max3 = 10 stays
+    h[9] = 9
+    assert R.three_maxima(h) == [4, 7, -1]
+    h[2], h[9] = 100, 10
+    assert R.three_maxima(h) == [2, 4, 7]                    # an equal count later in bin order does not take ind1: it becomes ind2
+    assert R.three_maxima(np.zeros(30, np.int32)) == [-1, -1, -1]
+
+
+# ---- the builders against the restatement ----
+
+def test_init_queries(om):
+    f = rand_frame(120, 5)
+    prev = f["xy"] + F(3.25)
+    got, want = om.init_queries(lib_frame(om, f), prev, 100), R.init_queries(f, prev, 100)
+    for k in want:
+        assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), k
+    assert got["valid"].sum() == (f["octave"] == 0).sum() and 0 < got["valid"].sum() < 120
+    assert np.all(got["level_range"] == 0) and np.all(got["radius"] == F(100))
+
+
+def test_motion_queries(om, err):
+    n = 200
+    f = rand_frame(n, 6, octaves=8)
+    rng = np.random.default_rng(8)
+    X = np.stack([rng.uniform(-8, 8, n), rng.uniform(-5, 5, n), rng.uniform(-2, 20, n)], 1).astype(F)
+    has, outl = (rng.uniform(size=n) < 0.85).astype(np.uint8), (rng.uniform(size=n) < 0.1).astype(np.uint8)
+    T = np.array([[0.9998, -0.0175, 0.01, 0.05], [0.0175, 0.9998, -0.003, -0.02], [-0.01, 0.0032, 0.9999, 0.3]], F)
+    fx, fy, cx, cy = 500.0, 510.0, 320.0, 240.0
+    sf = (F(1.2) ** np.arange(8)).astype(F)
+    # hand cases with the identity pose: behind the camera, exactly on min_x and max_x (kept), just past max_x, zc == 0 (u not finite), octave 0
+    I = np.eye(3, 4, dtype=F)
+    Xh = np.array([[1, 1, -4], [-3.2, 0, 5], [3.2, 0, 5], [3.3, 0, 5], [1, 1, 0], [0, 0, 5]], F)
+    fh = R.make_frame(np.zeros((6, 2)), [1, 2, 3, 1, 1, 0], [0] * 6, np.zeros((6, 32)), BOUNDS)
+    one = np.ones(6, np.uint8)
+    got = om.motion_queries(lib_frame(om, fh), one, 0 * one, Xh, I, fx, fy, cx, cy, BOUNDS, sf, 15.0)
+    assert got["valid"].tolist() == [0, 1, 1, 0, 0, 1]
+    assert got["centre_xy"][1, 0] == F(0.0) and got["centre_xy"][2, 0] == F(640.0)          # 500 * 3.2f * (float)(1 / 5.0) + 320 is exactly 640 in float32
+    assert got["level_range"][5].tolist() == [-1, 1] and got["level_range"][1].tolist() == [1, 3]
+    assert got["radius"][2] == F(F(15.0) * sf[3]) and got["radius"][0] == 0 and got["centre_xy"][0].tolist() == [0, 0]
+    want = R.motion_queries(fh, one, 0 * one, Xh, I, fx, fy, cx, cy, BOUNDS, sf, 15.0)
+    for k in want:
+        assert np.array_equal(got[k], want[k]), k
+    # a seeded frame
+    got = om.motion_queries(lib_frame(om, f), has, outl, X, T, fx, fy, cx, cy, BOUNDS, sf, 15.0)
+    want = R.motion_queries(f, has, outl, X, T, fx, fy, cx, cy, BOUNDS, sf, 15.0)
+    for k in want:
+        assert got[k].dtype == want[k].dtype and np.array_equal(got[k].view(np.uint8), want[k].view(np.uint8)), k
+    assert 20 < got["valid"].sum() < n - 20
+    with pytest.raises(err):
+        om.motion_queries(lib_frame(om, f), has, outl, X, T, fx, fy, cx, cy, BOUNDS, sf[:4], 15.0)       # an octave outside scale_factors
+
+
+def test_chunk_planner(om, err):
+    c = [10, 0, 25, 5, 5, 100, 1]
+    assert om.plan_chunks(c, 1 << 30).tolist() == [0, 7]
+    assert om.plan_chunks(c, 1).tolist() == list(range(8))
+    assert om.plan_chunks(c, 35 * 6).tolist() == [0, 3, 5, 6, 7]
+    with pytest.raises(err):
+        om.plan_chunks([3, -1], 100)
+
+
+# ---- the rules on hand-built jobs (the restatement alone) ----
+
+def flip(d, bits):
+    d = np.array(d, np.uint8).copy()
+    for b in bits:
+        d[b // 8] ^= np.uint8(1 << (b % 8))
+    return d
+
+
+def test_rules_by_hand():
+    base = np.arange(32, dtype=np.uint8)
+    # train: three keypoints in one window at distances 20, 20, 40 from the base descriptor
+    tr = R.make_frame([[100, 100], [101, 100], [102, 100]], [0] * 3, [0, 0, 0], [flip(base, range(20)), flip(base, range(20, 40)), flip(base, range(40))], BOUNDS)
+    qf = R.make_frame([[100, 100]], [0], [0], [base], BOUNDS)
+    job = {"query_frame": 0, "train_frame": 1, "rule": R.CLAIM, "centre_xy": np.array([[100, 100]], F), "radius": np.array([10], F), "level_range": np.array([[-1, -1]], np.int32),
+           "query_index": np.array([0], np.int32), "valid": None}
+    r = R.run_job([qf, tr], job)
+    assert r["cdist"].tolist() == [20, 20, 40] and r["match"].tolist() == [0] and r["dist"].tolist() == [20]      # the first of two equal least distances
+    r = R.run_job([qf, tr], dict(job, rule=R.INIT))
+    assert r["match"].tolist() == [-1] and r["n_ratio_rejected"] == 1                                            # best2 == best: 20 < 20 * 0.9 fails
+    r = R.run_job([qf, tr], dict(job, rule=R.INIT, radius=np.array([1.5], F)), nn_ratio=0.5)                     # candidates 0 and 1 ... |dx| = 1 < 1.5; 2 is at 2
+    assert r["index"].tolist() == [0, 1]
+    tr2 = R.make_frame([[100, 100], [101, 100]], [0] * 2, [0, 0], [flip(base, range(20)), flip(base, range(40))], BOUNDS)
+    r = R.run_job([qf, tr2], dict(job, rule=R.INIT), nn_ratio=0.5)
+    assert r["match"].tolist() == [-1]                                                                           # the ratio tie: 20 < 40 * 0.5 fails
+    r = R.run_job([qf, tr2], dict(job, rule=R.INIT), nn_ratio=0.51)
+    assert r["match"].tolist() == [0]
+    r = R.run_job([qf, tr2], dict(job, rule=R.INIT), th_low=20)
+    assert r["match"].tolist() == [0]
+    r = R.run_job([qf, tr2], dict(job, rule=R.INIT), th_low=19)
+    assert r["match"].tolist() == [-1] and r["n_ratio_rejected"] == 0
+    r = R.run_job([qf, tr2], dict(job), th_high=20)
+    assert r["match"].tolist() == [0]
+    r = R.run_job([qf, tr2], dict(job), th_high=19)
+    assert r["match"].tolist() == [-1]
+    # one candidate alone: best2 = INT_MAX
+    r = R.run_job([qf, R.make_frame([[100, 100]], [0], [0], [flip(base, range(50))], BOUNDS)], dict(job, rule=R.INIT))
+    assert r["match"].tolist() == [0] and r["dist"].tolist() == [50]
