@@ -1170,7 +1170,8 @@ iba_status iba_project_gradient(double zn, uint8_t rgb[3]);                     
  * (cv::fastAtan2). O6's tie rule is stated above. The BRIEF test-pair table is an INPUT (256 x 4 int8: x0 y0 x1 y1 per test); the library ships none.
  * Masks, undistortion and ComputeKeyPointsOld are not provided. Windowed matching is iba_orb_match below; the matchers that remain unprovided are
  * SearchByBoW and SearchForTriangulation (they need the DBoW2 vocabulary), Fuse, SearchBySim3, and the SearchByProjection overloads that take map
- * points or a key frame.
+ * points or a key frame. Two-view initialisation is iba_twoview_init further below; what Tracking::CreateInitialMapMonocular does after a success
+ * (global BA, median-depth scaling) and the >= 100-matches gates around the call are the caller's.
  * DEVICE: one chain per chunk over flat tables (one row per image and level, per 64 x 16 tile, per cell, per keypoint): resize level by level, score,
  * cell count, scan, ordered cell write, the candidates down, O6 on the host, the keypoints up, orientation, blur, descriptor (csrc/iba_orb_kernels.hpp).
  * MEMORY: a chunk of consecutive images takes IBA_ORB_BYTES_PER_PIXEL bytes per pyramid pixel (pyramid, scores, blurred levels, the candidate
@@ -1352,6 +1353,154 @@ iba_status iba_orb_match_motion_queries(const iba_orb_frame* last_frame, const u
                                         const float Tcw12[12] /* the current frame's */, float fx, float fy, float cx, float cy, const float bounds[4] /* the current frame's min_x max_x min_y max_y */,
                                         const float* scale_factors, int32_t n_scale_factors, float th,
                                         float* centre_xy, float* radius, int32_t* level_range, int32_t* query_index, uint8_t* valid);
+
+/*
+ * ---- Two-view initialisation [the camera side's third brick: the reference's Initializer::Initialize and everything it calls
+ * (src/orb_slam/src/Initializer.cc: FindHomography :124, FindFundamental :175, ComputeH21 :226, ComputeF21 :268, CheckHomography :305, CheckFundamental
+ * :390, ReconstructF :470, ReconstructH :572, Triangulate :734, Normalize :749, CheckRT :798, DecomposeE :909)] ----
+ * A call takes B frame pairs on one device. A pair is the positions of both frames, the matches12 array (what iba_orb_matches_read returns in match for
+ * an INIT job built by iba_orb_match_init_queries), the pinhole intrinsics and the RANSAC sets. The MATCH LIST is the pairs (i, matches12[i]) with
+ * matches12[i] >= 0 in ascending i; N is its length. Per pair the call runs `iterations` hypotheses of a homography and of a fundamental matrix, scores
+ * each over every match, picks a model by the score ratio, decomposes it into 8 or 4 motion hypotheses, triangulates every inlier under each and accepts
+ * or refuses the pair. What Tracking::CreateInitialMapMonocular does after a success (global BA, median-depth scaling) and the >= 100-matches gates
+ * around the call are the caller's.
+ * ARITHMETIC. float32 wherever the reference's plain C++ is float, with the C++ promotions of the cited line: 1.0/(...) is a double division rounded to
+ * float; 0.9*N, 0.7*maxGood, 0.75*bestGood and cosParallax<0.99998 compare in double; 4.0*mSigma2 is a double product rounded to float. Every operation
+ * rounded, left to right, no contraction. Every cv::Mat operation (3 x 3 and 3 x 4 products, inv, determinant, norm, dot, the SVDs) is the library's
+ * own restatement in float64 on the widened float32 entries, a fixed sequence of + - x / sqrt; each element that lands in a CV_32F matrix is rounded
+ * once to float32. A product element is ((a0 b0 + a1 b1) + a2 b2); a product of three matrices is two products, left first, the intermediate rounded;
+ * det = (a (e i - f h) - b (d i - f g)) + c (d h - e g); inv = the cofactors, each divided by det; norm = sqrt((x x + y y) + z z). A NaN stored
+ * into Hi, H12i, Fi, a score or a cosine is stored as 0x7FC00000 (devices differ in the NaN they produce; no decision reads its bits).
+ * tests/twoview_ref.py restates T1-T11 in numpy; the device results are compared byte for byte, parallax_deg within one float32 ulp.
+ *
+ *   T1 normalise.  (host, :749-795 exactly) over ALL keypoints of the frame, matched or not: the float32 sums meanX, meanY, meanDevX, meanDevY are
+ *                  sequential in index order; mean = sum / n; sX = (float)(1.0 / meanDevX); out = (x - meanX) * sX; T = [sX 0 -meanX*sX; 0 sY
+ *                  -meanY*sY; 0 0 1].
+ *   T2 null vector. The right singular vector of the least singular value of an m x n matrix (16 x 9, 8 x 9, 4 x 4, 3 x 3) by one-sided (Hestenes)
+ *                  Jacobi in float64: G = the float32 matrix widened, V = I; sweep the pairs p < q in row-cyclic order; alpha = sum g_p^2, beta =
+ *                  sum g_q^2, gamma = sum g_p g_q over the rows in order; skip the pair iff gamma^2 <= alpha beta 2^-104, or alpha or beta <= 2^-104 x (the sum of
+ *                  the squares of the matrix' entries, summed once in row-major order: a column at the rounding level of the matrix is null and rests;
+ *                  without this clause every matrix of rank below n, the 8 x 9 ones, runs to the cap on its vanishing column); else zeta = (beta -
+ *                  alpha) / (2 gamma), t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)) with sign(0) = +1, c = 1 / sqrt(1 + t^2), s = c t;
+ *                  g_p' = c g_p - s g_q, g_q' = s g_p + c g_q, the same for V's columns. Stop after the first sweep that rotates nothing, after 30
+ *                  sweeps at the latest (a debug counter reports that case). The answer is V's column under G's column of least squared norm, the
+ *                  first on a tie, rounded to float32; its sign is whatever falls out (every consumer is sign-invariant or tries both signs). The
+ *                  3 x 3 SVD of T4, T7, T8 is the same routine: w_k = sqrt of the squared column norms, sorted descending (stable), V's columns
+ *                  with them, u_k = G's column / w_k; u_3 = u_1 x u_2 where w_3 <= 2^-23 w_1; u, w, vt rounded to float32.
+ *   T3 H hypothesis. (:226-266, :159-161) A (16 x 9) from the 8 normalised pairs as written; Hn = T2's vector reshaped; H21i = T2inv Hn T1 with
+ *                  T2inv = [1/sx 0 -tx/sx; 0 1/sy -ty/sy; 0 0 1] in closed form; H12i = inv of H21i. A singular H21i gives non-finite entries
+ *                  which T5 scores as IEEE dictates.
+ *   T4 F hypothesis. (:268-303, :212) Fpre from T2 on A (8 x 9); v3 = T2 on Fpre (3 x 3); Fn = Fpre - (Fpre v3) v3^T, which is what
+ *                  u diag(w1, w2, 0) vt equals, without forming u; F21i = T2^T Fn T1.
+ *   T5 scores.     CheckHomography :305-388 and CheckFundamental :390-468 in float32 exactly as written, th = 5.991f (3.841f and 5.991f),
+ *                  invSigmaSquare = (float)(1.0 / (sigma * sigma)); the score is the SEQUENTIAL float32 sum over the matches in list order, the two
+ *                  terms of a match interleaved. The order of that sum is part of the rule: it decides which iteration wins.
+ *   T6 selection.  Per model the first iteration whose score is strictly greater than every earlier one, starting from 0.0f (a NaN score never
+ *                  wins); none: best_it = -1 and the score 0. Its inlier flags are bIn of T5. RH = SH / (SH + SF) in float32 (0 where both are 0);
+ *                  RH > rh_threshold takes the H path (model = 1). The chosen path's model having no iteration is status NO_MODEL.
+ *   T7 motion from F. (:478-497, :909-929) E = K^T F K; the SVD of T2; t = u_3 / norm(u_3); R1 = U W Vt, R2 = U W^T Vt with W = [0 -1 0; 1 0 0;
+ *                  0 0 1], each negated where its determinant is < 0. Hypotheses (R1, t), (R2, t), (R1, -t), (R2, -t) in that order.
+ *   T8 motion from H. (:584-686 as written: Faugeras, 8 hypotheses, float32 scalars) A = inv(K) H21 K; the SVD of T2; s = (float)(det U * det Vt);
+ *                  the early refusal (double)(d1/d2) < 1.00001 || (double)(d2/d3) < 1.00001 is status H_DEGENERATE; R = ((s U) Rp) Vt with s U
+ *                  elementwise in float32; tp scaled in float32, t = U tp divided by its norm. The plane normals are not computed: nothing reads them.
+ *   T9 CheckRT.    (:798-907, :734-747) per (motion hypothesis, inlier match of the chosen model): P1 = K [I | 0], P2 = K [R | t], O2 = -R^T t;
+ *                  A's rows in float32 as written (x * P.row(2) - P.row(0), ...); x = T2 on A (4 x 4); p = x / x_3 in float32; then, in this order,
+ *                  verdict 1: p not finite; dist1, dist2 (float32 of the float64 norms), cosParallax = (float)(dot / (double)(dist1 * dist2));
+ *                  2: p_z <= 0 && cos < 0.99998; p2 = R p + t (one rounding per element); 3: p2_z <= 0 && cos < 0.99998; 4: squareError1 > th2;
+ *                  5: squareError2 > th2 with th2 = (float)(4.0 * sigma^2); 6: good. 0 is a match that is no inlier of the chosen model. n_good
+ *                  counts verdict 6. points is written for every good match, triangulated only where cos < 0.99998 as well: the reference's
+ *                  behaviour. cos_parallax = the good cosines' value at sorted position min(50, n_good - 1) (ascending; 1.0f where n_good == 0,
+ *                  which gives the reference's parallax 0); parallax_deg = (float)(acos((double)c) * 180 / pi), computed on the HOST.
+ *   T10 acceptance. ReconstructF :499-569 and ReconstructH :689-731 as written: nMinGood = max((int)(0.9 * N), min_triangulated) with N = the chosen
+ *                  model's inliers, nsimilar over n_good > 0.7 * maxGood, the else-if chain on equal counts (the FIRST hypothesis at maxGood),
+ *                  parallax > min_parallax_deg in the first and >= in the second, secondBestGood < 0.75 * bestGood, bestGood > min_triangulated,
+ *                  bestGood > 0.9 * N.
+ *   T11 status.    OK; TOO_FEW_MATCHES (N < 8: the reference would draw from an empty list; the library's own rule, decided on the host);
+ *                  NO_MODEL (T6); H_DEGENERATE (T8); NO_CLEAR_WINNER; TOO_FEW_POINTS; LOW_PARALLAX. Where the reference's single return false
+ *                  covers several reasons the order of the tests in its code decides: F path maxGood < nMinGood (TOO_FEW_POINTS), nsimilar > 1
+ *                  (NO_CLEAR_WINNER), the parallax (LOW_PARALLAX); H path the second-best test (NO_CLEAR_WINNER), the parallax (LOW_PARALLAX), the
+ *                  two count tests (TOO_FEW_POINTS). chosen is the hypothesis whose parallax was tested (status OK, LOW_PARALLAX, or the H path's
+ *                  TOO_FEW_POINTS), else -1. R21, t21, points and triangulated are zeros unless the status is OK; n_hyp is 0 where T7 / T8 were
+ *                  not reached or refused.
+ *
+ * UNPINNED, together: every cv::Mat operation named under ARITHMETIC (OpenCV's gemm, inv, determinant, norm and its Jacobi SVD may round and order
+ * otherwise; nothing here is compared with recorded OpenCV output), hence T2, and what T3, T4, T7, T8 and T9 build on it; the sign of every null
+ * vector; the sets of iba_twoview_sets (the reference draws from DUtils::Random, C rand(), which is not vendored; sets is an INPUT so a caller can
+ * hand in the reference's own); acos of the host's libm in parallax_deg; TOO_FEW_MATCHES. KNOWN DEVIATION: the reference compares RH with the double
+ * 0.40, the library with the float32 option (0.40f): they differ for RH == 0.40f alone.
+ * DEVICE (csrc/iba_twoview_kernels.hpp), one launch chain per chunk of pairs: hypotheses (one lane per (pair, iteration, model), T2's work matrices
+ * in a lane-minor LDS slab); scores (one lane per hypothesis, a wave = 64 hypotheses of one pair and model, the match coordinates wave-uniform;
+ * the sum stays in a register and is never reduced across lanes); selection (one wave per (pair, model), then the winner's inlier flags); motion
+ * hypotheses (one lane per pair); CheckRT (one lane per (pair, hypothesis, match); n_good by ballot and integer atomics); the k-th cosine by a
+ * radix select on the ordered keys (integer histograms in LDS); acceptance (one lane per pair); without keep_stages a gather of the candidate
+ * hypothesis' per-match entries, so that only those come down. Only integer counts are combined by atomics. A
+ * pair goes up once (32 bytes per match, 32 per set) and comes down once; T1, the set check and TOO_FEW_MATCHES are the host's before the device is touched.
+ * ERRORS, all IBA_ERR_INVALID_ARG with a message (iba_twoview_last_error, per thread) BEFORE the device is touched: a NULL argument (a frame's arrays
+ * may be NULL only where its n == 0; sets only where N < 8) or a wrong struct_size; B < 1; n1 or n2 < 0 or above IBA_ORB_MATCH_MAX_KEYPOINTS; a
+ * match index >= n2; a position that is not finite; fx or fy not finite or <= 0, cx or cy not finite; sigma not finite or <= 0; iterations outside
+ * 1..IBA_TWOVIEW_MAX_ITERATIONS; a set index outside [0, N) or repeated inside its set, for pairs with N >= 8; min_triangulated < 0; a threshold that
+ * is not finite; a pair or hypothesis index outside the result; a stage accessor on a result without keep_stages. A pair with N < 8 is legal
+ * (status), and so is n1 == 0.
+ */
+#define IBA_TWOVIEW_MAX_ITERATIONS 4096
+typedef enum iba_twoview_status {
+    IBA_TWOVIEW_OK = 0, IBA_TWOVIEW_TOO_FEW_MATCHES = 1, IBA_TWOVIEW_NO_MODEL = 2, IBA_TWOVIEW_H_DEGENERATE = 3, IBA_TWOVIEW_NO_CLEAR_WINNER = 4,
+    IBA_TWOVIEW_TOO_FEW_POINTS = 5, IBA_TWOVIEW_LOW_PARALLAX = 6
+} iba_twoview_status;
+typedef struct iba_twoview_pair {             /* host pointers, read during the call only */
+    const float*   xy1;        /* n1 x 2 */
+    const float*   xy2;        /* n2 x 2 */
+    const int32_t* matches12;  /* n1: an index into frame 2, or < 0 */
+    const int32_t* sets;       /* iterations x 8 indices into the match list, distinct inside a set (iba_twoview_sets); NULL only where N < 8 */
+    int32_t n1, n2;
+    float fx, fy, cx, cy;
+} iba_twoview_pair;
+typedef struct iba_twoview_options {
+    int32_t struct_size;        /* sizeof(iba_twoview_options) */
+    float   sigma;              /* 1.0f */
+    int32_t iterations;         /* 200, 1..IBA_TWOVIEW_MAX_ITERATIONS */
+    float   min_parallax_deg;   /* 1.0f */
+    int32_t min_triangulated;   /* 50 */
+    float   rh_threshold;       /* 0.40f */
+    int32_t keep_stages;        /* 0; 1 keeps every iteration's matrices and scores and every motion hypothesis' points and verdicts */
+} iba_twoview_options;
+typedef struct iba_twoview_result {
+    int32_t status;             /* iba_twoview_status */
+    int32_t n_matches;          /* N */
+    int32_t model;              /* 0 = F, 1 = H */
+    int32_t n_hyp;              /* 4, 8, or 0 */
+    int32_t chosen;             /* -1: none */
+    int32_t best_it_H, best_it_F;   /* -1: none */
+    int32_t n_inliers_H, n_inliers_F;
+    float SH, SF, RH;
+    float H21[9], F21[9];
+    int32_t n_good[8];
+    float cos_parallax[8], parallax_deg[8];
+    float R21[9], t21[3];
+} iba_twoview_result;
+typedef struct iba_twoview_batch iba_twoview_batch;
+iba_status iba_default_twoview_options(iba_twoview_options* opt);
+const char* iba_twoview_last_error(void);                            /* never NULL; of this thread's last iba_twoview* call that failed */
+/* *out is NULL on failure; release it with iba_twoview_free */
+iba_status iba_twoview_init(const iba_twoview_pair* pairs, int32_t B, const iba_twoview_options* opt, int device, iba_twoview_batch** out);
+void       iba_twoview_free(iba_twoview_batch* r);
+int32_t    iba_twoview_n_pairs(const iba_twoview_batch* r);          /* 0 for NULL */
+iba_status iba_twoview_read(const iba_twoview_batch* r, int32_t pair, iba_twoview_result* result);
+/* the match list (N x 2: index in frame 1, index in frame 2) and the chosen model's inlier flags (N bytes); either may be NULL */
+iba_status iba_twoview_matches(const iba_twoview_batch* r, int32_t pair, int32_t* list, uint8_t* inlier);
+/* of the chosen motion hypothesis, indexed by the keypoint of frame 1: points n1 x 3, triangulated n1 bytes; either may be NULL */
+iba_status iba_twoview_points(const iba_twoview_batch* r, int32_t pair, float* points, uint8_t* triangulated);
+/* stage accessors, keep_stages only; every output may be NULL. Per iteration Hi, H12i, Fi (iterations x 9 each) and the two scores (iterations each);
+ * zeros for a pair with N < 8. Per motion hypothesis (0 <= hyp < 8; zeros at or above n_hyp) R, t, n_good, and per match of the list the triangulated
+ * point (N x 3, zeros for verdicts 0 and 1) and the verdict code of T9 (N bytes). */
+iba_status iba_twoview_iterations(const iba_twoview_batch* r, int32_t pair, float* Hi, float* H12i, float* Fi, float* score_H, float* score_F);
+iba_status iba_twoview_hypothesis(const iba_twoview_batch* r, int32_t pair, int32_t hyp, float R[9], float t[3], int32_t* n_good, float* points, uint8_t* verdict);
+/* host only, pure functions (precedents: iba_orb_plan, iba_orb_match_init_queries). T1 on n >= 0 positions: out_xy n x 2 and T (3 x 3 row-major);
+ * n == 0 gives a T that is not finite, as the reference's would be. */
+iba_status iba_twoview_normalize(const float* xy, int32_t n, float* out_xy, float T[9]);
+/* the reference's draw-without-replacement loop (:82-97: swap with back, pop) over the library's OWN generator, splitmix64 on seed with
+ * randi = next() % size (UNPINNED, see above): out takes iterations x 8 indices into a match list of N >= 8 entries */
+iba_status iba_twoview_sets(int32_t N, int32_t iterations, uint64_t seed, int32_t* out);
 
 /* The ABI version the LIBRARY was built with (IBA_ABI_VERSION of its header). iba_params carries no struct_size: a caller compiled against
  * an older header would pass a shorter struct. Callers compare iba_abi_version() with their own IBA_ABI_VERSION before iba_create(). */

@@ -51,6 +51,8 @@
  *                                                         iba_debug_orb_stage_ms; tools/orb_bench.py); same results
  *   IBA_ORB_MATCH_BUDGET, IBA_ORB_MATCH_TIMING            the same two for iba_orb_match (6 bytes per candidate-list entry; iba_debug_orb_match_chunks,
  *                                                         iba_debug_orb_match_stage_ms; tools/orb_match_bench.py); same results
+ *   IBA_TWOVIEW_BUDGET, IBA_TWOVIEW_TIMING                the same two for iba_twoview_init (187 bytes per match and 148 per iteration of a pair; iba_debug_twoview_stage_ms;
+ *                                                         tools/twoview_bench.py); same results
  *   IBA_GROUP_REDUCE_HOST (flag of iba_group_create_ex, not a variable), IBA_DEBUG_FAIL_RANK / IBA_DEBUG_FAIL_PHASE: inject one
  *                                                         failure into a group's evaluation (tests of the fail-not-hang path)
  */
@@ -257,6 +259,18 @@ iba_status iba_debug_orb_match_stage_ms(const iba_orb_matches* m, float ms[4]);
 /* debug, host only: the chunk planner on its own: the cut of n_jobs jobs with the given candidate counts under budget bytes; cut receives *n_cut
  * <= n_jobs + 1 ascending job indices, the first 0 and the last n_jobs */
 iba_status iba_debug_orb_match_plan(const int64_t* candidates, int32_t n_jobs, uint64_t budget, int32_t* cut, int32_t* n_cut);
+/* debug, host only: the whole of iba_twoview_init through the host restatement of its rules (csrc/iba_twoview_host.hpp over the arithmetic the
+ * kernels compile, csrc/iba_twoview_math.hpp), no device; the same checks, the same result object and accessors */
+iba_status iba_debug_twoview_host(const iba_twoview_pair* pairs, int32_t B, const iba_twoview_options* opt, iba_twoview_batch** out);
+/* debug, host only: rule T2 on its own on a row-major float32 matrix of 16 x 9, 8 x 9, 4 x 4 or 3 x 3: v takes n entries, *sweeps the sweeps
+ * that rotated (30: the cap was reached); v64 (n entries, may be NULL) the float64 column v was rounded from */
+iba_status iba_debug_twoview_null_vector(const float* A, int32_t m, int32_t n, float* v, double* v64, int32_t* sweeps);
+/* debug: the null-vector solves of the call behind r whose 30th sweep still rotated; 0 for NULL */
+int32_t iba_debug_twoview_sweep_cap_hits(const iba_twoview_batch* r);
+/* debug: with IBA_TWOVIEW_TIMING set at the call (under IBA_DEBUG_ENV=1), times in ms from HIP events, summed over the chunks: [0] hypotheses,
+ * [1] scores, [2] selection, [3] motion hypotheses, [4] CheckRT, [5] the k-th cosine, [6] acceptance (with the gather of the candidate hypothesis' entries where the stages are not kept). Zeros without the variable and for
+ * iba_debug_twoview_host. Same results. IBA_TWOVIEW_BUDGET: the bytes a chunk of pairs may take on the device in place of 1 GiB (same results). */
+iba_status iba_debug_twoview_stage_ms(const iba_twoview_batch* r, float ms[7]);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,273 @@
+"""Two-view initialisation, without a device (include/iba_mi355x.h, iba_twoview*): the symbols and layouts, every argument check through the C ABI,
+the two host builders and the whole call through the host restatement (iba_debug_twoview_host) against tests/twoview_ref.py byte for byte, rule T2
+on its own against numpy's float64 SVD, and the conditions the scene list itself must meet."""
+import ctypes as C
+import importlib
+import re
+
+import numpy as np
+import pytest
+
+import twoview_ref as R
+import twoview_scene as S
+
+PKG = "spatial-temporal-lidar-camera-calibration_amd"
+F = np.float32
+
+
+@pytest.fixture(scope="module")
+def tv():
+    importlib.import_module(PKG)
+    return importlib.import_module(PKG + ".twoview")
+
+
+@pytest.fixture(scope="module")
+def err():
+    return importlib.import_module(PKG).IbaError
+
+
+def lib_pair(tv, p):
+    return tv.pair(p["xy1"], p["xy2"], p["matches12"], p["K"], p.get("sets"))
+
+
+# ---- symbols, layouts, ABI ----
+
+def test_symbols_and_layouts(tv):
+    L = tv._lib()
+    names = ("iba_default_twoview_options", "iba_twoview_last_error", "iba_twoview_init", "iba_twoview_free", "iba_twoview_n_pairs", "iba_twoview_read", "iba_twoview_matches",
+             "iba_twoview_points", "iba_twoview_iterations", "iba_twoview_hypothesis", "iba_twoview_normalize", "iba_twoview_sets", "iba_debug_twoview_host",
+             "iba_debug_twoview_null_vector", "iba_debug_twoview_sweep_cap_hits", "iba_debug_twoview_stage_ms")
+    pkg = importlib.import_module(PKG)
+    hdr = "".join(open(p).read() for p in pkg.HEADER_PATHS)
+    for name in names:
+        getattr(L, name)
+        assert re.search(r"\b%s\s*\(" % name, hdr), name + " is not declared"
+    assert L.iba_abi_version() == 4 and re.search(r"#define\s+IBA_ABI_VERSION\s+4\b", hdr)
+    o = tv.options()
+    assert (o.struct_size, o.iterations, o.min_triangulated, o.keep_stages) == (C.sizeof(tv.IbaTwoviewOptions), 200, 50, 0)
+    assert (o.sigma, o.min_parallax_deg, o.rh_threshold) == (F(1.0), F(1.0), F(0.40))
+    assert C.sizeof(tv.IbaTwoviewOptions) == 28 and C.sizeof(tv.IbaTwoviewPair) == 56 and tv.IbaTwoviewPair.n1.offset == 32 and tv.IbaTwoviewPair.cy.offset == 52
+    assert C.sizeof(tv.IbaTwoviewResult) == 4 * (9 + 3 + 18 + 24 + 12) and tv.IbaTwoviewResult.H21.offset == 48 and tv.IbaTwoviewResult.R21.offset == 216
+    assert L.iba_twoview_last_error() is not None and L.iba_twoview_n_pairs(None) == 0 and L.iba_debug_twoview_sweep_cap_hits(None) == 0
+    for k in range(1, 12):
+        assert re.search(r"\bT%d " % k, hdr), "rule T%d is not stated" % k
+    assert "UNPINNED, together" in hdr and "CreateInitialMapMonocular" in hdr
+
+
+# ---- argument checks: all before the device is touched (device -1 would answer with another status) ----
+
+def _expect(err, fn, text):
+    with pytest.raises(err) as e:
+        fn()
+    assert e.value.status == 1, str(e.value)
+    assert text in str(e.value), str(e.value)
+
+
+@pytest.fixture(scope="module")
+def good():
+    return S.with_sets(S.make_pair(3, n=40, outliers=0.0), 20, 5)
+
+
+def _variant(p, **kw):
+    q = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in p.items()}
+    q.update(kw)
+    return q
+
+
+def test_argument_checks(tv, err, good):
+    L = tv._lib()
+    call = lambda p, **f: tv.init([lib_pair(tv, p)], device=-1, **dict(dict(iterations=20), **f))
+    with pytest.raises(err) as e:                       # a good call reaches the device: it fails on the device number, not on an argument
+        call(good)
+    assert e.value.status != 1
+    _expect(err, lambda: tv.init([], device=-1), "B < 1")
+    o, out = tv.options(), C.c_void_p(None)
+    assert L.iba_twoview_init(None, 1, C.addressof(o), -1, C.addressof(out)) == 1 and b"pairs is NULL" in L.iba_twoview_last_error()
+    pa = lib_pair(tv, good)
+    assert L.iba_twoview_init(C.addressof(pa), 1, None, -1, C.addressof(out)) == 1 and b"opt is NULL" in L.iba_twoview_last_error()
+    assert L.iba_twoview_init(C.addressof(pa), 1, C.addressof(o), -1, None) == 1 and b"out is NULL" in L.iba_twoview_last_error()
+    assert L.iba_default_twoview_options(None) == 1
+    _expect(err, lambda: call(good, struct_size=24), "struct_size")
+    for v in (0.0, -1.0, np.nan, np.inf):
+        _expect(err, lambda: call(good, sigma=v), "sigma")
+    for v in (0, -3, tv.MAX_ITERATIONS + 1):
+        _expect(err, lambda: call(good, iterations=v), "iterations")
+    _expect(err, lambda: call(good, min_triangulated=-1), "min_triangulated")
+    _expect(err, lambda: call(good, min_parallax_deg=np.nan), "min_parallax_deg")
+    _expect(err, lambda: call(good, rh_threshold=np.inf), "rh_threshold")
+    for k, v in (("fx", 0.0), ("fx", np.nan), ("fy", -700.0), ("fy", np.inf)):
+        K = dict(zip(("fx", "fy", "cx", "cy"), good["K"]))
+        K[k] = v
+        _expect(err, lambda: call(_variant(good, K=tuple(K.values()))), "fx or fy")
+    _expect(err, lambda: call(_variant(good, K=(700, 700, np.nan, 188))), "cx or cy")
+    _expect(err, lambda: call(_variant(good, K=(700, 700, 620, -np.inf))), "cx or cy")
+    m = good["matches12"].copy()
+    m[int(np.nonzero(m >= 0)[0][0])] = len(good["xy2"])
+    _expect(err, lambda: call(_variant(good, matches12=m)), "matches12[")
+    for key, text in (("xy1", "frame 1"), ("xy2", "frame 2")):
+        for v in (np.nan, np.inf):
+            a = good[key].copy()
+            a[7, 1] = v
+            _expect(err, lambda: call(_variant(good, **{key: a})), "keypoint 7 of " + text)
+    N = S.n_matches(good)
+    for v, text in ((-1, "holds -1"), (N, "holds %d" % N)):
+        s = good["sets"].copy()
+        s[3, 2] = v
+        _expect(err, lambda: call(_variant(good, sets=s)), text)
+    s = good["sets"].copy()
+    s[4, 6] = s[4, 1]
+    _expect(err, lambda: call(_variant(good, sets=s)), "twice")
+    _expect(err, lambda: call(_variant(good, sets=None)), "sets is NULL")
+    # struct fields a Python wrapper cannot make wrong by construction
+    p = lib_pair(tv, good)
+    for field, v, text in (("n1", -1, "n1"), ("n2", -1, "n2"), ("n1", 32769, "n1"), ("n2", 32769, "n2")):
+        q = lib_pair(tv, good)
+        setattr(q, field, v)
+        assert L.iba_twoview_init(C.addressof(q), 1, C.addressof(tv.options(iterations=20)), -1, C.addressof(out)) == 1 and text.encode() in L.iba_twoview_last_error()
+    for field in ("xy1", "xy2", "matches12"):
+        q = lib_pair(tv, good)
+        setattr(q, field, None)
+        assert L.iba_twoview_init(C.addressof(q), 1, C.addressof(tv.options(iterations=20)), -1, C.addressof(out)) == 1 and b"NULL" in L.iba_twoview_last_error()
+    del p
+
+
+def test_accessor_checks_and_legal_small_pairs(tv, err):
+    few = S.make_pair(6, n=9, unmatched=0.5, outliers=0.0)                  # N < 8: legal, sets may be NULL
+    empty = {"xy1": np.zeros((0, 2), F), "xy2": np.zeros((5, 2), F), "matches12": np.zeros(0, np.int32), "K": S.K4}
+    r = tv.init_host([lib_pair(tv, few), lib_pair(tv, empty)], iterations=10)
+    assert len(r) == 2 and r.read(0)["status"] == R.TOO_FEW_MATCHES and r.read(1)["status"] == R.TOO_FEW_MATCHES and r.read(1)["n_matches"] == 0
+    assert r.read(0)["chosen"] == -1 and r.read(0)["best_it_H"] == -1 and not r.points(0)[0].any() and r.points(1)[0].shape == (0, 3)
+    for fn in (lambda: r.read(2), lambda: r.read(-1), lambda: r.matches(2), lambda: r.points(-1)):
+        _expect(err, fn, "outside the result")
+    _expect(err, lambda: r.iterations_of(0), "keep_stages")
+    _expect(err, lambda: r.hypothesis(0, 0), "keep_stages")
+    r.close()
+    r = tv.init_host([lib_pair(tv, few)], iterations=10, keep_stages=1)
+    _expect(err, lambda: r.hypothesis(0, 8), "outside 0..7")
+    _expect(err, lambda: r.hypothesis(0, -1), "outside 0..7")
+    _expect(err, lambda: r.iterations_of(1), "outside the result")
+    assert not r.iterations_of(0)["Hi"].any() and not r.hypothesis(0, 3)["verdict"].any()
+    r.close()
+    L = tv._lib()
+    assert L.iba_twoview_read(None, 0, None) == 1 and L.iba_debug_twoview_stage_ms(None, None) == 1
+
+
+# ---- the two host builders ----
+
+def test_normalize_against_reference(tv, err):
+    rng = np.random.default_rng(11)
+    for n in (1, 2, 7, 300, 2001):
+        xy = np.stack([rng.uniform(0, S.W, n), rng.uniform(0, S.H, n)], 1).astype(F)
+        out, T = tv.normalize(xy)
+        eo, eT = R.normalize(xy)
+        if n > 1:                                       # one point: the deviations are 0, the scale infinite and 0 * inf a NaN whose sign is the machine's
+            assert out.tobytes() == eo.tobytes(), n
+        assert np.array_equal(T.view(np.uint32)[~np.isnan(T)], eT.view(np.uint32)[~np.isnan(eT)]), n
+    xy = np.array([[1, 1], [3, 5], [1, 5], [3, 1]], F)   # means 2 and 3, mean deviations 1 and 2
+    out, T = tv.normalize(xy)
+    assert np.array_equal(T, np.array([[1, 0, -2], [0, 0.5, -1.5], [0, 0, 1]], F)) and np.array_equal(out, np.array([[-1, -1], [1, 1], [-1, 1], [1, -1]], F))
+    bad = xy.copy()
+    bad[2, 0] = np.nan
+    _expect(err, lambda: tv.normalize(bad), "not finite")
+    assert tv._lib().iba_twoview_normalize(None, 3, None, None) == 1
+
+
+def test_sets_against_reference(tv, err):
+    for N, it, seed in ((8, 50, 1), (9, 40, 2), (300, 200, 1000), (32768, 3, 2 ** 64 - 1)):
+        s = tv.sets(N, it, seed)
+        assert s.tobytes() == R.make_sets(N, it, seed).tobytes(), (N, it, seed)
+        assert s.min() >= 0 and s.max() < N and all(len(set(row)) == 8 for row in s.tolist())
+        if N == 8:
+            assert all(sorted(row) == list(range(8)) for row in s.tolist())
+    assert not np.array_equal(tv.sets(100, 10, 1), tv.sets(100, 10, 2))
+    _expect(err, lambda: tv.sets(7, 10, 1), "N = 7")
+    _expect(err, lambda: tv.sets(8, 0, 1), "iterations")
+    _expect(err, lambda: tv.sets(8, tv.MAX_ITERATIONS + 1, 1), "iterations")
+    assert tv._lib().iba_twoview_sets(8, 1, 0, None) == 1
+
+
+# ---- T2 on its own against numpy's float64 SVD, on the design matrices of the scenes ----
+
+def _design_matrices():
+    """every 16 x 9 and 8 x 9 design matrix of the scene list (the scene whose T1 is not finite has none that an SVD could take), and the 4 x 4
+    triangulation matrices of the accepted general scene's chosen hypothesis"""
+    out = []
+    for (name, _, _, _), p in zip(S.SCENES, S.scene_pairs()):
+        if p["sets"] is None or name == "no_model":
+            continue
+        lst = np.nonzero(p["matches12"] >= 0)[0]
+        mn = np.concatenate([R.normalize(p["xy1"])[0][lst], R.normalize(p["xy2"])[0][p["matches12"][lst]]], 1)
+        pn = mn[p["sets"]]
+        out += list(R.design_h(pn)) + list(R.design_f(pn))
+    return out
+
+
+def test_null_vector_against_numpy_svd(tv):
+    eps = 2.0 ** -52
+    mats = _design_matrices()
+    assert len(mats) == 2 * 6 * S.ITERATIONS
+    worst = 0.0
+    for A in mats:
+        v, v64, sweeps = tv.null_vector(A)
+        assert sweeps < R.MAX_SWEEPS, "the sweep cap was reached"
+        sv = np.linalg.svd(A.astype(np.float64), compute_uv=False)
+        smin = sv[-1] if A.shape[0] >= A.shape[1] else 0.0          # a wide matrix has a null space: its least singular value is 0
+        assert np.array_equal(v64.astype(F), v)                     # the bound is float64's: it is the float64 vector that meets it
+        res = abs(np.linalg.norm(A.astype(np.float64) @ v64) - smin)
+        assert res <= 256 * eps * sv[0], (res, sv[0])
+        assert abs(np.linalg.norm(v64) - 1.0) <= 256 * eps
+        worst = max(worst, res / sv[0])
+    ev, esw = R.null_vector(np.stack(mats[:S.ITERATIONS]))           # and the reference's T2 is the library's, byte for byte
+    assert all(np.array_equal(tv.null_vector(A)[0], ev[i]) and tv.null_vector(A)[2] == esw[i] for i, A in enumerate(mats[:S.ITERATIONS]))
+    print("T2: worst |norm(A v) - sigma_min| / sigma_max = %.3g (bound %.3g) over %d matrices" % (worst, 256 * eps, len(mats)))
+    A = np.diag(np.array([3, 1, 2, 0.5], F))            # a known answer: the least column is the fourth
+    v, _, sweeps = tv.null_vector(A)
+    assert sweeps == 0 and np.array_equal(np.abs(v), np.array([0, 0, 0, 1], F))
+    with pytest.raises(Exception):
+        tv.null_vector(np.zeros((5, 5), F))
+
+
+# ---- the whole call on the host against the reference ----
+
+def test_scene_list_conditions_on_the_reference():
+    refs = S.scene_reference()
+    got = [e["status"] for e in refs]
+    assert got == [st for _, st, _, _ in S.SCENES], got
+    for (name, _, model, _), e in zip(S.SCENES, refs):
+        assert model is None or e["model"] == model, name
+    assert any(e["status"] == R.OK and e["model"] == 0 for e in refs) and any(e["status"] == R.OK and e["model"] == 1 for e in refs)
+    for st in (R.H_DEGENERATE, R.NO_CLEAR_WINNER, R.TOO_FEW_POINTS, R.LOW_PARALLAX, R.TOO_FEW_MATCHES, R.NO_MODEL):
+        assert st in got
+    for e in refs:
+        if e["status"] in (R.OK, R.LOW_PARALLAX):       # acos' one-ulp freedom must not be able to flip a status
+            assert abs(float(e["parallax_deg"][e["chosen"]]) - 1.0) > 1e-3
+        if e["status"] == R.OK:
+            assert e["triangulated"].sum() > 50 and abs(float(e["t21"][0])) > 0.9 and np.all(e["points"][e["triangulated"] > 0, 2] > 0)
+    ok = refs[0]
+    assert 4.0 < ok["parallax_deg"][ok["chosen"]] < 6.0 and 0.03 < ok["RH"] < 0.2 and 0.4 < refs[1]["RH"] < 0.6
+
+
+def test_host_restatement_equals_reference(tv):
+    pairs, refs = S.scene_pairs(), S.scene_reference()
+    r = tv.init_host([lib_pair(tv, p) for p in pairs], iterations=S.ITERATIONS, keep_stages=1)
+    assert len(r) == len(refs)
+    for b, ((name, _, _, _), e) in enumerate(zip(S.SCENES, refs)):
+        assert S.differences(r, b, e) == [], name
+    assert r.sweep_cap_hits == sum(e["sweep_cap_hits"] for e in refs) and not r.stage_ms.any()
+    r.close()
+    r = tv.init_host([lib_pair(tv, p) for p in pairs], iterations=S.ITERATIONS)          # without the stages: the same outputs
+    for b, e in enumerate(refs):
+        assert S.differences(r, b, e, stages=False) == [], S.SCENES[b][0]
+    r.close()
+
+
+def test_host_options_reach_the_rules(tv):
+    p = S.scene_pairs()[0]
+    for opts in (dict(sigma=0.5), dict(min_parallax_deg=30.0), dict(min_triangulated=250), dict(rh_threshold=0.01)):
+        e = S.reference(p, S.ITERATIONS, **opts)
+        r = tv.init_host([lib_pair(tv, p)], iterations=S.ITERATIONS, keep_stages=1, **opts)
+        assert S.differences(r, 0, e) == [], opts
+        r.close()
+    assert S.reference(p, S.ITERATIONS, min_parallax_deg=30.0)["status"] == R.LOW_PARALLAX
+    assert S.reference(p, S.ITERATIONS, min_triangulated=250)["status"] == R.TOO_FEW_POINTS
+    assert S.reference(p, S.ITERATIONS, rh_threshold=0.01)["model"] == 1
