@@ -1502,6 +1502,131 @@ iba_status iba_twoview_normalize(const float* xy, int32_t n, float* out_xy, floa
  * randi = next() % size (UNPINNED, see above): out takes iterations x 8 indices into a match list of N >= 8 entries */
 iba_status iba_twoview_sets(int32_t N, int32_t iterations, uint64_t seed, int32_t* out);
 
+/*
+ * ---- Motion-only pose optimisation [the camera side's fourth brick: the reference's Optimizer::PoseOptimization (src/orb_slam/src/Optimizer.cc:409-616),
+ * which its tracker calls after every windowed match: TrackWithMotionModel, TrackReferenceKeyFrame, TrackLocalMap, and up to three times per
+ * candidate in Relocalization (Tracking.cc:774, 897, 939, 1470-1501)] ----
+ * A call takes B independent jobs on one device. A job is a start pose Tcw (3 x 4 row-major, float64), n 3D-2D edges (world point, undistorted
+ * keypoint position, the information of the keypoint's pyramid level) and the pinhole intrinsics. Per job the WHOLE schedule - `rounds` rounds of up
+ * to `iterations` Levenberg-Marquardt iterations of up to 10 trials each, the inlier / outlier classification between the rounds - runs inside one
+ * kernel: the host does nothing between the upload and the download. Only monocular edges (EdgeSE3ProjectXYZOnlyPose) are built: this pipeline has
+ * mvuRight < 0 everywhere; STEREO EDGES ARE NOT PROVIDED.
+ * ARITHMETIC. float64 on the widened float32 inputs; every operation rounded, left to right as written, no contraction, nothing but + - x / sqrt up
+ * to a step of theta = pi (P6). A NaN stored into an output is stored as the canonical quiet NaN (0x7FF8000000000000, 0x7FC00000).
+ * tests/pose_ref.py restates P1-P8 in numpy; device, host restatement (iba_debug_pose_host) and numpy agree byte for byte.
+ *
+ *   P1 edge.       p = R X + t: p_x = ((T00 X + T01 Y) + T02 Z) + T03, p_y and p_z likewise with rows 1 and 2. e_x = obs_x - ((fx p_x) / p_z + cx),
+ *                  e_y = obs_y - ((fy p_y) / p_z + cy). chi2 = inv_sigma2 (e_x e_x + e_y e_y). The Jacobian is the analytic 2 x 6 of
+ *                  EdgeSE3ProjectXYZOnlyPose::linearizeOplus, rotation columns first, with iz = 1 / p_z and iz2 = iz iz:
+ *                    J00 = ((p_x p_y) iz2) fx   J01 = (-(1 + (p_x p_x) iz2)) fx   J02 = (p_y iz) fx      J03 = (-iz) fx   J04 = 0          J05 = (p_x iz2) fx
+ *                    J10 = (1 + (p_y p_y) iz2) fy   J11 = (-((p_x p_y) iz2)) fy   J12 = (-(p_x iz)) fy   J13 = 0          J14 = (-iz) fy   J15 = (p_y iz2) fy
+ *                  p_z <= 0 is NOT tested, because the reference does not test it: the non-finite chi2 that follows makes a trial fail (P5) as
+ *                  IEEE dictates.
+ *   P2 Huber.      As BaseUnaryEdge::constructQuadraticForm applies RobustKernelHuber: dsqr = delta delta; chi2 > dsqr: sq = sqrt(chi2), rho = (2 sq)
+ *                  delta - dsqr, rho' = delta / sq; else (and in a round without the kernel) rho = chi2, rho' = 1. w = rho' inv_sigma2 scales the
+ *                  information: H_pq += w (J0p J0q + J1p J1q) for p <= q, b_p -= w (J0p e_x + J1p e_y), with the zeros of J as literal factors; the
+ *                  chi2 sum takes rho. The same way as iba_ba.
+ *   P3 sums.       21 (H, upper triangle by rows) + 6 (b) + 1 (robust chi2) sums per linearisation; a trial takes the chi2 sum alone. The order is
+ *                  a function of n alone: edge i belongs to lane i mod 256; a lane adds its ACTIVE edges in ascending index onto +0.0; the 256 lane
+ *                  sums are combined by the balanced binary tree v[l] = v[2l] + v[2l + 1], eight levels. (Six levels are a wave's DPP sum, two the
+ *                  four waves' partial sums through LDS.) It does not depend on the chunk, the grid, or whether the job's edges sat on chip.
+ *   P4 solve.      A = H with lambda added on the diagonal; A dx = b by ldlt6_factor / ldlt6_apply (LDL^T without pivoting, the library's own; a pivot
+ *                  that is not positive and finite fails). A failed factorisation is a failed trial with chi2 = DBL_MAX.
+ *   P5 LM.         g2o's OptimizationAlgorithmLevenberg as iba_ba restates it. Iteration 0: lambda = 1e-5 x the largest |H_kk|, ni = 2. Per iteration
+ *                  current = the chi2 sum at the pose, then trials: the step of P4, T' = P6, temp = the chi2 sum at T'; rho = (current - temp) /
+ *                  scale with scale = 1e-3 + sum_k dx_k (lambda dx_k + b_k), k ascending (1e-3 alone after a failed factorisation); the factorisation
+ *                  succeeded, rho > 0 and temp finite: accept T', t = 2 rho - 1, alpha = min(1 - (t t) t, 2/3), lambda *= max(1/3, alpha), ni = 2, current = temp; else lambda
+ *                  *= ni, ni *= 2, and a lambda that is not finite ends the optimisation. Trials repeat while rho < 0, at most 10; the optimisation
+ *                  ends after an iteration with 10 trials or rho == 0, or after `iterations` iterations.
+ *   P6 update.     T' = Exp(dx) T with dx = (omega, upsilon), the pose kept as a 3 x 4 float64: s = (w0 w0 + w1 w1) + w2 w2; Re = (I + A O) + B O2,
+ *                  V = (I + B O) + C O2 entry by entry with O = [omega]x and O2 = [-(w1 w1 + w2 w2), w0 w1, w0 w2; ., -(w0 w0 + w2 w2), w1 w2; ., .,
+ *                  -(w0 w0 + w1 w1)]; te_r = (V_r0 u0 + V_r1 u1) + V_r2 u2; R' = Re R with ((a0 b0 + a1 b1) + a2 b2), t'_r = (((Re_r0 t0 + Re_r1
+ *                  t1) + Re_r2 t2) + te_r). A = sin(th)/th, B = (1 - cos(th))/th^2, C = (th - sin(th))/th^3 are the library's own fixed series in s,
+ *                  14 terms each (k = 0..13; the first omitted term at th = pi is below 2^-53 of the leading one), nested a = 1 - (s / d_k) a from k =
+ *                  13 down to 3 with d_k = (2k + off - 1)(2k + off), off = 1, 2, 3, the last two steps (k = 2, 1) in double-double (Dekker's
+ *                  two_sum / two_prod, + - x / only), then x 1, x 0.5, / 6. No transcendental on the device up to th = pi, no small-angle branch,
+ *                  one bit pattern everywhere, each coefficient within one ulp of its leading term. s > the double nearest pi^2: libm's sin,
+ *                  cos and sqrt; a debug counter (iba_debug_pose_big_steps) reports such steps and NO byte-for-byte claim covers them.
+ *   P7 classification. After each round every edge, active or not, is evaluated at the round's final accepted pose: (float)chi2 > chi2_threshold
+ *                  marks an outlier and deactivates the edge, otherwise it is active again (a NaN chi2 is no outlier, as in the reference). The
+ *                  rule iba_ba uses.
+ *   P8 schedule.   n < 3: nothing runs, n_inliers = 0, the pose is the start pose, rounds_run = 0. Every round restarts from the start pose with
+ *                  the current active set (Optimizer.cc:542); rounds 0..robust_rounds-1 use the Huber kernel; n < 10 stops after the first round
+ *                  (optimizer.edges().size() < 10). The result is the last round's pose, n_inliers = n - its n_bad. Per round: chi2 (the robust
+ *                  sum over the round's active edges at its final pose), n_bad, lm_iterations (begun), trials.
+ *   P9 edges from matches. (host only, pure) mCurrentFrame.mvpMapPoints[match[q]] = the last frame's point of query q, for the queries in ascending
+ *                  order (a later query overwrites), then the loop of Optimizer.cc:445-484: the current frame's keypoints that hold a point in
+ *                  ascending index give xyz, obs = the keypoint's position, inv_sigma2 = inv_level_sigma2[octave] and the keypoint's index
+ *                  (vnIndexEdgeMono).
+ *
+ * UNPINNED, together (g2o is third party and absent): the Jacobian's association in P1, the Huber form of P2, all of P4 (g2o solves with Eigen's
+ * Cholesky of the 6 x 6 block) and P5 (tau, rho, the clamp, ni, the stop), Exp of P6 (g2o's SE3Quat::exp branches at small theta and calls libm), and
+ * the order of every sum. KNOWN DEVIATIONS: g2o keeps the pose as a normalised quaternion and Converter::toSE3Quat re-orthonormalises the float pose;
+ * here the caller's Tcw12 is used as given and never re-orthonormalised. g2o's active edges can carry the errors of a rejected last trial into the
+ * classification; P7 evaluates at the accepted pose.
+ * DEVICE (csrc/iba_pose_kernels.hpp): one workgroup of 256 lanes per job, grid-stride over the jobs of a chunk, ONE launch per chunk. A job's edges
+ * are loaded once into LDS (24 bytes and a flag each) up to IBA_POSE_ONCHIP_EDGES; the edges above that are re-read from global memory by the same
+ * arithmetic. Per evaluation the lanes do their edges, the wave sums by DPP, the four partial sums meet in LDS, one lane solves and updates in LDS
+ * and the new pose is broadcast through LDS. No atomics on floating-point values. iba_pose_eval is one linearisation by the same device functions.
+ * Chunks of consecutive jobs run under 1 GiB, or a quarter of the free device memory where that is less; a chunk boundary changes no byte.
+ * ERRORS, all IBA_ERR_INVALID_ARG with a message (iba_pose_last_error, per thread) BEFORE the device is touched: a NULL argument (a job's edge
+ * arrays may be NULL only where n == 0) or a wrong struct_size; B < 1; n < 0 or above IBA_ORB_MATCH_MAX_KEYPOINTS; a pose, point, observation,
+ * information or intrinsic that is not finite; fx or fy <= 0; inv_sigma2 < 0; rounds outside 1..8, iterations outside 1..100, robust_rounds outside
+ * 0..8, a threshold or delta that is not finite, chi2_threshold < 0, huber_delta <= 0; a job or round index outside the result; the stage accessor
+ * on a result without keep_stages. n == 0 is legal.
+ */
+#define IBA_POSE_ONCHIP_EDGES 1024
+#define IBA_POSE_MAX_ROUNDS 8
+typedef struct iba_pose_job {                 /* host pointers, read during the call only */
+    const double* Tcw12;       /* 3 x 4 row-major: the start pose */
+    const float*  xyz;         /* n x 3: MapPoint::GetWorldPos */
+    const float*  obs;         /* n x 2: mvKeysUn[i].pt */
+    const float*  inv_sigma2;  /* n: mvInvLevelSigma2[octave] */
+    int32_t n;
+    float fx, fy, cx, cy;
+} iba_pose_job;
+typedef struct iba_pose_options {
+    int32_t struct_size;        /* sizeof(iba_pose_options) */
+    int32_t rounds;             /* 4, 1..8 */
+    int32_t iterations;         /* 10, 1..100 */
+    float   chi2_threshold;     /* 5.991f */
+    float   huber_delta;        /* (float)sqrt(5.991) */
+    int32_t robust_rounds;      /* 3: the Huber kernel is off after this many rounds */
+    int32_t keep_stages;        /* 0; 1 allows iba_pose_stage */
+} iba_pose_options;
+typedef struct iba_pose_result {
+    int32_t n;
+    int32_t n_inliers;          /* nInitialCorrespondences - nBad; 0 where n < 3 */
+    int32_t rounds_run;
+    int32_t reserved;
+    double  Tcw12[12];
+    float   Tcw12f[12];         /* the rounding of Converter::toCvMat */
+    double  chi2[IBA_POSE_MAX_ROUNDS];
+    int32_t n_bad[IBA_POSE_MAX_ROUNDS], lm_iterations[IBA_POSE_MAX_ROUNDS], trials[IBA_POSE_MAX_ROUNDS];
+} iba_pose_result;
+typedef struct iba_pose_batch iba_pose_batch;
+iba_status iba_default_pose_options(iba_pose_options* opt);
+const char* iba_pose_last_error(void);                               /* never NULL; of this thread's last iba_pose* call that failed */
+/* *out is NULL on failure; release it with iba_pose_free */
+iba_status iba_pose_optimize(const iba_pose_job* jobs, int32_t B, const iba_pose_options* opt, int device, iba_pose_batch** out);
+/* one linearisation per job AT the job's Tcw12 (P1-P3, delta = (float)sqrt(5.991)): active is NULL (all edges of all jobs) or one pointer per job
+ * (NULL = all, else n bytes); H is B x 36 (both triangles), b B x 6, chi2_robust B; chi2_edges is NULL or one pointer per job (NULL, or n doubles:
+ * the chi2 of every edge, active or not) */
+iba_status iba_pose_eval(const iba_pose_job* jobs, int32_t B, const uint8_t* const* active, int32_t robust, int device, double* H, double* b, double* chi2_robust,
+                         double* const* chi2_edges);
+void       iba_pose_free(iba_pose_batch* r);
+int32_t    iba_pose_n_jobs(const iba_pose_batch* r);                 /* 0 for NULL */
+iba_status iba_pose_read(const iba_pose_batch* r, int32_t job, iba_pose_result* result);
+/* per edge the outlier flag and the float32 chi2 of the last classification (n each, zeros where n < 3); either may be NULL */
+iba_status iba_pose_edges(const iba_pose_batch* r, int32_t job, uint8_t* outlier, float* chi2);
+/* keep_stages only: the pose at the end of round `round` < rounds_run */
+iba_status iba_pose_stage(const iba_pose_batch* r, int32_t job, int32_t round, double Tcw12[12]);
+/* host only, pure (P9). match and query_index are those of the CLAIM job built by iba_orb_match_motion_queries (query_index NULL: query q is keypoint
+ * q of the last frame); the outputs take up to n_cur entries each; *n is the number of edges */
+iba_status iba_pose_edges_from_matches(const int32_t* match, const int32_t* query_index, int32_t n_queries, const float* last_world_xyz /* n_last x 3 */, int32_t n_last,
+                                       const float* cur_xy /* n_cur x 2 */, const int32_t* cur_octave /* n_cur */, int32_t n_cur, const float* inv_level_sigma2, int32_t n_levels,
+                                       float* xyz, float* obs, float* inv_sigma2, int32_t* keypoint_index, int32_t* n);
+
 /* The ABI version the LIBRARY was built with (IBA_ABI_VERSION of its header). iba_params carries no struct_size: a caller compiled against
  * an older header would pass a shorter struct. Callers compare iba_abi_version() with their own IBA_ABI_VERSION before iba_create(). */
 int32_t iba_abi_version(void);

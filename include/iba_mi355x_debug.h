@@ -53,6 +53,9 @@
  *                                                         iba_debug_orb_match_stage_ms; tools/orb_match_bench.py); same results
  *   IBA_TWOVIEW_BUDGET, IBA_TWOVIEW_TIMING                the same two for iba_twoview_init (187 bytes per match and 148 per iteration of a pair; iba_debug_twoview_stage_ms;
  *                                                         tools/twoview_bench.py); same results
+ *   IBA_POSE_BUDGET, IBA_POSE_ONCHIP, IBA_POSE_TIMING     iba_pose_optimize / iba_pose_eval: the bytes a chunk of jobs may take on the device in place of 1 GiB
+ *                                                         (iba_debug_pose_chunks), an on-chip edge capacity below IBA_POSE_ONCHIP_EDGES, and HIP events around
+ *                                                         the kernel (iba_debug_pose_kernel_ms; tools/pose_bench.py); same results
  *   IBA_GROUP_REDUCE_HOST (flag of iba_group_create_ex, not a variable), IBA_DEBUG_FAIL_RANK / IBA_DEBUG_FAIL_PHASE: inject one
  *                                                         failure into a group's evaluation (tests of the fail-not-hang path)
  */
@@ -271,6 +274,21 @@ int32_t iba_debug_twoview_sweep_cap_hits(const iba_twoview_batch* r);
  * [1] scores, [2] selection, [3] motion hypotheses, [4] CheckRT, [5] the k-th cosine, [6] acceptance (with the gather of the candidate hypothesis' entries where the stages are not kept). Zeros without the variable and for
  * iba_debug_twoview_host. Same results. IBA_TWOVIEW_BUDGET: the bytes a chunk of pairs may take on the device in place of 1 GiB (same results). */
 iba_status iba_debug_twoview_stage_ms(const iba_twoview_batch* r, float ms[7]);
+/* debug: iba_pose_optimize as the host restatement of its rules (csrc/iba_pose_host.hpp over csrc/iba_pose_math.hpp), the whole call without a
+ * device; the result is read with the iba_pose_* accessors. Byte for byte what the device gives (tests/test_gpu_pose.py). */
+iba_status iba_debug_pose_host(const iba_pose_job* jobs, int32_t B, const iba_pose_options* opt, iba_pose_batch** out);
+/* debug: iba_pose_eval on the host, the same outputs */
+iba_status iba_debug_pose_eval_host(const iba_pose_job* jobs, int32_t B, const uint8_t* const* active, int32_t robust, double* H, double* b, double* chi2_robust,
+                                    double* const* chi2_edges);
+/* debug: rule P6's three coefficients at s = theta^2 <= pi^2 (host only): out = sin(th)/th, (1 - cos(th))/th^2, (th - sin(th))/th^3 */
+iba_status iba_debug_pose_series(double s, double out[3]);
+/* debug: Exp(dx) T of rule P6 on the host; *big = 1 where theta > pi took libm */
+iba_status iba_debug_pose_exp(const double dx[6], const double T[12], double Tn[12], int32_t* big);
+/* debug: the steps of the call beyond theta = pi (rule P6), the chunks it ran as, and the kernel time in ms from HIP events summed over the chunks;
+ * 0 for NULL */
+int32_t iba_debug_pose_big_steps(const iba_pose_batch* r);
+int32_t iba_debug_pose_chunks(const iba_pose_batch* r);
+float   iba_debug_pose_kernel_ms(const iba_pose_batch* r);
 
 #ifdef __cplusplus
 }
