@@ -1435,6 +1435,9 @@ iba_status iba_orb_match_motion_queries(const iba_orb_frame* last_frame, const u
  * radix select on the ordered keys (integer histograms in LDS); acceptance (one lane per pair); without keep_stages a gather of the candidate
  * hypothesis' per-match entries, so that only those come down. Only integer counts are combined by atomics. A
  * pair goes up once (32 bytes per match, 32 per set) and comes down once; T1, the set check and TOO_FEW_MATCHES are the host's before the device is touched.
+ * MEMORY: a pair takes 187 bytes per match and 148 per iteration on the device while its chunk runs; a call is cut into chunks of consecutive pairs
+ * (at most 32768) that stay under 1 GiB, or under a quarter of the device memory free at the call where that is less; a chunk holds at least one pair
+ * and a chunk boundary changes no byte. The result is host memory.
  * ERRORS, all IBA_ERR_INVALID_ARG with a message (iba_twoview_last_error, per thread) BEFORE the device is touched: a NULL argument (a frame's arrays
  * may be NULL only where its n == 0; sets only where N < 8) or a wrong struct_size; B < 1; n1 or n2 < 0 or above IBA_ORB_MATCH_MAX_KEYPOINTS; a
  * match index >= n2; a position that is not finite; fx or fy not finite or <= 0, cx or cy not finite; sigma not finite or <= 0; iterations outside

@@ -51,7 +51,7 @@
  *                                                         iba_debug_orb_stage_ms; tools/orb_bench.py); same results
  *   IBA_ORB_MATCH_BUDGET, IBA_ORB_MATCH_TIMING            the same two for iba_orb_match (6 bytes per candidate-list entry; iba_debug_orb_match_chunks,
  *                                                         iba_debug_orb_match_stage_ms; tools/orb_match_bench.py); same results
- *   IBA_TWOVIEW_BUDGET, IBA_TWOVIEW_TIMING                the same two for iba_twoview_init (187 bytes per match and 148 per iteration of a pair; iba_debug_twoview_stage_ms;
+ *   IBA_TWOVIEW_BUDGET, IBA_TWOVIEW_TIMING                the same two for iba_twoview_init (187 bytes per match and 148 per iteration of a pair; iba_debug_twoview_chunks, iba_debug_twoview_stage_ms;
  *                                                         tools/twoview_bench.py); same results
  *   IBA_POSE_BUDGET, IBA_POSE_ONCHIP, IBA_POSE_TIMING     iba_pose_optimize / iba_pose_eval: the bytes a chunk of jobs may take on the device in place of 1 GiB
  *                                                         (iba_debug_pose_chunks), an on-chip edge capacity below IBA_POSE_ONCHIP_EDGES, and HIP events around
@@ -270,6 +270,8 @@ iba_status iba_debug_twoview_host(const iba_twoview_pair* pairs, int32_t B, cons
 iba_status iba_debug_twoview_null_vector(const float* A, int32_t m, int32_t n, float* v, double* v64, int32_t* sweeps);
 /* debug: the null-vector solves of the call behind r whose 30th sweep still rotated; 0 for NULL */
 int32_t iba_debug_twoview_sweep_cap_hits(const iba_twoview_batch* r);
+/* debug: the chunks the call behind r ran as (a chunk none of whose pairs has 8 matches counts too); 0 for iba_debug_twoview_host and for NULL */
+int32_t iba_debug_twoview_chunks(const iba_twoview_batch* r);
 /* debug: with IBA_TWOVIEW_TIMING set at the call (under IBA_DEBUG_ENV=1), times in ms from HIP events, summed over the chunks: [0] hypotheses,
  * [1] scores, [2] selection, [3] motion hypotheses, [4] CheckRT, [5] the k-th cosine, [6] acceptance (with the gather of the candidate hypothesis' entries where the stages are not kept). Zeros without the variable and for
  * iba_debug_twoview_host. Same results. IBA_TWOVIEW_BUDGET: the bytes a chunk of pairs may take on the device in place of 1 GiB (same results). */

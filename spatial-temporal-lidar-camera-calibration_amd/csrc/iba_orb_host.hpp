@@ -284,17 +284,5 @@ inline void distribute(const int32_t* xy, const int32_t* score, int32_t n, int32
     }
 }
 
-// a batch cut into chunks of consecutive images whose bytes stay under the budget; a chunk holds at least one image. cut[c] .. cut[c + 1]
-inline std::vector<int32_t> cut_chunks(const std::vector<uint64_t>& bytes, uint64_t budget) {
-    std::vector<int32_t> cut(1, 0);
-    uint64_t at = 0;
-    for (size_t i = 0; i < bytes.size(); ++i) {
-        if (i > (size_t)cut.back() && at + bytes[i] > budget) { cut.push_back((int32_t)i); at = 0; }
-        at += bytes[i];
-    }
-    cut.push_back((int32_t)bytes.size());
-    return cut;
-}
-
 }  // namespace orb
 }  // namespace iba

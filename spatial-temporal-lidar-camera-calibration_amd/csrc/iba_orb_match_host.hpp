@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/iba_mi355x.h"
+#include "iba_chunks.hpp"
 #include "iba_orb_host.hpp"
 
 namespace iba {
@@ -152,7 +153,7 @@ inline std::string motion_queries(const iba_orb_frame* f, const uint8_t* has_poi
 inline std::vector<int32_t> plan_chunks(const std::vector<int64_t>& candidates, uint64_t budget) {
     std::vector<uint64_t> bytes(candidates.size());
     for (size_t j = 0; j < candidates.size(); ++j) bytes[j] = IBA_ORB_MATCH_BYTES_PER_CANDIDATE * (uint64_t)candidates[j];
-    return orb::cut_chunks(bytes, budget);
+    return cut_chunks(bytes, budget);
 }
 
 }  // namespace orbm

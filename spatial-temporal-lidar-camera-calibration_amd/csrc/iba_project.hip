@@ -1,8 +1,8 @@
 // Scan-to-image projection (include/iba_mi355x.h, iba_project_* / iba_projection_*): the C ABI, the result object and the launch chain of a call.
 // The kernels and their launches are iba_project_kernels.hpp (compiled beside the evaluation kernels, whose quotient helper they share); the
-// validation, the palette and the cut into chunks are iba_project_host.hpp. A call: poses on the host (P1), the job table up, then per chunk of
-// jobs a fill of the key image and the splat, resolve and visible kernels, all on the handle's stream; the counters come down and the stream is
-// synchronised ONCE. The result owns its device buffers (DevBuf) and reads nothing of the handle afterwards: its accessors copy on the null stream.
+// validation, the palette and the bytes of a job are iba_project_host.hpp. A per-call unit (iba_call.hpp) on the handle's stream, ONE chain for all
+// chunks: poses on the host (P1), the job table up, then per chunk of jobs a fill of the key image and the splat, resolve and visible kernels; the
+// counters come down. The result owns its device buffers (DevBuf) and reads nothing of the handle afterwards: its accessors copy on the null stream.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,9 +13,9 @@
 
 #include "../../include/iba_mi355x.h"
 #include "../../include/iba_mi355x_debug.h"
+#include "iba_call.hpp"
 #include "iba_device_buf.hpp"
 #include "iba_host_math.hpp"
-#include "iba_internal.hpp"
 #include "iba_project_host.hpp"
 
 using iba::DevBuf;
@@ -37,30 +37,13 @@ struct iba_projection {
 };
 
 namespace {
-thread_local std::string t_err;
-iba_status fail(iba_status s, const std::string& m) { t_err = m; return s; }
-iba_status fail_hip(const char* what, hipError_t e) { (void)hipGetLastError(); return fail(IBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
+thread_local iba::CallError t_err;
 
-#define PRJ_TRY(expr)                                                   \
-    do {                                                                \
-        const hipError_t _e = (expr);                                   \
-        if (_e != hipSuccess) return fail_hip(#expr, _e);               \
-    } while (0)
-
-// events of a timed call (debug), destroyed with the scope
-struct EventSet {
-    std::vector<hipEvent_t> e;
-    ~EventSet() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
-    hipError_t create(size_t n) {
-        for (size_t i = 0; i < n; ++i) { hipEvent_t x = nullptr; const hipError_t err = hipEventCreate(&x); if (err != hipSuccess) return err; e.push_back(x); }
-        return hipSuccess;
-    }
-};
 // one launch on the null stream between two events (debug): its time into *ms
 template <class F>
 hipError_t timed(bool timing, float* ms, F launch) {
     if (!timing) return launch();
-    EventSet ev;
+    iba::EventSet ev;
     hipError_t err = ev.create(2);
     if (err == hipSuccess) err = hipEventRecord(ev.e[0], nullptr);
     if (err == hipSuccess) err = launch();
@@ -74,9 +57,7 @@ uint64_t job_pixels(const ProjJob& j) { return (uint64_t)j.Wi * (uint64_t)j.Hi; 
 
 // the job index of an accessor: "" or the refusal
 iba_status check_job(const iba_projection* p, int32_t job, const char* who) {
-    if (!p) return fail(IBA_ERR_INVALID_ARG, std::string(who) + ": the result is NULL");
-    if (job < 0 || (size_t)job >= p->jobs.size()) return fail(IBA_ERR_INVALID_ARG, std::string(who) + ": job " + std::to_string(job) + " is outside the result's " + std::to_string(p->jobs.size()) + " jobs");
-    return IBA_OK;
+    return t_err.check_index(!p, job, p ? p->jobs.size() : 0, std::string(who) + ": ", "job");
 }
 
 // the launch chain of a call on a result whose job table is complete; on failure the caller deletes the result
@@ -85,11 +66,8 @@ iba_status run_chain(const iba::ProjectView& v, iba_projection* res) {
     const int32_t J = (int32_t)jobs.size();
     const ProjJob& last = jobs[(size_t)J - 1];
     const uint64_t n_rec = last.rec_base + last.P, n_pix = last.img_base + job_pixels(last);
-    PRJ_TRY(hipSetDevice(v.device));
-    size_t free_b = 0, total_b = 0;
-    PRJ_TRY(hipMemGetInfo(&free_b, &total_b));
-    uint64_t budget = std::min<uint64_t>(IBA_PROJECT_BUDGET_BYTES, (uint64_t)free_b / 4u);
-    if (const char* e = iba::debug_env("IBA_PROJECT_BUDGET")) budget = std::strtoull(e, nullptr, 10);
+    uint64_t budget = 0;
+    IBA_CALL_TRY(iba::call_budget(v.device, IBA_PROJECT_BUDGET_BYTES, "IBA_PROJECT_BUDGET", &budget));
     std::vector<uint64_t> pixels((size_t)J);
     for (int32_t j = 0; j < J; ++j) pixels[(size_t)j] = job_pixels(jobs[(size_t)j]);
     const std::vector<int32_t> cut = prj::cut_chunks(pixels, budget);
@@ -100,19 +78,20 @@ iba_status run_chain(const iba::ProjectView& v, iba_projection* res) {
         for (int32_t j = cut[(size_t)c]; j < cut[(size_t)c + 1]; ++j) { res->jobs[(size_t)j].key_base = at; at += pixels[(size_t)j]; }
         key_cap = std::max(key_cap, at);
     }
-    DevBuf<unsigned long long> d_keys;       // the z-buffer of one chunk: lives for this call only
-    PRJ_TRY(d_keys.alloc((size_t)key_cap));
-    PRJ_TRY(res->d_jobs.alloc((size_t)J));
-    PRJ_TRY(res->d_depth.alloc((size_t)n_pix));
-    PRJ_TRY(res->d_index.alloc((size_t)n_pix));
-    PRJ_TRY(res->d_rec.alloc((size_t)n_rec));
-    PRJ_TRY(res->d_cnt.alloc((size_t)J * prj::kCounters));
     hipStream_t st = v.stream;
+    DevBuf<unsigned long long> d_keys;       // the z-buffer of one chunk: lives for this call only
+    iba::EventSet ev;
+    iba::SyncOnExit sync(st);                // after d_keys; the host arrays of the chain are the result's (jobs, counts), which outlive this function
+    IBA_CALL_TRY(d_keys.alloc((size_t)key_cap));
+    IBA_CALL_TRY(res->d_jobs.alloc((size_t)J));
+    IBA_CALL_TRY(res->d_depth.alloc((size_t)n_pix));
+    IBA_CALL_TRY(res->d_index.alloc((size_t)n_pix));
+    IBA_CALL_TRY(res->d_rec.alloc((size_t)n_rec));
+    IBA_CALL_TRY(res->d_cnt.alloc((size_t)J * prj::kCounters));
     const bool timing = iba::debug_env("IBA_PROJECT_TIMING") != nullptr;   // (debug: four events per chunk, read after the synchronise)
-    EventSet ev;
-    if (timing) PRJ_TRY(ev.create(4 * (size_t)res->n_chunks));
-    PRJ_TRY(hipMemcpyAsync(res->d_jobs.p, jobs.data(), sizeof(ProjJob) * (size_t)J, hipMemcpyHostToDevice, st));
-    PRJ_TRY(hipMemsetAsync(res->d_cnt.p, 0, sizeof(uint32_t) * (size_t)J * prj::kCounters, st));
+    if (timing) IBA_CALL_TRY(ev.create(4 * (size_t)res->n_chunks));
+    IBA_CALL_TRY(hipMemcpyAsync(res->d_jobs.p, jobs.data(), sizeof(ProjJob) * (size_t)J, hipMemcpyHostToDevice, st));
+    IBA_CALL_TRY(hipMemsetAsync(res->d_cnt.p, 0, sizeof(uint32_t) * (size_t)J * prj::kCounters, st));
     for (int32_t c = 0; c < res->n_chunks; ++c) {
         const int32_t a = cut[(size_t)c], b = cut[(size_t)c + 1], nj = b - a;
         const ProjJob& ja = jobs[(size_t)a]; const ProjJob& jz = jobs[(size_t)b - 1];
@@ -120,20 +99,21 @@ iba_status run_chain(const iba::ProjectView& v, iba_projection* res) {
         const uint32_t pt_blocks = jz.first_block + (jz.P + (uint32_t)prj::kSlice - 1u) / (uint32_t)prj::kSlice - ja.first_block;
         const uint32_t px_blocks = jz.first_pblock + (uint32_t)((job_pixels(jz) + (uint64_t)prj::kThreads - 1u) / (uint64_t)prj::kThreads) - ja.first_pblock;
         uint32_t* cnt = res->d_cnt.p + (size_t)a * prj::kCounters;
-        PRJ_TRY(hipMemsetAsync(d_keys.p, 0xFF, sizeof(unsigned long long) * (size_t)chunk_pix, st));
-        if (timing) PRJ_TRY(hipEventRecord(ev.e[4 * (size_t)c], st));
-        PRJ_TRY(iba::project_splat(st, v.pts4, res->d_jobs.p + a, nj, ja.first_block, pt_blocks, res->opt.splat, res->opt.z_min, res->opt.z_max, d_keys.p, res->d_rec.p, cnt));
-        if (timing) PRJ_TRY(hipEventRecord(ev.e[4 * (size_t)c + 1], st));
-        PRJ_TRY(iba::project_resolve(st, res->d_jobs.p + a, nj, ja.first_pblock, px_blocks, d_keys.p, res->d_depth.p, res->d_index.p, cnt));
-        if (timing) PRJ_TRY(hipEventRecord(ev.e[4 * (size_t)c + 2], st));
-        PRJ_TRY(iba::project_visible(st, res->d_jobs.p + a, nj, ja.first_block, pt_blocks, res->opt.occlusion_tol, res->d_rec.p, res->d_depth.p, cnt, nullptr, nullptr));
-        if (timing) PRJ_TRY(hipEventRecord(ev.e[4 * (size_t)c + 3], st));
+        IBA_CALL_TRY(hipMemsetAsync(d_keys.p, 0xFF, sizeof(unsigned long long) * (size_t)chunk_pix, st));
+        if (timing) IBA_CALL_TRY(hipEventRecord(ev.e[4 * (size_t)c], st));
+        IBA_CALL_TRY(iba::project_splat(st, v.pts4, res->d_jobs.p + a, nj, ja.first_block, pt_blocks, res->opt.splat, res->opt.z_min, res->opt.z_max, d_keys.p, res->d_rec.p, cnt));
+        if (timing) IBA_CALL_TRY(hipEventRecord(ev.e[4 * (size_t)c + 1], st));
+        IBA_CALL_TRY(iba::project_resolve(st, res->d_jobs.p + a, nj, ja.first_pblock, px_blocks, d_keys.p, res->d_depth.p, res->d_index.p, cnt));
+        if (timing) IBA_CALL_TRY(hipEventRecord(ev.e[4 * (size_t)c + 2], st));
+        IBA_CALL_TRY(iba::project_visible(st, res->d_jobs.p + a, nj, ja.first_block, pt_blocks, res->opt.occlusion_tol, res->d_rec.p, res->d_depth.p, cnt, nullptr, nullptr));
+        if (timing) IBA_CALL_TRY(hipEventRecord(ev.e[4 * (size_t)c + 3], st));
     }
     res->counts.assign((size_t)J * prj::kCounters, 0u);
-    PRJ_TRY(hipMemcpyAsync(res->counts.data(), res->d_cnt.p, sizeof(uint32_t) * (size_t)J * prj::kCounters, hipMemcpyDeviceToHost, st));
-    PRJ_TRY(hipStreamSynchronize(st));
+    IBA_CALL_TRY(hipMemcpyAsync(res->counts.data(), res->d_cnt.p, sizeof(uint32_t) * (size_t)J * prj::kCounters, hipMemcpyDeviceToHost, st));
+    IBA_CALL_TRY(hipStreamSynchronize(st));
+    sync.disarm();
     for (size_t c = 0; timing && c < (size_t)res->n_chunks; ++c)
-        for (int k = 0; k < 3; ++k) { float ms = 0.f; PRJ_TRY(hipEventElapsedTime(&ms, ev.e[4 * c + k], ev.e[4 * c + k + 1])); res->ms[k] += ms; }
+        for (int k = 0; k < 3; ++k) { float ms = 0.f; IBA_CALL_TRY(hipEventElapsedTime(&ms, ev.e[4 * c + k], ev.e[4 * c + k + 1])); res->ms[k] += ms; }
     return IBA_OK;
 }
 
@@ -146,16 +126,16 @@ iba_status run_chain(const iba::ProjectView& v, iba_projection* res) {
 
 extern "C" {
 
-const char* iba_project_last_error(void) { return t_err.c_str(); }
+const char* iba_project_last_error(void) { return t_err.msg.c_str(); }
 
 iba_status iba_default_project_options(iba_project_options* opt) {
-    if (!opt) return fail(IBA_ERR_INVALID_ARG, "iba_default_project_options: opt is NULL");
+    if (!opt) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_default_project_options: opt is NULL");
     prj::default_options(*opt);
     return IBA_OK;
 }
 
 iba_status iba_project_gradient(double zn, uint8_t rgb[3]) {
-    if (!rgb) return fail(IBA_ERR_INVALID_ARG, "iba_project_gradient: rgb is NULL");
+    if (!rgb) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_project_gradient: rgb is NULL");
     prj::gradient(zn, rgb);
     return IBA_OK;
 }
@@ -163,8 +143,8 @@ iba_status iba_project_gradient(double zn, uint8_t rgb[3]) {
 iba_status iba_project_run(iba_handle* h, const double* x7, const int32_t* frames, int32_t J, const iba_project_options* opt, iba_projection** out) {
     const std::string who = "iba_project_run: ";
     if (out) *out = nullptr;
-    if (!h) return fail(IBA_ERR_INVALID_ARG, who + "h is NULL");
-    if (!out) return fail(IBA_ERR_INVALID_ARG, who + "out is NULL");
+    if (!h) return t_err.fail(IBA_ERR_INVALID_ARG, who + "h is NULL");
+    if (!out) return t_err.fail(IBA_ERR_INVALID_ARG, who + "out is NULL");
     const iba::ProjectView v = iba::project_view(h);
     std::vector<double> intr;
     if (!v.scans_only) {
@@ -176,7 +156,7 @@ iba_status iba_project_run(iba_handle* h, const double* x7, const int32_t* frame
         }
     }
     const std::string why = prj::validate(opt, x7, frames, J, v.n_frames, v.scans_only ? nullptr : intr.data());
-    if (!why.empty()) return fail(IBA_ERR_INVALID_ARG, who + why);
+    if (!why.empty()) return t_err.fail(IBA_ERR_INVALID_ARG, who + why);
     // the job table: P1 on the host, the camera, the places of the job's records, pixels and blocks
     iba_projection* res = new iba_projection();
     res->device = v.device; res->opt = *opt;
@@ -198,10 +178,10 @@ iba_status iba_project_run(iba_handle* h, const double* x7, const int32_t* frame
         rec += jb.P; pix += job_pixels(jb);
         blocks += (jb.P + (uint64_t)prj::kSlice - 1u) / (uint64_t)prj::kSlice;
         pblocks += (job_pixels(jb) + (uint64_t)prj::kThreads - 1u) / (uint64_t)prj::kThreads;
-        if (blocks >= (1ull << 31) || pblocks >= (1ull << 31)) { delete res; return fail(IBA_ERR_UNSUPPORTED, who + "the jobs of one call need 2^31 blocks or more (split the call)"); }
+        if (blocks >= (1ull << 31) || pblocks >= (1ull << 31)) { delete res; return t_err.fail(IBA_ERR_UNSUPPORTED, who + "the jobs of one call need 2^31 blocks or more (split the call)"); }
     }
     const iba_status s = run_chain(v, res);
-    if (s != IBA_OK) { t_err = who + t_err; delete res; return s; }
+    if (s != IBA_OK) { t_err.msg = who + t_err.msg; delete res; return s; }
     *out = res;
     return IBA_OK;
 }
@@ -216,21 +196,21 @@ int32_t iba_projection_n_jobs(const iba_projection* p) { return p ? (int32_t)p->
 
 iba_status iba_projection_size(const iba_projection* p, int32_t job, int32_t* W, int32_t* H) {
     PRJ_ACCESS(p, job, "iba_projection_size");
-    if (!W || !H) return fail(IBA_ERR_INVALID_ARG, "iba_projection_size: W or H is NULL");
+    if (!W || !H) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_projection_size: W or H is NULL");
     *W = (int32_t)p->jobs[(size_t)job].Wi; *H = (int32_t)p->jobs[(size_t)job].Hi;
     return IBA_OK;
 }
 
 iba_status iba_projection_pose(const iba_projection* p, int32_t job, double Rt12[12]) {
     PRJ_ACCESS(p, job, "iba_projection_pose");
-    if (!Rt12) return fail(IBA_ERR_INVALID_ARG, "iba_projection_pose: Rt12 is NULL");
+    if (!Rt12) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_projection_pose: Rt12 is NULL");
     std::memcpy(Rt12, p->jobs[(size_t)job].Rt, 12 * sizeof(double));
     return IBA_OK;
 }
 
 iba_status iba_projection_counts(const iba_projection* p, int32_t job, iba_project_counts* counts) {
     PRJ_ACCESS(p, job, "iba_projection_counts");
-    if (!counts) return fail(IBA_ERR_INVALID_ARG, "iba_projection_counts: counts is NULL");
+    if (!counts) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_projection_counts: counts is NULL");
     const uint32_t zero[prj::kCounters] = {0};
     const uint32_t* c = p->counts.empty() ? zero : &p->counts[(size_t)job * prj::kCounters];
     counts->n_points = (int64_t)p->jobs[(size_t)job].P;
@@ -241,21 +221,21 @@ iba_status iba_projection_counts(const iba_projection* p, int32_t job, iba_proje
 
 iba_status iba_projection_depth(iba_projection* p, int32_t job, float* depth_HxW) {
     PRJ_ACCESS(p, job, "iba_projection_depth");
-    if (!depth_HxW) return fail(IBA_ERR_INVALID_ARG, "iba_projection_depth: the output is NULL");
+    if (!depth_HxW) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_projection_depth: the output is NULL");
     const ProjJob& jb = p->jobs[(size_t)job];
     if (p->device < 0 || !job_pixels(jb)) return IBA_OK;
-    PRJ_TRY(hipSetDevice(p->device));
-    PRJ_TRY(hipMemcpy(depth_HxW, p->d_depth.p + jb.img_base, sizeof(float) * (size_t)job_pixels(jb), hipMemcpyDeviceToHost));
+    IBA_CALL_TRY(hipSetDevice(p->device));
+    IBA_CALL_TRY(hipMemcpy(depth_HxW, p->d_depth.p + jb.img_base, sizeof(float) * (size_t)job_pixels(jb), hipMemcpyDeviceToHost));
     return IBA_OK;
 }
 
 iba_status iba_projection_index(iba_projection* p, int32_t job, uint32_t* index_HxW) {
     PRJ_ACCESS(p, job, "iba_projection_index");
-    if (!index_HxW) return fail(IBA_ERR_INVALID_ARG, "iba_projection_index: the output is NULL");
+    if (!index_HxW) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_projection_index: the output is NULL");
     const ProjJob& jb = p->jobs[(size_t)job];
     if (p->device < 0 || !job_pixels(jb)) return IBA_OK;
-    PRJ_TRY(hipSetDevice(p->device));
-    PRJ_TRY(hipMemcpy(index_HxW, p->d_index.p + jb.img_base, sizeof(uint32_t) * (size_t)job_pixels(jb), hipMemcpyDeviceToHost));
+    IBA_CALL_TRY(hipSetDevice(p->device));
+    IBA_CALL_TRY(hipMemcpy(index_HxW, p->d_index.p + jb.img_base, sizeof(uint32_t) * (size_t)job_pixels(jb), hipMemcpyDeviceToHost));
     return IBA_OK;
 }
 
@@ -264,8 +244,8 @@ iba_status iba_projection_points(iba_projection* p, int32_t job, double* uv_nx2,
     const ProjJob& jb = p->jobs[(size_t)job];
     if (p->device < 0 || !jb.P) return IBA_OK;
     std::vector<ProjRec> rec((size_t)jb.P);
-    PRJ_TRY(hipSetDevice(p->device));
-    PRJ_TRY(hipMemcpy(rec.data(), p->d_rec.p + jb.rec_base, sizeof(ProjRec) * (size_t)jb.P, hipMemcpyDeviceToHost));
+    IBA_CALL_TRY(hipSetDevice(p->device));
+    IBA_CALL_TRY(hipMemcpy(rec.data(), p->d_rec.p + jb.rec_base, sizeof(ProjRec) * (size_t)jb.P, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < rec.size(); ++i) {
         if (uv_nx2) { uv_nx2[2 * i] = rec[i].u; uv_nx2[2 * i + 1] = rec[i].v; }
         if (z_n) z_n[i] = rec[i].z;
@@ -276,36 +256,36 @@ iba_status iba_projection_points(iba_projection* p, int32_t job, double* uv_nx2,
 
 iba_status iba_projection_colorize(iba_projection* p, int32_t job, const uint8_t* rgb_HxWx3, uint8_t* point_rgb_nx3) {
     PRJ_ACCESS(p, job, "iba_projection_colorize");
-    if (!rgb_HxWx3 || !point_rgb_nx3) return fail(IBA_ERR_INVALID_ARG, "iba_projection_colorize: the image or the output is NULL");
+    if (!rgb_HxWx3 || !point_rgb_nx3) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_projection_colorize: the image or the output is NULL");
     const ProjJob& jb = p->jobs[(size_t)job];
     if (p->device < 0 || !jb.P) return IBA_OK;
-    PRJ_TRY(hipSetDevice(p->device));
+    IBA_CALL_TRY(hipSetDevice(p->device));
     DevBuf<uint8_t> d_img, d_out;
-    PRJ_TRY(d_img.upload(rgb_HxWx3, 3 * (size_t)job_pixels(jb)));
-    PRJ_TRY(d_out.alloc(3 * (size_t)jb.P));
+    IBA_CALL_TRY(d_img.upload(rgb_HxWx3, 3 * (size_t)job_pixels(jb)));
+    IBA_CALL_TRY(d_out.alloc(3 * (size_t)jb.P));
     const uint32_t n_blocks = (jb.P + (uint32_t)prj::kSlice - 1u) / (uint32_t)prj::kSlice;
-    PRJ_TRY(timed(iba::debug_env("IBA_PROJECT_TIMING") != nullptr, &p->ms[3], [&] {
+    IBA_CALL_TRY(timed(iba::debug_env("IBA_PROJECT_TIMING") != nullptr, &p->ms[3], [&] {
         return iba::project_visible(nullptr, p->d_jobs.p + job, 1, jb.first_block, n_blocks, p->opt.occlusion_tol, p->d_rec.p, p->d_depth.p, nullptr, d_img.p, d_out.p);
     }));
-    PRJ_TRY(hipMemcpy(point_rgb_nx3, d_out.p, 3 * (size_t)jb.P, hipMemcpyDeviceToHost));
+    IBA_CALL_TRY(hipMemcpy(point_rgb_nx3, d_out.p, 3 * (size_t)jb.P, hipMemcpyDeviceToHost));
     return IBA_OK;
 }
 
 iba_status iba_projection_overlay(iba_projection* p, int32_t job, const uint8_t* rgb_HxWx3, uint8_t* out_HxWx3) {
     PRJ_ACCESS(p, job, "iba_projection_overlay");
-    if (!out_HxWx3) return fail(IBA_ERR_INVALID_ARG, "iba_projection_overlay: the output is NULL");
+    if (!out_HxWx3) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_projection_overlay: the output is NULL");
     const ProjJob& jb = p->jobs[(size_t)job];
     const size_t bytes = 3 * (size_t)job_pixels(jb);
     if (p->device < 0 || !bytes) return IBA_OK;
-    PRJ_TRY(hipSetDevice(p->device));
+    IBA_CALL_TRY(hipSetDevice(p->device));
     DevBuf<uint8_t> d_img, d_out;
-    if (rgb_HxWx3) PRJ_TRY(d_img.upload(rgb_HxWx3, bytes));
-    PRJ_TRY(d_out.alloc(bytes));
+    if (rgb_HxWx3) IBA_CALL_TRY(d_img.upload(rgb_HxWx3, bytes));
+    IBA_CALL_TRY(d_out.alloc(bytes));
     const uint32_t n_blocks = (uint32_t)((job_pixels(jb) + (uint64_t)prj::kThreads - 1u) / (uint64_t)prj::kThreads);
-    PRJ_TRY(timed(iba::debug_env("IBA_PROJECT_TIMING") != nullptr, &p->ms[4], [&] {
+    IBA_CALL_TRY(timed(iba::debug_env("IBA_PROJECT_TIMING") != nullptr, &p->ms[4], [&] {
         return iba::project_overlay(nullptr, p->d_jobs.p + job, n_blocks, p->d_depth.p, p->d_index.p, rgb_HxWx3 ? d_img.p : nullptr, d_out.p, p->opt.z_near, p->opt.z_far);
     }));
-    PRJ_TRY(hipMemcpy(out_HxWx3, d_out.p, bytes, hipMemcpyDeviceToHost));
+    IBA_CALL_TRY(hipMemcpy(out_HxWx3, d_out.p, bytes, hipMemcpyDeviceToHost));
     return IBA_OK;
 }
 
@@ -313,11 +293,11 @@ iba_status iba_projection_overlay(iba_projection* p, int32_t job, const uint8_t*
 
 iba_status iba_debug_project_validate(int32_t n_frames, const double* intrinsics6, const double* x7, const int32_t* frames, int32_t J, const iba_project_options* opt) {
     const std::string why = prj::validate(opt, x7, frames, J, n_frames, intrinsics6);
-    return why.empty() ? IBA_OK : fail(IBA_ERR_INVALID_ARG, "iba_project_run: " + why);
+    return why.empty() ? IBA_OK : t_err.fail(IBA_ERR_INVALID_ARG, "iba_project_run: " + why);
 }
 
 iba_status iba_debug_project_stub(int32_t n_jobs, iba_projection** out) {
-    if (!out || n_jobs < 0) return fail(IBA_ERR_INVALID_ARG, "iba_debug_project_stub: out is NULL or n_jobs < 0");
+    if (!out || n_jobs < 0) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_debug_project_stub: out is NULL or n_jobs < 0");
     iba_projection* res = new iba_projection();
     prj::default_options(res->opt);
     res->jobs.resize((size_t)n_jobs);
@@ -329,7 +309,7 @@ iba_status iba_debug_project_stub(int32_t n_jobs, iba_projection** out) {
 int32_t iba_debug_projection_chunks(const iba_projection* p) { return p ? p->n_chunks : 0; }
 
 iba_status iba_debug_projection_kernel_ms(const iba_projection* p, float ms[5]) {
-    if (!p || !ms) return fail(IBA_ERR_INVALID_ARG, "iba_debug_projection_kernel_ms: a NULL argument");
+    if (!p || !ms) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_debug_projection_kernel_ms: a NULL argument");
     std::memcpy(ms, p->ms, sizeof(p->ms));
     return IBA_OK;
 }

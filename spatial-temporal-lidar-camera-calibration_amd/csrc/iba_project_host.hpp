@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/iba_mi355x.h"
+#include "iba_chunks.hpp"
 
 #if defined(__HIPCC__)
 #define IBA_PROJ_HD __host__ __device__
@@ -111,16 +112,9 @@ inline std::string validate(const iba_project_options* opt, const double* x7, co
 }
 
 // chunk c = jobs [cut[c], cut[c + 1]): consecutive jobs while their images stay within `budget` bytes; a chunk holds at least one job
-inline std::vector<int32_t> cut_chunks(const std::vector<uint64_t>& pixels, uint64_t budget) {
-    std::vector<int32_t> cut{0};
-    uint64_t used = 0;
-    for (size_t j = 0; j < pixels.size(); ++j) {
-        const uint64_t b = pixels[j] * kBytesPerPixel;
-        if (used > 0 && used + b > budget) { cut.push_back((int32_t)j); used = 0; }
-        used += b;
-    }
-    cut.push_back((int32_t)pixels.size());
-    return cut;
+inline std::vector<int32_t> cut_chunks(std::vector<uint64_t> pixels, uint64_t budget) {
+    for (uint64_t& p : pixels) p *= kBytesPerPixel;
+    return iba::cut_chunks(pixels, budget);
 }
 
 }  // namespace project

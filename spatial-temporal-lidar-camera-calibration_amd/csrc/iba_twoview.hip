@@ -1,7 +1,7 @@
 // Two-view initialisation (include/iba_mi355x.h, iba_twoview*): the C ABI, the result object's accessors and the launch chain of a call. The kernels
 // are iba_twoview_kernels.hpp, the arithmetic iba_twoview_math.hpp, the host rules (argument checks, T1, the set generator, the host restatement, the
-// last step with acos) iba_twoview_host.hpp. A call checks and prepares every pair on the host, cuts the pairs into chunks under a byte budget, and
-// runs one chain per chunk: tables up, seven kernels, results down, one synchronisation. The result is host memory.
+// last step with acos) iba_twoview_host.hpp. A per-call unit (iba_call.hpp): every pair is prepared on the host; the chain of a chunk of pairs:
+// tables up, seven kernels, results down. The result is host memory.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,8 +12,8 @@
 
 #include "../../include/iba_mi355x.h"
 #include "../../include/iba_mi355x_debug.h"
+#include "iba_call.hpp"
 #include "iba_device_buf.hpp"
-#include "iba_internal.hpp"
 #include "iba_twoview_host.hpp"
 #include "iba_twoview_kernels.hpp"
 
@@ -21,24 +21,7 @@ using iba::DevBuf;
 namespace tv = iba::tv;
 
 namespace {
-thread_local std::string t_err;
-iba_status fail(iba_status s, const std::string& m) { t_err = m; return s; }
-iba_status fail_hip(const char* what, hipError_t e) { (void)hipGetLastError(); return fail(IBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
-#define TV_TRY(expr)                                                    \
-    do {                                                                \
-        const hipError_t _e = (expr);                                   \
-        if (_e != hipSuccess) return fail_hip(#expr, _e);               \
-    } while (0)
-
-struct EventSet {
-    std::vector<hipEvent_t> e;
-    ~EventSet() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
-    hipError_t create(size_t n) {
-        for (size_t i = 0; i < n; ++i) { hipEvent_t x = nullptr; const hipError_t err = hipEventCreate(&x); if (err != hipSuccess) return err; e.push_back(x); }
-        return hipSuccess;
-    }
-};
+thread_local iba::CallError t_err;
 
 constexpr uint64_t kBudgetBytes = 1ull << 30;
 // device bytes of a pair: per match 32 (coordinates) + 2 (flags) + 8 x 17 (points, cosine, verdict per hypothesis) + 17 (the candidate's), per iteration 32 (set) + 116
@@ -49,7 +32,18 @@ iba_status run_chunk(iba_twoview_batch* res, const std::vector<tv::PairPrep>& pr
     const iba_twoview_options& opt = res->opt;
     const int32_t nP = b - a, I = opt.iterations;
     hipStream_t st = nullptr;
+    // the host arrays of the chain first, then its device buffers, then the guard: it waits for the stream before any of them unwinds
     std::vector<tv::PairRec> recs((size_t)nP);
+    std::vector<float> h_mxy, h_mn, h_pts, h_cos, h_Hi, h_H12i, h_Fi, h_sH, h_sF;
+    std::vector<int32_t> h_sets, h_aux;
+    std::vector<iba_twoview_result> h_res;
+    std::vector<tv::Cam> h_cams;
+    std::vector<uint8_t> h_inl, h_verdict;
+    int32_t hits = 0;
+    DevBuf<tv::PairRec> d_pairs; DevBuf<float4> d_mxy, d_mn; DevBuf<int32_t> d_sets, d_aux, d_hits; DevBuf<float> d_Hi, d_H12i, d_Fi, d_sH, d_sF, d_pts, d_cos;
+    DevBuf<uint8_t> d_inl, d_verdict, d_sel_verdict; DevBuf<iba_twoview_result> d_res; DevBuf<tv::Cam> d_cams; DevBuf<float> d_sel_pts, d_sel_cos;
+    iba::EventSet ev;
+    iba::SyncOnExit sync(st);
     size_t M = 0;
     int32_t maxN = 0;
     for (int32_t k = 0; k < nP; ++k) {
@@ -60,11 +54,11 @@ iba_status run_chunk(iba_twoview_batch* res, const std::vector<tv::PairPrep>& pr
         std::memcpy(r.T1, q.T1, sizeof(r.T1)); std::memcpy(r.T2inv, q.T2inv, sizeof(r.T2inv)); std::memcpy(r.T2t, q.T2t, sizeof(r.T2t));
         M += (size_t)r.N; maxN = std::max(maxN, r.N);
     }
-    if (maxN == 0) return IBA_OK;                     // every pair of the chunk has its status already
-    if (8ull * M >= (1ull << 31) || (uint64_t)nP * (uint64_t)I * 9ull >= (1ull << 31)) return fail(IBA_ERR_UNSUPPORTED, "a chunk of 2^31 per-hypothesis entries or more");
+    if (maxN == 0) { sync.disarm(); return IBA_OK; }  // every pair of the chunk has its status already: nothing was queued
+    if (8ull * M >= (1ull << 31) || (uint64_t)nP * (uint64_t)I * 9ull >= (1ull << 31)) return t_err.fail(IBA_ERR_UNSUPPORTED, "a chunk of 2^31 per-hypothesis entries or more");
     const size_t nI = (size_t)nP * (size_t)I;
-    std::vector<float> h_mxy(4 * M), h_mn(4 * M);
-    std::vector<int32_t> h_sets(8 * nI, 0);
+    h_mxy.resize(4 * M); h_mn.resize(4 * M);
+    h_sets.assign(8 * nI, 0);
     for (int32_t k = 0; k < nP; ++k) {
         const tv::PairPrep& q = prep[(size_t)(a + k)];
         const tv::PairRec& r = recs[(size_t)k];
@@ -72,32 +66,29 @@ iba_status run_chunk(iba_twoview_batch* res, const std::vector<tv::PairPrep>& pr
         std::memcpy(&h_mxy[4 * (size_t)r.m_base], q.mxy.data(), sizeof(float) * 4 * (size_t)r.N); std::memcpy(&h_mn[4 * (size_t)r.m_base], q.mn.data(), sizeof(float) * 4 * (size_t)r.N);
         std::memcpy(&h_sets[8 * (size_t)k * (size_t)I], q.sets.data(), sizeof(int32_t) * 8 * (size_t)I);
     }
-    DevBuf<tv::PairRec> d_pairs; DevBuf<float4> d_mxy, d_mn; DevBuf<int32_t> d_sets, d_aux, d_hits; DevBuf<float> d_Hi, d_H12i, d_Fi, d_sH, d_sF, d_pts, d_cos;
-    DevBuf<uint8_t> d_inl, d_verdict, d_sel_verdict; DevBuf<iba_twoview_result> d_res; DevBuf<tv::Cam> d_cams; DevBuf<float> d_sel_pts, d_sel_cos;
-    TV_TRY(d_pairs.alloc((size_t)nP)); TV_TRY(d_mxy.alloc(M)); TV_TRY(d_mn.alloc(M)); TV_TRY(d_sets.alloc(8 * nI)); TV_TRY(d_aux.alloc(4 * (size_t)nP)); TV_TRY(d_hits.alloc(1));
-    TV_TRY(d_Hi.alloc(9 * nI)); TV_TRY(d_H12i.alloc(9 * nI)); TV_TRY(d_Fi.alloc(9 * nI)); TV_TRY(d_sH.alloc(nI)); TV_TRY(d_sF.alloc(nI));
-    TV_TRY(d_pts.alloc(24 * M)); TV_TRY(d_cos.alloc(8 * M)); TV_TRY(d_inl.alloc(2 * M)); TV_TRY(d_verdict.alloc(8 * M)); TV_TRY(d_res.alloc((size_t)nP)); TV_TRY(d_cams.alloc(8 * (size_t)nP));
+    IBA_CALL_TRY(d_pairs.alloc((size_t)nP)); IBA_CALL_TRY(d_mxy.alloc(M)); IBA_CALL_TRY(d_mn.alloc(M)); IBA_CALL_TRY(d_sets.alloc(8 * nI)); IBA_CALL_TRY(d_aux.alloc(4 * (size_t)nP)); IBA_CALL_TRY(d_hits.alloc(1));
+    IBA_CALL_TRY(d_Hi.alloc(9 * nI)); IBA_CALL_TRY(d_H12i.alloc(9 * nI)); IBA_CALL_TRY(d_Fi.alloc(9 * nI)); IBA_CALL_TRY(d_sH.alloc(nI)); IBA_CALL_TRY(d_sF.alloc(nI));
+    IBA_CALL_TRY(d_pts.alloc(24 * M)); IBA_CALL_TRY(d_cos.alloc(8 * M)); IBA_CALL_TRY(d_inl.alloc(2 * M)); IBA_CALL_TRY(d_verdict.alloc(8 * M)); IBA_CALL_TRY(d_res.alloc((size_t)nP)); IBA_CALL_TRY(d_cams.alloc(8 * (size_t)nP));
     const bool keep = opt.keep_stages != 0;
-    if (!keep) { TV_TRY(d_sel_pts.alloc(3 * M)); TV_TRY(d_sel_cos.alloc(M)); TV_TRY(d_sel_verdict.alloc(M)); }
-    std::vector<iba_twoview_result> h_res((size_t)nP);
+    if (!keep) { IBA_CALL_TRY(d_sel_pts.alloc(3 * M)); IBA_CALL_TRY(d_sel_cos.alloc(M)); IBA_CALL_TRY(d_sel_verdict.alloc(M)); }
+    h_res.resize((size_t)nP);
     for (int32_t k = 0; k < nP; ++k) h_res[(size_t)k] = res->pair[(size_t)(a + k)].r;
-    TV_TRY(hipMemcpyAsync(d_pairs.p, recs.data(), sizeof(tv::PairRec) * (size_t)nP, hipMemcpyHostToDevice, st));
-    TV_TRY(hipMemcpyAsync(d_mxy.p, h_mxy.data(), sizeof(float) * 4 * M, hipMemcpyHostToDevice, st));
-    TV_TRY(hipMemcpyAsync(d_mn.p, h_mn.data(), sizeof(float) * 4 * M, hipMemcpyHostToDevice, st));
-    TV_TRY(hipMemcpyAsync(d_sets.p, h_sets.data(), sizeof(int32_t) * 8 * nI, hipMemcpyHostToDevice, st));
-    TV_TRY(hipMemcpyAsync(d_res.p, h_res.data(), sizeof(iba_twoview_result) * (size_t)nP, hipMemcpyHostToDevice, st));
-    TV_TRY(hipMemsetAsync(d_aux.p, 0, sizeof(int32_t) * 4 * (size_t)nP, st)); TV_TRY(hipMemsetAsync(d_hits.p, 0, sizeof(int32_t), st));
-    TV_TRY(hipMemsetAsync(d_Hi.p, 0, sizeof(float) * 9 * nI, st)); TV_TRY(hipMemsetAsync(d_H12i.p, 0, sizeof(float) * 9 * nI, st)); TV_TRY(hipMemsetAsync(d_Fi.p, 0, sizeof(float) * 9 * nI, st));
-    TV_TRY(hipMemsetAsync(d_sH.p, 0, sizeof(float) * nI, st)); TV_TRY(hipMemsetAsync(d_sF.p, 0, sizeof(float) * nI, st));
-    TV_TRY(hipMemsetAsync(d_pts.p, 0, sizeof(float) * 24 * M, st)); TV_TRY(hipMemsetAsync(d_cos.p, 0, sizeof(float) * 8 * M, st));
-    TV_TRY(hipMemsetAsync(d_inl.p, 0, 2 * M, st)); TV_TRY(hipMemsetAsync(d_verdict.p, 0, 8 * M, st)); TV_TRY(hipMemsetAsync(d_cams.p, 0, sizeof(tv::Cam) * 8 * (size_t)nP, st));
-    EventSet ev;
-    if (timing) TV_TRY(ev.create(8));
+    IBA_CALL_TRY(hipMemcpyAsync(d_pairs.p, recs.data(), sizeof(tv::PairRec) * (size_t)nP, hipMemcpyHostToDevice, st));
+    IBA_CALL_TRY(hipMemcpyAsync(d_mxy.p, h_mxy.data(), sizeof(float) * 4 * M, hipMemcpyHostToDevice, st));
+    IBA_CALL_TRY(hipMemcpyAsync(d_mn.p, h_mn.data(), sizeof(float) * 4 * M, hipMemcpyHostToDevice, st));
+    IBA_CALL_TRY(hipMemcpyAsync(d_sets.p, h_sets.data(), sizeof(int32_t) * 8 * nI, hipMemcpyHostToDevice, st));
+    IBA_CALL_TRY(hipMemcpyAsync(d_res.p, h_res.data(), sizeof(iba_twoview_result) * (size_t)nP, hipMemcpyHostToDevice, st));
+    IBA_CALL_TRY(hipMemsetAsync(d_aux.p, 0, sizeof(int32_t) * 4 * (size_t)nP, st)); IBA_CALL_TRY(hipMemsetAsync(d_hits.p, 0, sizeof(int32_t), st));
+    IBA_CALL_TRY(hipMemsetAsync(d_Hi.p, 0, sizeof(float) * 9 * nI, st)); IBA_CALL_TRY(hipMemsetAsync(d_H12i.p, 0, sizeof(float) * 9 * nI, st)); IBA_CALL_TRY(hipMemsetAsync(d_Fi.p, 0, sizeof(float) * 9 * nI, st));
+    IBA_CALL_TRY(hipMemsetAsync(d_sH.p, 0, sizeof(float) * nI, st)); IBA_CALL_TRY(hipMemsetAsync(d_sF.p, 0, sizeof(float) * nI, st));
+    IBA_CALL_TRY(hipMemsetAsync(d_pts.p, 0, sizeof(float) * 24 * M, st)); IBA_CALL_TRY(hipMemsetAsync(d_cos.p, 0, sizeof(float) * 8 * M, st));
+    IBA_CALL_TRY(hipMemsetAsync(d_inl.p, 0, 2 * M, st)); IBA_CALL_TRY(hipMemsetAsync(d_verdict.p, 0, 8 * M, st)); IBA_CALL_TRY(hipMemsetAsync(d_cams.p, 0, sizeof(tv::Cam) * 8 * (size_t)nP, st));
+    if (timing) IBA_CALL_TRY(ev.create(8));
     const float invs = tv::inv_sigma_square(opt.sigma), sigma2 = opt.sigma * opt.sigma, th2 = (float)(4.0 * (double)sigma2);
     const uint32_t pair_blocks = (uint32_t)((nP + 63) / 64);
     int stage = 0;
-#define TV_STAGE() do { TV_TRY(hipGetLastError()); if (timing) TV_TRY(hipEventRecord(ev.e[(size_t)++stage], st)); } while (0)
-    if (timing) TV_TRY(hipEventRecord(ev.e[0], st));
+#define TV_STAGE() do { IBA_CALL_TRY(hipGetLastError()); if (timing) IBA_CALL_TRY(hipEventRecord(ev.e[(size_t)++stage], st)); } while (0)
+    if (timing) IBA_CALL_TRY(hipEventRecord(ev.e[0], st));
     hipLaunchKernelGGL(tv::tv_hyp_kernel, dim3((uint32_t)((nI + tv::kHypLanes - 1) / tv::kHypLanes), 2), dim3(tv::kHypLanes), 0, st, d_pairs.p, (int)I, (int)nI, d_sets.p, d_mn.p, d_Hi.p, d_H12i.p,
                        d_Fi.p, d_hits.p);
     TV_STAGE();
@@ -114,37 +105,37 @@ iba_status run_chunk(iba_twoview_batch* res, const std::vector<tv::PairPrep>& pr
     TV_STAGE();
     hipLaunchKernelGGL(tv::tv_accept_kernel, dim3(pair_blocks), dim3(64), 0, st, d_pairs.p, (int)nP, (int)opt.min_triangulated, d_res.p, d_aux.p);
     if (!keep) {                                      // without the stages only the candidate hypothesis' entries come down
-        TV_TRY(hipGetLastError());
+        IBA_CALL_TRY(hipGetLastError());
         hipLaunchKernelGGL(tv::tv_gather_kernel, dim3((uint32_t)((maxN + tv::kRtThreads - 1) / tv::kRtThreads), (uint32_t)nP), dim3(tv::kRtThreads), 0, st, d_pairs.p, d_res.p, d_aux.p, d_pts.p, d_cos.p,
                            d_verdict.p, d_sel_pts.p, d_sel_cos.p, d_sel_verdict.p);
     }
     TV_STAGE();
 #undef TV_STAGE
     // ---- everything down ----
-    std::vector<int32_t> h_aux(4 * (size_t)nP);
-    std::vector<tv::Cam> h_cams(8 * (size_t)nP);
-    std::vector<uint8_t> h_inl(2 * M), h_verdict(keep ? 8 * M : M);                 // kept: per hypothesis; else the candidate's alone
-    std::vector<float> h_pts(keep ? 24 * M : 3 * M), h_cos(keep ? 8 * M : M), h_Hi, h_H12i, h_Fi, h_sH, h_sF;
-    int32_t hits = 0;
-    TV_TRY(hipMemcpyAsync(h_res.data(), d_res.p, sizeof(iba_twoview_result) * (size_t)nP, hipMemcpyDeviceToHost, st));
-    TV_TRY(hipMemcpyAsync(h_aux.data(), d_aux.p, sizeof(int32_t) * 4 * (size_t)nP, hipMemcpyDeviceToHost, st));
-    TV_TRY(hipMemcpyAsync(h_cams.data(), d_cams.p, sizeof(tv::Cam) * 8 * (size_t)nP, hipMemcpyDeviceToHost, st));
-    TV_TRY(hipMemcpyAsync(h_inl.data(), d_inl.p, 2 * M, hipMemcpyDeviceToHost, st));
-    TV_TRY(hipMemcpyAsync(h_verdict.data(), keep ? d_verdict.p : d_sel_verdict.p, h_verdict.size(), hipMemcpyDeviceToHost, st));
-    TV_TRY(hipMemcpyAsync(h_pts.data(), keep ? d_pts.p : d_sel_pts.p, sizeof(float) * h_pts.size(), hipMemcpyDeviceToHost, st));
-    TV_TRY(hipMemcpyAsync(h_cos.data(), keep ? d_cos.p : d_sel_cos.p, sizeof(float) * h_cos.size(), hipMemcpyDeviceToHost, st));
-    TV_TRY(hipMemcpyAsync(&hits, d_hits.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    h_aux.resize(4 * (size_t)nP);
+    h_cams.resize(8 * (size_t)nP);
+    h_inl.resize(2 * M); h_verdict.resize(keep ? 8 * M : M);                        // kept: per hypothesis; else the candidate's alone
+    h_pts.resize(keep ? 24 * M : 3 * M); h_cos.resize(keep ? 8 * M : M);
+    IBA_CALL_TRY(hipMemcpyAsync(h_res.data(), d_res.p, sizeof(iba_twoview_result) * (size_t)nP, hipMemcpyDeviceToHost, st));
+    IBA_CALL_TRY(hipMemcpyAsync(h_aux.data(), d_aux.p, sizeof(int32_t) * 4 * (size_t)nP, hipMemcpyDeviceToHost, st));
+    IBA_CALL_TRY(hipMemcpyAsync(h_cams.data(), d_cams.p, sizeof(tv::Cam) * 8 * (size_t)nP, hipMemcpyDeviceToHost, st));
+    IBA_CALL_TRY(hipMemcpyAsync(h_inl.data(), d_inl.p, 2 * M, hipMemcpyDeviceToHost, st));
+    IBA_CALL_TRY(hipMemcpyAsync(h_verdict.data(), keep ? d_verdict.p : d_sel_verdict.p, h_verdict.size(), hipMemcpyDeviceToHost, st));
+    IBA_CALL_TRY(hipMemcpyAsync(h_pts.data(), keep ? d_pts.p : d_sel_pts.p, sizeof(float) * h_pts.size(), hipMemcpyDeviceToHost, st));
+    IBA_CALL_TRY(hipMemcpyAsync(h_cos.data(), keep ? d_cos.p : d_sel_cos.p, sizeof(float) * h_cos.size(), hipMemcpyDeviceToHost, st));
+    IBA_CALL_TRY(hipMemcpyAsync(&hits, d_hits.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (keep) {
         h_Hi.resize(9 * nI); h_H12i.resize(9 * nI); h_Fi.resize(9 * nI); h_sH.resize(nI); h_sF.resize(nI);
-        TV_TRY(hipMemcpyAsync(h_Hi.data(), d_Hi.p, sizeof(float) * 9 * nI, hipMemcpyDeviceToHost, st));
-        TV_TRY(hipMemcpyAsync(h_H12i.data(), d_H12i.p, sizeof(float) * 9 * nI, hipMemcpyDeviceToHost, st));
-        TV_TRY(hipMemcpyAsync(h_Fi.data(), d_Fi.p, sizeof(float) * 9 * nI, hipMemcpyDeviceToHost, st));
-        TV_TRY(hipMemcpyAsync(h_sH.data(), d_sH.p, sizeof(float) * nI, hipMemcpyDeviceToHost, st));
-        TV_TRY(hipMemcpyAsync(h_sF.data(), d_sF.p, sizeof(float) * nI, hipMemcpyDeviceToHost, st));
+        IBA_CALL_TRY(hipMemcpyAsync(h_Hi.data(), d_Hi.p, sizeof(float) * 9 * nI, hipMemcpyDeviceToHost, st));
+        IBA_CALL_TRY(hipMemcpyAsync(h_H12i.data(), d_H12i.p, sizeof(float) * 9 * nI, hipMemcpyDeviceToHost, st));
+        IBA_CALL_TRY(hipMemcpyAsync(h_Fi.data(), d_Fi.p, sizeof(float) * 9 * nI, hipMemcpyDeviceToHost, st));
+        IBA_CALL_TRY(hipMemcpyAsync(h_sH.data(), d_sH.p, sizeof(float) * nI, hipMemcpyDeviceToHost, st));
+        IBA_CALL_TRY(hipMemcpyAsync(h_sF.data(), d_sF.p, sizeof(float) * nI, hipMemcpyDeviceToHost, st));
     }
-    TV_TRY(hipStreamSynchronize(st));
+    IBA_CALL_TRY(hipStreamSynchronize(st));
+    sync.disarm();
     if (timing)
-        for (int k = 0; k < 7; ++k) { float ms = 0.f; TV_TRY(hipEventElapsedTime(&ms, ev.e[(size_t)k], ev.e[(size_t)k + 1])); res->ms[k] += ms; }
+        for (int k = 0; k < 7; ++k) { float ms = 0.f; IBA_CALL_TRY(hipEventElapsedTime(&ms, ev.e[(size_t)k], ev.e[(size_t)k + 1])); res->ms[k] += ms; }
     res->sweeps30 += hits;
     for (int32_t k = 0; k < nP; ++k) {
         const tv::PairRec& r = recs[(size_t)k];
@@ -179,17 +170,29 @@ iba_status run_chunk(iba_twoview_batch* res, const std::vector<tv::PairPrep>& pr
 }
 
 iba_status check_pair_index(const iba_twoview_batch* r, int32_t pair, const std::string& who) {
-    if (!r) return fail(IBA_ERR_INVALID_ARG, who + "the result is NULL");
-    if (pair < 0 || (size_t)pair >= r->pair.size()) return fail(IBA_ERR_INVALID_ARG, who + "pair " + std::to_string(pair) + " is outside the result's " + std::to_string(r->pair.size()) + " pairs");
+    return t_err.check_index(!r, pair, r ? r->pair.size() : 0, who, "pair");
+}
+
+// the chains of a call: consecutive pairs under the byte budget, at most 32768 and at least one per chunk
+iba_status run_chunks(iba_twoview_batch* res, const std::vector<tv::PairPrep>& prep, int device, bool timing) {
+    uint64_t budget = 0;
+    IBA_CALL_TRY(iba::call_budget(device, kBudgetBytes, "IBA_TWOVIEW_BUDGET", &budget));
+    std::vector<uint64_t> bytes(prep.size());
+    for (size_t b = 0; b < prep.size(); ++b) bytes[b] = pair_bytes(prep[b].N, res->opt.iterations);
+    const std::vector<int32_t> cut = iba::cut_chunks(bytes, budget, 32768);
+    for (size_t c = 0; c + 1 < cut.size(); ++c) {
+        ++res->chunks;
+        if (const iba_status s = run_chunk(res, prep, cut[c], cut[c + 1], timing)) return s;
+    }
     return IBA_OK;
 }
 
 iba_status run(const char* name, const iba_twoview_pair* pairs, int32_t B, const iba_twoview_options* opt, int device, bool on_host, iba_twoview_batch** out) {
     const std::string who = std::string(name) + ": ";
     if (out) *out = nullptr;
-    if (!out) return fail(IBA_ERR_INVALID_ARG, who + "out is NULL");
+    if (!out) return t_err.fail(IBA_ERR_INVALID_ARG, who + "out is NULL");
     const std::string why = tv::check_call(pairs, B, opt);
-    if (!why.empty()) return fail(IBA_ERR_INVALID_ARG, who + why);
+    if (!why.empty()) return t_err.fail(IBA_ERR_INVALID_ARG, who + why);
     iba_twoview_batch* res = new iba_twoview_batch();
     res->opt = *opt;
     res->pair.resize((size_t)B);
@@ -200,22 +203,12 @@ iba_status run(const char* name, const iba_twoview_pair* pairs, int32_t B, const
         for (int32_t b = 0; b < B; ++b) tv::host_pair(prep[(size_t)b], *opt, res->pair[(size_t)b], &res->sweeps30);
     } else {
         for (int32_t b = 0; b < B; ++b) tv::start_result(prep[(size_t)b], res->pair[(size_t)b]);
-        uint64_t budget = kBudgetBytes;
-        if (const char* e = iba::debug_env("IBA_TWOVIEW_BUDGET")) budget = std::strtoull(e, nullptr, 10);
         const bool timing = iba::debug_env("IBA_TWOVIEW_TIMING") != nullptr;
-        const hipError_t e = hipSetDevice(device);
-        if (e != hipSuccess) s = fail_hip("hipSetDevice(device)", e);
-        for (int32_t a = 0; a < B && s == IBA_OK;) {      // consecutive pairs under the budget, at least one
-            int32_t b = a;
-            uint64_t bytes = 0;
-            do { bytes += pair_bytes(prep[(size_t)b].N, opt->iterations); ++b; } while (b < B && b - a < 32768 && bytes + pair_bytes(prep[(size_t)b].N, opt->iterations) <= budget);
-            s = run_chunk(res, prep, a, b, timing);
-            a = b;
-        }
+        s = run_chunks(res, prep, device, timing);
         if (s == IBA_OK)
             for (int32_t b = 0; b < B; ++b) tv::finish(*opt, opt->keep_stages != 0, res->pair[(size_t)b]);
     }
-    if (s != IBA_OK) { t_err = who + t_err; delete res; return s; }
+    if (s != IBA_OK) { t_err.msg = who + t_err.msg; delete res; return s; }
     *out = res;
     return IBA_OK;
 }
@@ -224,10 +217,10 @@ iba_status run(const char* name, const iba_twoview_pair* pairs, int32_t B, const
 
 extern "C" {
 
-const char* iba_twoview_last_error(void) { return t_err.c_str(); }
+const char* iba_twoview_last_error(void) { return t_err.msg.c_str(); }
 
 iba_status iba_default_twoview_options(iba_twoview_options* opt) {
-    if (!opt) return fail(IBA_ERR_INVALID_ARG, "iba_default_twoview_options: opt is NULL");
+    if (!opt) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_default_twoview_options: opt is NULL");
     std::memset(opt, 0, sizeof(*opt));
     opt->struct_size = (int32_t)sizeof(*opt);
     opt->sigma = 1.0f; opt->iterations = 200; opt->min_parallax_deg = 1.0f; opt->min_triangulated = 50; opt->rh_threshold = 0.40f; opt->keep_stages = 0;
@@ -244,7 +237,7 @@ int32_t iba_twoview_n_pairs(const iba_twoview_batch* r) { return r ? (int32_t)r-
 
 iba_status iba_twoview_read(const iba_twoview_batch* r, int32_t pair, iba_twoview_result* result) {
     if (const iba_status s = check_pair_index(r, pair, "iba_twoview_read: ")) return s;
-    if (!result) return fail(IBA_ERR_INVALID_ARG, "iba_twoview_read: result is NULL");
+    if (!result) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_twoview_read: result is NULL");
     *result = r->pair[(size_t)pair].r;
     return IBA_OK;
 }
@@ -268,7 +261,7 @@ iba_status iba_twoview_points(const iba_twoview_batch* r, int32_t pair, float* p
 iba_status iba_twoview_iterations(const iba_twoview_batch* r, int32_t pair, float* Hi, float* H12i, float* Fi, float* score_H, float* score_F) {
     const std::string who = "iba_twoview_iterations: ";
     if (const iba_status s = check_pair_index(r, pair, who)) return s;
-    if (!r->opt.keep_stages) return fail(IBA_ERR_INVALID_ARG, who + "the call did not ask for keep_stages");
+    if (!r->opt.keep_stages) return t_err.fail(IBA_ERR_INVALID_ARG, who + "the call did not ask for keep_stages");
     const tv::PairRes& o = r->pair[(size_t)pair];
     const size_t I = (size_t)r->opt.iterations;
     const auto put = [](float* dst, const std::vector<float>& src, size_t n) {
@@ -282,8 +275,8 @@ iba_status iba_twoview_iterations(const iba_twoview_batch* r, int32_t pair, floa
 iba_status iba_twoview_hypothesis(const iba_twoview_batch* r, int32_t pair, int32_t hyp, float R[9], float t[3], int32_t* n_good, float* points, uint8_t* verdict) {
     const std::string who = "iba_twoview_hypothesis: ";
     if (const iba_status s = check_pair_index(r, pair, who)) return s;
-    if (!r->opt.keep_stages) return fail(IBA_ERR_INVALID_ARG, who + "the call did not ask for keep_stages");
-    if (hyp < 0 || hyp >= 8) return fail(IBA_ERR_INVALID_ARG, who + "hypothesis " + std::to_string(hyp) + " is outside 0..7");
+    if (!r->opt.keep_stages) return t_err.fail(IBA_ERR_INVALID_ARG, who + "the call did not ask for keep_stages");
+    if (hyp < 0 || hyp >= 8) return t_err.fail(IBA_ERR_INVALID_ARG, who + "hypothesis " + std::to_string(hyp) + " is outside 0..7");
     const tv::PairRes& o = r->pair[(size_t)pair];
     const size_t N = (size_t)o.N;
     if (R) std::memcpy(R, o.hyp_R + 9 * hyp, 9 * sizeof(float));
@@ -296,15 +289,15 @@ iba_status iba_twoview_hypothesis(const iba_twoview_batch* r, int32_t pair, int3
 }
 
 iba_status iba_twoview_normalize(const float* xy, int32_t n, float* out_xy, float T[9]) {
-    if (n < 0 || !T || (n && (!xy || !out_xy))) return fail(IBA_ERR_INVALID_ARG, "iba_twoview_normalize: n < 0 or a NULL argument");
-    for (int32_t i = 0; i < 2 * n; ++i) if (!std::isfinite(xy[i])) return fail(IBA_ERR_INVALID_ARG, "iba_twoview_normalize: position " + std::to_string(i / 2) + " is not finite");
+    if (n < 0 || !T || (n && (!xy || !out_xy))) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_twoview_normalize: n < 0 or a NULL argument");
+    for (int32_t i = 0; i < 2 * n; ++i) if (!std::isfinite(xy[i])) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_twoview_normalize: position " + std::to_string(i / 2) + " is not finite");
     tv::normalize(xy, n, out_xy, T);
     return IBA_OK;
 }
 
 iba_status iba_twoview_sets(int32_t N, int32_t iterations, uint64_t seed, int32_t* out) {
     const std::string why = tv::make_sets(N, iterations, seed, out);
-    return why.empty() ? IBA_OK : fail(IBA_ERR_INVALID_ARG, "iba_twoview_sets: " + why);
+    return why.empty() ? IBA_OK : t_err.fail(IBA_ERR_INVALID_ARG, "iba_twoview_sets: " + why);
 }
 
 // ---- debug (include/iba_mi355x_debug.h) ----
@@ -314,14 +307,14 @@ iba_status iba_debug_twoview_host(const iba_twoview_pair* pairs, int32_t B, cons
 }
 
 iba_status iba_debug_twoview_null_vector(const float* A, int32_t m, int32_t n, float* v, double* v64, int32_t* sweeps) {
-    if (!A || !v || !sweeps) return fail(IBA_ERR_INVALID_ARG, "iba_debug_twoview_null_vector: a NULL argument");
+    if (!A || !v || !sweeps) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_debug_twoview_null_vector: a NULL argument");
     double G[144], V[81];
     for (int32_t i = 0; i < m * n && i < 144; ++i) G[i] = (double)A[i];
     if (m == 16 && n == 9) *sweeps = tv::null_vector<16, 9, 1, 0>(G, V, v);
     else if (m == 8 && n == 9) *sweeps = tv::null_vector<8, 9, 1, 0>(G, V, v);
     else if (m == 4 && n == 4) *sweeps = tv::null_vector<4, 4, 1, 1>(G, V, v);
     else if (m == 3 && n == 3) *sweeps = tv::null_vector<3, 3, 1, 1>(G, V, v);
-    else return fail(IBA_ERR_INVALID_ARG, "iba_debug_twoview_null_vector: the sizes are 16 x 9, 8 x 9, 4 x 4 and 3 x 3");
+    else return t_err.fail(IBA_ERR_INVALID_ARG, "iba_debug_twoview_null_vector: the sizes are 16 x 9, 8 x 9, 4 x 4 and 3 x 3");
     if (v64)                                          // the column v was rounded from: the one of V that rounds to it
         for (int32_t c = 0; c < n; ++c) {
             bool is = true;
@@ -333,8 +326,10 @@ iba_status iba_debug_twoview_null_vector(const float* A, int32_t m, int32_t n, f
 
 int32_t iba_debug_twoview_sweep_cap_hits(const iba_twoview_batch* r) { return r ? r->sweeps30 : 0; }
 
+int32_t iba_debug_twoview_chunks(const iba_twoview_batch* r) { return r ? r->chunks : 0; }
+
 iba_status iba_debug_twoview_stage_ms(const iba_twoview_batch* r, float ms[7]) {
-    if (!r || !ms) return fail(IBA_ERR_INVALID_ARG, "iba_debug_twoview_stage_ms: a NULL argument");
+    if (!r || !ms) return t_err.fail(IBA_ERR_INVALID_ARG, "iba_debug_twoview_stage_ms: a NULL argument");
     std::memcpy(ms, r->ms, sizeof(r->ms));
     return IBA_OK;
 }

@@ -297,5 +297,6 @@ struct iba_twoview_batch {
     iba_twoview_options opt{};
     std::vector<iba::tv::PairRes> pair;
     int32_t sweeps30 = 0;                       // null-vector solves whose 30th sweep still rotated (debug)
+    int32_t chunks = 0;                         // chains the call ran as (debug); 0 on the host
     float ms[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 };

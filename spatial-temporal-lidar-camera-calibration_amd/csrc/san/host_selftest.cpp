@@ -236,8 +236,20 @@ static void projection_host() {
     b.camera[4] = 8193.0; b.camera[5] = 8192.0; CHECK(!prj::validate(&b, x, fr, 2, 2, intr).empty());
     const std::vector<uint64_t> px = {960, 960, 0, 960, 5000, 960};
     CHECK((prj::cut_chunks(px, 2 * 16 * 960) == std::vector<int32_t>{0, 3, 4, 5, 6}));      // (an empty job costs nothing; a job beyond the budget runs alone)
-    CHECK((prj::cut_chunks(px, 1) == std::vector<int32_t>{0, 1, 2, 4, 5, 6}) && (prj::cut_chunks(px, ~0ull >> 1) == std::vector<int32_t>{0, 6}));
+    // (a chunk closes once it holds a job, not a byte: the zero-pixel job runs alone here. The validation refuses W or H < 1, so none reaches the cutter)
+    CHECK((prj::cut_chunks(px, 1) == std::vector<int32_t>{0, 1, 2, 3, 4, 5, 6}) && (prj::cut_chunks(px, ~0ull >> 1) == std::vector<int32_t>{0, 6}));
     CHECK((prj::cut_chunks({}, 100) == std::vector<int32_t>{0, 0}));
+    // the shared cutter itself (iba_chunks.hpp): the orb-match vector of tests/test_orb_match_cpu.py::test_chunk_planner, the item cap, the edges
+    using iba::cut_chunks;
+    const std::vector<uint64_t> cand = {6 * 10, 6 * 0, 6 * 25, 6 * 5, 6 * 5, 6 * 100, 6 * 1}, ones(7, 1);
+    CHECK((cut_chunks(cand, 1ull << 30) == std::vector<int32_t>{0, 7}) && (cut_chunks(cand, 1) == std::vector<int32_t>{0, 1, 2, 3, 4, 5, 6, 7}));
+    CHECK((cut_chunks(cand, 35 * 6) == std::vector<int32_t>{0, 3, 5, 6, 7}));
+    CHECK((cut_chunks(ones, 1ull << 30, 2) == std::vector<int32_t>{0, 2, 4, 6, 7}) && (cut_chunks(ones, 1ull << 30, 1) == std::vector<int32_t>{0, 1, 2, 3, 4, 5, 6, 7}));
+    CHECK((cut_chunks({3, 3, 50, 3, 3}, 10) == std::vector<int32_t>{0, 2, 3, 5}));         // an item larger than the budget runs alone
+    CHECK((cut_chunks({}, 100) == std::vector<int32_t>{0, 0}));
+    const uint64_t half = ~0ull >> 1;                                                       // the sums stay below 2^64: no wrap
+    CHECK((cut_chunks({half, half, 2, half - 1, 1, ~0ull, ~0ull, 1}, half) == std::vector<int32_t>{0, 1, 2, 3, 5, 6, 7, 8}));
+    CHECK((cut_chunks({half - 1, 1, 1}, half) == std::vector<int32_t>{0, 2, 3}));
     uint8_t c[3];
     const double zs[] = {-1.0, 0.0, 0.125, 0.25, 0.5, 0.75, 0.999999, 1.0, 2.0, NAN, INFINITY};
     const int want[][3] = {{0, 0, 255}, {0, 0, 255}, {0, 128, 255}, {0, 255, 255}, {0, 255, 0}, {255, 255, 0}, {255, 0, 0}, {255, 0, 0}, {255, 0, 0}, {0, 0, 255}, {255, 0, 0}};

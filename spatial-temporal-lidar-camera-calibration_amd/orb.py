@@ -1,10 +1,12 @@
 """ctypes mirror of the ORB feature extraction (include/iba_mi355x.h, iba_orb_*; csrc/iba_orb.hip): the options, the batch call, the result object
 with its stage accessors, and the two host-only pure functions (plan, distribute). Plumbing only: nothing is computed here."""
 import ctypes as C
+from functools import partial
 
 import numpy as np
 
-from . import IbaError, load_library
+from . import load_library
+from ._percall import Result, options_from, ptr as _p, raise_last
 
 
 class IbaOrbImage(C.Structure):
@@ -14,10 +16,6 @@ class IbaOrbImage(C.Structure):
 class IbaOrbOptions(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_features", C.c_int32), ("scale_factor", C.c_float), ("n_levels", C.c_int32), ("ini_th_fast", C.c_int32),
                 ("min_th_fast", C.c_int32), ("keep_stages", C.c_int32), ("reserved", C.c_int32), ("pattern", C.c_void_p)]
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def _lib():
@@ -46,21 +44,13 @@ def _lib():
     return L
 
 
-def _raise(L, st):
-    raise IbaError(st, L.iba_orb_last_error().decode())
+_raise = partial(raise_last, "iba_orb_last_error")
 
 
 def orb_options(pattern=None, **fields):
     """iba_default_orb_options with fields overridden. pattern: int8 [256, 4] (x0 y0 x1 y1 per test); the returned struct keeps the array alive."""
     L = _lib()
-    o = IbaOrbOptions()
-    st = L.iba_default_orb_options(C.byref(o))
-    if st != 0:
-        _raise(L, st)
-    for k, v in fields.items():
-        if k not in dict(IbaOrbOptions._fields_):
-            raise AttributeError(k)
-        setattr(o, k, v)
+    o = options_from(IbaOrbOptions, L.iba_default_orb_options, L.iba_orb_last_error, **fields)
     if pattern is not None:
         o._pattern = np.ascontiguousarray(pattern, np.int8).reshape(256, 4)
         o.pattern = o._pattern.ctypes.data
@@ -123,11 +113,13 @@ def describe(gray, xy, angle, pattern, device=0):
     return blurred, desc
 
 
-class OrbFeatures:
+class OrbFeatures(Result):
     """iba_orb_features wrapper: the keypoints and descriptors of the images of one iba_orb_extract; close() it"""
+    FREE, LAST_ERROR = "iba_orb_free", "iba_orb_last_error"
 
     def __init__(self, lib, p, n_levels):
-        self.lib, self.p, self.n_levels = lib, p, n_levels
+        super().__init__(lib, p)
+        self.n_levels = n_levels
 
     @classmethod
     def stub(cls, n_images, n_levels=8, keep_stages=0):
@@ -138,21 +130,6 @@ class OrbFeatures:
         if st != 0:
             _raise(L, st)
         return cls(L, p, n_levels)
-
-    def _chk(self, st):
-        if st != 0:
-            _raise(self.lib, st)
-
-    def close(self):
-        if getattr(self, "p", None) and self.p.value:
-            self.lib.iba_orb_free(self.p)
-            self.p = C.c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __len__(self):
         return int(self.lib.iba_orb_n_images(self.p))

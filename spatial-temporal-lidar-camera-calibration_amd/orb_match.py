@@ -1,10 +1,12 @@
 """ctypes mirror of the windowed ORB matching (include/iba_mi355x.h, iba_orb_match*; csrc/iba_orb_match.hip): frames, jobs and options, the batch
 call, the result object with its stage accessors, and the two host-only query builders. Plumbing only: nothing is computed here."""
 import ctypes as C
+from functools import partial
 
 import numpy as np
 
-from . import IbaError, load_library
+from . import load_library
+from ._percall import Result, options_from, ptr as _p, raise_last
 
 INIT, CLAIM = 0, 1
 N_CELLS, HISTO = 64 * 48, 30
@@ -30,10 +32,6 @@ class IbaOrbMatchCounts(C.Structure):
                 ("hist", C.c_int32 * HISTO), ("ind", C.c_int32 * 3)]
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def _lib():
     L = load_library()
     L.iba_orb_match_last_error.restype = C.c_char_p
@@ -56,22 +54,13 @@ def _lib():
     return L
 
 
-def _raise(L, st):
-    raise IbaError(st, L.iba_orb_match_last_error().decode())
+_raise = partial(raise_last, "iba_orb_match_last_error")
 
 
 def match_options(**fields):
     """iba_default_orb_match_options with fields overridden"""
     L = _lib()
-    o = IbaOrbMatchOptions()
-    st = L.iba_default_orb_match_options(C.byref(o))
-    if st != 0:
-        _raise(L, st)
-    for k, v in fields.items():
-        if k not in dict(IbaOrbMatchOptions._fields_):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return options_from(IbaOrbMatchOptions, L.iba_default_orb_match_options, L.iba_orb_match_last_error, **fields)
 
 
 def frame(xy, octave, angle, desc, bounds):
@@ -149,11 +138,13 @@ def plan_chunks(candidates, budget):
     return cut[:n.value].copy()
 
 
-class OrbMatches:
+class OrbMatches(Result):
     """iba_orb_matches wrapper: the results of the jobs of one iba_orb_match; close() it"""
+    FREE, LAST_ERROR = "iba_orb_matches_free", "iba_orb_match_last_error"
 
     def __init__(self, lib, p, frame_n):
-        self.lib, self.p, self.frame_n = lib, p, frame_n
+        super().__init__(lib, p)
+        self.frame_n = frame_n
 
     @classmethod
     def stub(cls, n_jobs, n_frames, keep_stages=0):
@@ -164,21 +155,6 @@ class OrbMatches:
         if st != 0:
             _raise(L, st)
         return cls(L, p, [0] * n_frames)
-
-    def _chk(self, st):
-        if st != 0:
-            _raise(self.lib, st)
-
-    def close(self):
-        if getattr(self, "p", None) and self.p.value:
-            self.lib.iba_orb_matches_free(self.p)
-            self.p = C.c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __len__(self):
         return int(self.lib.iba_orb_matches_n_jobs(self.p))

@@ -1,10 +1,12 @@
 """ctypes mirror of the motion-only pose optimisation (include/iba_mi355x.h, iba_pose*; csrc/iba_pose.hip): jobs and options, the batch call, the
 result object with its accessors, the single linearisation, the host-only edge builder and the debug hooks. Plumbing only: nothing is computed here."""
 import ctypes as C
+from functools import partial
 
 import numpy as np
 
-from . import IbaError, load_library
+from . import load_library
+from ._percall import Result, options_from, ptr as _p, raise_last
 
 ONCHIP_EDGES = 1024
 MAX_ROUNDS = 8
@@ -23,10 +25,6 @@ class IbaPoseOptions(C.Structure):
 class IbaPoseResult(C.Structure):
     _fields_ = [("n", C.c_int32), ("n_inliers", C.c_int32), ("rounds_run", C.c_int32), ("reserved", C.c_int32), ("Tcw12", C.c_double * 12), ("Tcw12f", C.c_float * 12),
                 ("chi2", C.c_double * MAX_ROUNDS), ("n_bad", C.c_int32 * MAX_ROUNDS), ("lm_iterations", C.c_int32 * MAX_ROUNDS), ("trials", C.c_int32 * MAX_ROUNDS)]
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def _lib():
@@ -54,22 +52,13 @@ def _lib():
     return L
 
 
-def _raise(L, st):
-    raise IbaError(st, L.iba_pose_last_error().decode())
+_raise = partial(raise_last, "iba_pose_last_error")
 
 
 def options(**fields):
     """iba_default_pose_options with fields overridden"""
     L = _lib()
-    o = IbaPoseOptions()
-    st = L.iba_default_pose_options(C.addressof(o))
-    if st != 0:
-        _raise(L, st)
-    for k, v in fields.items():
-        if k not in dict(IbaPoseOptions._fields_):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return options_from(IbaPoseOptions, L.iba_default_pose_options, L.iba_pose_last_error, **fields)
 
 
 def job(Tcw, xyz, obs, inv_sigma2, K):
@@ -94,26 +83,13 @@ def _job_array(jobs):
     return ja
 
 
-class Pose:
+class Pose(Result):
     """iba_pose_batch wrapper: the results of the jobs of one iba_pose_optimize; close() it"""
+    FREE, LAST_ERROR = "iba_pose_free", "iba_pose_last_error"
 
     def __init__(self, lib, p, n):
-        self.lib, self.p, self.n = lib, p, n
-
-    def _chk(self, st):
-        if st != 0:
-            _raise(self.lib, st)
-
-    def close(self):
-        if getattr(self, "p", None) and self.p.value:
-            self.lib.iba_pose_free(self.p)
-            self.p = C.c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(lib, p)
+        self.n = n
 
     def __len__(self):
         return int(self.lib.iba_pose_n_jobs(self.p))

@@ -1,10 +1,12 @@
 """ctypes mirror of the scan-to-image projection (include/iba_mi355x.h, iba_project_* / iba_projection_*; csrc/iba_project.hip): the options, the run
 on a handle, and the result object whose accessors copy one job's product down. Plumbing only: nothing is computed here."""
 import ctypes as C
+from functools import partial
 
 import numpy as np
 
-from . import IbaError, load_library
+from . import load_library
+from ._percall import Result, options_from, ptr as _p, raise_last
 
 IN_FRONT, INSIDE, VISIBLE = 1, 2, 4
 
@@ -19,10 +21,6 @@ class IbaProjectCounts(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def _lib():
@@ -49,24 +47,16 @@ def _lib():
     return L
 
 
-def _raise(L, st):
-    raise IbaError(st, L.iba_project_last_error().decode())
+_raise = partial(raise_last, "iba_project_last_error")
 
 
 def project_options(**fields):
     """iba_default_project_options with fields overridden; camera takes six numbers (fx, fy, cx, cy, W, H)"""
     L = _lib()
-    o = IbaProjectOptions()
-    st = L.iba_default_project_options(C.byref(o))
-    if st != 0:
-        _raise(L, st)
-    for k, v in fields.items():
-        if k not in dict(IbaProjectOptions._fields_):
-            raise AttributeError(k)
-        if k == "camera":
-            o.camera[:] = [float(x) for x in np.asarray(v, np.float64).reshape(6)]
-        else:
-            setattr(o, k, v)
+    camera = fields.pop("camera", None)
+    o = options_from(IbaProjectOptions, L.iba_default_project_options, L.iba_project_last_error, **fields)
+    if camera is not None:
+        o.camera[:] = [float(x) for x in np.asarray(camera, np.float64).reshape(6)]
     return o
 
 
@@ -92,11 +82,9 @@ def validate(n_frames, intrinsics6, x7, frames, J, opt):
         _raise(L, st)
 
 
-class Projection:
+class Projection(Result):
     """iba_projection wrapper: the products of the jobs of one iba_project_run, on the device until an accessor copies one job down; close() it"""
-
-    def __init__(self, lib, p):
-        self.lib, self.p = lib, p
+    FREE, LAST_ERROR = "iba_projection_free", "iba_project_last_error"
 
     @classmethod
     def stub(cls, n_jobs):
@@ -107,21 +95,6 @@ class Projection:
         if st != 0:
             _raise(L, st)
         return cls(L, p)
-
-    def _chk(self, st):
-        if st != 0:
-            _raise(self.lib, st)
-
-    def close(self):
-        if getattr(self, "p", None) and self.p.value:
-            self.lib.iba_projection_free(self.p)
-            self.p = C.c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __len__(self):
         return int(self.lib.iba_projection_n_jobs(self.p))

@@ -1,10 +1,12 @@
 """ctypes mirror of the two-view initialisation (include/iba_mi355x.h, iba_twoview*; csrc/iba_twoview.hip): pairs and options, the batch call, the
 result object with its stage accessors, the two host-only builders and the debug hooks. Plumbing only: nothing is computed here."""
 import ctypes as C
+from functools import partial
 
 import numpy as np
 
-from . import IbaError, load_library
+from . import load_library
+from ._percall import Result, options_from, ptr as _p, raise_last
 
 OK, TOO_FEW_MATCHES, NO_MODEL, H_DEGENERATE, NO_CLEAR_WINNER, TOO_FEW_POINTS, LOW_PARALLAX = range(7)
 STATUS_NAMES = ("OK", "TOO_FEW_MATCHES", "NO_MODEL", "H_DEGENERATE", "NO_CLEAR_WINNER", "TOO_FEW_POINTS", "LOW_PARALLAX")
@@ -32,10 +34,6 @@ SCALARS = ("status", "n_matches", "model", "n_hyp", "chosen", "best_it_H", "best
 ARRAYS = ("H21", "F21", "n_good", "cos_parallax", "parallax_deg", "R21", "t21")
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def _lib():
     L = load_library()
     L.iba_twoview_last_error.restype = C.c_char_p
@@ -55,26 +53,18 @@ def _lib():
     L.iba_twoview_sets.argtypes = [C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]
     L.iba_debug_twoview_null_vector.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.iba_debug_twoview_sweep_cap_hits.argtypes = [C.c_void_p]
+    L.iba_debug_twoview_chunks.argtypes = [C.c_void_p]
     L.iba_debug_twoview_stage_ms.argtypes = [C.c_void_p, C.c_void_p]
     return L
 
 
-def _raise(L, st):
-    raise IbaError(st, L.iba_twoview_last_error().decode())
+_raise = partial(raise_last, "iba_twoview_last_error")
 
 
 def options(**fields):
     """iba_default_twoview_options with fields overridden"""
     L = _lib()
-    o = IbaTwoviewOptions()
-    st = L.iba_default_twoview_options(C.addressof(o))
-    if st != 0:
-        _raise(L, st)
-    for k, v in fields.items():
-        if k not in dict(IbaTwoviewOptions._fields_):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return options_from(IbaTwoviewOptions, L.iba_default_twoview_options, L.iba_twoview_last_error, **fields)
 
 
 def pair(xy1, xy2, matches12, K, sets=None):
@@ -126,29 +116,21 @@ def null_vector(A):
     return v, v64, sw.value
 
 
-class Twoview:
+class Twoview(Result):
     """iba_twoview_batch wrapper: the results of the pairs of one iba_twoview_init; close() it"""
+    FREE, LAST_ERROR = "iba_twoview_free", "iba_twoview_last_error"
 
     def __init__(self, lib, p, n1, iterations):
-        self.lib, self.p, self.n1, self.iterations = lib, p, n1, iterations
-
-    def _chk(self, st):
-        if st != 0:
-            _raise(self.lib, st)
-
-    def close(self):
-        if getattr(self, "p", None) and self.p.value:
-            self.lib.iba_twoview_free(self.p)
-            self.p = C.c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(lib, p)
+        self.n1, self.iterations = n1, iterations
 
     def __len__(self):
         return int(self.lib.iba_twoview_n_pairs(self.p))
+
+    @property
+    def chunks(self):
+        """iba_debug_twoview_chunks: the chunks the call ran as; 0 on the host"""
+        return int(self.lib.iba_debug_twoview_chunks(self.p))
 
     @property
     def sweep_cap_hits(self):

@@ -93,6 +93,31 @@ def test_repeated_pairs_and_batch_slices(tv):
     r3.close()
 
 
+def test_chunk_boundaries_change_no_byte(tv, monkeypatch):
+    """the five pairs (ragged N; one below 8 matches) as one chunk, one chunk per pair and something between: the same bytes. The third budget is
+    the documented cost (include/iba_mi355x_debug.h: 187 bytes per match + 148 per iteration) of the two smallest pairs, which are neighbours, plus
+    2 KiB for the fixed records of each; every other pair of neighbours costs far more, so they share a chunk and no chunk holds three."""
+    five = [S.scene_pairs()[k] for k in (0, 1, 3, 6, 2)]
+    refs = [S.scene_reference()[k] for k in (0, 1, 3, 6, 2)]
+    cost = sorted(187 * S.n_matches(p) + 148 * S.ITERATIONS for p in five)
+    between = cost[0] + cost[1] + 2 * 2048
+    assert between < sum(cost)
+    parallax = None
+    for budget, want in ((None, lambda c: c == 1), ("1", lambda c: c == 5), (str(between), lambda c: 1 < c < 5)):
+        if budget is not None:
+            monkeypatch.setenv("IBA_TWOVIEW_BUDGET", budget)
+        r = tv.init([lib_pair(tv, p) for p in five], iterations=S.ITERATIONS, keep_stages=1)
+        if budget is not None:
+            monkeypatch.delenv("IBA_TWOVIEW_BUDGET")
+        assert want(r.chunks), (budget, r.chunks)
+        for b in range(5):
+            assert S.differences(r, b, refs[b]) == [], (budget, b)
+        got = [r.read(b)["parallax_deg"].tobytes() for b in range(5)]
+        assert parallax is None or got == parallax, budget
+        parallax = got
+        r.close()
+
+
 def test_singular_hypothesis_and_scattered_unmatched(tv):
     """set 0 is eight collinear points of frame 1: its homography is singular, H12i is not finite, and the score is whatever IEEE gives; a third of
     matches12 is -1"""
