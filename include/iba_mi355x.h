@@ -1630,6 +1630,169 @@ iba_status iba_pose_edges_from_matches(const int32_t* match, const int32_t* quer
                                        const float* cur_xy /* n_cur x 2 */, const int32_t* cur_octave /* n_cur */, int32_t n_cur, const float* inv_level_sigma2, int32_t n_levels,
                                        float* xyz, float* obs, float* inv_sigma2, int32_t* keypoint_index, int32_t* n);
 
+/*
+ * ---- Bundle adjustment [the camera side's fifth brick: the reference's Optimizer::BundleAdjustment (src/orb_slam/src/Optimizer.cc:215-407: the global
+ * BA of Tracking::CreateInitialMapMonocular, Tracking.cc:686, and of LoopClosing.cc:651) and Optimizer::LocalBundleAdjustment from its "Setup
+ * optimizer" on (:671-937, LocalMapping.cc:80)] ----
+ * A call takes B independent jobs on one device. A job is n_cameras poses Tcw (3 x 4 row-major, float64) with a `fixed` byte each, n_points points
+ * (float32, widened as Converter::toVector3d does), n_edges monocular edges (point, camera, undistorted keypoint position, the information of the
+ * keypoint's pyramid level) IN ANY ORDER, and one set of pinhole intrinsics. Camera poses AND points are optimised together by Levenberg-Marquardt on
+ * the point-marginalised (Schur) reduced camera system. STEREO EDGES ARE NOT PROVIDED (as in iba_pose), pbStopFlag IS NOT PROVIDED, and a job has at
+ * most IBA_BUNDLE_MAX_FREE_CAMERAS cameras that are not fixed (a reduced system of 384 unknowns): a global BA over a larger map is out of scope.
+ * ARITHMETIC. float64, every operation rounded, left to right as written, no contraction, nothing but + - x / sqrt up to a step of theta = pi (P6).
+ * A NaN stored into an output is the canonical quiet NaN. The device and the host restatement (iba_debug_bundle_host, the same text of arithmetic:
+ * csrc/iba_bundle_math.hpp) agree byte for byte; the order of every sum is a function of the job's own index arrays alone and never of the batch, the
+ * chunk, the grid or the launch shape.
+ *
+ *   B1 edge.       p = R X + t, the error e, chi2 and the 2 x 6 pose Jacobian Jc are exactly P1's (pose::edge, not written again). The 2 x 3 point
+ *                  Jacobian is that of EdgeSE3ProjectXYZ::linearizeOplus, -(1/p_z) [fx, 0, -fx p_x/p_z; 0, fy, -fy p_y/p_z] R, associated as: iz =
+ *                  1 / p_z, a = (-(fx p_x)) iz, b = (-(fy p_y)) iz; Jl_0c = (-iz) (fx R_0c + a R_2c), Jl_1c = (-iz) (fy R_1c + b R_2c) (the literal
+ *                  zeros are left out). isDepthPositive is p_z > 0 at the current estimates (false for a NaN).
+ *   B2 Huber.      P2. w = rho' inv_sigma2 scales all of Hpp, Hll, Hpl, bp, bl: Hpp_pq += w (Jc_0p Jc_0q + Jc_1p Jc_1q) (p <= q), bp_p -= w (Jc_0p e_x
+ *                  + Jc_1p e_y), Hll and bl likewise from Jl, and W = Hpl (6 x 3) of ONE edge is W_rc = w (Jc_0r Jl_0c + Jc_1r Jl_1c).
+ *   B3 sums.       A free camera's 21 + 6 sums run over its edges in ascending edge index: the k-th edge of that list (active or not) belongs to
+ *                  lane k mod 64, a lane adds its ACTIVE edges in ascending k onto +0.0, and the 64 lane sums are combined by the balanced tree
+ *                  v[l] = v[2l] + v[2l + 1] (one wave per camera, the DPP sum of iba_pose). A point's 6 + 3 sums and its robust chi2 partial are
+ *                  sequential over its active edges in ascending edge index (one lane per point). The job's robust chi2 is the sum of the partials
+ *                  of the participating points under P3's rule with point p on lane p mod 256.
+ *   B4 what takes part. A point with no active edge is left out and keeps its value (g2o's initializeOptimization(level)). A free camera with no
+ *                  active edge is left out likewise: its step is zero and it has NO ROW in the reduced system, whose rows are the participating
+ *                  free cameras in ascending camera index. A fixed camera contributes to Hll and bl only.
+ *   B5 point blocks. Per participating point A = Hll + lambda I is inverted by cofactors: c00 = a11 a22 - a12 a12, c01 = a02 a12 - a01 a22, c02 = a01
+ *                  a12 - a02 a11, c11 = a00 a22 - a02 a02, c12 = a01 a02 - a00 a12, c22 = a00 a11 - a01 a01, det = (a00 c00 + a01 c01) + a02 c02,
+ *                  A^-1_ij = c_ij (1 / det). A det that is not positive and finite fails the trial as P4's pivot does.
+ *   B6 Schur.      S_ab = [a == b](Hpp_a + lambda I) - sum_p W_pa A_p^-1 W_pb^T and bs_a = bp_a - sum_p W_pa A_p^-1 bl_p. The blocks (a <= b, both
+ *                  free) and per block its items (point, edge of a, edge of b), points ascending, are a host-side plan of the indices alone
+ *                  (iba_bundle_plan); outliers only mask items. Per item Y = W_a A^-1 with Y_rc = (W_r0 A_0c + W_r1 A_1c) + W_r2 A_2c, the term
+ *                  G_rs = (Y_r0 Wb_s0 + Y_r1 Wb_s1) + Y_r2 Wb_s2 and, in a diagonal block, g_r = (Y_r0 bl_0 + Y_r1 bl_1) + Y_r2 bl_2. A block's 36
+ *                  (+ 6) sums follow the camera rule: the k-th item of its list on lane k mod 64, active items ascending onto +0.0, the tree. Only
+ *                  the lower triangle of S is formed: entry (6 rb + s, 6 ra + r) = -G_rs for a < b, and (6 ra + r, 6 ra + s), s <= r, = (Hpp_sr +
+ *                  [r == s] lambda) - G_rs on the diagonal.
+ *   B7 solve.      Cholesky without pivoting, entry by entry: d = s_jj - sum_{k<j} l_jk l_jk, l_jj = sqrt(d), l_ij = (s_ij - sum_{k<j} l_ik l_jk) /
+ *                  l_jj, k ascending, each product subtracted from the running value one at a time. y_i = (bs_i - sum_{k<i} l_ik y_k) / l_ii, k
+ *                  ascending; dp_i = (y_i - sum_{k>i} l_ki dp_k) / l_ii, k DESCENDING from the last row. A d that is not positive and finite is a
+ *                  failed trial. The kernel runs the columns in parallel (one lane per row) and gives the same bytes. Then per participating point
+ *                  dl = A^-1 (bl - sum_a W_pa^T dp_a): v_c = bl_c, and per active edge of the point with a camera that has a row, ascending, v_c
+ *                  -= (((((W_0c d0 + W_1c d1) + W_2c d2) + W_3c d3) + W_4c d4) + W_5c d5); dl_c = (A_c0 v0 + A_c1 v1) + A_c2 v2. Cameras are
+ *                  updated by P6 (unchanged), points by X + dl.
+ *   B8 LM.         P5, generalised in three places: lambda at iteration 0 of every round is 1e-5 x the largest |diagonal| over the Hpp AND the
+ *                  Hll of the participating vertices; scale = 1e-3 + sum dx (lambda dx + b) over every participating unknown, one running sum,
+ *                  cameras ascending then points ascending; the trial's chi2 is B3's. The 10-trial rule, the acceptance, the alpha clamp, ni and
+ *                  the stops are P5's. A failed B5 or B7 is P4's failed trial.
+ *   B9 schedule.   A round continues from the previous round's estimate (LocalBundleAdjustment never resets it). After round r < rounds - 1
+ *                  every still-active edge with (float)chi2 > chi2_threshold or without positive depth is deactivated for good (setLevel(1) is
+ *                  never undone). The kernel is on for rounds < robust_rounds. After the last round every edge, active or not, is classified at
+ *                  the final estimates into the reported outlier flag and float32 chi2: the reference's vToErase is the flagged (camera, point)
+ *                  pairs. Per round: chi2 (the robust sum over the round's active edges at its final estimate), n_bad (edges deactivated so far;
+ *                  for the last round the flagged edges), lm_iterations (begun), trials. n_edges == 0 is legal and changes nothing.
+ *   B10 plan.      Edges come in any order; the per-point and per-camera lists are stable in edge index. A (point, camera) pair that occurs twice
+ *                  is refused: the reference's std::map<KeyFrame*, size_t> cannot hold one.
+ *
+ * UNPINNED, together (g2o is third party and absent): the associations of B1 and B2, all of B5-B7 (g2o's block solver and Eigen's or CSparse's
+ * factorisation), B8 and the order of every sum. KNOWN DEVIATIONS: the two of iba_pose: the given poses are never re-orthonormalised, and classification is
+ * at the accepted estimate; g2o's chi2() of an edge at level 1 is stale from the first round, here every edge is evaluated at the final estimates;
+ * the edge order inside a point is ascending edge index where the reference's is pointer order.
+ * DEVICE (csrc/iba_bundle_kernels.hpp): ONE LAUNCH CHAIN PER LM EVALUATION over the flat tables of all jobs of a chunk - edges (one lane each), point
+ * and camera sums, the job's chi2 and the sequencer's first half (one workgroup per job, one lane sequencing), point inverses, the blocks of the
+ * reduced system (one wave each), the factorisation (one workgroup per job, the matrix in global memory), the steps and trial estimates, the
+ * sequencer's second half - so one large job and a thousand small ones both fill the machine. No workgroup waits for another: kernel boundaries are
+ * the only grid-wide synchronisation. The host reads ONE word per step (the jobs still running) and stops enqueuing at zero; it does no arithmetic
+ * between the upload and the download. Chunks of consecutive jobs run under 1 GiB, or a quarter of the free device memory where that is less; a job
+ * above the budget is a chunk of its own; a chunk boundary changes no byte.
+ * ERRORS, all IBA_ERR_INVALID_ARG with a message (iba_bundle_last_error, per thread) BEFORE the device is touched: a NULL argument (a job's arrays
+ * may be NULL only where their count is 0) or a wrong struct_size; B < 1; a count outside 0..IBA_BUNDLE_MAX_COUNT; a pose, point, observation,
+ * information or intrinsic that is not finite; fx or fy <= 0; inv_sigma2 < 0; an edge's point or camera out of range; a duplicate (point, camera);
+ * more than IBA_BUNDLE_MAX_FREE_CAMERAS free cameras; 2^31 pair items or more; rounds outside 1..4, iterations[r] outside 1..100, robust_rounds
+ * outside 0..4, a threshold or delta that is not finite, chi2_threshold < 0, huber_delta <= 0; a job or round index outside the result; the stage
+ * accessor on a result without keep_stages.
+ */
+#define IBA_BUNDLE_MAX_FREE_CAMERAS 64
+#define IBA_BUNDLE_MAX_ROUNDS 4
+#define IBA_BUNDLE_MAX_COUNT (1 << 24)        /* of a job's cameras, points and edges each: every index fits int32 */
+typedef struct iba_bundle_job {               /* host pointers, read during the call only */
+    const double*  Tcw12;        /* n_cameras x 12 */
+    const uint8_t* fixed;        /* n_cameras: 1 = the camera is not optimised (keyframe 0, the fixed cameras of a local window) */
+    const float*   xyz;          /* n_points x 3: MapPoint::GetWorldPos */
+    const int32_t* edge_point;   /* n_edges */
+    const int32_t* edge_camera;  /* n_edges */
+    const float*   obs;          /* n_edges x 2: mvKeysUn[i].pt */
+    const float*   inv_sigma2;   /* n_edges: mvInvLevelSigma2[octave] */
+    int32_t n_cameras, n_points, n_edges;
+    float fx, fy, cx, cy;
+} iba_bundle_job;
+typedef struct iba_bundle_options {
+    int32_t struct_size;                          /* sizeof(iba_bundle_options) */
+    int32_t rounds;                               /* 2, 1..4 */
+    int32_t iterations[IBA_BUNDLE_MAX_ROUNDS];    /* {5, 10}, 1..100 each */
+    int32_t robust_rounds;                        /* 1: the Huber kernel is off after this many rounds */
+    float   chi2_threshold;                       /* 5.991f */
+    float   huber_delta;                          /* (float)sqrt(5.991); the global schedule: (float)sqrt(5.99), as BundleAdjustment writes it */
+    int32_t keep_stages;                          /* 0; 1 allows iba_bundle_stage */
+} iba_bundle_options;
+typedef struct iba_bundle_result {
+    int32_t n_cameras, n_points, n_edges, n_free;
+    int32_t n_outliers;                           /* the edges flagged by the last classification */
+    int32_t rounds_run;
+    double  chi2[IBA_BUNDLE_MAX_ROUNDS];
+    int32_t n_bad[IBA_BUNDLE_MAX_ROUNDS], lm_iterations[IBA_BUNDLE_MAX_ROUNDS], trials[IBA_BUNDLE_MAX_ROUNDS];
+} iba_bundle_result;
+/* what iba_bundle_eval fills per job: every pointer may be NULL (not wanted). A camera or point that does not take part (B4) reports zeros. */
+typedef struct iba_bundle_eval_out {
+    double* Hpp;          /* n_cameras x 36, both triangles */
+    double* bp;           /* n_cameras x 6 */
+    double* Hll;          /* n_points x 9 */
+    double* bl;           /* n_points x 3 */
+    double* chi2_edges;   /* n_edges: every edge's chi2 (no kernel), active or not */
+    double* S;            /* n_reduced x n_reduced, both triangles mirrored from the lower one; room for (6 x free cameras)^2 */
+    double* bs;           /* n_cameras x 6 */
+    double* dp;           /* n_cameras x 6 */
+    double* dl;           /* n_points x 3 */
+    double  chi2_robust, lambda;
+    int32_t n_reduced;    /* 6 x the participating free cameras */
+    int32_t solved;       /* 0: B5 or B7 failed; S, bs, dp, dl are zeros */
+} iba_bundle_eval_out;
+typedef struct iba_bundle_batch iba_bundle_batch;
+iba_status iba_default_bundle_options(iba_bundle_options* opt);     /* the local schedule: 2 rounds of {5, 10}, the first robust */
+/* the global schedule: one round of n_iterations (1..100), the Huber kernel on where robust != 0, delta = (float)sqrt(5.99) */
+iba_status iba_bundle_options_global(iba_bundle_options* opt, int32_t n_iterations, int32_t robust);
+const char* iba_bundle_last_error(void);                            /* never NULL; of this thread's last iba_bundle* call that failed */
+/* *out is NULL on failure; release it with iba_bundle_free */
+iba_status iba_bundle_optimize(const iba_bundle_job* jobs, int32_t B, const iba_bundle_options* opt, int device, iba_bundle_batch** out);
+/* one linearisation per job AT the job's estimates and one step at the given lambda (B1-B7, delta = (float)sqrt(5.991)): active is NULL (all edges of
+ * all jobs) or one pointer per job (NULL = all, else n_edges bytes); outs takes B entries whose pointers the caller has set */
+iba_status iba_bundle_eval(const iba_bundle_job* jobs, int32_t B, const uint8_t* const* active, int32_t robust, double lambda, int device, iba_bundle_eval_out* outs);
+void       iba_bundle_free(iba_bundle_batch* r);
+int32_t    iba_bundle_n_jobs(const iba_bundle_batch* r);            /* 0 for NULL */
+iba_status iba_bundle_read(const iba_bundle_batch* r, int32_t job, iba_bundle_result* result);
+/* the final poses: n_cameras x 12 each; either may be NULL. Tcw12f is the rounding of Converter::toCvMat */
+iba_status iba_bundle_cameras(const iba_bundle_batch* r, int32_t job, double* Tcw12, float* Tcw12f);
+iba_status iba_bundle_points(const iba_bundle_batch* r, int32_t job, double* xyz, float* xyzf);   /* n_points x 3 each; either may be NULL */
+/* per edge the outlier flag and the float32 chi2 of the last classification (n_edges each); either may be NULL */
+iba_status iba_bundle_edges(const iba_bundle_batch* r, int32_t job, uint8_t* outlier, float* chi2);
+/* keep_stages only: the estimates at the end of round `round` < rounds_run; either may be NULL */
+iba_status iba_bundle_stage(const iba_bundle_batch* r, int32_t job, int32_t round, double* Tcw12, double* xyz);
+/* host only, pure (B6, B10): the plan of one job. point_offsets (n_points + 1), point_edges (n_edges), camera_offsets (n_cameras + 1), camera_edges
+ * (n_edges), block_cameras (2 per block), block_offsets (n_blocks + 1) and items (point, edge of a, edge of b: 3 per item) may each be NULL; n_blocks
+ * and n_items are always written, so a first call sizes the arrays of a second */
+iba_status iba_bundle_plan(const iba_bundle_job* job, int32_t* point_offsets, int32_t* point_edges, int32_t* camera_offsets, int32_t* camera_edges, int32_t* n_blocks,
+                           int32_t* n_items, int32_t* block_cameras, int32_t* block_offsets, int32_t* items);
+/* host only, pure: the joining helper of one LocalMapping step, Optimizer.cc:620-669 and the vertex and edge order of :682-779 over the map's
+ * observation table. observations: n_observations rows (map point, keyframe, keypoint), ids counting from 0; point_bad (n_map_points) and
+ * keyframe_bad (n_keyframes) are the isBad() flags; covisible: the current keyframe's GetVectorCovisibleKeyFrames in the caller's order. Out:
+ *   camera_keyframe, fixed (up to n_keyframes)  the job's cameras as keyframe ids: the *n_local local ones (the current one first, then the covisibles
+ *                                that are not bad), then the fixed ones in first-seen order; fixed = 1 for keyframe 0 and for every fixed camera
+ *   point_id (up to n_map_points) the local points in the reference's walk order: per local camera its map points in ascending keypoint index, a
+ *                                point that is not bad and not yet listed
+ *   edge_point, edge_camera, edge_keypoint (up to n_observations)  per local point its observations by keyframes that are not bad, in ASCENDING
+ *                                KEYFRAME ID (the reference's order is that of the keyframes' addresses): the job's index arrays, and the keypoint
+ *                                whose mvKeysUn position and octave give obs and inv_sigma2
+ * Refused: an id out of range, a (map point, keyframe) or (keyframe, keypoint) pair that occurs twice, a covisible that is the current keyframe or
+ * is listed twice, a NULL array that would be written. */
+iba_status iba_bundle_local_window(const int32_t* observations, int32_t n_observations, const uint8_t* point_bad, int32_t n_map_points, const uint8_t* keyframe_bad,
+                                   int32_t n_keyframes, int32_t current, const int32_t* covisible, int32_t n_covisible, int32_t* camera_keyframe, uint8_t* fixed,
+                                   int32_t* n_local, int32_t* n_cameras, int32_t* point_id, int32_t* n_points, int32_t* edge_point, int32_t* edge_camera,
+                                   int32_t* edge_keypoint, int32_t* n_edges);
+
 /* The ABI version the LIBRARY was built with (IBA_ABI_VERSION of its header). iba_params carries no struct_size: a caller compiled against
  * an older header would pass a shorter struct. Callers compare iba_abi_version() with their own IBA_ABI_VERSION before iba_create(). */
 int32_t iba_abi_version(void);

@@ -56,6 +56,9 @@
  *   IBA_POSE_BUDGET, IBA_POSE_ONCHIP, IBA_POSE_TIMING     iba_pose_optimize / iba_pose_eval: the bytes a chunk of jobs may take on the device in place of 1 GiB
  *                                                         (iba_debug_pose_chunks), an on-chip edge capacity below IBA_POSE_ONCHIP_EDGES, and HIP events around
  *                                                         the kernel (iba_debug_pose_kernel_ms; tools/pose_bench.py); same results
+ *   IBA_BUNDLE_BUDGET, IBA_BUNDLE_TIMING                  iba_bundle_optimize / iba_bundle_eval: the bytes a chunk of jobs may take on the device in place of 1 GiB
+ *                                                         (iba_debug_bundle_chunks) and HIP events around a chunk's launch chains
+ *                                                         (iba_debug_bundle_kernel_ms; tools/bundle_bench.py); same results
  *   IBA_GROUP_REDUCE_HOST (flag of iba_group_create_ex, not a variable), IBA_DEBUG_FAIL_RANK / IBA_DEBUG_FAIL_PHASE: inject one
  *                                                         failure into a group's evaluation (tests of the fail-not-hang path)
  */
@@ -291,6 +294,18 @@ iba_status iba_debug_pose_exp(const double dx[6], const double T[12], double Tn[
 int32_t iba_debug_pose_big_steps(const iba_pose_batch* r);
 int32_t iba_debug_pose_chunks(const iba_pose_batch* r);
 float   iba_debug_pose_kernel_ms(const iba_pose_batch* r);
+
+/* debug: iba_bundle_optimize as the host restatement of its rules (csrc/iba_bundle_host.hpp over csrc/iba_bundle_math.hpp, the text the kernels
+ * compile), the whole call without a device; the result is read with the iba_bundle_* accessors. Byte for byte what the device gives
+ * (tests/test_gpu_bundle.py). */
+iba_status iba_debug_bundle_host(const iba_bundle_job* jobs, int32_t B, const iba_bundle_options* opt, iba_bundle_batch** out);
+/* debug: iba_bundle_eval on the host, the same outputs */
+iba_status iba_debug_bundle_eval_host(const iba_bundle_job* jobs, int32_t B, const uint8_t* const* active, int32_t robust, double lambda, iba_bundle_eval_out* outs);
+/* debug: the steps of the call beyond theta = pi (rule P6), the chunks it ran as, and the time in ms from HIP events around the launch chains of
+ * the chunks (the host's one-word reads between the steps included), summed over the chunks; 0 for NULL */
+int32_t iba_debug_bundle_big_steps(const iba_bundle_batch* r);
+int32_t iba_debug_bundle_chunks(const iba_bundle_batch* r);
+float   iba_debug_bundle_kernel_ms(const iba_bundle_batch* r);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,4 @@
-"""What the ctypes mirrors of the per-call units share (project, orb, orb_match, twoview, pose; csrc/iba_call.hpp is the native side): the array
+"""What the ctypes mirrors of the per-call units share (project, orb, orb_match, twoview, pose, bundle; csrc/iba_call.hpp is the native side): the array
 pointer, the error of a failed call, the result object's ownership and the options-with-overrides pattern. Plumbing only."""
 import ctypes as C
 

@@ -1,4 +1,4 @@
-// The front end of a per-call unit (iba_project.hip, iba_orb.hip, iba_orb_match.hip, iba_twoview.hip, iba_pose.hip): a unit without a handle checks
+// The front end of a per-call unit (iba_project.hip, iba_orb.hip, iba_orb_match.hip, iba_twoview.hip, iba_pose.hip, iba_bundle.hip): a unit without a handle checks
 // its call on the host, cuts the work into chunks under a byte budget (iba_chunks.hpp), runs one launch chain per chunk, synchronises once and
 // returns a host-side result object. What those units share is here: the error slot, IBA_CALL_TRY, the events of a timed call, the guard that
 // keeps a chain's host arrays alive until its stream is idle, the budget rule and the index check of an accessor. HIP host code.

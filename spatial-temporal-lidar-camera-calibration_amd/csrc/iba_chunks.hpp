@@ -1,4 +1,4 @@
-// The one chunk cutter of the per-call units (iba_project, iba_orb, iba_orb_match, iba_twoview, iba_pose): a call's items (jobs, images, pairs) cut
+// The one chunk cutter of the per-call units (iba_project, iba_orb, iba_orb_match, iba_twoview, iba_pose, iba_bundle): a call's items (jobs, images, pairs) cut
 // into chunks of consecutive items under a byte budget. Plain C++: the sanitizer self-tests compile it with g++ through the *_host.hpp headers.
 #pragma once
 #include <cstdint>

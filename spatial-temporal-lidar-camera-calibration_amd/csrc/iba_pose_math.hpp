@@ -185,15 +185,16 @@ IBA_POSE_HD int lm_propose(Lm* s, const double* sums, const double* T, LmWork* w
     icp::ldlt6_apply(w->L, w->d, sums + 21, w->dx);
     return exp_update(w->dx, T, w->Tn);
 }
-// the verdict on the trial: chi_trial is the chi2 sum at Tn (unused where ok == 0). Returns 1 where Tn is accepted; sets again / stop.
-IBA_POSE_HD int lm_judge(Lm* s, const double* sums, const LmWork* w, double chi_trial) {
-    const double temp = s->ok ? chi_trial : kMax;
-    double rho = s->current - temp, scale = 1e-3;
-    if (s->ok) for (int k = 0; k < 6; ++k) scale = scale + w->dx[k] * (s->lambda * w->dx[k] + sums[21 + k]);
+// the verdict on a trial whose scale is known (P5): ok = 0 is a failed factorisation (scale and chi_trial unused). Returns 1 where the trial is
+// accepted; sets again / stop. The core of lm_judge, and of the bundle adjustment's sequencer (iba_bundle_math.hpp), whose scale runs over more unknowns.
+IBA_POSE_HD int lm_verdict(Lm* s, int ok, double scale_ok, double chi_trial) {
+    const double temp = ok ? chi_trial : kMax;
+    double rho = s->current - temp;
+    const double scale = ok ? scale_ok : 1e-3;
     rho = rho / scale;
     s->rho = rho;
     int accept = 0;
-    if (s->ok && rho > 0.0 && finite_(temp)) {
+    if (ok && rho > 0.0 && finite_(temp)) {
         const double t = 2.0 * rho - 1.0;
         double alpha = 1.0 - (t * t) * t;
         if (2.0 / 3.0 < alpha) alpha = 2.0 / 3.0;
@@ -208,6 +209,12 @@ IBA_POSE_HD int lm_judge(Lm* s, const double* sums, const LmWork* w, double chi_
     s->again = (rho < 0.0 && s->qmax < kMaxTrials) ? 1 : 0;
     if (!s->again) s->stop = (s->qmax == kMaxTrials || rho == 0.0) ? 1 : 0;
     return accept;
+}
+// the verdict on the trial: chi_trial is the chi2 sum at Tn (unused where ok == 0). Returns 1 where Tn is accepted; sets again / stop.
+IBA_POSE_HD int lm_judge(Lm* s, const double* sums, const LmWork* w, double chi_trial) {
+    double scale = 1e-3;
+    if (s->ok) for (int k = 0; k < 6; ++k) scale = scale + w->dx[k] * (s->lambda * w->dx[k] + sums[21 + k]);
+    return lm_verdict(s, s->ok, scale, chi_trial);
 }
 
 // The sequencer of one optimize(): what the one lane (or the host) does between two evaluations. phase 0: `sums` holds the linearisation at T; phase 1:
