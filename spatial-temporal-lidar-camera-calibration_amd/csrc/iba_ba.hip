@@ -22,6 +22,8 @@
 
 #include "../../include/iba_mi355x.h"
 #include "iba_device_buf.hpp"
+#include "iba_lm.hpp"
+#include "iba_wave_sum.hpp"
 
 namespace {
 
@@ -69,20 +71,6 @@ struct BaDev {
 };
 struct BaX { double x[7]; };
 constexpr int kBaThreads = 256, kBaSums = 36;   // 28 (upper H) + 7 (b) + 1 (robust chi2)
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double ba_dpp(double x) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    int lo = (int)(unsigned)b, hi = (int)(unsigned)(b >> 32);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, false);
-    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo));
-}
-__device__ __forceinline__ double ba_wave_sum(double x) {   // total in lane 63, fixed association order
-    x += ba_dpp<0x111, 0xf>(x); x += ba_dpp<0x112, 0xf>(x); x += ba_dpp<0x114, 0xf>(x); x += ba_dpp<0x118, 0xf>(x);
-    x += ba_dpp<0x142, 0xa>(x); x += ba_dpp<0x143, 0xc>(x);
-    return x;
-}
 
 __global__ __launch_bounds__(kBaThreads) void ba_edge_kernel(BaDev d, BaX X, const uint8_t* __restrict__ active, int robust, double delta,
                                                               double* __restrict__ block_sums, double* __restrict__ chi2_edges) {
@@ -132,9 +120,11 @@ __global__ __launch_bounds__(kBaThreads) void ba_edge_kernel(BaDev d, BaX X, con
         for (int p = 0; p < 7; ++p) acc[28 + p] -= w * (e0.v[p] * e0.a + e1.v[p] * e1.a);
         acc[35] += rho0;
     }
+    // the tail iba::block_sum_store states, written out: that helper takes all K wave sums at once, and with 36 of them in flight this kernel compiles
+    // to other code than with each one stored as it is formed
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int i = 0; i < kBaSums; ++i) { const double t = ba_wave_sum(acc[i]); if (lane == 63) s_part[wave][i] = t; }
+    for (int i = 0; i < kBaSums; ++i) { const double t = iba::wave_sum_f64(acc[i]); if (lane == 63) s_part[wave][i] = t; }
     __syncthreads();
     if (threadIdx.x < kBaSums) {
         double t = s_part[0][threadIdx.x];
@@ -234,22 +224,6 @@ iba_status iba_ba_eval(iba_ba_handle* h, const double* x, const uint8_t* active,
     return IBA_OK;
 }
 
-// solves the 7x7 symmetric system (Cholesky); false if not positive definite
-static bool ba_solve7(const double* A, const double* b, double* x) {
-    double L[49]; std::memset(L, 0, sizeof(L));
-    for (int i = 0; i < 7; ++i)
-        for (int j = 0; j <= i; ++j) {
-            double s = A[i * 7 + j];
-            for (int k = 0; k < j; ++k) s -= L[i * 7 + k] * L[j * 7 + k];
-            if (i == j) { if (!(s > 0)) return false; L[i * 7 + i] = std::sqrt(s); }
-            else L[i * 7 + j] = s / L[j * 7 + j];
-        }
-    double y[7];
-    for (int i = 0; i < 7; ++i) { double s = b[i]; for (int k = 0; k < i; ++k) s -= L[i * 7 + k] * y[k]; y[i] = s / L[i * 7 + i]; }
-    for (int i = 6; i >= 0; --i) { double s = y[i]; for (int k = i + 1; k < 7; ++k) s -= L[k * 7 + i] * x[k]; x[i] = s / L[i * 7 + i]; }
-    return true;
-}
-
 iba_status iba_ba_optimize(iba_ba_handle* h, const double* x0, iba_ba_result* res) {
     if (!h || !x0 || !res) return ba_fail(h, IBA_ERR_INVALID_ARG, "null argument");
     const size_t N = (size_t)h->n_edges;
@@ -282,7 +256,7 @@ iba_status iba_ba_optimize(iba_ba_handle* h, const double* x0, iba_ba_result* re
                 double A[49], dx[7], xn[7];
                 std::memcpy(A, H, sizeof(A));
                 for (int k = 0; k < 7; ++k) A[k * 8] += lambda;
-                const bool ok2 = ba_solve7(A, b, dx);
+                const bool ok2 = iba::chol_solve7(A, b, dx);
                 double temp = std::numeric_limits<double>::max();
                 if (ok2) {
                     for (int k = 0; k < 7; ++k) xn[k] = x[k] + dx[k];   // CalibVertex::oplusImpl: additive

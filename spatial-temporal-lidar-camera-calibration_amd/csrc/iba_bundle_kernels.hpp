@@ -30,10 +30,10 @@ __global__ __launch_bounds__(kThreads) void camera_kernel(Tab t, int n) {
     const int cam = blockIdx.x * (kThreads / kWave) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (cam >= n || !camera_runs(t, cam)) return;
     double acc[kCamSums];
-    const double cnt = pose::wave_sum((double)camera_lane(t, cam, lane, acc));   // a count below 2^24: exact
+    const double cnt = wave_sum_f64((double)camera_lane(t, cam, lane, acc));   // a count below 2^24: exact
 #pragma unroll
     for (int k = 0; k < kCamSums; ++k) {
-        const double s = pose::wave_sum(acc[k]);
+        const double s = wave_sum_f64(acc[k]);
         if (lane == 63) t.cam_sums[(size_t)kCamSums * cam + k] = s;
     }
     if (lane == 63) t.cam_cnt[cam] = (int32_t)cnt;
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(kThreads) void front_kernel(Tab t, int n_jobs, DevO
         const int kind = t.ctl[j].kind;
         if (kind == kDone) continue;
         const bool sums = kind == kLinearise || kind == kTrial;
-        if (sums) { const double s = pose::wave_sum(chi_lane(t, t.job[j], tid)); if (lane == 63) part[wave] = s; }
+        if (sums) { const double s = wave_sum_f64(chi_lane(t, t.job[j], tid)); if (lane == 63) part[wave] = s; }
         if (kind == kLinearise) mx[tid] = diag_lane(t, t.job[j], tid);
         __syncthreads();
         if (tid == 0) {
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(kThreads) void block_kernel(Tab t, int n) {
     double acc[kBlockSums];
     block_lane(t, blk, lane, acc);
 #pragma unroll
-    for (int k = 0; k < kBlockSums; ++k) acc[k] = pose::wave_sum(acc[k]);
+    for (int k = 0; k < kBlockSums; ++k) acc[k] = wave_sum_f64(acc[k]);
     if (lane == 63) block_store(t, blk, acc);
 }
 // B7 in parallel: lane i owns row i. Column j of the factor needs the columns before it, so a barrier separates the columns; every entry is still

@@ -22,6 +22,7 @@
 
 #include "iba_build.hpp"
 #include "iba_types.hpp"
+#include "iba_wave_sum.hpp"
 
 namespace iba {
 
@@ -487,33 +488,6 @@ __global__ __launch_bounds__(64) void iba_knn_dump_kernel(DevProblem dp, int fra
     }
 }
 
-// ---- wave64 sum on the VALU (DPP row shifts + row broadcasts, no LDS traffic); total lands in lane 63 ----
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned long long dpp_u64(unsigned long long b) {
-    int lo = (int)(unsigned int)b, hi = (int)(unsigned int)(b >> 32);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, false);
-    return ((unsigned long long)(unsigned int)hi << 32) | (unsigned long long)(unsigned int)lo;
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_f64(double x) { return __longlong_as_double((long long)dpp_u64<CTRL, ROW_MASK>((unsigned long long)__double_as_longlong(x))); }
-__device__ __forceinline__ double wave_sum_f64(double x) {   // fixed association order => bitwise reproducible
-    x += dpp_f64<0x111, 0xf>(x); x += dpp_f64<0x112, 0xf>(x); x += dpp_f64<0x114, 0xf>(x); x += dpp_f64<0x118, 0xf>(x);   // row_shr 1,2,4,8
-    x += dpp_f64<0x142, 0xa>(x);   // row_bcast:15 -> rows 1,3
-    x += dpp_f64<0x143, 0xc>(x);   // row_bcast:31 -> rows 2,3
-    return x;
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x) {   // inclusive prefix over the lanes of the wave (the total in lane 63)
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false); x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false); x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false); x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);
-    return x;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long x) {
-    x += dpp_u64<0x111, 0xf>(x); x += dpp_u64<0x112, 0xf>(x); x += dpp_u64<0x114, 0xf>(x); x += dpp_u64<0x118, 0xf>(x);
-    x += dpp_u64<0x142, 0xa>(x); x += dpp_u64<0x143, 0xc>(x);
-    return x;
-}
 // ---- fixed-order block reduction of NV doubles per thread; the totals are returned in v[] on every thread ----
 template <int NV>
 __device__ inline void block_reduce(double* v, double* s_red /* (kWaves+1)*kRedSlots doubles */) {

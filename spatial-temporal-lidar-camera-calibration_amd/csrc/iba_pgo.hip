@@ -1,6 +1,6 @@
 // Pose-graph optimisation on the device (include/iba_mi355x.h, iba_pgo_*): Open3D's GlobalOptimization — LM, pruning of uncertain edges by
 // line-process weight, LM again — on a graph that stays on the device. Kernels: iba_pgo_kernels.hpp; plan and checks: iba_pgo_host.hpp.
-// The LM loop below reads kScal doubles per trial and nothing else.
+// The LM loop is iba_graph_lm.hpp's (shared with iba_smooth, as is the scaffolding of iba_pgo_solve.hpp); it reads kScal doubles per trial and nothing else.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -81,15 +81,13 @@ iba_status linearize(iba_pgo* pg, bool recompute_w, double* scal_host) {
     if (pg->E > 0)
         hipLaunchKernelGGL(pgo_edge_kernel<true>, dim3(pg->nbE), dim3(kThreads), 0, st, edge_dev(pg), (const double*)pg->poses[pg->cur].p, pg->mu, recompute_w ? 1 : 0, pg->weight.p,
                            pg->zeta.p, pg->A.p, pg->g.p, pg->epart.p);
-    hipLaunchKernelGGL(pgo_final_kernel, dim3(1), dim3(64), 0, st, (const double*)pg->epart.p, pg->nbE, 1, 0, pg->scal.p);
+    final_launch(st, pg->epart.p, pg->nbE, 1, 0, pg->scal.p);
     hipLaunchKernelGGL(pgo_node_kernel, dim3(pg->N), dim3(64), 0, st, (int)pg->N, (const int32_t*)pg->ar.inc_off.p, (const int32_t*)pg->ar.inc_edge.p, (const double*)pg->A.p,
                        (const double*)pg->g.p, (const double*)pg->poses[pg->cur].p, pg->D.p, pg->b.p, pg->npart.p);
-    hipLaunchKernelGGL(pgo_final_kernel, dim3(1), dim3(64), 0, st, (const double*)pg->npart.p, (int)pg->N, 1, 2, pg->scal.p + 1);
-    if (hipMemcpyAsync(scal_host, pg->scal.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return fail(pg, IBA_ERR_HIP, "iba_pgo: download of the scalars");
-    const hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(pg, IBA_ERR_HIP, std::string("iba_pgo: linearise kernels: ") + hipGetErrorString(e));
-    pg->linearized = true;
-    return IBA_OK;
+    final_launch(st, pg->npart.p, (int)pg->N, 1, 2, pg->scal.p + 1);
+    const iba_status rs = read_scalars(pg, 4, scal_host, "iba_pgo", "linearise");
+    if (rs == IBA_OK) pg->linearized = true;
+    return rs;
 }
 
 // the launch chain of (H + lambda I) delta = b; no synchronisation
@@ -100,61 +98,27 @@ iba_status trial(iba_pgo* pg, double lambda, double* scal_host) {
     hipStream_t st = pg->stream;
     hipLaunchKernelGGL(pgo_update_kernel, dim3(pg->nbN), dim3(kThreads), 0, st, (int)pg->N, (const double*)pg->poses[pg->cur].p, (const double*)pg->delta.p, (const double*)pg->b.p, lambda,
                        pg->poses[1 - pg->cur].p, pg->upart.p);
-    hipLaunchKernelGGL(pgo_final_kernel, dim3(1), dim3(64), 0, st, (const double*)pg->upart.p, pg->nbN, 2, 0, pg->scal.p + 4);
+    final_launch(st, pg->upart.p, pg->nbN, 2, 0, pg->scal.p + 4);
     if (pg->E > 0)
         hipLaunchKernelGGL(pgo_edge_kernel<false>, dim3(pg->nbE), dim3(kThreads), 0, st, edge_dev(pg), (const double*)pg->poses[1 - pg->cur].p, pg->mu, 0, pg->weight.p,
                            (double*)nullptr, (double*)nullptr, (double*)nullptr, pg->epart.p);
-    hipLaunchKernelGGL(pgo_final_kernel, dim3(1), dim3(64), 0, st, (const double*)pg->epart.p, pg->nbE, 1, 0, pg->scal.p + 6);
-    if (hipMemcpyAsync(scal_host, pg->scal.p, kScal * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return fail(pg, IBA_ERR_HIP, "iba_pgo: download of the scalars");
-    const hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(pg, IBA_ERR_HIP, std::string("iba_pgo: trial kernels: ") + hipGetErrorString(e));
-    if (scal_host[7] != 0.0) return fail(pg, IBA_ERR_UNSUPPORTED, "iba_pgo: H + lambda I is not positive definite to working precision (lambda = " + std::to_string(lambda) + ")");
-    return IBA_OK;
+    final_launch(st, pg->epart.p, pg->nbE, 1, 0, pg->scal.p + 6);
+    return read_scalars(pg, kScal, scal_host, "iba_pgo", "trial", lambda);
 }
 
-// one LM pass (rule 6), then the reference-node compensation
+// one LM pass (rule 6: iba_graph_lm.hpp), then the reference-node compensation
 iba_status lm_pass(iba_pgo* pg, iba_pgo_pass* out, uint8_t trace_bit) {
     const iba_pgo_options& o = pg->opt;
     double ref_before[16];
     if (o.reference_node >= 0 && hipMemcpy(ref_before, pg->poses[pg->cur].p + 16 * (size_t)o.reference_node, sizeof(ref_before), hipMemcpyDeviceToHost) != hipSuccess)
         return fail(pg, IBA_ERR_HIP, "iba_pgo: download of the reference node");
-    double sc[kScal];
-    iba_status st = linearize(pg, false, sc);
+    // rule 6 itself; the line-process weights are recomputed, and the accepted trial becomes the poses, only behind an accepted trial
+    iba::GraphLmResult lm;
+    const iba_status st = iba::graph_lm(iba::graph_lm_options(o),
+        [&](bool after_accept, double* sc) { if (after_accept) pg->cur = 1 - pg->cur; return linearize(pg, after_accept, sc); },
+        [&](double lambda, double* ts) { solve_launch(pg, lambda); return trial(pg, lambda, ts); }, pg->trace, trace_bit, lm);
     if (st != IBA_OK) return st;
-    double r = sc[0], lambda = 1e-5 * sc[3], nu = 2.0;
-    int stop = IBA_PGO_STOP_NONE, iterations = 0, trials = 0;
-    while (stop == IBA_PGO_STOP_NONE) {
-        if (sc[2] < o.min_right_term) { stop = IBA_PGO_STOP_RIGHT_TERM; break; }
-        if (iterations >= o.max_iteration) { stop = IBA_PGO_STOP_MAX_ITERATION; break; }
-        const double xnorm = std::sqrt(sc[1]);
-        for (int k = 0; k < o.max_iteration_lm; ++k) {
-            solve_launch(pg, lambda);
-            double ts[kScal];
-            st = trial(pg, lambda, ts);
-            if (st != IBA_OK) return st;
-            ++trials;
-            if (std::sqrt(ts[5]) < o.min_relative_increment * (xnorm + o.min_relative_increment)) { stop = IBA_PGO_STOP_INCREMENT; pg->trace.push_back(2 | trace_bit); break; }
-            const double r_new = ts[6], rho = (r - r_new) / (ts[4] + 1e-3);
-            if (rho > 0.0) {
-                const double t = 2.0 * rho - 1.0;
-                lambda *= std::max(o.lower_scale_factor, std::min(1.0 - t * t * t, o.upper_scale_factor));
-                nu = 2.0;
-                pg->trace.push_back(1 | trace_bit);
-                pg->cur = 1 - pg->cur;
-                const double r_before = r;
-                st = linearize(pg, true, sc);
-                if (st != IBA_OK) return st;
-                r = sc[0];
-                if (r_before - r_new < o.min_relative_residual_increment * r_before) stop = IBA_PGO_STOP_RESIDUAL_INCREMENT;
-                break;
-            }
-            pg->trace.push_back(0 | trace_bit);
-            lambda *= nu; nu *= 2.0;
-        }
-        ++iterations;
-        if (stop == IBA_PGO_STOP_NONE && r < o.min_residual) stop = IBA_PGO_STOP_RESIDUAL;
-    }
-    out->iterations = iterations; out->trials = trials; out->stop = stop; out->reserved = 0; out->residual = r; out->lambda = lambda;
+    out->iterations = lm.iterations; out->trials = lm.trials; out->stop = lm.stop; out->reserved = 0; out->residual = lm.residual; out->lambda = lm.lambda;
     if (o.reference_node >= 0) {
         double ref_after[16], inv[12];
         if (hipMemcpy(ref_after, pg->poses[pg->cur].p + 16 * (size_t)o.reference_node, sizeof(ref_after), hipMemcpyDeviceToHost) != hipSuccess)
@@ -293,28 +257,16 @@ iba_status iba_pgo_linearize(iba_pgo* pg, double* zeta, double* weight, double* 
     const iba_status st = linearize(pg, false, sc);
     if (st != IBA_OK) return st;
     const size_t m = (size_t)pg->E, n = (size_t)pg->N;
-    hipError_t e = hipSuccess;
-    auto dn = [&](double* dst, const double* srcp, size_t count) { if (dst && count && e == hipSuccess) e = hipMemcpy(dst, srcp, count * sizeof(double), hipMemcpyDeviceToHost); };
+    Download dn;
     dn(zeta, pg->zeta.p, 6 * m); dn(weight, pg->weight.p, m); dn(A, pg->A.p, 36 * m); dn(b, pg->b.p, 6 * n);
-    if (e != hipSuccess) return fail(pg, IBA_ERR_HIP, std::string("iba_pgo_linearize: ") + hipGetErrorString(e));
+    if (dn.e != hipSuccess) return fail(pg, IBA_ERR_HIP, std::string("iba_pgo_linearize: ") + hipGetErrorString(dn.e));
     if (residual) *residual = sc[0];
     return IBA_OK;
 }
 
 iba_status iba_pgo_solve(iba_pgo* pg, double lambda, double* delta) {
     if (!pg) return fail(nullptr, IBA_ERR_INVALID_ARG, "iba_pgo_solve: pg is NULL");
-    if (!delta) return fail(pg, IBA_ERR_INVALID_ARG, "iba_pgo_solve: delta is NULL");
-    if (!std::isfinite(lambda) || lambda < 0.0) return fail(pg, IBA_ERR_INVALID_ARG, "iba_pgo_solve: lambda is not finite or negative");
-    if (!pg->linearized) return fail(pg, IBA_ERR_STATE, "iba_pgo_solve: no linearisation at the current poses (call iba_pgo_linearize)");
-    if (hipSetDevice(pg->device) != hipSuccess) return fail(pg, IBA_ERR_HIP, "iba_pgo_solve: hipSetDevice");
-    solve_launch(pg, lambda);
-    double flag = 0.0;
-    hipError_t e = hipMemcpyAsync(delta, pg->delta.p, 6 * (size_t)pg->N * sizeof(double), hipMemcpyDeviceToHost, pg->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&flag, pg->scal.p + 7, sizeof(double), hipMemcpyDeviceToHost, pg->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(pg->stream);
-    if (e != hipSuccess) return fail(pg, IBA_ERR_HIP, std::string("iba_pgo_solve: ") + hipGetErrorString(e));
-    if (flag != 0.0) return fail(pg, IBA_ERR_UNSUPPORTED, "iba_pgo_solve: H + lambda I is not positive definite to working precision (lambda = " + std::to_string(lambda) + ")");
-    return IBA_OK;
+    return solve_call(pg, lambda, delta, "iba_pgo_solve", pg->linearized ? nullptr : "no linearisation at the current poses (call iba_pgo_linearize)");
 }
 
 iba_status iba_pgo_optimize(iba_pgo* pg, iba_pgo_result* res) {
@@ -362,9 +314,7 @@ iba_status iba_pgo_read(iba_pgo* pg, double* nodes16, double* weight, uint8_t* p
 }
 
 iba_status iba_debug_pgo_trace(iba_pgo* pg, uint8_t* trials, int32_t cap, int32_t* n) {
-    if (!pg || !n || cap < 0 || (cap && !trials)) return fail(pg, IBA_ERR_INVALID_ARG, "iba_debug_pgo_trace: bad argument");
-    for (int32_t k = 0; k < cap && k < (int32_t)pg->trace.size(); ++k) trials[k] = pg->trace[k];
-    *n = (int32_t)pg->trace.size();
+    if (!trace_out(pg ? &pg->trace : nullptr, trials, cap, n)) return fail(pg, IBA_ERR_INVALID_ARG, "iba_debug_pgo_trace: bad argument");
     return IBA_OK;
 }
 

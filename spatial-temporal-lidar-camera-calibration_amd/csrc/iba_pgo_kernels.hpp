@@ -15,7 +15,7 @@
 //               pgo_edge_kernel<false> the trial residual.
 // The separator matrix is the lower triangle, column-major: entry (i, j), i >= j, at S[j * n + i].
 // The kernels here have external linkage: this header goes into ONE unit (iba_pgo.hip). Other units reach them through iba_pgo_solve.hpp, and take the
-// constants, the wave reductions and the rigid algebra from iba_pgo_math.hpp.
+// constants and the rigid algebra from iba_pgo_math.hpp, the wave reductions and the block tail behind them from iba_wave_sum.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,7 +38,6 @@ struct EdgeDev {
 template <bool FULL>
 __global__ __launch_bounds__(kThreads) void pgo_edge_kernel(EdgeDev d, const double* __restrict__ poses, double mu, int recompute_w, double* __restrict__ weight,
                                                             double* __restrict__ zeta_out, double* __restrict__ A_out, double* __restrict__ g_out, double* __restrict__ partial) {
-    __shared__ double s_part[kThreads / 64];
     const int e = blockIdx.x * kThreads + threadIdx.x;
     double c = 0.0;
     if (e < d.E) {
@@ -86,10 +85,8 @@ __global__ __launch_bounds__(kThreads) void pgo_edge_kernel(EdgeDev d, const dou
             }
         }
     }
-    const double tsum = wave_sum(c);
-    if ((threadIdx.x & 63) == 63) s_part[threadIdx.x >> 6] = tsum;
-    __syncthreads();
-    if (threadIdx.x == 0) { double t = s_part[0]; for (int w = 1; w < kThreads / 64; ++w) t += s_part[w]; partial[blockIdx.x] = t; }
+    const double tsum[1] = {wave_sum_f64(c)};
+    block_sum_store<1, kThreads>(tsum, partial);
 }
 
 // One 64-lane block per node. Lanes 0-35: D_i entry, lanes 36-41: b_i entry, lane 42: |vec6(pose_i)|^2. partial[node] = {|x_i|^2, max |b_i|, max diag D_i}
@@ -114,7 +111,7 @@ __global__ __launch_bounds__(64) void pgo_node_kernel(int N, const int32_t* __re
 #pragma unroll
         for (int k = 1; k < 6; ++k) xx += x[k] * x[k];
     }
-    mb = wave_max(mb); md = wave_max(md); xx = wave_sum(xx);
+    mb = wave_max_f64(mb); md = wave_max_f64(md); xx = wave_sum_f64(xx);
     if (l == 63) { partial[3 * (size_t)i] = xx; partial[3 * (size_t)i + 1] = mb; partial[3 * (size_t)i + 2] = md; }
 }
 
@@ -123,8 +120,8 @@ __global__ __launch_bounds__(64) void pgo_final_kernel(const double* __restrict_
     const int l = threadIdx.x, stride = nsum + nmax;
     for (int k = 0; k < stride; ++k) {
         double v = 0.0;
-        if (k < nsum) { for (int blk = l; blk < nblocks; blk += 64) v += partial[(size_t)blk * stride + k]; v = wave_sum(v); }
-        else { for (int blk = l; blk < nblocks; blk += 64) v = fmax(v, partial[(size_t)blk * stride + k]); v = wave_max(v); }
+        if (k < nsum) { for (int blk = l; blk < nblocks; blk += 64) v += partial[(size_t)blk * stride + k]; v = wave_sum_f64(v); }
+        else { for (int blk = l; blk < nblocks; blk += 64) v = fmax(v, partial[(size_t)blk * stride + k]); v = wave_max_f64(v); }
         if (l == 63) out[k] = v;
     }
 }
@@ -317,7 +314,7 @@ __global__ __launch_bounds__(kThreads) void pgo_sep_solve_kernel(const double* _
     for (int j = n - 1; j >= 0; --j) {
         double v = 0.0;
         for (int i = j + 1 + t; i < n; i += kThreads) v += S[(size_t)j * n + i] * s_x[i];
-        v = wave_sum(v);
+        v = wave_sum_f64(v);
         if ((t & 63) == 63) s_w[t >> 6] = v;
         __syncthreads();
         if (t == 0) { double s = s_w[0]; for (int k = 1; k < kThreads / 64; ++k) s += s_w[k]; s_x[j] = (s_x[j] - s) / S[(size_t)j * n + j]; }
@@ -359,7 +356,6 @@ __global__ __launch_bounds__(64) void pgo_run_back_kernel(RunDev r, int n_sep, c
 // trial pose_i = T(delta_i) pose_i; partial[block] = {sum delta . (lambda delta + b), sum |delta|^2}
 __global__ __launch_bounds__(kThreads) void pgo_update_kernel(int N, const double* __restrict__ poses, const double* __restrict__ delta, const double* __restrict__ b, double lambda,
                                                               double* __restrict__ trial, double* __restrict__ partial) {
-    __shared__ double s_part[kThreads / 64][2];
     const int i = blockIdx.x * kThreads + threadIdx.x;
     double dot = 0.0, dd = 0.0;
     if (i < N) {
@@ -374,10 +370,8 @@ __global__ __launch_bounds__(kThreads) void pgo_update_kernel(int N, const doubl
 #pragma unroll
         for (int k = 0; k < 6; ++k) { dot += dl[k] * (lambda * dl[k] + b[6 * (size_t)i + k]); dd += dl[k] * dl[k]; }
     }
-    dot = wave_sum(dot); dd = wave_sum(dd);
-    if ((threadIdx.x & 63) == 63) { s_part[threadIdx.x >> 6][0] = dot; s_part[threadIdx.x >> 6][1] = dd; }
-    __syncthreads();
-    if (threadIdx.x < 2) { double t = s_part[0][threadIdx.x]; for (int w = 1; w < kThreads / 64; ++w) t += s_part[w][threadIdx.x]; partial[2 * (size_t)blockIdx.x + threadIdx.x] = t; }
+    const double tsum[2] = {wave_sum_f64(dot), wave_sum_f64(dd)};
+    block_sum_store<2, kThreads>(tsum, partial);
 }
 
 // pose_i = C pose_i (the reference-node compensation of rule 6), C a rigid 3x4

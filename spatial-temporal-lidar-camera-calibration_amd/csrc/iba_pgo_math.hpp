@@ -1,5 +1,6 @@
-// The pieces of the pose-graph optimiser's device code that other units build on (iba_smooth_kernels.hpp): the launch constants, the wave reductions
-// by DPP and the rigid 3x4 algebra of rules 1-3. No kernel is defined here; iba_pgo_kernels.hpp holds those and is compiled into one unit only.
+// The pieces of the pose-graph optimiser's device code that other units build on (iba_smooth_kernels.hpp): the launch constants and the rigid 3x4
+// algebra of rules 1-3; the wave reductions both use come with it from iba_wave_sum.hpp. No kernel is defined here; iba_pgo_kernels.hpp holds those
+// and is compiled into one unit only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +8,7 @@
 
 #include "../../include/iba_mi355x.h"
 #include "iba_icp_math.hpp"
+#include "iba_wave_sum.hpp"
 
 namespace iba { namespace pgo {
 
@@ -15,26 +17,6 @@ constexpr int kNB = 48;         // Cholesky panel width: 8 blocks of 6
 constexpr int kTile = 32;       // trailing-update tile
 constexpr int kMaxSepDim = 6 * IBA_PGO_MAX_SEPARATORS;
 constexpr int kScal = 8;        // scalars the host reads: 0 r, 1 |x|^2, 2 max |b|, 3 max diag H, 4 delta . (lambda delta + b), 5 |delta|^2, 6 r_new, 7 a pivot failed
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp(double x) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    int lo = (int)(unsigned)b, hi = (int)(unsigned)(b >> 32);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, false);
-    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo));
-}
-// total in lane 63, fixed association order (inputs of a max are >= 0, so the 0 a masked-off lane reads is neutral for both)
-__device__ __forceinline__ double wave_sum(double x) {
-    x += dpp<0x111, 0xf>(x); x += dpp<0x112, 0xf>(x); x += dpp<0x114, 0xf>(x); x += dpp<0x118, 0xf>(x);
-    x += dpp<0x142, 0xa>(x); x += dpp<0x143, 0xc>(x);
-    return x;
-}
-__device__ __forceinline__ double wave_max(double x) {
-    x = fmax(x, dpp<0x111, 0xf>(x)); x = fmax(x, dpp<0x112, 0xf>(x)); x = fmax(x, dpp<0x114, 0xf>(x)); x = fmax(x, dpp<0x118, 0xf>(x));
-    x = fmax(x, dpp<0x142, 0xa>(x)); x = fmax(x, dpp<0x143, 0xc>(x));
-    return x;
-}
 
 // ---- the rigid 3x4 algebra of rules 1-3 (rows of 4; works on the first 12 entries of a row-major 4x4 as well) ----
 IBA_ICP_HD inline void mul12(const double* A, const double* B, double* C) {

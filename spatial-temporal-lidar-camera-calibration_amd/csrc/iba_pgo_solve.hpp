@@ -1,13 +1,19 @@
 // The block-arrowhead solve of (H + lambda I) delta = b as one object: a Plan on the device, the work buffers of the elimination and the launch chain
 // over the kernels of iba_pgo_kernels.hpp. iba_pgo and iba_smooth both hold one: the same kernels, the same launches, the same bytes. The kernels are
 // compiled into iba_pgo.hip alone, where launch() and final_launch() are defined; this header carries no device code.
+// Behind it, the host scaffolding both units put around that chain (the LM loop itself is iba_graph_lm.hpp). H there is a unit's handle; the helpers
+// use the members both handles name alike (device, stream, ar, D, b, A, delta, scal, err) and leave the message in H::err.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <string>
+#include <vector>
 
 #include "iba_device_buf.hpp"
+#include "iba_graph_lm.hpp"
 #include "iba_pgo_host.hpp"
 #include "iba_pgo_math.hpp"
 
@@ -40,5 +46,55 @@ struct Arrow {
 
 // pgo_final_kernel on st: out[k] = the sum (k < nsum) or max (the next nmax) over the blocks of partial[block * (nsum + nmax) + k]
 void final_launch(hipStream_t st, const double* partial, int nblocks, int nsum, int nmax, double* out);
+
+static_assert(kScal == kGraphLmScal, "the LM driver reads the trial's scalars in kScal's layout");
+
+inline std::string not_positive_definite(const std::string& who, double lambda) {
+    return who + ": H + lambda I is not positive definite to working precision (lambda = " + std::to_string(lambda) + ")";
+}
+
+// The end of a chain whose result is scalars: the first n of h->scal to the host and the chain's one synchronise. `stage` names the chain in the
+// message. n == kScal: the chain had a solve in it, and scal[7] says whether one of its pivots failed.
+template <class H>
+iba_status read_scalars(H* h, int n, double* host, const std::string& who, const char* stage, double lambda = 0.0) {
+    if (hipMemcpyAsync(host, h->scal.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess) { h->err = who + ": download of the scalars"; return IBA_ERR_HIP; }
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { h->err = who + ": " + stage + " kernels: " + hipGetErrorString(e); return IBA_ERR_HIP; }
+    if (n == kScal && host[7] != 0.0) { h->err = not_positive_definite(who, lambda); return IBA_ERR_UNSUPPORTED; }
+    return IBA_OK;
+}
+
+// The body of iba_*_solve behind the entry point's test of the handle itself. `state`: why the handle has no linearisation to solve, nullptr when
+// it has one; the entry point works it out, and it is reported behind the argument checks, where both units have always had it.
+template <class H>
+iba_status solve_call(H* h, double lambda, double* delta, const std::string& who, const char* state) {
+    const auto fail = [&](iba_status st, const std::string& m) { h->err = who + ": " + m; return st; };
+    if (!delta) return fail(IBA_ERR_INVALID_ARG, "delta is NULL");
+    if (!std::isfinite(lambda) || lambda < 0.0) return fail(IBA_ERR_INVALID_ARG, "lambda is not finite or negative");
+    if (state) return fail(IBA_ERR_STATE, state);
+    if (hipSetDevice(h->device) != hipSuccess) return fail(IBA_ERR_HIP, "hipSetDevice");
+    h->ar.launch(h->stream, h->D.p, h->b.p, h->A.p, lambda, h->delta.p, h->scal.p);
+    double flag = 0.0;
+    hipError_t e = hipMemcpyAsync(delta, h->delta.p, 6 * (size_t)h->ar.N * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&flag, h->scal.p + 7, sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(IBA_ERR_HIP, hipGetErrorString(e));
+    if (flag != 0.0) { h->err = not_positive_definite(who, lambda); return IBA_ERR_UNSUPPORTED; }
+    return IBA_OK;
+}
+
+// iba_debug_*_trace: the bytes the last LM run pushed (nullptr: no handle). false: a bad argument.
+inline bool trace_out(const std::vector<uint8_t>* trace, uint8_t* trials, int32_t cap, int32_t* n) {
+    if (!trace || !n || cap < 0 || (cap && !trials)) return false;
+    for (int32_t k = 0; k < cap && k < (int32_t)trace->size(); ++k) trials[k] = (*trace)[k];
+    *n = (int32_t)trace->size();
+    return true;
+}
+
+// Blocking downloads in sequence: a null destination or an empty source is passed over, and so is everything after the first failure (kept in e)
+struct Download {
+    hipError_t e = hipSuccess;
+    void operator()(double* dst, const double* src, size_t count) { if (dst && count && e == hipSuccess) e = hipMemcpy(dst, src, count * sizeof(double), hipMemcpyDeviceToHost); }
+};
 
 } }  // namespace iba::pgo

@@ -88,7 +88,7 @@ __device__ __forceinline__ void job_sums(Shared& sh, const JobView& v, const dou
     for (; i < v.n; i += kThreads) add_edge<FULL, 0>(sh, v, i, acc, T, robust, delta);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int k = FULL ? 0 : kSums - 1; k < kSums; ++k) { const double t = wave_sum(acc[k]); if (lane == 63) sh.part[wave][k] = t; }
+    for (int k = FULL ? 0 : kSums - 1; k < kSums; ++k) { const double t = wave_sum_f64(acc[k]); if (lane == 63) sh.part[wave][k] = t; }
     __syncthreads();
     if ((int)threadIdx.x < kSums && (FULL || threadIdx.x == kSums - 1))
         out[threadIdx.x] = (sh.part[0][threadIdx.x] + sh.part[1][threadIdx.x]) + (sh.part[2][threadIdx.x] + sh.part[3][threadIdx.x]);

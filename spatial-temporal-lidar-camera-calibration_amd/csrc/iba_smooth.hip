@@ -1,6 +1,7 @@
 // Robust smoothing of a growing pose graph on the device (include/iba_mi355x.h, iba_smooth_*): the converged optimum the reference's iSAM2 stage
 // approaches. Kernels: iba_smooth_kernels.hpp; the solve: iba_pgo_solve.hpp (iba_pgo's own); checks and plan: iba_smooth_host.hpp.
-// The graph is kept on the host as it is appended; sync() brings the device up to it before anything runs. The LM loop reads kScal doubles per trial.
+// The graph is kept on the host as it is appended; sync() brings the device up to it before anything runs. The LM loop (iba_graph_lm.hpp) and the
+// scaffolding around the chains (iba_pgo_solve.hpp) are the ones iba_pgo uses; the loop reads kScal doubles per trial.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -127,11 +128,9 @@ iba_status linearize(iba_smooth* s, double* scal_host, const std::string& name) 
     hipLaunchKernelGGL(smooth_node_kernel, dim3(s->N_dev), dim3(64), 0, st, (int)s->N_dev, (const int32_t*)s->ar.inc_off.p, (const int32_t*)s->ar.inc_edge.p, (const int32_t*)s->d_fi.p,
                        (const double*)s->A.p, (const double*)s->g.p, (const double*)s->poses[s->cur].p, s->D.p, s->b.p, s->npart.p);
     final_launch(st, (const double*)s->npart.p, (int)s->N_dev, 1, 2, s->scal.p + 1);
-    if (hipMemcpyAsync(scal_host, s->scal.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return fail(s, IBA_ERR_HIP, name + ": download of the scalars");
-    const hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(s, IBA_ERR_HIP, name + ": linearise kernels: " + hipGetErrorString(e));
-    s->linearized = true;
-    return IBA_OK;
+    const iba_status rs = iba::pgo::read_scalars(s, 4, scal_host, name, "linearise");
+    if (rs == IBA_OK) s->linearized = true;
+    return rs;
 }
 
 // trial poses into poses[1 - cur] from delta, F there; scal[0..7] on the host afterwards
@@ -144,11 +143,7 @@ iba_status trial(iba_smooth* s, double lambda, double* scal_host, const std::str
         hipLaunchKernelGGL(smooth_factor_kernel<false>, dim3(s->nbF), dim3(kThreads), 0, st, factor_dev(s), (const double*)s->poses[1 - s->cur].p, (double*)nullptr, (double*)nullptr,
                            (double*)nullptr, (double*)nullptr, s->fpart.p);
     final_launch(st, (const double*)s->fpart.p, s->nbF, 1, 0, s->scal.p + 6);
-    if (hipMemcpyAsync(scal_host, s->scal.p, kScal * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return fail(s, IBA_ERR_HIP, name + ": download of the scalars");
-    const hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(s, IBA_ERR_HIP, name + ": trial kernels: " + hipGetErrorString(e));
-    if (scal_host[7] != 0.0) return fail(s, IBA_ERR_UNSUPPORTED, name + ": H + lambda I is not positive definite to working precision (lambda = " + std::to_string(lambda) + ")");
-    return IBA_OK;
+    return iba::pgo::read_scalars(s, kScal, scal_host, name, "trial", lambda);
 }
 
 }  // namespace
@@ -234,10 +229,9 @@ iba_status iba_smooth_linearize(iba_smooth* s, double* r, double* w, double* A, 
     st = linearize(s, sc, "iba_smooth_linearize");
     if (st != IBA_OK) return st;
     const size_t m = (size_t)s->F_dev, n = (size_t)s->N_dev;
-    hipError_t e = hipSuccess;
-    auto dn = [&](double* dst, const double* srcp, size_t count) { if (dst && count && e == hipSuccess) e = hipMemcpy(dst, srcp, count * sizeof(double), hipMemcpyDeviceToHost); };
+    iba::pgo::Download dn;
     dn(r, s->r.p, 6 * m); dn(w, s->weight.p, m); dn(A, s->A.p, 36 * m); dn(D, s->D.p, 36 * n); dn(b, s->b.p, 6 * n);
-    if (e != hipSuccess) return fail(s, IBA_ERR_HIP, std::string("iba_smooth_linearize: ") + hipGetErrorString(e));
+    if (dn.e != hipSuccess) return fail(s, IBA_ERR_HIP, std::string("iba_smooth_linearize: ") + hipGetErrorString(dn.e));
     if (F) *F = sc[0];
     return IBA_OK;
 }
@@ -245,20 +239,10 @@ iba_status iba_smooth_linearize(iba_smooth* s, double* r, double* w, double* A, 
 iba_status iba_smooth_solve(iba_smooth* s, double lambda, double* delta) {
     if (!s) return fail(nullptr, IBA_ERR_INVALID_ARG, "iba_smooth_solve: s is NULL");
     { iba_status ds; if (is_dead(s, "iba_smooth_solve", &ds)) return ds; }
-    if (!delta) return fail(s, IBA_ERR_INVALID_ARG, "iba_smooth_solve: delta is NULL");
-    if (!std::isfinite(lambda) || lambda < 0.0) return fail(s, IBA_ERR_INVALID_ARG, "iba_smooth_solve: lambda is not finite or negative");
-    if (s->N < 1) return fail(s, IBA_ERR_STATE, "iba_smooth_solve: the graph has no node");
-    if (!s->linearized || s->N != s->N_dev || (int32_t)s->fi.size() != s->F_dev)
-        return fail(s, IBA_ERR_STATE, "iba_smooth_solve: no linearisation of the current graph at the current estimates (call iba_smooth_linearize)");
-    if (hipSetDevice(s->device) != hipSuccess) return fail(s, IBA_ERR_HIP, "iba_smooth_solve: hipSetDevice");
-    s->ar.launch(s->stream, s->D.p, s->b.p, s->A.p, lambda, s->delta.p, s->scal.p);
-    double flag = 0.0;
-    hipError_t e = hipMemcpyAsync(delta, s->delta.p, 6 * (size_t)s->N_dev * sizeof(double), hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&flag, s->scal.p + 7, sizeof(double), hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    if (e != hipSuccess) return fail(s, IBA_ERR_HIP, std::string("iba_smooth_solve: ") + hipGetErrorString(e));
-    if (flag != 0.0) return fail(s, IBA_ERR_UNSUPPORTED, "iba_smooth_solve: H + lambda I is not positive definite to working precision (lambda = " + std::to_string(lambda) + ")");
-    return IBA_OK;
+    const char* state = nullptr;
+    if (s->N < 1) state = "the graph has no node";
+    else if (!s->linearized || s->N != s->N_dev || (int32_t)s->fi.size() != s->F_dev) state = "no linearisation of the current graph at the current estimates (call iba_smooth_linearize)";
+    return iba::pgo::solve_call(s, lambda, delta, "iba_smooth_solve", state);
 }
 
 iba_status iba_smooth_update(iba_smooth* s, iba_smooth_result* res) {
@@ -272,45 +256,13 @@ iba_status iba_smooth_update(iba_smooth* s, iba_smooth_result* res) {
     res->struct_size = (int32_t)sizeof(*res);
     res->n_nodes = s->N_dev; res->n_factors = s->F_dev;
     s->trace.clear();
-    const iba_smooth_options& o = s->opt;
-    double sc[kScal];
-    st = linearize(s, sc, name);
+    iba::GraphLmResult lm;   // S4
+    st = iba::graph_lm(iba::graph_lm_options(s->opt),
+        [&](bool after_accept, double* sc) { if (after_accept) s->cur = 1 - s->cur; return linearize(s, sc, name); },
+        [&](double lambda, double* ts) { s->ar.launch(s->stream, s->D.p, s->b.p, s->A.p, lambda, s->delta.p, s->scal.p); return trial(s, lambda, ts, name); }, s->trace, 0, lm);
+    res->F_start = lm.residual_start; res->lambda_start = lm.lambda_start;
     if (st != IBA_OK) return st;
-    double F = sc[0], lambda = 1e-5 * sc[3], nu = 2.0;
-    res->F_start = F; res->lambda_start = lambda;
-    int stop = IBA_PGO_STOP_NONE, iterations = 0, trials = 0;
-    while (stop == IBA_PGO_STOP_NONE) {
-        if (sc[2] < o.min_right_term) { stop = IBA_PGO_STOP_RIGHT_TERM; break; }
-        if (iterations >= o.max_iteration) { stop = IBA_PGO_STOP_MAX_ITERATION; break; }
-        const double xnorm = std::sqrt(sc[1]);
-        for (int k = 0; k < o.max_iteration_lm; ++k) {
-            s->ar.launch(s->stream, s->D.p, s->b.p, s->A.p, lambda, s->delta.p, s->scal.p);
-            double ts[kScal];
-            st = trial(s, lambda, ts, name);
-            if (st != IBA_OK) return st;
-            ++trials;
-            if (std::sqrt(ts[5]) < o.min_relative_increment * (xnorm + o.min_relative_increment)) { stop = IBA_PGO_STOP_INCREMENT; s->trace.push_back(2); break; }
-            const double F_new = ts[6], rho = (F - F_new) / (ts[4] + 1e-3);
-            if (rho > 0.0) {
-                const double t = 2.0 * rho - 1.0;
-                lambda *= std::max(o.lower_scale_factor, std::min(1.0 - t * t * t, o.upper_scale_factor));
-                nu = 2.0;
-                s->trace.push_back(1);
-                s->cur = 1 - s->cur;
-                const double F_before = F;
-                st = linearize(s, sc, name);
-                if (st != IBA_OK) return st;
-                F = sc[0];
-                if (F_before - F_new < o.min_relative_residual_increment * F_before) stop = IBA_PGO_STOP_RESIDUAL_INCREMENT;
-                break;
-            }
-            s->trace.push_back(0);
-            lambda *= nu; nu *= 2.0;
-        }
-        ++iterations;
-        if (stop == IBA_PGO_STOP_NONE && F < o.min_residual) stop = IBA_PGO_STOP_RESIDUAL;
-    }
-    res->iterations = iterations; res->trials = trials; res->stop = stop; res->F = F; res->lambda = lambda; res->max_b = sc[2];
+    res->iterations = lm.iterations; res->trials = lm.trials; res->stop = lm.stop; res->F = lm.residual; res->lambda = lm.lambda; res->max_b = lm.max_b;
     return IBA_OK;
 }
 
@@ -337,9 +289,7 @@ iba_status iba_smooth_read(iba_smooth* s, int32_t first, int32_t count, double* 
 }
 
 iba_status iba_debug_smooth_trace(iba_smooth* s, uint8_t* trials, int32_t cap, int32_t* n) {
-    if (!s || !n || cap < 0 || (cap && !trials)) return fail(s, IBA_ERR_INVALID_ARG, "iba_debug_smooth_trace: bad argument");
-    for (int32_t k = 0; k < cap && k < (int32_t)s->trace.size(); ++k) trials[k] = s->trace[k];
-    *n = (int32_t)s->trace.size();
+    if (!iba::pgo::trace_out(s ? &s->trace : nullptr, trials, cap, n)) return fail(s, IBA_ERR_INVALID_ARG, "iba_debug_smooth_trace: bad argument");
     return IBA_OK;
 }
 

@@ -20,8 +20,6 @@ namespace iba { namespace smooth {
 using pgo::kThreads;
 using pgo::mul12;
 using pgo::inv12;
-using pgo::wave_sum;
-using pgo::wave_max;
 
 constexpr double kSeriesTh2 = 1e-2;     // theta^2 below which every coefficient is its series in theta^2
 constexpr double kSeriesU2 = 2.5e-3;    // (|v| / w)^2 of the quaternion below which atan(u) / u is its series
@@ -165,7 +163,6 @@ struct FactorDev {
 template <bool FULL>
 __global__ __launch_bounds__(kThreads) void smooth_factor_kernel(FactorDev d, const double* __restrict__ poses, double* __restrict__ r_out, double* __restrict__ w_out,
                                                                  double* __restrict__ A_out, double* __restrict__ g_out, double* __restrict__ partial) {
-    __shared__ double s_part[kThreads / 64];
     const int f = blockIdx.x * kThreads + threadIdx.x;
     double cost = 0.0;
     if (f < d.F) {
@@ -207,10 +204,8 @@ __global__ __launch_bounds__(kThreads) void smooth_factor_kernel(FactorDev d, co
             }
         }
     }
-    const double tsum = wave_sum(cost);
-    if ((threadIdx.x & 63) == 63) s_part[threadIdx.x >> 6] = tsum;
-    __syncthreads();
-    if (threadIdx.x == 0) { double t = s_part[0]; for (int w = 1; w < kThreads / 64; ++w) t += s_part[w]; partial[blockIdx.x] = t; }
+    const double tsum[1] = {wave_sum_f64(cost)};
+    block_sum_store<1, kThreads>(tsum, partial);
 }
 
 // One 64-lane block per node. inc: factor * 2 + (the node is the factor's i), ascending factor. Lanes 0-35: D entry, lanes 36-41: b entry (+g for i,
@@ -236,14 +231,13 @@ __global__ __launch_bounds__(64) void smooth_node_kernel(int N, const int32_t* _
 #pragma unroll
         for (int k = 1; k < 6; ++k) xx += x[k] * x[k];
     }
-    mb = wave_max(mb); md = wave_max(md); xx = wave_sum(xx);
+    mb = wave_max_f64(mb); md = wave_max_f64(md); xx = wave_sum_f64(xx);
     if (l == 63) { partial[3 * (size_t)i] = xx; partial[3 * (size_t)i + 1] = mb; partial[3 * (size_t)i + 2] = md; }
 }
 
 // trial pose_i = Exp(delta_i) pose_i; partial[block] = {sum delta . (lambda delta + b), sum |delta|^2}
 __global__ __launch_bounds__(kThreads) void smooth_update_kernel(int N, const double* __restrict__ poses, const double* __restrict__ delta, const double* __restrict__ b, double lambda,
                                                                  double* __restrict__ trial, double* __restrict__ partial) {
-    __shared__ double s_part[kThreads / 64][2];
     const int i = blockIdx.x * kThreads + threadIdx.x;
     double dot = 0.0, dd = 0.0;
     if (i < N) {
@@ -258,10 +252,8 @@ __global__ __launch_bounds__(kThreads) void smooth_update_kernel(int N, const do
 #pragma unroll
         for (int k = 0; k < 6; ++k) { dot += dl[k] * (lambda * dl[k] + b[6 * (size_t)i + k]); dd += dl[k] * dl[k]; }
     }
-    dot = wave_sum(dot); dd = wave_sum(dd);
-    if ((threadIdx.x & 63) == 63) { s_part[threadIdx.x >> 6][0] = dot; s_part[threadIdx.x >> 6][1] = dd; }
-    __syncthreads();
-    if (threadIdx.x < 2) { double t = s_part[0][threadIdx.x]; for (int w = 1; w < kThreads / 64; ++w) t += s_part[w][threadIdx.x]; partial[2 * (size_t)blockIdx.x + threadIdx.x] = t; }
+    const double tsum[2] = {wave_sum_f64(dot), wave_sum_f64(dd)};
+    block_sum_store<2, kThreads>(tsum, partial);
 }
 
 } }  // namespace iba::smooth

@@ -19,6 +19,7 @@
 #include "../../../include/iba_mi355x.h"
 #include "../../../include/iba_mi355x_debug.h"
 #include "../iba_icp_math.hpp"
+#include "../iba_graph_lm.hpp"
 #include "../iba_lm.hpp"
 #include "../iba_project_host.hpp"
 
@@ -93,6 +94,64 @@ static void lm_step_quadratic() {
     CHECK(stopped && trials > 0 && accepted > 0 && step.radius > o.initial_trust_region_radius);   // every step of a quadratic is a good one: the radius only grew
     CHECK(cost <= 1e-9 * cost0);
     for (int i = 0; i < 6; ++i) CHECK(std::fabs(x[i] - m[i]) < 1e-4);
+}
+
+// the LM loop of the graph units (iba_graph_lm.hpp: rule 6 of iba_pgo, S4 of iba_smooth) behind scripted callables: no device, and no arithmetic
+// beyond powers of two, so every outcome below follows from the rules alone
+static void graph_lm_driver() {
+    const double r0 = 64.0, diag = 1024.0, lambda0 = 1e-5 * diag;
+    struct Script {
+        double max_b = 1.0, step2 = 1048576.0, r_new = 65.0;   // what the callables answer: max |b|, the trial's |delta|^2 and residual
+        int fail_at_trial = 0;                                 // the trial call (from 1) that answers IBA_ERR_HIP
+        int n_lin = 0, n_lin_after_accept = 0, n_trial = 0;
+        double r = 64.0;
+        std::vector<double> lambdas;
+        std::vector<uint8_t> trace;
+        iba::GraphLmResult out;
+        iba_status run(const iba::GraphLmOptions& o, uint8_t trace_bit) {
+            return iba::graph_lm(o,
+                [&](bool after_accept, double* sc) { ++n_lin; if (after_accept) { ++n_lin_after_accept; r = r_new; } sc[0] = r; sc[1] = 4.0; sc[2] = max_b; sc[3] = 1024.0; return IBA_OK; },
+                [&](double lambda, double* ts) {
+                    lambdas.push_back(lambda);
+                    if (++n_trial == fail_at_trial) return IBA_ERR_HIP;
+                    for (int k = 0; k < iba::kGraphLmScal; ++k) ts[k] = 0.0;
+                    ts[4] = 1.0; ts[5] = step2; ts[6] = r_new;
+                    return IBA_OK;
+                }, trace, trace_bit, out);
+        }
+    };
+    const iba::GraphLmOptions base{100, 20, 1e-6, 1e-6, 1e-6, 1e-6, 0.5, 0.25};
+    {   // at the optimum: max |b| below min_right_term
+        Script s; s.max_b = 1.0 / 1073741824.0;
+        CHECK(s.run(base, 0) == IBA_OK && s.out.stop == IBA_PGO_STOP_RIGHT_TERM && s.out.iterations == 0 && s.out.trials == 0 && s.trace.empty() && s.n_trial == 0 && s.n_lin == 1);
+        CHECK(s.out.residual == r0 && s.out.residual_start == r0 && s.out.lambda == lambda0 && s.out.lambda_start == lambda0 && s.out.max_b == s.max_b);
+    }
+    {   // no budget
+        Script s; iba::GraphLmOptions o = base; o.max_iteration = 0;
+        CHECK(s.run(o, 0) == IBA_OK && s.out.stop == IBA_PGO_STOP_MAX_ITERATION && s.out.iterations == 0 && s.out.trials == 0 && s.trace.empty() && s.n_trial == 0);
+    }
+    for (const uint8_t bit : {(uint8_t)0, (uint8_t)0x80}) {   // never improves: nu is not reset between the outer iterations, so lambda climbs by 2^(1 + 2 + ... + 6)
+        Script s; iba::GraphLmOptions o = base; o.max_iteration_lm = 3; o.max_iteration = 2;
+        CHECK(s.run(o, bit) == IBA_OK && s.out.stop == IBA_PGO_STOP_MAX_ITERATION && s.out.iterations == 2 && s.out.trials == 6 && s.n_lin == 1);
+        CHECK(s.trace == std::vector<uint8_t>(6, bit));
+        CHECK(s.out.lambda == lambda0 * 2097152.0 && s.out.lambda_start == lambda0 && s.out.residual == r0);
+        CHECK((s.lambdas == std::vector<double>{lambda0, lambda0 * 2.0, lambda0 * 8.0, lambda0 * 64.0, lambda0 * 1024.0, lambda0 * 32768.0}));
+    }
+    {   // a tiny step: the outer count still moves
+        Script s; s.step2 = 0.0;
+        CHECK(s.run(base, 0) == IBA_OK && s.out.stop == IBA_PGO_STOP_INCREMENT && s.out.iterations == 1 && s.out.trials == 1 && s.trace == std::vector<uint8_t>{2} && s.n_lin == 1);
+        CHECK(s.out.lambda == lambda0 && s.out.residual == r0);
+    }
+    {   // accepted, then flat: rho > 0 and r - r_new = 2^-20 < 1e-6 * 64
+        Script s; s.r_new = r0 - 1.0 / 1048576.0;
+        CHECK(s.run(base, 0) == IBA_OK && s.out.stop == IBA_PGO_STOP_RESIDUAL_INCREMENT && s.out.iterations == 1 && s.out.trials == 1 && s.trace == std::vector<uint8_t>{1});
+        CHECK(s.n_lin == 2 && s.n_lin_after_accept == 1 && s.out.residual == s.r_new && s.out.residual_start == r0);
+        CHECK(s.out.lambda == lambda0 * 0.5);   // rho ~ 1e-6: 1 - (2 rho - 1)^3 ~ 2, clamped to the upper factor
+    }
+    {   // a callable fails: its status comes back, and nothing is pushed for the trial that failed
+        Script s; s.fail_at_trial = 2;
+        CHECK(s.run(base, 0) == IBA_ERR_HIP && s.trace == std::vector<uint8_t>{0} && s.n_trial == 2 && s.out.lambda_start == lambda0);
+    }
 }
 
 static void handeye() {
@@ -262,6 +321,7 @@ int main(int argc, char** argv) {
     if (!scratch) { std::perror("mkdtemp"); return 2; }
     mads_and_whitening();
     lm_step_quadratic();
+    graph_lm_driver();
     handeye();
     projection_host();
     small_files(scratch);
