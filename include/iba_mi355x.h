@@ -1169,8 +1169,8 @@ iba_status iba_project_gradient(double zn, uint8_t rgb[3]);                     
  * O4 FAST score (cv::FAST's corner score), O5 the per-cell non-maximum suppression (cv::FAST with nonmaxSuppression), O7 the polynomial arctangent
  * (cv::fastAtan2). O6's tie rule is stated above. The BRIEF test-pair table is an INPUT (256 x 4 int8: x0 y0 x1 y1 per test); the library ships none.
  * Masks, undistortion and ComputeKeyPointsOld are not provided. Windowed matching is iba_orb_match below; the matchers that remain unprovided are
- * SearchByBoW and SearchForTriangulation (they need the DBoW2 vocabulary), Fuse, SearchBySim3, and the SearchByProjection overloads that take map
- * points or a key frame. Two-view initialisation is iba_twoview_init further below; what Tracking::CreateInitialMapMonocular does after a success
+ * SearchByBoW and SearchForTriangulation (they need the DBoW2 vocabulary), Fuse, SearchBySim3, and the SearchByProjection overloads that take a
+ * key frame (the overload that takes map points is iba_map_match further below). Two-view initialisation is iba_twoview_init further below; what Tracking::CreateInitialMapMonocular does after a success
  * (global BA, median-depth scaling) and the >= 100-matches gates around the call are the caller's.
  * DEVICE: one chain per chunk over flat tables (one row per image and level, per 64 x 16 tile, per cell, per keypoint): resize level by level, score,
  * cell count, scan, ordered cell write, the candidates down, O6 on the host, the keypoints up, orientation, blur, descriptor (csrc/iba_orb_kernels.hpp).
@@ -1629,6 +1629,145 @@ iba_status iba_pose_stage(const iba_pose_batch* r, int32_t job, int32_t round, d
 iba_status iba_pose_edges_from_matches(const int32_t* match, const int32_t* query_index, int32_t n_queries, const float* last_world_xyz /* n_last x 3 */, int32_t n_last,
                                        const float* cur_xy /* n_cur x 2 */, const int32_t* cur_octave /* n_cur */, int32_t n_cur, const float* inv_level_sigma2, int32_t n_levels,
                                        float* xyz, float* obs, float* inv_sigma2, int32_t* keypoint_index, int32_t* n);
+
+/*
+ * ---- Local-map point matching [the camera side's sixth brick: the reference's Tracking::SearchLocalPoints (src/orb_slam/src/Tracking.cc:1141-1191):
+ * Frame::isInFrustum (Frame.cc:269-325) for every local map point, then ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th)
+ * (ORBmatcher.cc:45-137) on GetFeaturesInArea (rule M3), with MapPoint::PredictScale and the two distance bounds (MapPoint.cc:386-430)] ----
+ * The step between iba_pose_optimize on the previous frame's matches and the second pose optimisation of TrackLocalMap: a frame is matched against
+ * the MAP. A call takes F frames (iba_orb_frame, as iba_orb_match takes them), ONE table of P map points and J jobs; a job projects the points it
+ * lists into one frame under one pose and matches those in view against the frame's keypoints. Frames and the point table go up once, however many
+ * jobs name them. Float arithmetic is float32 unless a cast says otherwise, every operation rounded, evaluated left to right, no contraction;
+ * tests/map_match_ref.py restates every rule in numpy, sequentially as the reference is written, and the device and the host restatement
+ * (iba_debug_map_match_host) are compared with it byte for byte. The float decisions are ONE text, csrc/iba_map_match_math.hpp.
+ *
+ *   L1 frustum.    Per listed point, in list order. A point whose skip byte is set (the reference's isBad() and mnLastFrameSeen == the frame's id)
+ *                  gets status SKIPPED and is not projected. Pc_i = ((R_i0 X + R_i1 Y) + R_i2 Z) + t_i with the job's Tcw12 (the order of
+ *                  iba_orb_match_motion_queries). PcZ < 0.0f: DEPTH. invz = 1.0f / PcZ correctly rounded, formed as (float)(1.0 / (double)PcZ).
+ *                  u = (fx * PcX) * invz + cx, v = (fy * PcY) * invz + cy. u or v not finite: NOT_FINITE (the library's own rule; the reference
+ *                  lets a NaN through its comparisons; PcZ == +0 or -0 ends here). u < min_x || u > max_x || v < min_y || v > max_y of the frame's
+ *                  bounds: BOUNDS (a centre exactly on a bound is kept). Ow_i = -((R_0i t_0 + R_1i t_1) + R_2i t_2), formed once per job; PO = P - Ow;
+ *                  dist = (float)sqrt((PO_0^2 + PO_1^2) + PO_2^2) with the squares and sums in double (cv::norm). dist < 0.8f * min_dist || dist >
+ *                  1.2f * max_dist: DISTANCE (exactly on a bound is kept). view_cos = (float)(((PO_0 n_0 + PO_1 n_1) + PO_2 n_2) / dist), all in
+ *                  double (Mat::dot returns double). view_cos not finite or < view_cos_limit: ANGLE. ratio = max_dist / dist (float32, correctly
+ *                  rounded). level = the least n with ratio <= scale_factors[n], n_levels - 1 where there is none; ratio <= 1 gives 0. Status
+ *                  IN_VIEW carries u, v, view_cos and level.
+ *   L2 query.      r = ((double)view_cos > 0.998) ? 2.5f : 4.0f (the comparison is in double because the reference's literal is a double: view_cos
+ *                  == (float)0.998 lies above it); if (th != 1.0f) r *= th; radius = r * scale_factors[level]; levels (level - 1, level).
+ *   L3 list.       The candidate list is M3's on the frame's grid (M2) with that centre, radius and levels; the distances are M4 against the
+ *                  point's descriptor.
+ *   L4 resolve.    Per keypoint of the frame a claimed bit, set at the start where the job's occupied byte is (the reference's mvpMapPoints[idx]
+ *                  && Observations() > 0). The in-view points in list order: over the candidates that are not claimed and whose distance is below
+ *                  256, take the two lexicographic minima of (distance, list position): (best, level1, idx) and (best2, level2), the levels being
+ *                  the candidates' octaves. A missing slot is (256, -1). Accept iff a first was found, best <= th_high and not (level1 == level2 &&
+ *                  (float)best > nn_ratio * (float)best2). On accept: claim the keypoint, match[point] = keypoint, dist[point] = best,
+ *                  point_of[keypoint] = the point's list position. This overload has no rotation check.
+ *                  WHY THE TWO MINIMA ARE THE REFERENCE'S SCAN. The reference keeps (bestDist, bestLevel, bestIdx) and (bestDist2, bestLevel2),
+ *                  starts both at (256, -1) and walks the list with `if (dist < bestDist) {second = first; first = this} else if (dist <
+ *                  bestDist2) {second = this}`. Invariant: after any prefix, first and second are the two least (distance, position) pairs of the
+ *                  prefix below 256. A new candidate has the largest position so far. dist < bestDist: it is the new least pair and the old first,
+ *                  which was below the old second, is the new second. Else dist >= bestDist, so it follows the first; dist < bestDist2 puts it
+ *                  before the old second, so it is the new second. Else dist >= bestDist2 and a larger position: it follows both, nothing changes.
+ *                  A candidate at 256 passes neither strict test. (Where no candidate is left the reference would index mvpMapPoints[-1] if it
+ *                  accepted; `a first was found` is the library's guard and changes nothing for th_high < 256.)
+ *   L5 outputs per job. Per listed point: status (uint8), u, v, view_cos, level, radius (zeros where not in view), match (the keypoint or -1), dist
+ *                  (the accepted distance or -1). Per keypoint of the frame: point_of (the position in the job's list that claimed it, or -1).
+ *                  Counts: one per status (status[IN_VIEW] is the reference's nToMatch), n_candidates (the sum of the list lengths), n_matches.
+ *                  With keep_stages the candidate lists as iba_orb_matches_lists gives them.
+ *   L6 edges.      (iba_map_match_pose_edges, host only, pure) the joining helper to iba_pose_job: the frame's keypoints in ascending index; a
+ *                  keypoint that was claimed in the call (point_of >= 0) holds points[point_of]; else one that had a point before the call
+ *                  (prior_point, table indices or -1) holds that; every such keypoint yields one edge: xyz from the table, obs = the keypoint's
+ *                  position, inv_sigma2 = inv_level_sigma2[octave] and the keypoint's index, as iba_pose_edges_from_matches does for a CLAIM job.
+ *
+ * UNPINNED, together: the order of the sums of Pc and Ow (the reference forms them with OpenCV's 3 x 3 float product), dist (cv::norm's own
+ * accumulation) and the dot product. KNOWN DEVIATIONS: (1) the level: the reference takes ceil(log(ratio) / mfLogScaleFactor) through libm, clamped to
+ * [0, n_levels - 1]; the table rule gives the same integer except where ratio lies within rounding of a table entry, and keeps transcendentals off
+ * the device, as P6 does (profiles/map_match_parity.md counts the differences on the test scene). (2) As in M7 every claim of the call counts,
+ * where the reference skips a claimed keypoint only if its map point has Observations() > 0. (3) NOT_FINITE, above.
+ * NOT PROVIDED: stereo (mvuRight, mTrackProjXR), the KeyFrame and Sim3 overloads of SearchByProjection, Fuse, the BoW matchers, UpdateLocalMap
+ * (choosing the local points and their order is the caller's) and the IncreaseVisible / IncreaseFound bookkeeping (the statuses and matches say
+ * which points it applies to).
+ * DEVICE (csrc/iba_map_match_kernels.hpp). Before the chunks, over the whole call: the frustum kernel - a flat table of (job, list position)
+ * slots, one lane per slot, blocks that do not straddle a job so that pose, intrinsics, bounds and scale table are uniform per block; it writes the
+ * status and the slot's query record, and counts the statuses by wave ballot into LDS with one integer atomic per counter and block; then the
+ * matcher's own grid kernels (cell, scan, ordered fill) and its list kernel counting every slot's list - the point descriptors lie behind the
+ * keypoint descriptors in the one flat descriptor table, so that kernel is unchanged. Per chunk of consecutive jobs: scan, the list kernel writing
+ * candidates and distances, and the resolve kernel: ONE wave per job, because L4 is sequential; the claimed state is a bitmap in LDS (32768 keypoints
+ * take 4 KB: there is no global fallback) seeded from occupied; the lanes stride over a point's segment keeping their two least keys, the wave's
+ * first is a 64-bit key minimum and its second the least of the winner lane's second and the other lanes' firsts; lane 0 reads the two octaves and
+ * applies the acceptance; one barrier follows each point with a non-empty segment. No floating-point atomics, no order depends on atomic arrival.
+ * MEMORY: the candidate lists (IBA_MAP_MATCH_BYTES_PER_CANDIDATE bytes per entry, sized from the count pass) are cut into chunks of consecutive
+ * jobs under IBA_MAP_MATCH_BUDGET_BYTES, or under a quarter of the device memory free at the call where that is less; a chunk holds at least one job
+ * and a chunk boundary changes no byte. A chunk whose lists hold 2^31 entries or more answers IBA_ERR_UNSUPPORTED. The result is host memory.
+ * ERRORS, all IBA_ERR_INVALID_ARG with a message (iba_map_match_last_error, per thread) BEFORE the device is touched: a NULL argument (the table's
+ * arrays may be NULL only where P == 0; skip and occupied may always be NULL; points may be NULL only where n_points == P: all P in order) or a
+ * wrong struct_size; J < 1, F < 1, P < 0; a frame that iba_orb_match would refuse; a job's frame or a listed point out of range; n_points < 0; a
+ * pose entry, point, normal, distance, intrinsic or th that is not finite or whose magnitude is above 1e6; n_levels outside [1,
+ * IBA_MAP_MATCH_MAX_LEVELS]; a scale table that is not finite, does not start at 1 or does not ascend strictly; th_high outside [0, 256]; nn_ratio
+ * not finite or <= 0; view_cos_limit not finite; a job index outside the result; the stage accessor on a result without keep_stages. A job with
+ * n_points == 0 and a frame with n == 0 are legal.
+ */
+#define IBA_MAP_MATCH_BUDGET_BYTES (1ull << 30)
+#define IBA_MAP_MATCH_BYTES_PER_CANDIDATE 6ull
+#define IBA_MAP_MATCH_MAX_LEVELS 64
+#define IBA_MAP_MATCH_N_STATUS 7
+typedef enum iba_map_match_status {
+    IBA_MAP_MATCH_IN_VIEW = 0, IBA_MAP_MATCH_SKIPPED = 1, IBA_MAP_MATCH_DEPTH = 2, IBA_MAP_MATCH_NOT_FINITE = 3, IBA_MAP_MATCH_BOUNDS = 4, IBA_MAP_MATCH_DISTANCE = 5,
+    IBA_MAP_MATCH_ANGLE = 6
+} iba_map_match_status;
+typedef struct iba_map_points {               /* host pointers, read during the call only */
+    const float*   xyz;        /* n x 3: MapPoint::GetWorldPos */
+    const float*   normal;     /* n x 3: MapPoint::GetNormal */
+    const float*   min_dist;   /* n: mfMinDistance, raw (L1 applies the 0.8f) */
+    const float*   max_dist;   /* n: mfMaxDistance, raw (L1 applies the 1.2f) */
+    const uint8_t* desc;       /* n x 32: MapPoint::GetDescriptor */
+    int32_t n;
+} iba_map_points;
+typedef struct iba_map_match_job {            /* host pointers, read during the call only */
+    int32_t frame;                  /* index into the call's frame array */
+    int32_t n_levels;               /* entries of scale_factors, 1..IBA_MAP_MATCH_MAX_LEVELS */
+    int32_t n_points;
+    float   th;
+    float   fx, fy, cx, cy;
+    const float*   Tcw12;           /* 3 x 4 row-major float32: the frame's mTcw */
+    const float*   scale_factors;   /* n_levels: the frame's mvScaleFactors, [0] == 1, ascending */
+    const int32_t* points;          /* n_points indices into the table in the order of mvpLocalMapPoints, or NULL: all P in order */
+    const uint8_t* skip;            /* n_points, or NULL: none */
+    const uint8_t* occupied;        /* one byte per keypoint of the frame, or NULL: none */
+} iba_map_match_job;
+typedef struct iba_map_match_options {
+    int32_t struct_size;        /* sizeof(iba_map_match_options) */
+    int32_t th_high;            /* 100 */
+    float   nn_ratio;           /* 0.8f: the ORBmatcher of SearchLocalPoints */
+    float   view_cos_limit;     /* 0.5f */
+    int32_t keep_stages;        /* 0; 1 keeps the candidate lists for iba_map_matches_lists */
+} iba_map_match_options;
+typedef struct iba_map_match_counts {
+    int32_t n_points;
+    int32_t status[IBA_MAP_MATCH_N_STATUS];   /* by iba_map_match_status; status[IBA_MAP_MATCH_IN_VIEW] = nToMatch */
+    int32_t n_candidates, n_matches;
+} iba_map_match_counts;
+typedef struct iba_map_matches iba_map_matches;
+iba_status iba_default_map_match_options(iba_map_match_options* opt);
+const char* iba_map_match_last_error(void);                          /* never NULL; of this thread's last iba_map_match* call that failed */
+/* *out is NULL on failure; release it with iba_map_matches_free */
+iba_status iba_map_match(const iba_orb_frame* frames, int32_t F, const iba_map_points* points, const iba_map_match_job* jobs, int32_t J, const iba_map_match_options* opt, int device,
+                         iba_map_matches** out);
+void       iba_map_matches_free(iba_map_matches* m);
+int32_t    iba_map_matches_n_jobs(const iba_map_matches* m);         /* 0 for NULL */
+iba_status iba_map_matches_job(const iba_map_matches* m, int32_t job, iba_map_match_counts* counts);
+/* L5 per listed point, n_points entries each; any may be NULL */
+iba_status iba_map_matches_read(const iba_map_matches* m, int32_t job, uint8_t* status, float* u, float* v, float* view_cos, int32_t* level, float* radius, int32_t* match, int32_t* dist);
+/* L5 per keypoint of the job's frame (frame n entries) */
+iba_status iba_map_matches_keypoints(const iba_map_matches* m, int32_t job, int32_t* point_of);
+/* keep_stages only: off[n_points + 1] and, per entry, the keypoint and the distance in M3's order; their length is the job's n_candidates. Every
+ * output may be NULL. */
+iba_status iba_map_matches_lists(const iba_map_matches* m, int32_t job, int32_t* off, int32_t* index, uint16_t* dist);
+/* host only, pure (L6). prior_point and point_of may be NULL (none); points NULL: list position k is table point k, and n_points must be P; the
+ * outputs take up to n_kp entries each; *n is the number of edges */
+iba_status iba_map_match_pose_edges(const int32_t* prior_point /* n_kp */, const int32_t* point_of /* n_kp */, const int32_t* points /* n_points */, int32_t n_points,
+                                    const float* table_xyz /* P x 3 */, int32_t P, const float* xy /* n_kp x 2 */, const int32_t* octave /* n_kp */, int32_t n_kp,
+                                    const float* inv_level_sigma2, int32_t n_levels, float* xyz, float* obs, float* inv_sigma2, int32_t* keypoint_index, int32_t* n);
 
 /*
  * ---- Bundle adjustment [the camera side's fifth brick: the reference's Optimizer::BundleAdjustment (src/orb_slam/src/Optimizer.cc:215-407: the global

@@ -59,6 +59,9 @@
  *   IBA_BUNDLE_BUDGET, IBA_BUNDLE_TIMING                  iba_bundle_optimize / iba_bundle_eval: the bytes a chunk of jobs may take on the device in place of 1 GiB
  *                                                         (iba_debug_bundle_chunks) and HIP events around a chunk's launch chains
  *                                                         (iba_debug_bundle_kernel_ms; tools/bundle_bench.py); same results
+ *   IBA_MAP_MATCH_BUDGET, IBA_MAP_MATCH_TIMING            iba_map_match: the bytes a chunk's candidate lists may take (6 per entry) in place of 1 GiB and the
+ *                                                         free-memory rule (iba_debug_map_match_chunks), and HIP events around the stages
+ *                                                         (iba_debug_map_match_stage_ms; tools/map_match_bench.py); same results
  *   IBA_GROUP_REDUCE_HOST (flag of iba_group_create_ex, not a variable), IBA_DEBUG_FAIL_RANK / IBA_DEBUG_FAIL_PHASE: inject one
  *                                                         failure into a group's evaluation (tests of the fail-not-hang path)
  */
@@ -306,6 +309,19 @@ iba_status iba_debug_bundle_eval_host(const iba_bundle_job* jobs, int32_t B, con
 int32_t iba_debug_bundle_big_steps(const iba_bundle_batch* r);
 int32_t iba_debug_bundle_chunks(const iba_bundle_batch* r);
 float   iba_debug_bundle_kernel_ms(const iba_bundle_batch* r);
+
+/* debug: iba_map_match as the host restatement of its rules (csrc/iba_map_match_host.hpp over csrc/iba_map_match_math.hpp, the text the kernels
+ * compile), the whole call without a device; the same checks, the same result object and accessors. Byte for byte what the device gives
+ * (tests/test_gpu_map_match.py). */
+iba_status iba_debug_map_match_host(const iba_orb_frame* frames, int32_t F, const iba_map_points* points, const iba_map_match_job* jobs, int32_t J, const iba_map_match_options* opt,
+                                    iba_map_matches** out);
+/* debug: the chunks the jobs of the call behind m were cut into (IBA_MAP_MATCH_BUDGET: bytes a chunk's candidate lists may take in place of
+ * IBA_MAP_MATCH_BUDGET_BYTES and the free-memory rule, read at every call under IBA_DEBUG_ENV=1; same results); 0 for iba_debug_map_match_host and
+ * for NULL */
+int32_t iba_debug_map_match_chunks(const iba_map_matches* m);
+/* debug: with IBA_MAP_MATCH_TIMING set at the call (under IBA_DEBUG_ENV=1), times in ms from HIP events, summed over the chunks: [0] frustum,
+ * [1] grid (cell, scan, fill) + list count, [2] scan + list write with the distances, [3] resolve. Zeros without the variable. Same results. */
+iba_status iba_debug_map_match_stage_ms(const iba_map_matches* m, float ms[4]);
 
 #ifdef __cplusplus
 }

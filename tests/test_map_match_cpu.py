@@ -1,0 +1,320 @@
+"""Local-map point matching, without a device (include/iba_mi355x.h, iba_map_match*): the symbols and struct layouts, every argument check, the host
+restatement (iba_debug_map_match_host) and the edge helper against tests/map_match_ref.py byte for byte, and the end-to-end chain through
+iba_debug_pose_host. Every case a test names is first asserted on the REFERENCE's own output."""
+import ctypes as C
+import importlib
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import map_match_ref as R
+import map_match_scene as S
+
+PKG = "spatial-temporal-lidar-camera-calibration_amd"
+F = np.float32
+
+
+@pytest.fixture(scope="module")
+def mm():
+    importlib.import_module(PKG)
+    return importlib.import_module(PKG + ".map_match")
+
+
+@pytest.fixture(scope="module")
+def om():
+    return importlib.import_module(PKG + ".orb_match")
+
+
+@pytest.fixture(scope="module")
+def err():
+    return importlib.import_module(PKG).IbaError
+
+
+@pytest.fixture(scope="module")
+def hand():
+    sc = S.hand_scene()
+    return sc, R.run(sc["frames"], sc["table"], sc["jobs"])
+
+
+@pytest.fixture(scope="module")
+def rand():
+    sc = S.random_scene()
+    return sc, R.run(sc["frames"], sc["table"], sc["jobs"])
+
+
+# ---- symbols, layouts, ABI ----
+
+def test_symbols_and_layouts(mm):
+    L = mm._lib()
+    names = ("iba_default_map_match_options", "iba_map_match_last_error", "iba_map_match", "iba_map_matches_free", "iba_map_matches_n_jobs", "iba_map_matches_job",
+             "iba_map_matches_read", "iba_map_matches_keypoints", "iba_map_matches_lists", "iba_map_match_pose_edges", "iba_debug_map_match_host", "iba_debug_map_match_chunks",
+             "iba_debug_map_match_stage_ms")
+    pkg = importlib.import_module(PKG)
+    hdr = "".join(open(p).read() for p in pkg.HEADER_PATHS)
+    for name in names:
+        getattr(L, name)
+        assert re.search(r"\b%s\s*\(" % name, hdr), name + " is not declared"
+    assert L.iba_abi_version() == 4 and re.search(r"#define\s+IBA_ABI_VERSION\s+4\b", hdr)
+    o = mm.match_options()
+    assert (o.struct_size, o.th_high, o.keep_stages) == (C.sizeof(mm.IbaMapMatchOptions), 100, 0) and o.nn_ratio == F(0.8) and o.view_cos_limit == F(0.5)
+    assert C.sizeof(mm.IbaMapMatchOptions) == 20
+    assert C.sizeof(mm.IbaMapPoints) == 48 and mm.IbaMapPoints.n.offset == 40
+    assert C.sizeof(mm.IbaMapMatchJob) == 72 and mm.IbaMapMatchJob.Tcw12.offset == 32 and mm.IbaMapMatchJob.occupied.offset == 64
+    assert C.sizeof(mm.IbaMapMatchCounts) == 40 and mm.IbaMapMatchCounts.n_candidates.offset == 32
+    assert L.iba_map_match_last_error() is not None
+    assert L.iba_map_matches_n_jobs(None) == 0 and L.iba_debug_map_match_chunks(None) == 0
+    for rule in ("L1 frustum", "L2 query", "L3 list", "L4 resolve", "L5 outputs", "L6 edges", "NOT PROVIDED"):
+        assert rule in hdr, rule
+
+
+# ---- argument checks: all before the device is touched (device -1 would fail otherwise with another status) ----
+
+def _expect(err, fn, text):
+    with pytest.raises(err) as e:
+        fn()
+    assert e.value.status == 1, str(e.value)
+    assert text in str(e.value), str(e.value)
+
+
+def test_argument_checks(mm, om, err, hand):
+    sc, _ = hand
+    fr, tb, jb = S.lib_args(mm, om, sc)
+    t, j0 = sc["table"], sc["jobs"][0]
+    P = len(t["min_dist"])
+    call = lambda frames=fr, table=tb, jobs=jb[:1], **kw: mm.match(frames, table, jobs, device=-1, **kw)
+    job = lambda **kw: mm.job(**{**dict(frame=0, Tcw=j0["Tcw"], K=j0["K"], scale_factors=j0["scale_factors"], th=1.0, n_points=P), **kw})
+    table = lambda **kw: mm.points(**{**{k: t[k] for k in ("xyz", "normal", "min_dist", "max_dist", "desc")}, **kw})
+    L = mm._lib()
+    o = mm.match_options()
+    p = C.c_void_p(None)
+    fa = (om.IbaOrbFrame * 1)()
+    C.memmove(C.addressof(fa[0]), C.addressof(fr[0]), C.sizeof(om.IbaOrbFrame))
+    ja = (mm.IbaMapMatchJob * 1)()
+    C.memmove(C.addressof(ja[0]), C.addressof(jb[0]), C.sizeof(mm.IbaMapMatchJob))
+    A = C.addressof
+    # NULLs and counts
+    for args, text in (((A(fa), 1, A(tb), A(ja), 1, A(o), -1, None), b"out is NULL"), ((None, 1, A(tb), A(ja), 1, A(o), -1, A(p)), b"frames is NULL"),
+                       ((A(fa), 1, None, A(ja), 1, A(o), -1, A(p)), b"points is NULL"), ((A(fa), 1, A(tb), None, 1, A(o), -1, A(p)), b"jobs is NULL"),
+                       ((A(fa), 1, A(tb), A(ja), 1, None, -1, A(p)), b"opt is NULL"), ((A(fa), 0, A(tb), A(ja), 1, A(o), -1, A(p)), b"F < 1"),
+                       ((A(fa), 1, A(tb), A(ja), 0, A(o), -1, A(p)), b"J < 1")):
+        assert L.iba_map_match(*args) == 1 and text in L.iba_map_match_last_error(), text
+    assert p.value is None and L.iba_default_map_match_options(None) == 1
+    # options
+    _expect(err, lambda: call(struct_size=16), "struct_size")
+    for v in (-1, 257):
+        _expect(err, lambda: call(th_high=v), "th_high outside [0, 256]")
+    for v in (0.0, -0.5, float("nan"), float("inf")):
+        _expect(err, lambda: call(nn_ratio=v), "nn_ratio")
+    _expect(err, lambda: call(view_cos_limit=float("nan")), "view_cos_limit")
+    # the table
+    neg = table(); neg.n = -1
+    _expect(err, lambda: call(table=neg), "points: n < 0")
+    nul = table(); nul.normal = None
+    _expect(err, lambda: call(table=nul), "points: a NULL array")
+    for key, text in (("xyz", "point 3: xyz"), ("normal", "point 3: normal"), ("min_dist", "point 3: min_dist"), ("max_dist", "point 3: max_dist")):
+        for v, why in ((np.nan, "not finite"), (np.inf, "not finite"), (2e6, "above 1e6")):
+            a = t[key].copy(); a[3] = v
+            _expect(err, lambda: call(table=table(**{key: a})), text)
+            _expect(err, lambda: call(table=table(**{key: a})), why)
+    # frames: what iba_orb_match refuses
+    f0 = sc["frames"][0]
+    _expect(err, lambda: call(frames=[om.frame(f0["xy"], f0["octave"], f0["angle"], f0["desc"], (0, 0, 0, 480))]), "max <= min")
+    # jobs
+    _expect(err, lambda: call(jobs=[job(frame=1)]), "a frame index outside")
+    _expect(err, lambda: call(jobs=[job(frame=-1)]), "a frame index outside")
+    for k, v, why in ((5, np.nan, "not finite"), (11, np.inf, "not finite"), (3, -3e6, "above 1e6")):
+        T = j0["Tcw"].copy(); T[k] = v
+        _expect(err, lambda: call(jobs=[jb[0], job(Tcw=T)]), "job 1: Tcw")
+        _expect(err, lambda: call(jobs=[jb[0], job(Tcw=T)]), why)
+    _expect(err, lambda: call(jobs=[job(K=(500, np.nan, 320, 240))]), "an intrinsic")
+    _expect(err, lambda: call(jobs=[job(K=(500, 500, 3e6, 240))]), "above 1e6")
+    _expect(err, lambda: call(jobs=[job(th=np.inf)]), "th: ")
+    _expect(err, lambda: call(jobs=[job(scale_factors=np.zeros(0, F))]), "n_levels outside [1, 64]")
+    _expect(err, lambda: call(jobs=[job(scale_factors=np.linspace(1, 2, 65))]), "n_levels outside [1, 64]")
+    _expect(err, lambda: call(jobs=[job(scale_factors=[1.0, np.nan])]), "scale_factors")
+    for sf in ([1.2, 1.44], [1.0, 1.2, 1.2], [1.0, 0.9]):
+        _expect(err, lambda: call(jobs=[job(scale_factors=sf)]), "does not ascend from 1")
+    _expect(err, lambda: call(jobs=[job(n_points=P - 1)]), "points is NULL and n_points is not the table's")
+    _expect(err, lambda: call(jobs=[job(n_points=2, points=[0, P])]), "points[1] outside the table")
+    _expect(err, lambda: call(jobs=[job(n_points=1, points=[-1])]), "points[0] outside the table")
+    bad = job(); bad.n_points = -1
+    _expect(err, lambda: call(jobs=[bad]), "n_points < 0")
+    bad = job(); bad.Tcw12 = None
+    _expect(err, lambda: call(jobs=[bad]), "Tcw12 or scale_factors is NULL")
+    # the accessors on NULL
+    assert L.iba_map_matches_job(None, 0, None) == 1 and L.iba_map_matches_read(None, 0, *[None] * 8) == 1
+    assert L.iba_map_matches_keypoints(None, 0, None) == 1 and L.iba_map_matches_lists(None, 0, None, None, None) == 1
+    assert L.iba_debug_map_match_stage_ms(None, None) == 1
+    L.iba_map_matches_free(None)
+
+
+def test_legal_empties_pass_the_checks(mm, om, err, rand):
+    """a job with n_points == 0, a frame with n == 0 and an empty table are legal: the call gets as far as the device (which device -1 is not)"""
+    sc, _ = rand
+    fr, tb, jb = S.lib_args(mm, om, sc)
+    with pytest.raises(err) as e:
+        mm.match(fr, tb, [jb[4], jb[8]], device=-1)
+    assert e.value.status != 1, str(e.value)
+    none = mm.points(np.zeros((0, 3)), np.zeros((0, 3)), [], [], np.zeros((0, 32)))
+    j = sc["jobs"][0]
+    with pytest.raises(err) as e:
+        mm.match(fr, none, [mm.job(0, j["Tcw"], j["K"], j["scale_factors"], 1.0, 0)], device=-1)
+    assert e.value.status != 1, str(e.value)
+    m = mm.match_host(fr, none, [mm.job(0, j["Tcw"], j["K"], j["scale_factors"], 1.0, 0)])
+    assert len(m) == 1 and m.counts(0)["n_points"] == 0 and np.all(m.keypoints(0) == -1)
+    m.close()
+
+
+def test_accessor_checks(mm, om, err, hand):
+    sc, refs = hand
+    fr, tb, jb = S.lib_args(mm, om, sc)
+    m = mm.match_host(fr, tb, jb)
+    assert len(m) == len(jb) and m.n_chunks == 0 and not m.stage_ms.any()
+    for bad in (-1, len(jb)):
+        _expect(err, lambda: m.counts(bad), "outside the result's %d jobs" % len(jb))
+        _expect(err, lambda: m.read(bad), "outside the result's")
+        _expect(err, lambda: m.lists(bad), "outside the result's")
+    _expect(err, lambda: m.lists(0), "did not ask for keep_stages")
+    assert mm._lib().iba_map_matches_job(m.p, 0, None) == 1
+    S.assert_equal(m, refs, keep_stages=False)          # without keep_stages: the same results
+    m.close()
+
+
+# ---- the rules on the hand scene: every named case occurs in the reference's output, then the host restatement byte for byte ----
+
+def test_hand_scene_l1_l2(mm, om, hand):
+    sc, refs = hand
+    w, r = sc["where"], refs[0]
+    st = lambda name: int(r["status"][w[name]])
+    assert st("skipped") == R.SKIPPED and st("depth") == R.DEPTH and st("bounds") == R.BOUNDS
+    # PcZ == +0.0f, and -0.0f under the pose of job 3 (the expression of L1 on that pose and point gives a negative zero)
+    assert st("z_plus_zero") == R.NOT_FINITE
+    T3, Pm = sc["jobs"][3]["Tcw"], sc["table"]["xyz"][w["z_minus_zero"]]
+    pcz = F(F(F(F(T3[8] * Pm[0]) + F(T3[9] * Pm[1])) + F(T3[10] * Pm[2])) + T3[11])
+    assert pcz == 0 and np.signbit(pcz) and refs[3]["status"].tolist() == [R.NOT_FINITE, R.IN_VIEW, R.NOT_FINITE] and refs[3]["match"][1] == sc["kp"]["lone"][0]
+    # u exactly on min_x and max_x: kept
+    assert st("u_min_x") == R.IN_VIEW and r["u"][w["u_min_x"]] == F(0.0) and st("u_max_x") == R.IN_VIEW and r["u"][w["u_max_x"]] == F(640.0)
+    # dist exactly on 0.8f * min_dist and 1.2f * max_dist: kept; one ulp beyond: DISTANCE
+    t = sc["table"]
+    assert t["xyz"][w["dist_at_min"], 2] == F(F(0.8) * t["min_dist"][w["dist_at_min"]]) and st("dist_at_min") == R.IN_VIEW and st("dist_below_min") == R.DISTANCE
+    assert t["xyz"][w["dist_at_max"], 2] == F(F(1.2) * t["max_dist"][w["dist_at_max"]]) and st("dist_at_max") == R.IN_VIEW and st("dist_above_max") == R.DISTANCE
+    # view_cos exactly at the limit: kept
+    assert st("cos_at_limit") == R.IN_VIEW and r["view_cos"][w["cos_at_limit"]] == F(0.5) and st("cos_below_limit") == R.ANGLE
+    # view_cos == (float)0.998 lies above the double 0.998: r = 2.5; one ulp below: r = 4
+    lv = int(r["level"][w["cos_f0998"]])
+    assert r["view_cos"][w["cos_f0998"]] == F(0.998) and r["radius"][w["cos_f0998"]] == F(F(2.5) * S.SF[lv])
+    assert r["view_cos"][w["cos_below_f0998"]] < F(0.998) and r["radius"][w["cos_below_f0998"]] == F(F(4.0) * S.SF[lv]) and r["level"][w["cos_below_f0998"]] == lv
+    # ratio exactly scale_factors[3], one ulp above, <= 1, above the last entry
+    assert [int(r["level"][w[k]]) for k in ("ratio_at_sf3", "ratio_above_sf3", "ratio_one", "ratio_above_last")] == [3, 4, 0, 7]
+    assert F(t["max_dist"][w["ratio_at_sf3"]] / F(2.0)) == S.SF[3] and F(t["max_dist"][w["ratio_above_sf3"]] / F(2.0)) == S.up(S.SF[3])
+    # th == 1 against th != 1: the same views, twice the radius
+    in_view = r["status"] == R.IN_VIEW
+    assert np.array_equal(refs[1]["radius"][in_view], (F(2.0) * r["radius"][in_view]).astype(F)) and np.array_equal(refs[1]["u"], r["u"])
+    assert set(r["counts"].tolist()) - {0} and all(c > 0 for c in r["counts"])          # every status occurs
+    fr, tb, jb = S.lib_args(mm, om, sc)
+    m = mm.match_host(fr, tb, jb, keep_stages=1)
+    S.assert_equal(m, refs)
+    m.close()
+
+
+def test_hand_scene_l4(mm, om, hand):
+    sc, refs = hand
+    w, kp, r = sc["where"], sc["kp"], refs[0]
+    seg = np.diff(r["off"])
+    m, d = (lambda name: int(r["match"][w[name]])), (lambda name: int(r["dist"][w[name]]))
+    first = lambda name: int(r["index"][r["off"][w[name]]])                      # the first candidate in list order
+    assert {0, 1, 63, 64, 65, 200} <= set(seg.tolist())
+    for n in (63, 64, 65, 200):
+        assert seg[w["segment%d" % n]] == n and d("segment%d" % n) == 30
+    assert seg[w["segment0"]] == 0 and r["status"][w["segment0"]] == R.IN_VIEW
+    assert seg[w["lone"]] == 1 and (m("lone"), d("lone")) == (kp["lone"][0], 30)
+    assert seg[w["tie_same_level"]] == 2 and m("tie_same_level") == -1                                          # 20 > 0.8f * 20
+    assert seg[w["tie_zero"]] == 2 and (m("tie_zero"), d("tie_zero")) == (first("tie_zero"), 0)                 # 0 > 0.8f * 0 is false
+    assert seg[w["tie_other_level"]] == 2 and (m("tie_other_level"), d("tie_other_level")) == (first("tie_other_level"), 20)
+    assert sorted(sc["frames"][0]["octave"][kp["tie_other_level"]].tolist()) == [1, 2] and r["level"][w["tie_other_level"]] == 2
+    assert seg[w["only_256"]] == 1 and r["cdist"][r["off"][w["only_256"]]] == 256 and m("only_256") == -1
+    assert (m("at_th_high"), d("at_th_high")) == (kp["at_th_high"][0], 100) and m("above_th_high") == -1 and r["cdist"][r["off"][w["above_th_high"]]] == 101
+    assert (m("ratio_pass"), d("ratio_pass")) == (kp["ratio_pass"][0], 40) and m("ratio_refuse") == -1 and r["n_ratio_refused"] == 2
+    # a level-0 point: the range (-1, 0) leaves the octave-1 keypoint at distance 5 out of the list
+    assert r["level"][w["level0"]] == 0 and seg[w["level0"]] == 1 and (m("level0"), d("level0")) == (kp["level0"][1], 50)
+    # occupied: the keypoint at 10 is in the list and is skipped
+    assert seg[w["occupied"]] == 2 and (m("occupied"), d("occupied")) == (kp["occupied"][1], 40) and r["point_of"][kp["occupied"][0]] == -1
+    # the claim chain: a takes the first keypoint, b its second choice, c nothing; reversed (job 2), c and b take them and a nothing
+    assert [m("chain_a"), m("chain_b"), m("chain_c")] == [kp["chain"][0], kp["chain"][1], -1] and r["n_second_choice"] >= 2 and r["n_nothing_left"] == 1
+    P = len(r["status"])
+    rev = refs[2]["match"][::-1]
+    assert [int(rev[w[k]]) for k in ("chain_a", "chain_b", "chain_c")] == [-1, kp["chain"][1], kp["chain"][0]]
+    assert r["point_of"][kp["chain"][0]] == w["chain_a"] and refs[2]["point_of"][kp["chain"][0]] == P - 1 - w["chain_c"]
+    # th_high of the options: 99 refuses the candidate at 100
+    fr, tb, jb = S.lib_args(mm, om, sc)
+    low = R.run(sc["frames"], sc["table"], sc["jobs"], th_high=99, nn_ratio=0.5)
+    assert low[0]["match"][w["at_th_high"]] == -1 and low[0]["match"][w["ratio_pass"]] == -1 and low[0]["n_matches"] < r["n_matches"]
+    for opts, want in (({}, refs), ({"th_high": 99, "nn_ratio": 0.5}, low)):
+        res = mm.match_host(fr, tb, jb, keep_stages=1, **opts)
+        S.assert_equal(res, want)
+        res.close()
+
+
+def test_random_scene(mm, om, rand):
+    sc, refs = rand
+    assert [r["n_points"] for r in refs] == [300, 257, 257, 257, 0, 1, 255, 256, 300] and len(sc["frames"][2]["octave"]) == 0
+    assert all(refs[0]["counts"][s] > 0 for s in (R.IN_VIEW, R.DEPTH, R.BOUNDS, R.DISTANCE, R.ANGLE)) and refs[1]["counts"][R.SKIPPED] > 0
+    assert sum(r["n_ratio_refused"] for r in refs) > 0 and sum(r["n_th_refused"] for r in refs) > 0 and sum(r["n_second_choice"] for r in refs) > 0
+    assert refs[1]["n_nothing_left"] > 0 and len(set(refs[0]["level"][refs[0]["status"] == R.IN_VIEW].tolist())) >= 5
+    assert refs[5]["n_matches"] == 1 and refs[8]["counts"][R.IN_VIEW] > 0 and refs[8]["n_candidates"] == 0
+    # jobs 2 and 3: one list in two orders; the permutation changes which point holds which keypoint
+    a = dict(zip(sc["jobs"][2]["points"].tolist(), refs[2]["match"].tolist()))
+    b = dict(zip(sc["jobs"][3]["points"].tolist(), refs[3]["match"].tolist()))
+    assert a != b and np.array_equal(np.sort(refs[2]["u"]), np.sort(refs[3]["u"]))
+    # occupied keypoints are never claimed
+    assert np.all(refs[1]["point_of"][sc["jobs"][1]["occupied"] != 0] == -1) and refs[1]["n_matches"] > 0
+    fr, tb, jb = S.lib_args(mm, om, sc)
+    m = mm.match_host(fr, tb, jb, keep_stages=1)
+    S.assert_equal(m, refs)
+    m.close()
+
+
+# ---- L6 and the chain to the pose optimisation ----
+
+def test_pose_edges(mm, err, rand):
+    sc, refs = rand
+    job, ref, f = sc["jobs"][1], refs[1], sc["frames"][1]
+    rng = np.random.default_rng(2)
+    nk, P = len(f["octave"]), len(sc["table"]["min_dist"])
+    prior = np.where(rng.uniform(size=nk) < 0.3, rng.integers(0, P, nk), -1).astype(np.int32)
+    lv = (F(1.0) / (S.SF * S.SF)).astype(F)
+    both = int(np.sum((prior >= 0) & (ref["point_of"] >= 0)))
+    assert both > 0 and ref["n_matches"] > both                          # a keypoint that had a point and was claimed: the claim holds
+    for pp, po in ((prior, ref["point_of"]), (None, ref["point_of"]), (prior, None), (None, None)):
+        got = mm.pose_edges(pp, po, job["points"], len(job["points"]), sc["table"]["xyz"], f["xy"], f["octave"], lv)
+        want = R.pose_edges(pp, po, job["points"], sc["table"]["xyz"], f["xy"], f["octave"], lv)
+        for g, x in zip(got, want):
+            assert S.same_bytes(g, x)
+    assert len(got[0]) == 0 and len(mm.pose_edges(prior, ref["point_of"], job["points"], len(job["points"]), sc["table"]["xyz"], f["xy"], f["octave"], lv)[3]) == \
+        int(np.sum((prior >= 0) | (ref["point_of"] >= 0)))
+    # points == NULL: list position k is table point k
+    got = mm.pose_edges(None, refs[0]["point_of"], None, P, sc["table"]["xyz"], sc["frames"][0]["xy"], sc["frames"][0]["octave"], lv)
+    want = R.pose_edges(None, refs[0]["point_of"], None, sc["table"]["xyz"], sc["frames"][0]["xy"], sc["frames"][0]["octave"], lv)
+    assert all(S.same_bytes(g, x) for g, x in zip(got, want)) and len(got[3]) == refs[0]["n_matches"]
+    args = (job["points"], len(job["points"]), sc["table"]["xyz"], f["xy"], f["octave"])
+    _expect(err, lambda: mm.pose_edges(prior, ref["point_of"], *args, lv[:2]), "octave")
+    _expect(err, lambda: mm.pose_edges(np.full(nk, P, np.int32), None, *args, lv), "had point")
+    _expect(err, lambda: mm.pose_edges(None, np.full(nk, 257, np.int32), *args, lv), "claimed by list position")
+    _expect(err, lambda: mm.pose_edges(None, None, None, 5, sc["table"]["xyz"], f["xy"], f["octave"], lv), "points is NULL")
+
+
+def test_end_to_end_host(mm, om):
+    """iba_debug_map_match_host -> iba_map_match_pose_edges -> iba_debug_pose_host on the noise-free scene"""
+    S.check_end_to_end(mm, om, importlib.import_module(PKG + ".pose"), host=True)
+
+
+def test_selftest_program_builds_and_passes():
+    """the stand-alone sanitizer program over the host half and the shared math text: plain g++, run on the CPU"""
+    csrc = os.path.join(os.path.dirname(os.path.abspath(importlib.import_module(PKG).__file__)), "csrc")
+    subprocess.check_call(["make", "-C", csrc, "-s", "san/map_match_selftest_asan"])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([os.path.join(csrc, "san", "map_match_selftest_asan")], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0 and "map_match_selftest ok" in r.stdout, r.stdout + r.stderr
