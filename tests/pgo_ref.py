@@ -2,6 +2,8 @@
   * linearize(..., dtype=np.float64): rules 2-5 over all edges at once, every expression in the order the header gives (and the device uses); with
     dtype=np.longdouble the same rules with atan2 / sqrt / sin / cos in long double: the yardstick the parity gates measure both sides against.
   * dense_system / dense_solve: H as a dense 6N x 6N and numpy.linalg.solve — what Open3D does per LM trial.
+  * sparse_system / sparse_solve: the same H in scipy.sparse and its direct solve, for the sizes the dense H cannot follow to; block_residual: the
+    figure of the solve gate in long double from H's 6x6 blocks, without H.
   * plan: the arrowhead plan (chain / cross edges, separators, K doubling, runs) as plain Python.
   * optimize: rules 6 and 7; records every rho and every stopping comparison, check_margins asserts that none is a near-tie.
   * make_graph: the seeded generator (smooth trajectory, noisy odometry, loop edges, informations of the sum G^T G form of iba_scan_information).
@@ -253,6 +255,72 @@ def dense_solve(H, b, lam):
     return np.linalg.solve(H + lam * np.eye(len(H)), b)
 
 
+def system_blocks(N, pairs, A):
+    """the 6x6 blocks of H, each summed on its own in float64 in the order of `pairs` = (row node, column node, sign, index into A): what the dense
+    += / -= of dense_system does to the same entries -> (keys [nb, 2], blocks [nb, 6, 6])"""
+    blocks = {}
+    for i, j, sign, e in pairs:
+        blk = blocks.get((i, j))
+        if blk is None:
+            blk = blocks[(i, j)] = np.zeros((6, 6))
+        if sign > 0:
+            blk += A[e]
+        else:
+            blk -= A[e]
+    return np.array(list(blocks.keys()), np.int64).reshape(-1, 2), np.stack(list(blocks.values())) if blocks else np.zeros((0, 6, 6))
+
+
+def blocks_to_csc(N, keys, vals):
+    import scipy.sparse as sp
+    k6 = np.arange(6)
+    rows = (6 * keys[:, 0])[:, None, None] + k6[None, :, None] + 0 * k6[None, None, :]
+    cols = (6 * keys[:, 1])[:, None, None] + 0 * k6[None, :, None] + k6[None, None, :]
+    return sp.coo_matrix((vals.reshape(-1), (rows.reshape(-1), cols.reshape(-1))), shape=(6 * N, 6 * N)).tocsc()
+
+
+def blocks_residual(N, keys, vals, b, lam, delta):
+    """|(H + lam I) delta - b| / |b| in long double from the blocks of H; without a right-hand side the plain norm"""
+    bl, dl = np.asarray(b, np.longdouble).reshape(N, 6), np.asarray(delta, np.longdouble).reshape(N, 6)
+    r = np.longdouble(lam) * dl - bl
+    V, x = vals.astype(np.longdouble), dl[keys[:, 1]]
+    y = np.zeros((len(keys), 6), np.longdouble)
+    for k in range(6):
+        y = y + V[:, :, k] * x[:, k:k + 1]
+    np.add.at(r, keys[:, 0], y)
+    nb = float(np.sqrt(np.sum(bl * bl)))
+    return float(np.sqrt(np.sum(r * r))) / nb if nb > 0 else float(np.sqrt(np.sum(r * r)))
+
+
+def _edge_pairs(g, pruned):
+    for e in range(g.E):
+        if pruned is not None and pruned[e]:
+            continue
+        s, t = int(g.src[e]), int(g.tgt[e])
+        yield s, s, 1.0, e
+        yield t, t, 1.0, e
+        yield s, t, -1.0, e
+        yield t, s, -1.0, e
+
+
+def sparse_system(N, g, A, pruned=None):
+    """the H of dense_system as a scipy.sparse CSC matrix, entry for entry (at N = 4541 the dense H would take 5.9 GB)"""
+    return blocks_to_csc(N, *system_blocks(N, _edge_pairs(g, pruned), A))
+
+
+def sparse_solve(H, b, lam):
+    import scipy.sparse as sp
+    import scipy.sparse.linalg as spl
+    return spl.spsolve((H + lam * sp.identity(H.shape[0], format="csc")).tocsc(), np.asarray(b, np.float64).reshape(-1))
+
+
+def block_residual(N, g, A, b, lam, delta, pruned=None):
+    """|(H + lam I) delta - b| / |b| in long double without forming H: the figure _rel_residual of the device tests takes from the dense H. The
+    blocks are H's own, float64 sums of the A_e: a solve's residual sits at the rounding level of those sums (1e-16 |b|), so applying every A_e
+    on its own, as exact arithmetic would allow (y = A_e (delta_s - delta_t), r_s += y, r_t -= y), gives another figure there — on SOLVE_CASES' n3
+    1.15e-16 against 9.2e-17 — while on H's blocks the two agree to the order of a long-double sum."""
+    return blocks_residual(N, *system_blocks(N, _edge_pairs(g, pruned), np.asarray(A, np.float64).reshape(-1, 6, 6)), b, lam, delta)
+
+
 def plan(N, src, tgt, segment, cap=MAX_SEPARATORS, active=None):
     """-> dict(separators, runs [(first, last)], K, chain [N]); ValueError when the separators cannot be brought under cap"""
     chain = [-1] * N
@@ -480,3 +548,25 @@ SOLVE_CASES = [("n%d" % n, n, (), (), 4, None) for n in (1, 2, 3, 4, 5, 8, 9, 17
     ("three_panels_ragged", 70, (), (), 4, None),        # 18 separators: 108 = 48 + 48 + 12
     ("k_doubles_once", 40, ((13, 30),), (), 4, 8),       # K = 4: 12 separators > 8; K = 8: 7
 ]
+
+# (name, N, cross edges, segment, dict(K, separators, runs)): the shapes at which every loop of the solve iterates; their reference is sparse_solve.
+#   rows_and_back_second_block: 2 and 7 cut the runs (1-3), (5-7) into lengths 1, 1, 2 beside (9-11) in forward block 0; 7 | 8 and 101 | 102 are
+#   adjacent separators; (150, 21) is stored against the chain between runs of forward blocks 1 and 10. n = 474: 426 rows below the first
+#   panel, a 14 x 14 grid of tiles with a ragged last one, all four waves of the separator solve, run and separator ids beyond 64.
+#   at_the_cap / one_past_the_cap: the cap 1024 itself (no run at all, n = 6144 fills the separator solve's LDS) and the first doubling past it;
+#   k_doubles_twice: 2050 -> 1025 -> 513 separators.
+LARGE_SOLVE_CASES = [
+    ("rows_and_back_second_block", 280, ((2, 7), (101, 102), (150, 21), (30, 200), (263, 58)), 4, dict(K=4, separators=79, runs=74)),
+    ("at_the_cap", 1024, (), 1, dict(K=1, separators=1024, runs=0)),
+    ("one_past_the_cap", 1025, (), 1, dict(K=2, separators=513, runs=512)),
+    ("k_doubles_twice", 4100, (), 2, dict(K=8, separators=513, runs=513)),
+]
+_large_graphs = {}
+
+
+def large_case_graph(name):
+    """the graph of a LARGE_SOLVE_CASES entry, made once per process (the plan test and the device test share it; neither changes it)"""
+    if name not in _large_graphs:
+        _, N, cross, _, _ = next(c for c in LARGE_SOLVE_CASES if c[0] == name)
+        _large_graphs[name] = case_graph(N, cross, seed=1)
+    return _large_graphs[name]

@@ -4,6 +4,7 @@
   * linearize(..., dtype): S2 and S3 over all factors at once, the node gather in ascending factor index; with dtype=np.longdouble the same rules in
     long double — the yardstick the parity gates measure both sides against.
   * dense_system / dense_solve: H as a dense 6N x 6N; ld=True refines the float64 solve with long-double residuals until it is the long-double answer.
+  * sparse_system / sparse_solve / block_residual: the twins of tests/pgo_ref.py's, with the priors, for systems too large for the dense H.
   * optimize(g, opt, ld=None | "lin" | "solve"): rule S4 (rule 6 of iba_pgo_* on F); the two twins linearise, respectively solve, in long double.
     Every rho and every stopping comparison is recorded, check_margins asserts that none is a near-tie.
   * make_graph: a seeded chain with a prior on node 0, odometry factors, true loops and false loops (all loops robust).
@@ -320,6 +321,29 @@ def dense_system(N, g, A, b):
             H[i:i + 6, i:i + 6] += A[f]
             H[i:i + 6, j:j + 6] -= A[f]; H[j:j + 6, i:i + 6] -= A[f]
     return H, np.asarray(b).reshape(-1)
+
+
+def _factor_pairs(g):
+    for f in range(g.F):
+        i, j = g.fi[f], g.fj[f]
+        yield j, j, 1.0, f
+        if i >= 0:
+            yield i, i, 1.0, f
+            yield i, j, -1.0, f
+            yield j, i, -1.0, f
+
+
+def sparse_system(N, g, A):
+    """the H of dense_system as a scipy.sparse CSC matrix, entry for entry: the twin of tests/pgo_ref.py's, with the priors"""
+    return P.blocks_to_csc(N, *P.system_blocks(N, _factor_pairs(g), np.asarray(A, np.float64)))
+
+
+sparse_solve = P.sparse_solve
+
+
+def block_residual(N, g, A, b, lam, delta):
+    """|(H + lam I) delta - b| / |b| in long double from H's 6x6 blocks, without forming H: _rel_residual's figure (see tests/pgo_ref.py)"""
+    return P.blocks_residual(N, *P.system_blocks(N, _factor_pairs(g), np.asarray(A, np.float64).reshape(-1, 6, 6)), b, lam, delta)
 
 
 def dense_solve(H, b, lam, ld=False):

@@ -3,7 +3,7 @@ Gates:
   linearise   per output, |device - long double| <= 4 x |float64 restatement - long double| + one ulp of the output's scale, on the same case (the gate
               of tests/test_gpu_pgo.py). The scale is the sum of the absolute values of the terms of the output's largest sum (for r: its largest entry).
   solve       |(H + lambda I) delta - b| / |b| of the device against the same figure of the dense float64 solve of the SAME H, b (read back from the
-              device), both evaluated in long double, margin 8 x.
+              device), both evaluated in long double, margin 8 x; at n = 420 of the sparse direct solve of the same H, b.
   optimise    decisions reproduced exactly on seeds where the float64 reference and its two long-double twins (linearise / solve in long double) share
               one trial trace and no decision is a near-tie (asserted here, on the CPU side of the test); final poses within 4 x the larger distance
               of the float64 reference from the twins; the reference's max |b| at the device's poses no larger than at the reference's own
@@ -49,24 +49,32 @@ def _device(sm, g, nodes=None, **fields):
     return s
 
 
-def _lin_cases():
-    yield "E1", S.case_graph(2, seed=3)
-    for n in (64, 65, 66):
-        yield "E%d" % (n - 1), S.case_graph(n, seed=n, robust_chain=(5, 40))
-    yield "E129", S.case_graph(100, cross=[(i, i + 35 + (i % 5)) for i in range(0, 60, 2)], seed=9)
+# name -> the graph, made when its test runs. The prior counts as a factor: F256 fills a block of smooth_factor_kernel, F257 and F513 start another
+# with one factor; N = 257 starts a second block of smooth_update_kernel.
+_LIN_CASES = {
+    "E1": lambda: S.case_graph(2, seed=3),
+    "E63": lambda: S.case_graph(64, seed=64, robust_chain=(5, 40)), "E64": lambda: S.case_graph(65, seed=65, robust_chain=(5, 40)),
+    "E65": lambda: S.case_graph(66, seed=66, robust_chain=(5, 40)),
+    "E129": lambda: S.case_graph(100, cross=[(i, i + 35 + (i % 5)) for i in range(0, 60, 2)], seed=9),
     # factors against the chain (stored and cross), a duplicate of a chain factor and of a cross factor, a node of degree 6, the prior on node 5
-    yield "reversed_duplicate_prior5", S.case_graph(16, cross=((8, 1), (8, 12), (14, 8), (10, 11), (11, 10), (8, 12)), seed=4, reverse=(5, 9), prior_node=5)
+    "reversed_duplicate_prior5": lambda: S.case_graph(16, cross=((8, 1), (8, 12), (14, 8), (10, 11), (11, 10), (8, 12)), seed=4, reverse=(5, 9), prior_node=5),
+    "F256": lambda: S.case_graph(256, seed=256, robust_chain=(5, 40)), "F257": lambda: S.case_graph(257, seed=257, robust_chain=(5, 40)),
+    "F513": lambda: S.case_graph(513, seed=513, robust_chain=(5, 40)),
+}
 
 
-@pytest.mark.parametrize("name,g", list(_lin_cases()), ids=[n for n, _ in _lin_cases()])
-def test_linearise_against_long_double(sm, name, g):
+@pytest.mark.parametrize("name", list(_LIN_CASES))
+def test_linearise_against_long_double(sm, name):
+    g = _LIN_CASES[name]()
+    if name[0] == "F":
+        assert g.F == int(name[1:])
     s = _device(sm, g, segment=4)
     a, b = s.linearize(), s.linearize()
     s.close()
     for k in ("r", "w", "A", "D", "b"):
         assert a[k].tobytes() == b[k].tobytes(), k
     assert a["F"] == b["F"]
-    assert sum(1 for i in g.fi if i >= 0) == {"E1": 1, "E63": 63, "E64": 64, "E65": 65, "E129": 129}.get(name, 21)
+    assert sum(1 for i in g.fi if i >= 0) == {"E1": 1, "E63": 63, "E64": 64, "E65": 65, "E129": 129, "F256": 255, "F257": 256, "F513": 512}.get(name, 21)
     f64, ld = S.linearize(g.nodes, g), S.linearize(g.nodes, g, dtype=np.longdouble)
     for k in ("r", "w", "A", "D", "b", "F"):
         truth = np.asarray(ld[k])
@@ -105,8 +113,33 @@ def test_solve_against_the_dense_solve_of_the_same_system(sm, name, cross):
     s.close()
 
 
-# seeds on which the float64 reference and both twins share one trace with margins (found on the CPU; asserted below)
-OPT_CASES = [(40, 2, 43), (130, 3, 4)]
+def test_solve_against_the_sparse_solve_beyond_one_block(sm):
+    """N = 280 at segment 4: 70 separators (the first carries the prior's 1e12 through Arrow::upload) and 70 runs, n = 420: rows below a panel,
+    the separator solve's stride and run ids all pass 256 / 64. The gate of the test above, the reference S.sparse_solve (tests/test_smooth_cpu.py pins
+    it and S.block_residual on the dense ones); the dense solve's figure is noted beside it."""
+    g = S.case_graph(280, seed=1)
+    assert np.all(g.var[0] == 1e-12)
+    s = _device(sm, g, segment=4)
+    try:
+        lin = s.linearize()
+        H = S.sparse_system(g.N, g, lin["A"])
+        assert np.array_equal(np.stack([H[6 * i:6 * i + 6, 6 * i:6 * i + 6].toarray() for i in range(g.N)]), lin["D"])
+        Hd, bd = S.dense_system(g.N, g, lin["A"], lin["b"])
+        lam0 = 1e-5 * S.linearize(g.nodes, g)["max_diag_between"]
+        for lam in (lam0, 1.0, 1e6):
+            d1, d2 = s.solve(lam), s.solve(lam)
+            assert d1.tobytes() == d2.tobytes()
+            fig = lambda d: S.block_residual(g.N, g, lin["A"], lin["b"], lam, d)
+            dev, sparse, dense = fig(d1), fig(S.sparse_solve(H, lin["b"], lam)), fig(S.dense_solve(Hd, bd, lam))
+            _note(test="solve_large", case="n280_segment4", n=420, lam=lam, device=dev, sparse=sparse, dense=dense, ratio=dev / sparse)
+            assert dev <= 8.0 * sparse, (lam, dev, sparse)
+    finally:
+        s.close()
+
+
+# seeds on which the float64 reference and both twins share one trace with margins (found on the CPU; asserted below); N = 280: F = 284 and N span
+# two blocks of the factor and update kernels
+OPT_CASES = [(40, 2, 43), (130, 3, 4), (280, 3, 33)]
 
 
 def _reference(g):

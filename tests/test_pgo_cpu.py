@@ -115,19 +115,27 @@ def test_the_two_false_loops_are_pruned_and_only_they():
 
 def test_the_seeds_of_the_device_tests_have_no_near_tie():
     """tests/test_gpu_pgo.py compares decision sequences on these runs: none of their decisions may be close"""
-    for N, loops, seed in ((40, 3, 15), (130, 4, 81)):
-        res = R.optimize(R.make_graph(N, loops=loops, false_loops=1, seed=seed), R.options())
+    for N, loops, seed in ((40, 3, 15), (130, 4, 81), (280, 4, 161)):          # the last: two blocks of edges and of nodes
+        g = R.make_graph(N, loops=loops, false_loops=1, seed=seed)
+        res = R.optimize(g, R.options())
         R.check_margins(res)
         assert res["n_pruned"] == 1 and res["pruned"][-1]
+    assert g.E == 284 and [(p["iterations"], p["trials"], p["stop"]) for p in res["passes"]] == [(11, 11, 3), (13, 13, 3)]
+    assert np.max(np.abs(R.align_at(res["nodes"], g.truth) - g.truth)) < 0.5 * np.max(np.abs(R.align_at(g.nodes, g.truth) - g.truth))
 
 
-@pytest.mark.parametrize("case", R.SOLVE_CASES, ids=[c[0] for c in R.SOLVE_CASES])
+# the shapes of the solve tests, then those at and past the real cap IBA_PGO_MAX_SEPARATORS = 1024 (no environment override)
+PLAN_CASES = R.SOLVE_CASES + [(name, N, cross, (), segment, None) for name, N, cross, segment, _ in R.LARGE_SOLVE_CASES]
+LARGE_PLANS = {c[0]: c[4] for c in R.LARGE_SOLVE_CASES}
+
+
+@pytest.mark.parametrize("case", PLAN_CASES, ids=[c[0] for c in PLAN_CASES])
 def test_plan_of_the_library_is_the_python_plan(pgo, monkeypatch, case):
     name, N, cross, missing, segment, cap = case
     if cap is not None:
         monkeypatch.setenv("IBA_DEBUG_ENV", "1")
         monkeypatch.setenv("IBA_PGO_MAX_SEP", str(cap))
-    g = R.case_graph(N, cross, missing, seed=1)
+    g = R.large_case_graph(name) if name in LARGE_PLANS else R.case_graph(N, cross, missing, seed=1)
     got = pgo.pgo_plan(N, g.edge_tuples(), segment=segment)
     ref = R.plan(N, g.src, g.tgt, segment, cap or R.MAX_SEPARATORS)
     assert got["K"] == ref["K"] and got["separators"].tolist() == ref["separators"] and [tuple(r) for r in got["runs"].tolist()] == ref["runs"]
@@ -135,6 +143,64 @@ def test_plan_of_the_library_is_the_python_plan(pgo, monkeypatch, case):
         assert got["K"] == 2 * segment
     if name == "three_panels_ragged":
         assert 6 * len(got["separators"]) == 108
+    if name in LARGE_PLANS:
+        assert dict(K=got["K"], separators=len(got["separators"]), runs=len(got["runs"])) == LARGE_PLANS[name]
+    if name == "at_the_cap":          # K stays, no run is left, n = kMaxSepDim
+        assert got["K"] == segment and len(got["separators"]) == R.MAX_SEPARATORS and 6 * len(got["separators"]) == 6144
+    if name == "one_past_the_cap":
+        assert got["K"] == 2 * segment and all(a == b for a, b in got["runs"].tolist())
+    if name == "k_doubles_twice":
+        assert got["K"] == 4 * segment
+    if name == "rows_and_back_second_block":
+        ns, runs = len(got["separators"]), [tuple(r) for r in got["runs"].tolist()]
+        assert 6 * ns - 48 > 256 and ns > 64 and len(runs) > 64
+        assert sorted(b - a + 1 for a, b in runs[:4]) == [1, 1, 2, 3]                            # one forward block steps runs of three lengths
+        assert {7, 8, 101, 102} <= set(got["separators"].tolist())                              # adjacent separators: no run between them
+        assert [k // 4 for k, (a, b) in enumerate(runs) if a in (22, 149, 151)] == [1, 10, 10]   # (150, 21) reaches across forward blocks
+
+
+def _solve_figures(N, cross, missing):
+    g = R.case_graph(N, cross, missing, seed=1)
+    lin = R.linearize(g.nodes, g, np.ones(g.E))
+    H, b = R.dense_system(N, g, lin["A"], lin["b"])
+    return g, lin, H, b
+
+
+def _rel_residual(H, b, lam, delta):
+    """the figure of tests/test_gpu_pgo.py's solve gate, from the dense H"""
+    Hl, bl, dl = H.astype(np.longdouble), b.astype(np.longdouble), np.asarray(delta, np.longdouble).reshape(-1)
+    r = Hl @ dl + np.longdouble(lam) * dl - bl
+    nb = float(np.sqrt(np.sum(bl * bl)))
+    return float(np.sqrt(np.sum(r * r))) / nb if nb > 0 else float(np.sqrt(np.sum(r * r)))
+
+
+@pytest.mark.parametrize("case", R.SOLVE_CASES, ids=[c[0] for c in R.SOLVE_CASES])
+def test_sparse_system_is_the_dense_system_and_block_residual_its_figure(case):
+    """the sparse H equals the dense one entry for entry; block_residual gives _rel_residual's figure (both long double: they differ by the order
+    of a node's sum, 1e-3 relative is far outside that), on the dense solve and on a vector that is no solution"""
+    name, N, cross, missing, _, _ = case
+    g, lin, H, b = _solve_figures(N, cross, missing)
+    Hs = R.sparse_system(N, g, lin["A"])
+    assert Hs.format == "csc" and Hs.shape == H.shape and np.array_equal(Hs.toarray(), H)
+    rng = np.random.default_rng(N)
+    for lam in (1e-5 * float(np.max(np.diag(H))), 1.0, 1e6):
+        if g.E == 0 and lam == 0.0:
+            continue
+        for delta in (R.dense_solve(H, b, lam), rng.normal(size=6 * N)):
+            want, got = _rel_residual(H, b, lam, delta), R.block_residual(N, g, lin["A"], lin["b"], lam, delta)
+            assert abs(got - want) <= 1e-3 * want, (name, lam, got, want)
+
+
+def test_sparse_solve_is_as_good_as_the_dense_solve():
+    """what lets the margin of the dense gate carry over to the sparse reference: on case_graph(240), for the three lambdas of the solve gate, the
+    figures of the two solves are within a factor 2 of each other"""
+    g, lin, H, b = _solve_figures(240, (), ())
+    Hs = R.sparse_system(240, g, lin["A"])
+    for lam in (1e-5 * float(np.max(np.diag(H))), 1.0, 1e6):
+        sparse = R.block_residual(240, g, lin["A"], lin["b"], lam, R.sparse_solve(Hs, b, lam))
+        dense = R.block_residual(240, g, lin["A"], lin["b"], lam, R.dense_solve(H, b, lam))
+        print("pgo-figures sparse_vs_dense lam=%.6g sparse=%.3e dense=%.3e" % (lam, sparse, dense))
+        assert 0.5 * dense <= sparse <= 2.0 * dense, (lam, sparse, dense)
 
 
 def test_plan_refuses_cross_edges_beyond_the_cap(pgo, monkeypatch):

@@ -125,6 +125,24 @@ def test_the_issues_prototype_shapes_converge_and_turn_the_false_loop_off():
         assert res["F"] < S.linearize(g.nodes, g)["F"]
 
 
+@pytest.mark.parametrize("cross,prior_node", [((), 0), (((10, 13), (29, 3), (10, 13)), 5)])
+def test_sparse_twins_are_the_dense_system_and_its_figure(cross, prior_node):
+    """the sparse H (the prior's 1e12 diagonal in it) equals the dense one entry for entry; block_residual is the device tests' _rel_residual to 1e-3
+    (the pins of tests/test_pgo_cpu.py, on the smoother's factors); the figures of the sparse and the dense solve are printed side by side"""
+    g = S.case_graph(40, cross=cross, seed=1, prior_node=prior_node)
+    lin = S.linearize(g.nodes, g)
+    H, b = S.dense_system(g.N, g, lin["A"], lin["b"])
+    Hs = S.sparse_system(g.N, g, lin["A"])
+    assert Hs.shape == H.shape and np.array_equal(Hs.toarray(), H)
+    Hl, bl = H.astype(np.longdouble), b.astype(np.longdouble)
+    fig = lambda lam, d: float(np.sqrt(np.sum((Hl @ d.astype(np.longdouble) + np.longdouble(lam) * d.astype(np.longdouble) - bl) ** 2)) / np.sqrt(np.sum(bl * bl)))
+    for lam in (1e-5 * lin["max_diag_between"], 1.0, 1e6):
+        dense, sparse = S.dense_solve(H, b, lam), S.sparse_solve(Hs, b, lam)
+        for d in (dense, sparse, np.random.default_rng(2).normal(size=6 * g.N)):
+            assert abs(S.block_residual(g.N, g, lin["A"], lin["b"], lam, d) - fig(lam, d)) <= 1e-3 * fig(lam, d)
+        print("smooth-figures sparse_vs_dense lam=%.6g sparse=%.3e dense=%.3e" % (lam, fig(lam, sparse), fig(lam, dense)))
+
+
 # ---- the C ABI without a device ----
 @pytest.fixture(scope="module")
 def sm(pkg):
