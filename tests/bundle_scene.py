@@ -1,5 +1,7 @@
 """Seeded scenes for the bundle adjustment's tests: cameras on an arc looking at a point cloud, float32 observations with pixel noise scaled by the
 pyramid level, planted gross outliers, a chosen visibility pattern, and an "exact" variant in the manner of pose_scene.exact_scene."""
+import functools
+
 import numpy as np
 
 import bundle_ref as R
@@ -200,6 +202,62 @@ def scenes():
             make(12, 20, 9, n_fixed=1, visibility=0.5), exact_scene(4, 40, 10)]
 
 
+# ---- eight tiny scenes for the calls of more jobs than workgroups: cheap references, and jobs that finish at different steps ----
+TINY_TRIALS = ([5, 10], [5, 10], [7, 13], [5, 10], [5, 1], [5, 10], [1, 1], [5, 12])      # of the two rounds under R.LOCAL, from the reference
+
+
+@functools.lru_cache(maxsize=None)
+def tiny_scenes():
+    return (make(2, 6, 900), make(3, 9, 901, n_fixed=1), make(2, 8, 902, outliers=0.3), make(4, 5, 903, n_fixed=2, visibility=0.7), make(2, 1, 904),
+            make(3, 12, 905, n_fixed=0), make(2, 0, 906), make(5, 10, 907, n_fixed=1, visibility=0.6))
+
+
+@functools.lru_cache(maxsize=None)
+def tiny_reference():
+    """the reference's outputs of tiny_scenes() under R.LOCAL -> (with the stages, without them): computed once, shared, never written to"""
+    both = [R.optimize(ref_job(sc)) for sc in tiny_scenes()]
+    return tuple(R.with_stages(out, extras) for out, extras in both), tuple(out for out, _ in both)
+
+
+def check_tiny_reference():
+    """the trial counts the reference itself must give: the eight jobs ask for different numbers of steps; scene 2 has rejected trials (more trials
+    than iterations). Which two of them one workgroup takes is the order's business: check_second_trip"""
+    plain = [dict(out) for out in tiny_reference()[1]]
+    assert [d["trials"][:2].tolist() for d in plain] == [list(t) for t in TINY_TRIALS], [d["trials"][:2].tolist() for d in plain]
+    assert plain[2]["lm_iterations"][:2].tolist() == [5, 8]
+    assert len({sum(t) for t in TINY_TRIALS}) >= 5
+
+
+def cycle_of_tiny(n):
+    """the indices into tiny_scenes() of a call of n jobs: scene k % 8, and scene 0 again as the last. Where a grid of g workgroups (g a multiple of
+    8) walks the jobs with a stride of g, a workgroup's second job is then the SAME scene as its first: both finish at one step"""
+    return [k % 8 for k in range(n - 1)] + [0]
+
+
+def shifted_cycle_of_tiny(n, grid, shift=3):
+    """cycle_of_tiny with the scenes of the jobs from `grid` on moved on by `shift`: workgroup w of a grid of `grid` then takes scene w % 8 and, on its
+    second trip, scene (w + shift) % 8, which asks for another number of steps; all eight scenes still make the second trip, and the last job is
+    still scene 0"""
+    return [(k % 8 if k < grid else (k + shift) % 8) for k in range(n - 1)] + [0]
+
+
+def check_second_trip(order, grid, differ):
+    """on the references: the jobs grid..grid + 7 are the eight scenes; differ: among the workgroups that take two jobs there is one whose first job
+    needs fewer trials than its second (it is done while the second still runs) and one whose first needs more; else: each takes one scene twice"""
+    total = [sum(t) for t in TINY_TRIALS]
+    first, second = [total[order[w]] for w in range(len(order) - grid)], [total[k] for k in order[grid:]]
+    assert sorted(order[grid:grid + 8]) == list(range(8)) and order[0] == order[-1] == 0
+    if differ:
+        assert any(a < b for a, b in zip(first, second)) and any(a > b for a, b in zip(first, second)), (first, second)
+    else:
+        assert order[grid:] == order[:len(order) - grid]
+
+
+def without_stages(entries):
+    """the entries of an everything() list that a call without keep_stages has too"""
+    return [(k, v) for k, v in entries if not k.startswith("stage")]
+
+
 # ---- the linear algebra against a long-double dense solve of the FULL damped system ----
 def gate_share(dev, own, truth):
     """the gate of tests/test_gpu_pose.py and test_gpu_smooth.py: |device - truth| <= 4 |float64 restatement - truth| + one ulp of the output's scale
@@ -212,6 +270,11 @@ def gate_share(dev, own, truth):
     return float(np.max(np.where(gate > 0, d_dev / np.where(gate > 0, gate, 1), 0))) if truth.size else 0.0
 
 
+def eval_differences(bd, got, own):
+    """the names of the outputs of one job's iba_bundle_eval whose bytes differ from bundle_ref's"""
+    return [k for k in bd.EVAL_FIELDS + ("chi2_robust", "n_reduced", "solved") if np.ascontiguousarray(got[k]).tobytes() != np.ascontiguousarray(own[k]).tobytes()]
+
+
 def check_eval(bd, scs, masks, robust, lam, host, note):
     """iba_bundle_eval (host: iba_debug_bundle_eval_host) of the scenes against bundle_ref byte for byte, then under the gate against long double"""
     got = bd.evaluate([lib_job(bd, sc) for sc in scs], active=masks, robust=robust, lam=lam, host=host)
@@ -219,8 +282,7 @@ def check_eval(bd, scs, masks, robust, lam, host, note):
         q = ref_job(sc)
         m = None if masks is None else masks[j]
         own = R.evaluate(q, m, robust, lam)
-        for k in bd.EVAL_FIELDS + ("chi2_robust", "n_reduced", "solved"):
-            assert np.ascontiguousarray(got[j][k]).tobytes() == np.ascontiguousarray(own[k]).tobytes(), (j, k)
+        assert eval_differences(bd, got[j], own) == [], j
         if not all(np.isfinite(own[k]).all() for k in bd.EVAL_FIELDS) or not own["solved"]:
             continue                                      # this gate only; the bytes above were compared
         truth = R.full_system_longdouble(q, m, robust, lam)

@@ -39,6 +39,36 @@ def test_host_equals_reference(bd, opt):
         assert R.differences(res.everything(j), want) == [], j
 
 
+@pytest.mark.parametrize("opt", [dict(R.LOCAL), R.global_options(20, True)], ids=["local", "global-robust"])
+def test_host_without_stages_equals_reference(bd, err, opt):
+    """keep_stages = 0, the calls' default: the same outputs, no stage entry, and iba_bundle_stage refuses"""
+    scs = S.scenes()
+    res = bd.optimize_host([S.lib_job(bd, sc) for sc in scs], S.lib_options(bd, opt, keep_stages=0))
+    kept = bd.optimize_host([S.lib_job(bd, sc) for sc in scs], S.lib_options(bd, opt))
+    assert len(res) == len(scs) and res.big_steps == 0
+    for j, sc in enumerate(scs):
+        want, _ = S.ref_of(sc, stages=False, **opt)
+        got = res.everything(j)
+        assert not any(k.startswith("stage") for k, _ in got) and R.differences(got, want) == [], j
+        assert R.differences(got, S.without_stages(kept.everything(j))) == [], j
+    with pytest.raises(err, match="keep_stages"):
+        res.stage(0, 0)
+
+
+def test_host_tiny_scenes_twice_in_one_call(bd):
+    """the eight tiny scenes that the device's call of more jobs than workgroups cycles through, each twice in one call of 16 jobs, with and without
+    the stages: the restatement that test leans on, and the trial counts that make its jobs finish at different steps"""
+    S.check_tiny_reference()
+    kept, plain = S.tiny_reference()
+    print("the eight tiny jobs, trials per round: " + ", ".join(str(dict(e)["trials"][:2].tolist()) for e in plain))
+    jobs = [S.lib_job(bd, S.tiny_scenes()[k % 8]) for k in range(16)]
+    for keep, refs in ((1, kept), (0, plain)):
+        res = bd.optimize_host(jobs, S.lib_options(bd, R.LOCAL, keep_stages=keep))
+        assert len(res) == 16 and res.big_steps == 0
+        for j in range(16):
+            assert R.differences(res.everything(j), refs[j % 8]) == [], (keep, j)
+
+
 def test_exact_scene_comes_back(bd):
     sc = S.exact_scene(4, 40, 10)
     res = bd.optimize_host([S.lib_job(bd, sc)], S.lib_options(bd, R.global_options(30, False)))

@@ -1,7 +1,10 @@
 """Bundle adjustment on the device (include/iba_mi355x.h, iba_bundle*): iba_bundle_eval and iba_bundle_optimize BYTE FOR BYTE against the numpy
 restatement tests/bundle_ref.py (with keep_stages, so a mismatch names its round) and against the host restatement iba_debug_bundle_host, at the
 smallest shapes at which each rule can go wrong; the step and the sums under the project's gate against a long-double dense solve of the full damped
-system; the same bytes alone, inside a ragged batch, split into chunks and on a second call; the composition with iba_twoview_init; every error."""
+system; the same bytes alone, inside a ragged batch, split into chunks and on a second call; the composition with iba_twoview_init; every error.
+The calls' default, keep_stages = 0 (stage tables of length 0, other chunk cuts), runs against the same references, and a call of 4105 tiny jobs takes
+front_kernel and solve_kernel round their grid of 4096 workgroups a second time and back_kernel past its first block."""
+import functools
 import importlib
 
 import numpy as np
@@ -73,8 +76,42 @@ def ragged_scenes():
 
 @pytest.fixture(scope="module")
 def ragged():
+    return ragged_references()[:2]
+
+
+@functools.lru_cache(maxsize=None)
+def ragged_references():
+    """-> (the scenes, S.ref_of(sc)[0], S.ref_of(sc, stages=False)[0]) from ONE run of the reference per scene: the first is the second with the
+    stages of the same run appended, which is all that S.ref_of does"""
     scs = ragged_scenes()
-    return scs, [S.ref_of(sc)[0] for sc in scs]
+    plain = [S.ref_of(sc, stages=False) for sc in scs]
+    return scs, [R.with_stages(out, extras) for out, extras in plain], [out for out, _ in plain]
+
+
+@pytest.fixture(scope="module")
+def ragged_plain():
+    return ragged_references()[2]
+
+
+def run_plain(bd, err, scs, opt, refs=None, kept=None):
+    """keep_stages = 0, the calls' default, on the device and through the host restatement: every output against the reference without its stage
+    entries, against the host, and against the entries of the same names of a call that kept the stages; iba_bundle_stage refuses"""
+    refs = [S.ref_of(sc, stages=False, **opt)[0] for sc in scs] if refs is None else refs
+    jobs = [S.lib_job(bd, sc) for sc in scs]
+    o = S.lib_options(bd, opt, keep_stages=0)
+    d, h = bd.optimize(jobs, o), bd.optimize_host(jobs, o)
+    assert len(d) == len(scs) and d.big_steps == 0
+    for j, e in enumerate(refs):
+        got = d.everything(j)
+        assert not any(k.startswith("stage") for k, _ in e) and R.differences(got, e) == [], j
+        assert R.differences(got, h.everything(j)) == [], j
+        if kept is not None:
+            assert R.differences(got, S.without_stages(kept.everything(j))) == [], j
+    for res in (d, h):
+        with pytest.raises(err, match="keep_stages"):
+            res.stage(0, 0)
+    h.close()
+    return d
 
 
 def run_both(bd, scs, opt, refs=None):
@@ -214,6 +251,97 @@ def test_same_bytes_alone_in_a_batch_split_and_repeated(bd, ragged, debug_env):
     c = run_both(bd, scs, R.LOCAL, refs)                   # a second call
     assert c.chunks == 1
     c.close()
+
+
+# ---- keep_stages = 0, the calls' default ----
+def test_optimize_ragged_batch_without_stages(bd, err, ragged, ragged_plain):
+    scs, _ = ragged
+    kept = bd.optimize([S.lib_job(bd, sc) for sc in scs], S.lib_options(bd, R.LOCAL))
+    d = run_plain(bd, err, scs, R.LOCAL, ragged_plain, kept)
+    assert d.chunks == 1 and kept.chunks == 1
+    d.close()
+    kept.close()
+
+
+def test_optimize_the_cap_of_64_free_cameras_without_stages(bd, err):
+    scs = [S.make(65, 14, 300, n_fixed=1, visibility=0.5), S.make(12, 30, 301, n_fixed=1, visibility=0.6)]
+    opt = R.global_options(3, True)
+    kept = bd.optimize([S.lib_job(bd, sc) for sc in scs], S.lib_options(bd, opt))
+    run_plain(bd, err, scs, opt, kept=kept).close()
+    kept.close()
+
+
+def test_same_bytes_split_into_chunks_without_stages(bd, err, ragged, ragged_plain, debug_env):
+    """the budgets of test_same_bytes_alone_in_a_batch_split_and_repeated. Without the stage tables a job costs less, so the chunk cuts fall elsewhere;
+    the middle budget is three median jobs at 222 bytes per edge, the edge term of job_bytes without them (4 x 5 + 12 + 1 + 1 + 4 + 8 x 23)"""
+    scs, _ = ragged
+    alone = bd.optimize([S.lib_job(bd, scs[3])], S.lib_options(bd, R.LOCAL, keep_stages=0))
+    assert R.differences(alone.everything(0), ragged_plain[3]) == []
+    alone.close()
+    debug_env(IBA_BUNDLE_BUDGET=1)                        # every job a chunk of its own
+    a = run_plain(bd, err, scs[:8], R.LOCAL, ragged_plain[:8])
+    assert a.chunks == 8
+    a.close()
+    sizes = sorted(len(sc["edge_point"]) for sc in scs)
+    debug_env(IBA_BUNDLE_BUDGET=3 * 222 * sizes[len(sizes) // 2])
+    b = run_plain(bd, err, scs, R.LOCAL, ragged_plain)
+    print("chunks of the 40 ragged jobs without stages at three median jobs a chunk:", b.chunks)
+    assert 1 < b.chunks < len(scs)
+    b.close()
+    debug_env(IBA_BUNDLE_BUDGET=1 << 30)
+    c = run_plain(bd, err, scs, R.LOCAL, ragged_plain)     # a second call
+    assert c.chunks == 1
+    c.close()
+
+
+# ---- more jobs than workgroups ----
+MAX_GRID = 4096      # kMaxGrid of csrc/iba_bundle_kernels.hpp
+MANY = 4105          # front_kernel and solve_kernel run on min(n_jobs, 4096) workgroups: the first 9 take a second job; back_kernel: 17 blocks of 256 lanes
+
+
+@pytest.mark.parametrize("shifted", [False, True], ids=["cycle", "shifted"])
+def test_optimize_more_jobs_than_workgroups(bd, shifted):
+    """4105 jobs under the local schedule, the eight tiny scenes in turn and scene 0 once more as the last job: all eight make the second trip of a
+    workgroup (jobs 4096..4103). front_kernel and solve_kernel give job j to workgroup j % 4096, and 4096 is a multiple of 8, so in the plain cycle a
+    workgroup's two jobs are one scene and finish at one step. The shifted order moves the scenes of the second trip on by three: there a workgroup's
+    first job is done (kind == kDone, or no proposal for the solve) while its second still runs, and in another workgroup the other way round. Every
+    output and stage of every job against the reference and the host restatement, then the same call without the stages"""
+    S.check_tiny_reference()
+    order = S.shifted_cycle_of_tiny(MANY, MAX_GRID) if shifted else S.cycle_of_tiny(MANY)
+    assert len(order) == MANY > MAX_GRID and (MANY + 255) // 256 == 17 and MAX_GRID % 8 == 0 and order[:MAX_GRID] == S.cycle_of_tiny(MANY)[:MAX_GRID]
+    S.check_second_trip(order, MAX_GRID, differ=shifted)
+    tiny = [S.lib_job(bd, sc) for sc in S.tiny_scenes()]
+    jobs = [tiny[k] for k in order]
+    for keep, refs in zip((1, 0), S.tiny_reference()):
+        o = S.lib_options(bd, R.LOCAL, keep_stages=keep)
+        d, h = bd.optimize(jobs, o), bd.optimize_host(jobs, o)
+        assert len(d) == MANY and d.big_steps == 0 and d.chunks == 1
+        first = d.everything(0)
+        assert len(first) == (15 if keep else 11)
+        for j, k in enumerate(order):
+            got = d.everything(j)
+            assert R.differences(got, refs[k]) == [], (keep, j)
+            assert R.differences(got, h.everything(j)) == [], (keep, j)
+        assert R.differences(d.everything(MANY - 1), first) == []
+        d.close()
+        h.close()
+
+
+def test_eval_more_jobs_than_workgroups(bd):
+    """iba_bundle_eval goes through the same front_kernel and solve_kernel with o.eval set: 4105 jobs, the byte comparison of S.check_eval on every one.
+    iba_bundle_eval reports no chunk count. The jobs run as ONE chunk, so that workgroups do take a second job: job_bytes of an evaluation is that of
+    an optimisation without stages plus 8 bytes per edge (at most 36 edges: 288), less than the stage term of 4 x 8 x (12 cameras + 3 points) >= 768
+    that test_optimize_more_jobs_than_workgroups pays for the same jobs, and that call asserts chunks == 1 under the same budget"""
+    order = S.cycle_of_tiny(MANY)
+    S.check_second_trip(order, MAX_GRID, differ=False)    # an evaluation has no early finish: a workgroup's two jobs may be one scene
+    tiny = [S.lib_job(bd, sc) for sc in S.tiny_scenes()]
+    for robust, lam in ((True, 1e-3), (False, 10.0)):
+        own = [R.evaluate(S.ref_job(sc), None, robust, lam) for sc in S.tiny_scenes()]
+        assert sum(e["solved"] for e in own) >= 6
+        got = bd.evaluate([tiny[k] for k in order], robust=robust, lam=lam)
+        assert len(got) == MANY
+        for j, k in enumerate(order):
+            assert S.eval_differences(bd, got[j], own[k]) == [], (robust, lam, j)
 
 
 def test_composition_with_twoview_init(bd):

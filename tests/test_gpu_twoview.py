@@ -2,7 +2,8 @@
 restatement tests/twoview_ref.py, with keep_stages = 1 so that a mismatch names its stage; parallax_deg within one float32 ulp (acos is libm's).
 The scene list runs in ONE call of 70 iterations (iterations is an option of the call, so the pair with 200 iterations' worth of sets is a call of
 its own); the lane and wave edges of every kernel, repeated pairs, a hypothesis made singular on purpose, the host
-restatement and the composition with iba_orb_match follow."""
+restatement and the composition with iba_orb_match follow. The calls' default, keep_stages = 0, takes a kernel and a read-back of its own: the scene
+list, the gather's block edge, the chunk cuts and a call of 73 pairs (more than one block of the one-lane-per-pair kernels) run that way too."""
 import importlib
 
 import numpy as np
@@ -22,6 +23,11 @@ F = np.float32
 def tv():
     importlib.import_module(PKG)
     return importlib.import_module(PKG + ".twoview")
+
+
+@pytest.fixture(scope="module")
+def err():
+    return importlib.import_module(PKG).IbaError
 
 
 def lib_pair(tv, p):
@@ -115,6 +121,108 @@ def test_chunk_boundaries_change_no_byte(tv, monkeypatch):
         got = [r.read(b)["parallax_deg"].tobytes() for b in range(5)]
         assert parallax is None or got == parallax, budget
         parallax = got
+        r.close()
+
+
+# ---- keep_stages left at its default of 0: tv_gather_kernel, the sel_* arrays at m_base offsets, and the branch of run_chunk that reads them ----
+def run_plain(tv, pairs, iterations, refs):
+    """the device result WITHOUT stages against the reference of every pair: 0 differing bytes in every output -> the result"""
+    r = tv.init([lib_pair(tv, p) for p in pairs], iterations=iterations)
+    assert len(r) == len(refs)
+    for b, e in enumerate(refs):
+        assert S.differences(r, b, e, stages=False) == [], "pair %d (%s)" % (b, R_NAMES[e["status"]])
+    assert r.sweep_cap_hits == sum(e["sweep_cap_hits"] for e in refs)
+    return r
+
+
+def test_scene_list_without_stages(tv, err):
+    pairs, refs = S.scene_pairs(), S.scene_reference()
+    # the three ways through the branch: the gather runs (a candidate was named), the pair stopped before a candidate, the pair never reached the device
+    assert any(e["status"] in (R.OK, R.LOW_PARALLAX) and e["chosen"] >= 0 for e in refs)
+    assert any(e["status"] in (R.NO_CLEAR_WINNER, R.H_DEGENERATE, R.NO_MODEL) and e["chosen"] == -1 for e in refs)
+    assert any(e["n_matches"] < 8 for e in refs)
+    r = run_plain(tv, pairs, S.ITERATIONS, refs)
+    kept = tv.init([lib_pair(tv, p) for p in pairs], iterations=S.ITERATIONS, keep_stages=1)
+    for b in range(len(pairs)):
+        assert S.output_bytes(r, b) == S.output_bytes(kept, b), b          # parallax_deg too: one libm on one machine
+        for fn in (lambda: r.iterations_of(b), lambda: r.hypothesis(b, 0)):
+            with pytest.raises(err, match="keep_stages"):
+                fn()
+    kept.close()
+    r.close()
+
+
+def test_gather_block_and_wave_edges_without_stages(tv):
+    """the pairs of test_lane_and_wave_edges at 65 iterations: the N = 257 pair is accepted and its last match is a good point of the candidate, so the
+    gather's second block of 256 lanes writes a point that is read; it is the sixth pair of the call, so its m_base is not 0"""
+    sizes = (8, 9, 63, 64, 65, 257, 40)
+    pairs = [exact_pair(N, 20 + N, 65, outliers=0.0, noise=0.1) for N in sizes]
+    refs = [S.reference(p, 65) for p in pairs]
+    big = refs[sizes.index(257)]
+    assert sizes.index(257) > 0 and big["chosen"] >= 0 and big["status"] == R.OK and big["hyp_verdict"][big["chosen"]][256] == 6
+    assert big["points"][big["list"][256, 0]].any() and big["triangulated"][big["list"][256, 0]] == 1
+    assert sum(e["status"] == R.OK for e in refs) >= 3 and any(e["chosen"] == -1 for e in refs)
+    run_plain(tv, pairs, 65, refs).close()
+
+
+def test_chunk_boundaries_change_no_byte_without_stages(tv, monkeypatch):
+    """test_chunk_boundaries_change_no_byte with keep_stages at its default; then a call all of whose pairs have fewer than 8 matches: every chunk
+    returns before anything is queued"""
+    five = [S.scene_pairs()[k] for k in (0, 1, 3, 6, 2)]
+    refs = [S.scene_reference()[k] for k in (0, 1, 3, 6, 2)]
+    cost = sorted(187 * S.n_matches(p) + 148 * S.ITERATIONS for p in five)
+    between = cost[0] + cost[1] + 2 * 2048
+    assert between < sum(cost)
+    first = None
+    for budget, want in ((None, lambda c: c == 1), ("1", lambda c: c == 5), (str(between), lambda c: 1 < c < 5)):
+        if budget is not None:
+            monkeypatch.setenv("IBA_TWOVIEW_BUDGET", budget)
+        r = run_plain(tv, five, S.ITERATIONS, refs)
+        if budget is not None:
+            monkeypatch.delenv("IBA_TWOVIEW_BUDGET")
+        print("chunks without stages at budget %s: %d" % (budget, r.chunks))
+        assert want(r.chunks), (budget, r.chunks)
+        got = [S.output_bytes(r, b) for b in range(5)]
+        assert first is None or got == first, budget
+        first = got
+        r.close()
+    few = [S.make_pair(6, n=9, unmatched=0.5, outliers=0.0), {"xy1": np.zeros((0, 2), F), "xy2": np.zeros((5, 2), F), "matches12": np.zeros(0, np.int32), "K": S.K4},
+           S.make_pair(8, n=7, unmatched=0.0)]
+    assert all(S.n_matches(p) < 8 for p in few) and S.n_matches(few[2]) == 7
+    few_refs = [R.twoview(p["xy1"], p["xy2"], p["matches12"], p["K"], None, iterations=S.ITERATIONS) for p in few]
+    assert all(e["status"] == R.TOO_FEW_MATCHES for e in few_refs)
+    for budget in (None, "1"):
+        if budget is not None:
+            monkeypatch.setenv("IBA_TWOVIEW_BUDGET", budget)
+        r = run_plain(tv, few, S.ITERATIONS, few_refs)
+        if budget is not None:
+            monkeypatch.delenv("IBA_TWOVIEW_BUDGET")
+        assert r.chunks == (1 if budget is None else 3)
+        r.close()
+
+
+def test_more_pairs_than_one_block_of_lanes(tv):
+    """73 pairs at 9 iterations: tv_motion_kernel and tv_accept_kernel give one lane to a pair in blocks of 64, so the second block runs with 9 of its
+    lanes in use. The eight small pairs cycle and pair 0 comes once more as the last: an accepted pair, a pair refused by the acceptance and a pair
+    below 8 matches stand on both sides of index 64"""
+    S.check_small_reference()
+    order = S.cycle_of_small(73)
+    assert len(order) == 73 and order[72] == 0 and order[64:72] == list(range(8))
+    small = [lib_pair(tv, p) for p in S.small_pairs()]
+    refs = [S.small_reference()[k] for k in order]
+    for keep in (1, 0):
+        r = tv.init([small[k] for k in order], iterations=S.SMALL_ITERATIONS, keep_stages=keep)
+        assert len(r) == 73 and r.chunks == 1
+        for b, e in enumerate(refs):
+            assert S.differences(r, b, e, stages=bool(keep)) == [], (keep, b, R_NAMES[e["status"]])
+        assert r.sweep_cap_hits == sum(e["sweep_cap_hits"] for e in refs)
+        assert S.output_bytes(r, 0) == S.output_bytes(r, 72)
+        if keep:
+            for k, x in r.iterations_of(0).items():
+                assert x.tobytes() == r.iterations_of(72)[k].tobytes(), k
+            for hyp in range(8):
+                x, y = r.hypothesis(0, hyp), r.hypothesis(72, hyp)
+                assert all(np.asarray(x[k]).tobytes() == np.asarray(y[k]).tobytes() for k in x), hyp
         r.close()
 
 

@@ -261,6 +261,35 @@ def test_host_restatement_equals_reference(tv):
     r.close()
 
 
+def test_small_pairs_on_the_host(tv):
+    """the eight small pairs that the device's call of 73 pairs cycles through: what the reference says of them, and the host restatement against it
+    with and without the stages"""
+    S.check_small_reference()
+    print("the eight small pairs: " + ", ".join("N = %d %s" % (e["n_matches"], tv.STATUS_NAMES[e["status"]]) for e in S.small_reference()))
+    pairs = [lib_pair(tv, p) for p in S.small_pairs()]
+    for keep in (1, 0):
+        r = tv.init_host(pairs, iterations=S.SMALL_ITERATIONS, keep_stages=keep)
+        for b, e in enumerate(S.small_reference()):
+            assert S.differences(r, b, e, stages=bool(keep)) == [], (keep, b)
+        assert r.sweep_cap_hits == sum(e["sweep_cap_hits"] for e in S.small_reference())
+        r.close()
+
+
+def test_cosine_above_one_gives_nan_parallax(tv):
+    """a planar pair two of whose hypotheses have a 51st cosine of 1 + 2^-23: acos is NaN there in the library and in the reference alike (math.acos
+    alone would raise), the chosen hypothesis is another one and the pair is accepted"""
+    p = S.with_sets(S.make_pair(2, n=64, planar=True, unmatched=0.0, outliers=0.0), 9, 2)
+    e = S.reference(p, 9)
+    above = e["cos_parallax"] > 1
+    assert above.any() and np.isnan(e["parallax_deg"][above]).all() and not np.isnan(e["parallax_deg"][~above]).any()
+    assert e["status"] == R.OK and not above[e["chosen"]]
+    for keep in (1, 0):
+        r = tv.init_host([lib_pair(tv, p)], iterations=9, keep_stages=keep)
+        assert S.differences(r, 0, e, stages=bool(keep)) == [], keep
+        assert np.array_equal(np.isnan(r.read(0)["parallax_deg"]), np.isnan(e["parallax_deg"]))
+        r.close()
+
+
 def test_host_options_reach_the_rules(tv):
     p = S.scene_pairs()[0]
     for opts in (dict(sigma=0.5), dict(min_parallax_deg=30.0), dict(min_triangulated=250), dict(rh_threshold=0.01)):

@@ -414,7 +414,9 @@ def accept_h(n_good, N, min_tri):
 
 
 def parallax_deg(c):
-    return f32(math.acos(float(c)) * 180 / math.pi)
+    """a 51st cosine may round to the float32 above 1: acos is NaN there, as libm's is in the library, where math.acos would raise"""
+    c = float(c)
+    return f32(math.acos(c) * 180 / math.pi) if -1.0 <= c <= 1.0 else f32(np.nan)
 
 
 # ---- the whole of one pair ----

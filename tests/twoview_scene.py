@@ -89,6 +89,59 @@ def scene_reference(iterations=ITERATIONS):
     return tuple(reference(p, iterations) for p in scene_pairs(iterations))
 
 
+# ---- eight small pairs for the calls of more pairs than one block of lanes: cheap references, every way through the acceptance ----
+SMALL_ITERATIONS = 9
+# (the status the reference must give, make_pair's arguments; the sets' seed is the pair's). The seeds were picked by running the reference alone.
+SMALL = (
+    (ref.OK, dict(seed=5, n=64, noise=0.1)),                                   # F, accepted
+    (ref.TOO_FEW_POINTS, dict(seed=1, n=8, noise=0.1)),                        # F, refused by the acceptance: no candidate
+    (ref.LOW_PARALLAX, dict(seed=1, n=60, baseline=0.12, noise=0.05)),         # F, a candidate, refused on its parallax
+    (ref.OK, dict(seed=1, n=64, planar=True)),                                 # H, eight hypotheses, accepted
+    (ref.TOO_FEW_POINTS, dict(seed=4, n=40, noise=0.1)),
+    (ref.OK, dict(seed=2, n=56, noise=0.1)),
+    (ref.NO_CLEAR_WINNER, dict(seed=1, n=60, baseline=0.05, noise=0.02)),      # H, no candidate
+    (ref.TOO_FEW_MATCHES, dict(seed=6, n=9, unmatched=0.5)),                   # N < 8
+)
+
+
+@functools.lru_cache(maxsize=None)
+def small_pairs():
+    return tuple(with_sets(make_pair(**dict(dict(unmatched=0.0, outliers=0.0), **kw)), SMALL_ITERATIONS, kw["seed"]) for _, kw in SMALL)
+
+
+@functools.lru_cache(maxsize=None)
+def small_reference():
+    """the reference's results of small_pairs(): computed once, shared, never written to"""
+    return tuple(reference(p, SMALL_ITERATIONS) for p in small_pairs())
+
+
+def check_small_reference():
+    """what the reference itself must say of the eight: the statuses of SMALL; seven pairs of 8..64 matches and one below 8; an accepted pair, a pair
+    refused by the acceptance and the pair below 8 matches; no parallax so near the threshold that acos' one-ulp freedom could flip a status"""
+    refs = small_reference()
+    assert [e["status"] for e in refs] == [st for st, _ in SMALL], [e["status"] for e in refs]
+    N = [n_matches(p) for p in small_pairs()]
+    assert all(8 <= n <= 64 for n in N[:7]) and min(N[:7]) == 8 and max(N[:7]) == 64 and N[7] < 8, N
+    assert {e["model"] for e in refs if e["status"] == ref.OK} == {0, 1}
+    for e in refs:
+        if e["status"] in (ref.OK, ref.LOW_PARALLAX):
+            assert e["chosen"] >= 0 and abs(float(e["parallax_deg"][e["chosen"]]) - 1.0) > 1e-3
+        else:
+            assert e["chosen"] == -1
+
+
+def cycle_of_small(n):
+    """the indices into small_pairs() of a call of n pairs: pair k % 8, and pair 0 again as the last"""
+    return [k % 8 for k in range(n - 1)] + [0]
+
+
+def output_bytes(res, pair):
+    """the bytes of every output of one pair that does not need keep_stages: read() (parallax_deg too), matches() and points()"""
+    d = res.read(pair)
+    arrays = zip(("list", "inlier", "points", "triangulated"), res.matches(pair) + res.points(pair))
+    return [(k, np.asarray(d[k]).tobytes()) for k in sorted(d)] + [(k, x.tobytes()) for k, x in arrays]
+
+
 # ---- comparing a library result (twoview.Twoview) with a reference dict: every output and kept stage, named ----
 SCALARS = ("status", "n_matches", "model", "n_hyp", "chosen", "best_it_H", "best_it_F", "n_inliers_H", "n_inliers_F", "SH", "SF", "RH")
 ARRAYS = ("H21", "F21", "n_good", "cos_parallax", "R21", "t21")
@@ -114,7 +167,8 @@ def differences(res, pair, e, stages=True):
     d = res.read(pair)
     for k in SCALARS + ARRAYS:
         same(k, np.asarray(d[k]), np.asarray(e[k]))
-    far = int((ulp_apart(d["parallax_deg"], e["parallax_deg"]) > 1).sum())
+    both_nan = np.isnan(d["parallax_deg"]) & np.isnan(e["parallax_deg"])          # acos of a cosine above 1: a NaN's sign and payload are the machine's
+    far = int(((ulp_apart(d["parallax_deg"], e["parallax_deg"]) > 1) & ~both_nan).sum())
     if far:
         out.append(("parallax_deg", far))
     lst, inl = res.matches(pair)
