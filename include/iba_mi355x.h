@@ -1168,8 +1168,9 @@ iba_status iba_project_gradient(double zn, uint8_t rgb[3]);                     
  * the reference's OpenCV calls and NOT pinned to recorded OpenCV outputs: O2 resize (cv::resize INTER_LINEAR), O8 blur (GaussianBlur 7 x 7, sigma 2),
  * O4 FAST score (cv::FAST's corner score), O5 the per-cell non-maximum suppression (cv::FAST with nonmaxSuppression), O7 the polynomial arctangent
  * (cv::fastAtan2). O6's tie rule is stated above. The BRIEF test-pair table is an INPUT (256 x 4 int8: x0 y0 x1 y1 per test); the library ships none.
- * Masks, undistortion and ComputeKeyPointsOld are not provided. Windowed matching is iba_orb_match below; the matchers that remain unprovided are
- * SearchByBoW and SearchForTriangulation (they need the DBoW2 vocabulary), Fuse, SearchBySim3, and the SearchByProjection overloads that take a
+ * Masks, undistortion and ComputeKeyPointsOld are not provided. Windowed matching is iba_orb_match below. Of the two vocabulary matchers,
+ * SearchByBoW and SearchForTriangulation, the second is iba_triangulate further below with the DBoW2 node id of every keypoint as an INPUT (it needs
+ * the outcome of the vocabulary, not the vocabulary); SearchByBoW remains unprovided, as do Fuse, SearchBySim3, and the SearchByProjection overloads that take a
  * key frame (the overload that takes map points is iba_map_match further below). Two-view initialisation is iba_twoview_init further below; what Tracking::CreateInitialMapMonocular does after a success
  * (global BA, median-depth scaling) and the >= 100-matches gates around the call are the caller's.
  * DEVICE: one chain per chunk over flat tables (one row per image and level, per 64 x 16 tile, per cell, per keypoint): resize level by level, score,
@@ -1768,6 +1769,180 @@ iba_status iba_map_matches_lists(const iba_map_matches* m, int32_t job, int32_t*
 iba_status iba_map_match_pose_edges(const int32_t* prior_point /* n_kp */, const int32_t* point_of /* n_kp */, const int32_t* points /* n_points */, int32_t n_points,
                                     const float* table_xyz /* P x 3 */, int32_t P, const float* xy /* n_kp x 2 */, const int32_t* octave /* n_kp */, int32_t n_kp,
                                     const float* inv_level_sigma2, int32_t n_levels, float* xyz, float* obs, float* inv_sigma2, int32_t* keypoint_index, int32_t* n);
+
+/*
+ * ---- New-map-point creation [the camera side's seventh brick: the reference's LocalMapping::CreateNewMapPoints (src/orb_slam/src/LocalMapping.cc:
+ * 206-451) with ORBmatcher::SearchForTriangulation (ORBmatcher.cc:657-823), CheckDistEpipolarLine (:140-157) and ComputeF12 (LocalMapping.cc:535-552)] ----
+ * The step that makes the map grow: for a new keyframe and its best covisible neighbours, match the keypoints that have no map point under the
+ * epipolar constraint, triangulate every match and keep the points that pass the parallax, depth, reprojection and scale gates. A call takes F frames
+ * (iba_orb_frame, as iba_orb_match takes them; xy is mvKeysUn), K keyframes (a frame under a pose, with the DBoW2::FeatureVector node of every
+ * keypoint, the has-point bytes and the scene median depth) and J jobs (a current keyframe and its neighbours in the order of
+ * GetBestCovisibilityKeyFrames). Frames and keyframes go up once, however many jobs name them.
+ * THREE FACTS OF THE REFERENCE make every (job, neighbour, keypoint) outcome independent. (1) CreateNewMapPoints builds its matcher as
+ * ORBmatcher matcher(0.6,false): there is no rotation histogram. (2) This reference's SearchForTriangulation never sets vbMatched2: several
+ * keypoints of keyframe 1 may take the same keypoint of keyframe 2, and a query's result does not depend on any other query. (3) The only coupling
+ * between neighbours is that a keypoint of the current keyframe that got a point from neighbour i is skipped for the neighbours > i; both
+ * pKF2->AddMapPoint and mpCurrentKeyFrame->AddMapPoint happen after that neighbour's whole search. Hence the reference's sequential result is "the
+ * first neighbour in order whose outcome is a success", and later successes of the same keypoint are what the reference would never have searched (R7).
+ * JOBS ARE INDEPENDENT: each starts from the has_point bytes as given, even where two jobs name the same keyframe. Whoever wants the reference's
+ * keyframe-after-keyframe sequence makes one call per step and sets the bytes of the created points in between.
+ * Float arithmetic is float32 unless a cast says otherwise, every operation rounded, evaluated left to right, no contraction; tests/triangulate_ref.py
+ * restates every rule in numpy, sequentially as the reference is written (neighbour after neighbour, with a has_point array it updates after each),
+ * and the device and the host restatement (iba_debug_triangulate_host) are compared with it byte for byte. The float decisions are ONE text,
+ * csrc/iba_triangulate_math.hpp. The thresholds are options held as float32; where the reference's literal is a double the option is WIDENED to
+ * double and the comparison made in double (stated per rule; the widened float differs from the double literal by at most 2^-25 relative, so e.g.
+ * a ratio of exactly 0.01f is kept where the reference, comparing against the double 0.01 just above it, skips).
+ *
+ *   R1 pair prologue. Per (job, neighbour). Ow of both keyframes as L1 forms it. baseline = (float)sqrt((b_0^2 + b_1^2) + b_2^2) in double over the
+ *                  float32 differences b = Ow2 - Ow1. The neighbour is skipped, and every slot of it has status PAIR_SKIPPED, where
+ *                  (double)(baseline / median_depth) < (double)min_baseline_ratio (the reference's literal 0.01 is a double; the quotient is
+ *                  float32, correctly rounded). F12 = K1^-T [t12]x R12 K2^-1 with R12 = R1w R2w^T, t12 = -(R12 t2w) + t1w, the 3 x 3 products,
+ *                  inverses and transposes those of csrc/iba_twoview_math.hpp (mul33, mul331, inv33, transpose33: float64 on the widened entries, one
+ *                  rounding per element), associated ((K1^T)^-1 [t12]x) R12) K2^-1. The epipole in image 2, literally: C2 = R2w Ow1 + t2w, invz =
+ *                  1.0f / C2z, ex = fx2 * C2x * invz + cx2, ey = fy2 * C2y * invz + cy2; an epipole that is not finite makes R3's comparison
+ *                  false and gates nothing.
+ *   R2 queries.    The queries are the keypoints of the current keyframe without a point and with node >= 0. The candidates of a query are the
+ *                  keypoints of the neighbour with the same node, in ascending index; one that has a point is walked past. A keypoint that has a
+ *                  point has status HAS_POINT. A query whose node does not occur among the neighbour's keypoints (with or without a point), and a
+ *                  keypoint with node < 0, has status NO_NODE. (The reference walks the nodes ascending and inside a node the keypoints ascending,
+ *                  so the flat node array fixes the whole feature vector; by fact (2) the order of the queries changes nothing.)
+ *   R3 pick.       Walk the candidates in order with bestDist = th_low. A candidate is EXAMINED iff dist <= th_low && dist <= bestDist (dist = the
+ *                  256-bit Hamming distance, M4). It is TAKEN iff it passes two checks. It is not inside the epipole gate: dx = ex - x2, dy = ey -
+ *                  y2, refused where dx * dx + dy * dy < epipole_gate * scale_factors[octave2], in float32. And the epipolar line test: a = x1 *
+ *                  F12_00 + y1 * F12_10 + F12_20, b and c likewise with the second and third column, num = a * x2 + b * y2 + c, den = a * a + b * b,
+ *                  all float32 as written; den == 0 fails; dsqr = num * num / den; passes iff (double)dsqr < (double)chi2_line *
+ *                  (double)level_sigma2[octave2] (the reference's 3.84 is a double). A taken candidate sets bestDist = dist. Because dist > bestDist
+ *                  is what refuses a candidate, AN EQUAL DISTANCE REPLACES. No candidate taken: NO_MATCH.
+ *                  WHY THE WALK IS A MINIMUM. Call a candidate ELIGIBLE iff dist <= th_low and it passes both checks; the checks do not depend on
+ *                  bestDist. Invariant: after any prefix, bestDist is the least distance of the prefix's eligible candidates (th_low where there is
+ *                  none) and the held candidate is the LAST eligible one of the prefix at that distance. A new candidate that is not eligible is
+ *                  either not examined or examined and not taken; nothing changes. An eligible one with dist > bestDist is not examined; it is not
+ *                  a minimum, nothing changes. An eligible one with dist <= bestDist is examined and taken: it is at the new least distance and it
+ *                  is the last so far. So the walk yields the lexicographic minimum of (distance, DESCENDING position) over the eligible
+ *                  candidates, which the device reduces in parallel as the minimum of the key (dist << 32) | (0xFFFFFFFF - position).
+ *   R4 rays.       xn = ((x - cx) * invfx, (y - cy) * invfy, 1) with invfx = 1.0f / fx correctly rounded; ray = Rwc xn (mul331 with the transposed
+ *                  rotation). cos = (float)(dot / (norm1 * norm2)), all in double. The match is triangulated iff cos > 0 && (double)cos <
+ *                  (double)max_cos_parallax (the reference's 0.9998 is a double); otherwise PARALLAX.
+ *   R5 triangulation. The rows of the 4 x 4 matrix A are xn1_0 Tcw1[2] - Tcw1[0], xn1_1 Tcw1[2] - Tcw1[1] and the same two of keyframe 2, in float32,
+ *                  widened to double. The null vector is tv::null_vector<4,4,1,1>, the Jacobi of T9. x[3] == 0, or a quotient that is not finite:
+ *                  DEGENERATE (the library's guard; the reference tests only x[3] == 0). x3D = x[0..2] / x[3], correctly rounded.
+ *   R6 gates, in the reference's order. z_i = (float)(((R_20 X + R_21 Y) + R_22 Z) + t_2) in double (Mat::dot returns double), x_i and y_i likewise.
+ *                  (1) z1 <= 0: DEPTH1. (2) z2 <= 0: DEPTH2. (3) invz = (float)(1.0 / (double)z1), u = fx * x * invz + cx, v = fy * y * invz + cy, err2 =
+ *                  (u - kp_x)^2 + (v - kp_y)^2 in float32; (double)err2 > (double)chi2_mono * (double)level_sigma2[octave1]: REPROJ1 (5.991 is a
+ *                  double). (4) the same in keyframe 2: REPROJ2. (5) dist_i = (float)|x3D - Ow_i| (float32 differences, the norm in double); dist1 ==
+ *                  0 || dist2 == 0: ZERO_DIST. (6) ratioDist = dist2 / dist1, ratioOctave = scale_factors[octave1] / scale_factors[octave2], both
+ *                  correctly rounded, ratioFactor = 1.5f * scale_factor; ratioDist * ratioFactor < ratioOctave || ratioDist > ratioOctave *
+ *                  ratioFactor: SCALE. (7) Otherwise CREATED.
+ *   R7 first neighbour wins. Per keypoint of the current keyframe, the neighbours in order: every slot AFTER the keypoint's first CREATED neighbour
+ *                  is SUPERSEDED, with match -1, dist -1 and xyz zero, whatever its own outcome (a later success, a NO_MATCH, a PAIR_SKIPPED): it is
+ *                  the has-point the reference would have seen. Slots up to and including the first CREATED one keep their outcome.
+ *   R8 the new point. xyz is the triangulated point; desc the current keyframe's descriptor of idx1; normal = (n1 + n2) * 0.5f with n_i,k =
+ *                  (float)((double)(x - Ow_i)_k / |x - Ow_i|), the current keyframe first; max_dist = (float)|x - Ow_1| * scale_factors[octave1];
+ *                  min_dist = max_dist / scale_factors[n_levels - 1], correctly rounded. The created points of a job come in the reference's
+ *                  creation order: neighbour order first, ascending idx1 inside a neighbour.
+ *
+ * OUTPUTS per job: per (neighbour, keypoint of the current keyframe) slot, neighbour-major: status (uint8), match (idx2 or -1), dist (or -1), xyz
+ * (zeros unless R5 produced a point; kept for the refusals of R6). Counts: one per status, and per neighbour n_matches (the reference's nmatches of
+ * that round: the taken slots that are not SUPERSEDED) and n_created. The created points with idx1, the neighbour's position, idx2 and the five
+ * arrays of an iba_map_points table: a caller appends them to its table as they are. With keep_stages the length of every slot's candidate segment.
+ * UNPINNED: the sums of F12, the epipole, the rays and the projections (the reference forms them with OpenCV's float products), cv::norm's
+ * accumulation, cv::SVD against the Jacobi. KNOWN DEVIATIONS: (1) the widened float thresholds, above. (2) The reference's
+ * ComputeDistinctiveDescriptors and the order of the normal sum in UpdateNormalAndDepth follow the pointer order of a std::map<KeyFrame*, size_t>;
+ * R8 fixes both (with two observations at distance d the median rule picks either descriptor: profiles/triangulate_parity.md counts the points
+ * for which the other order would differ). (3) DEGENERATE for a quotient that is not finite.
+ * GUARDS. Under the default options DEGENERATE and ZERO_DIST are guards, as their tests are in the reference: x[3] == 0 needs parallel rays, which
+ * are PARALLAX first, and x3D == Ow_i makes z_i = r_2 . (x3D - Ow_i) zero, which is DEPTH1 / DEPTH2 first. REPROJ2 needs a candidate further than
+ * sqrt(chi2_mono) sigma from the reprojection yet nearer than sqrt(chi2_line) sigma, of the same octave, to the line, and the triangulated point
+ * reprojects between the two. tests/triangulate_scene.py reaches DEGENERATE and REPROJ2 with max_cos_parallax and chi2_line opened, the self-test
+ * ZERO_DIST with a hand-made centre.
+ * NOT PROVIDED: stereo (mvuRight, bOnlyStereo, UnprojectStereo), mbCheckOrientation = true, the CheckNewKeyFrames() early return, the choice of
+ * neighbours, computing the node ids (DBoW2), SearchInNeighbors / Fuse. iba_triangulate_median_depth (host only, pure) is
+ * KeyFrame::ComputeSceneMedianDepth: z = (float)dot + zcw with the dot of the pose's third row and the point in double, sorted ascending, element
+ * (n - 1) / q.
+ * DEVICE (csrc/iba_triangulate_kernels.hpp). The node order of every keyframe - its keypoints with node >= 0 sorted by (node, index) - is a host
+ * sort uploaded with the keyframes: the node array is read on the host for the checks anyway, a keyframe has a few thousand keys, and the sorted
+ * table is then an input like the frames, with no temporary storage and no further library on the device. Per chunk of consecutive jobs over flat
+ * tables: the prologue kernel (one lane per pair, R1); the segment kernel (one lane per slot, blocks that do not straddle a pair; binary search of the
+ * neighbour's sorted keys; writes HAS_POINT, NO_NODE, PAIR_SKIPPED where a slot ends); the pick kernel (W lanes per query, W = 8, 16 or 64: the
+ * query's 256 bits in registers, the lanes stride over the segment and keep their least key, the group minimum by xor shuffles inside the group);
+ * compaction of the matched slots by ballot prefix with one integer atomic per block for the base, and the triangulate kernel, one lane per
+ * matched slot, writing by slot index so that arrival order changes no byte; the resolve kernel, one lane per (job, keypoint), R7; counts by ballot
+ * with integer atomics, a scan over the blocks and the gather of the created points in R8's order. No floating-point atomics, and no result
+ * depends on the arrival order of an atomic.
+ * MEMORY: IBA_TRIANGULATE_BYTES_PER_SLOT bytes per slot; a call is cut into chunks of consecutive jobs under IBA_TRIANGULATE_BUDGET_BYTES, or under
+ * a quarter of the device memory free at the call where that is less; a chunk holds at least one job and a chunk boundary changes no byte. 2^31
+ * slots or more in a call answer IBA_ERR_UNSUPPORTED. The result is host memory.
+ * ERRORS, all IBA_ERR_INVALID_ARG with a message (iba_triangulate_last_error, per thread) BEFORE the device is touched: a NULL argument (has_point
+ * may always be NULL, node only where the frame has n == 0, neighbours only where n_neighbours == 0) or a wrong struct_size; J < 1, K < 1, F < 1; a
+ * frame that iba_orb_match would refuse; a keyframe's frame, a job's current or a neighbour out of range; a neighbour equal to current or listed
+ * twice; n_neighbours < 0; a pose entry or intrinsic that is not finite or whose magnitude is above 1e6; a median_depth that is not finite or <= 0
+ * on a keyframe used as a neighbour; n_levels outside [1, IBA_TRIANGULATE_MAX_LEVELS]; a scale table that is not finite, does not start at 1 or does
+ * not ascend strictly; a level_sigma2 or scale_factor that is not finite, above 1e6 or <= 0; an octave of a keyframe of the job outside [0, n_levels);
+ * th_low outside [0, 256]; a float threshold that is not finite; a job index outside the result; the stage accessor on a result without
+ * keep_stages; iba_triangulate_median_depth with n < 1 (the reference would index out of bounds) or q < 1. n_neighbours == 0 and frames with n == 0
+ * are legal.
+ */
+#define IBA_TRIANGULATE_BUDGET_BYTES (1ull << 30)
+#define IBA_TRIANGULATE_BYTES_PER_SLOT 120ull
+#define IBA_TRIANGULATE_MAX_LEVELS 64
+#define IBA_TRIANGULATE_N_STATUS 14
+typedef enum iba_triangulate_status {
+    IBA_TRIANGULATE_CREATED = 0, IBA_TRIANGULATE_HAS_POINT = 1, IBA_TRIANGULATE_NO_NODE = 2, IBA_TRIANGULATE_PAIR_SKIPPED = 3, IBA_TRIANGULATE_NO_MATCH = 4,
+    IBA_TRIANGULATE_PARALLAX = 5, IBA_TRIANGULATE_DEGENERATE = 6, IBA_TRIANGULATE_DEPTH1 = 7, IBA_TRIANGULATE_DEPTH2 = 8, IBA_TRIANGULATE_REPROJ1 = 9,
+    IBA_TRIANGULATE_REPROJ2 = 10, IBA_TRIANGULATE_ZERO_DIST = 11, IBA_TRIANGULATE_SCALE = 12, IBA_TRIANGULATE_SUPERSEDED = 13
+} iba_triangulate_status;
+typedef struct iba_triangulate_keyframe {     /* host pointers, read during the call only */
+    int32_t frame;                  /* index into the call's frame array */
+    float   fx, fy, cx, cy;
+    float   median_depth;           /* ComputeSceneMedianDepth(2) of this keyframe; used only where it is a neighbour */
+    const float*   Tcw12;           /* 3 x 4 row-major float32 */
+    const int32_t* node;            /* n of the frame: the DBoW2::FeatureVector node of every keypoint, < 0: in no node */
+    const uint8_t* has_point;       /* n bytes, or NULL: none has a point */
+} iba_triangulate_keyframe;
+typedef struct iba_triangulate_job {          /* host pointers, read during the call only */
+    int32_t current;                /* index into the call's keyframe array */
+    int32_t n_neighbours;
+    int32_t n_levels;               /* entries of scale_factors and level_sigma2, 1..IBA_TRIANGULATE_MAX_LEVELS */
+    float   scale_factor;           /* mfScaleFactor */
+    const int32_t* neighbours;      /* n_neighbours indices into the keyframe array, distinct, none equal to current */
+    const float*   scale_factors;   /* n_levels: mvScaleFactors, [0] == 1, ascending */
+    const float*   level_sigma2;    /* n_levels: mvLevelSigma2 */
+} iba_triangulate_job;
+typedef struct iba_triangulate_options {
+    int32_t struct_size;        /* sizeof(iba_triangulate_options) */
+    int32_t th_low;             /* 50 */
+    float   min_baseline_ratio; /* 0.01f, widened (R1) */
+    float   max_cos_parallax;   /* 0.9998f, widened (R4) */
+    float   epipole_gate;       /* 100.f (R3, float32) */
+    float   chi2_line;          /* 3.84f, widened (R3) */
+    float   chi2_mono;          /* 5.991f, widened (R6) */
+    int32_t keep_stages;        /* 0; 1 keeps the segment lengths for iba_triangulation_segments */
+} iba_triangulate_options;
+typedef struct iba_triangulate_counts {
+    int32_t n_keypoints;        /* of the current keyframe */
+    int32_t n_neighbours;       /* the job's slots are n_neighbours x n_keypoints, neighbour-major */
+    int32_t status[IBA_TRIANGULATE_N_STATUS];   /* by iba_triangulate_status, over the job's slots */
+    int32_t n_created;          /* = status[IBA_TRIANGULATE_CREATED]: the points of iba_triangulation_points */
+} iba_triangulate_counts;
+typedef struct iba_triangulation iba_triangulation;
+iba_status iba_default_triangulate_options(iba_triangulate_options* opt);
+const char* iba_triangulate_last_error(void);                        /* never NULL; of this thread's last iba_triangulat* call that failed */
+/* *out is NULL on failure; release it with iba_triangulation_free */
+iba_status iba_triangulate(const iba_orb_frame* frames, int32_t F, const iba_triangulate_keyframe* keyframes, int32_t K, const iba_triangulate_job* jobs, int32_t J,
+                           const iba_triangulate_options* opt, int device, iba_triangulation** out);
+void       iba_triangulation_free(iba_triangulation* t);
+int32_t    iba_triangulation_n_jobs(const iba_triangulation* t);     /* 0 for NULL */
+/* the counts; n_matches and n_created take n_neighbours entries each and may be NULL */
+iba_status iba_triangulation_job(const iba_triangulation* t, int32_t job, iba_triangulate_counts* counts, int32_t* n_matches, int32_t* n_created);
+/* per slot, n_neighbours x n_keypoints entries each (xyz three floats per slot); any may be NULL */
+iba_status iba_triangulation_read(const iba_triangulation* t, int32_t job, uint8_t* status, int32_t* match, int32_t* dist, float* xyz);
+/* R8: the job's n_created points in creation order; any may be NULL */
+iba_status iba_triangulation_points(const iba_triangulation* t, int32_t job, int32_t* idx1, int32_t* neighbour, int32_t* idx2, float* xyz /* x 3 */, float* normal /* x 3 */,
+                                    float* min_dist, float* max_dist, uint8_t* desc /* x 32 */);
+/* keep_stages only: per slot the length of its candidate segment (0 where the slot ended in R1 or R2) */
+iba_status iba_triangulation_segments(const iba_triangulation* t, int32_t job, int32_t* seg_len);
+/* host only, pure: KeyFrame::ComputeSceneMedianDepth(q) over n world points */
+iba_status iba_triangulate_median_depth(const float* Tcw12, const float* xyz /* n x 3 */, int32_t n, int32_t q, float* out);
 
 /*
  * ---- Bundle adjustment [the camera side's fifth brick: the reference's Optimizer::BundleAdjustment (src/orb_slam/src/Optimizer.cc:215-407: the global

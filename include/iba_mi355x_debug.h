@@ -62,6 +62,10 @@
  *   IBA_MAP_MATCH_BUDGET, IBA_MAP_MATCH_TIMING            iba_map_match: the bytes a chunk's candidate lists may take (6 per entry) in place of 1 GiB and the
  *                                                         free-memory rule (iba_debug_map_match_chunks), and HIP events around the stages
  *                                                         (iba_debug_map_match_stage_ms; tools/map_match_bench.py); same results
+ *   IBA_TRIANGULATE_BUDGET, IBA_TRIANGULATE_TIMING        the same two for iba_triangulate (120 bytes per (neighbour, keypoint) slot; iba_debug_triangulate_chunks,
+ *                                                         iba_debug_triangulate_stage_ms; tools/triangulate_bench.py); same results
+ *   IBA_TRIANGULATE_PICK_LANES                            8 / 16 / 64: the lanes per query of iba_triangulate's pick kernel in place of the shipped width
+ *                                                         (same results; A/B timing and the tests of all three)
  *   IBA_GROUP_REDUCE_HOST (flag of iba_group_create_ex, not a variable), IBA_DEBUG_FAIL_RANK / IBA_DEBUG_FAIL_PHASE: inject one
  *                                                         failure into a group's evaluation (tests of the fail-not-hang path)
  */
@@ -322,6 +326,19 @@ int32_t iba_debug_map_match_chunks(const iba_map_matches* m);
 /* debug: with IBA_MAP_MATCH_TIMING set at the call (under IBA_DEBUG_ENV=1), times in ms from HIP events, summed over the chunks: [0] frustum,
  * [1] grid (cell, scan, fill) + list count, [2] scan + list write with the distances, [3] resolve. Zeros without the variable. Same results. */
 iba_status iba_debug_map_match_stage_ms(const iba_map_matches* m, float ms[4]);
+
+/* debug: iba_triangulate as the host restatement of its rules (csrc/iba_triangulate_host.hpp over csrc/iba_triangulate_math.hpp, the text the
+ * kernels compile), the whole call without a device, neighbour after neighbour as the reference runs; the same checks, the same result object and
+ * accessors. Byte for byte what the device gives (tests/test_gpu_triangulate.py). */
+iba_status iba_debug_triangulate_host(const iba_orb_frame* frames, int32_t F, const iba_triangulate_keyframe* keyframes, int32_t K, const iba_triangulate_job* jobs, int32_t J,
+                                      const iba_triangulate_options* opt, iba_triangulation** out);
+/* debug: the chunks the jobs of the call behind t were cut into (IBA_TRIANGULATE_BUDGET: bytes a chunk's slots may take in place of
+ * IBA_TRIANGULATE_BUDGET_BYTES and the free-memory rule, read at every call under IBA_DEBUG_ENV=1; same results); 0 for iba_debug_triangulate_host
+ * and for NULL */
+int32_t iba_debug_triangulate_chunks(const iba_triangulation* t);
+/* debug: with IBA_TRIANGULATE_TIMING set at the call (under IBA_DEBUG_ENV=1), times in ms from HIP events, summed over the chunks: [0] prologue +
+ * segments, [1] pick, [2] compaction + triangulation, [3] resolve, counts, scan and gather. Zeros without the variable. Same results. */
+iba_status iba_debug_triangulate_stage_ms(const iba_triangulation* t, float ms[4]);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,137 @@
+"""New-map-point creation on the device (include/iba_mi355x.h, iba_triangulate*): every output of iba_triangulate byte for byte against
+tests/triangulate_ref.py (the rules in numpy, neighbour after neighbour as the reference runs, R3 as the literal walk) AND against the host
+restatement (iba_debug_triangulate_host), on the scenes of tests/triangulate_scene.py; tests/test_triangulate_cpu.py asserts on the reference's
+output that every named case occurs in them. Then the three pick widths, forced budgets (several chunks, the same bytes), the options that flip
+recorded cases, and the chain to iba_map_match."""
+import importlib
+
+import numpy as np
+import pytest
+
+import map_match_ref as LR
+import map_match_scene as LS
+import triangulate_ref as R
+import triangulate_scene as S
+
+PKG = "spatial-temporal-lidar-camera-calibration_amd"
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def tr():
+    importlib.import_module(PKG)
+    return importlib.import_module(PKG + ".triangulate")
+
+
+@pytest.fixture(scope="module")
+def om():
+    return importlib.import_module(PKG + ".orb_match")
+
+
+@pytest.fixture(scope="module")
+def scenes():
+    out = {}
+    for name, make in (("hand", S.hand_scene), ("random", S.random_scene)):
+        sc = make()
+        out[name] = (sc, R.run(sc["frames"], sc["keyframes"], sc["jobs"]))
+    return out
+
+
+@pytest.mark.parametrize("name", ["hand", "random"])
+def test_device_against_ref_and_host(tr, om, scenes, name):
+    sc, refs = scenes[name]
+    if name == "hand":
+        seg = set(refs[0]["seg_len"].reshape(-1).tolist())
+        assert {0, 1, 15, 16, 17, 63, 64, 65, 130} <= seg and refs[0]["counts"][R.SUPERSEDED] > 0 and refs[0]["n_equal_replaced"] > 0
+    else:
+        assert [r["n_keypoints"] * r["n_neighbours"] for r in refs] == [315 * 4, 0, 299 * 3, 0, 301] and all((r["n_keypoints"] * max(r["n_neighbours"], 1)) % 64 for r in refs if r["n_keypoints"])
+        assert refs[0]["n_created"] > 50 and refs[0]["counts"][R.SUPERSEDED] > 0
+    fr, kf, jb = S.lib_args(tr, om, sc)
+    dev = tr.triangulate(fr, kf, jb, keep_stages=1)
+    assert dev.n_chunks == 1
+    S.assert_equal(dev, refs)
+    host = tr.triangulate_host(fr, kf, jb, keep_stages=1)
+    S.same_results(dev, host, len(jb))
+    host.close()
+    dev.close()
+    plain = tr.triangulate(fr, kf, jb)                 # without keep_stages: the same results
+    S.assert_equal(plain, refs, keep_stages=False)
+    plain.close()
+
+
+@pytest.mark.parametrize("lanes", [8, 16, 64])
+def test_pick_widths_give_the_same_bytes(tr, om, scenes, monkeypatch, lanes):
+    monkeypatch.setenv("IBA_DEBUG_ENV", "1")
+    monkeypatch.setenv("IBA_TRIANGULATE_PICK_LANES", str(lanes))
+    for name in ("hand", "random"):
+        sc, refs = scenes[name]
+        fr, kf, jb = S.lib_args(tr, om, sc)
+        dev = tr.triangulate(fr, kf, jb, keep_stages=1)
+        S.assert_equal(dev, refs)
+        dev.close()
+
+
+def planned_chunks(slots, budget):
+    """the cut of consecutive jobs under a byte budget (120 bytes per slot, a chunk holds at least one job), restated"""
+    n, at, held = 1, 0, 0
+    for s in slots:
+        if held and (at > budget or 120 * s > budget - at):
+            n, at, held = n + 1, 0, 0
+        at, held = at + 120 * s, held + 1
+    return n
+
+
+def test_chunking_changes_no_byte(tr, om, scenes, monkeypatch):
+    sc, refs = scenes["random"]
+    slots = [r["n_keypoints"] * r["n_neighbours"] for r in refs]
+    fr, kf, jb = S.lib_args(tr, om, sc)
+    monkeypatch.setenv("IBA_DEBUG_ENV", "1")
+    for budget in (1, 120 * (slots[0] + slots[1]), 120 * max(slots)):
+        want = planned_chunks(slots, budget)
+        monkeypatch.setenv("IBA_TRIANGULATE_BUDGET", str(budget))
+        cut = tr.triangulate(fr, kf, jb, keep_stages=1)
+        monkeypatch.delenv("IBA_TRIANGULATE_BUDGET")
+        assert cut.n_chunks == want and (budget > 1 or want == len(jb)) and (budget == 1 or 1 < want < len(jb)), (budget, cut.n_chunks, want)
+        S.assert_equal(cut, refs)
+        cut.close()
+
+
+def test_options_flip_the_recorded_cases(tr, om, scenes):
+    sc, refs = scenes["hand"]
+    w = sc["where"]
+    fr, kf, jb = S.lib_args(tr, om, sc)
+    low = R.run(sc["frames"], sc["keyframes"], sc["jobs"], th_low=49)
+    assert refs[0]["status"][0, w["at_th_low"]] == R.CREATED and low[0]["status"][0, w["at_th_low"]] == R.NO_MATCH
+    opened = R.run(sc["frames"], sc["keyframes"], sc["jobs"], **S.OPEN)
+    assert refs[0]["status"][0, w["degenerate_open"]] == R.PARALLAX and opened[0]["status"][0, w["degenerate_open"]] == R.DEGENERATE
+    assert refs[0]["status"][0, w["parallax"]] == R.PARALLAX and opened[0]["status"][0, w["parallax"]] != R.PARALLAX
+    assert refs[0]["status"][0, w["reproj2_open"]] == R.NO_MATCH and opened[0]["status"][0, w["reproj2_open"]] == R.REPROJ2
+    for opts, want in (({"th_low": 49}, low), (S.OPEN, opened)):
+        dev = tr.triangulate(fr, kf, jb, keep_stages=1, **opts)
+        S.assert_equal(dev, want)
+        dev.close()
+
+
+def test_end_to_end_map_match_finds_the_new_points(tr, om):
+    """iba_triangulate -> the created points appended to an iba_map_points table as they are -> iba_map_match from a third frame"""
+    mm = importlib.import_module(PKG + ".map_match")
+    sc = S.noise_free_scene()
+    job = 4                                              # keyframe 0 against keyframe 1; the third frame is keyframe 3's
+    fr, kf, jb = S.lib_args(tr, om, sc)
+    dev = tr.triangulate(fr, kf, jb)
+    pts = dev.points(job)
+    dev.close()
+    assert len(pts["idx1"]) >= 30
+    table = LR.make_table(pts["xyz"], pts["normal"], pts["min_dist"], pts["max_dist"], pts["desc"])
+    third = sc["keyframes"][3]
+    mjob = LR.make_job(third["frame"], third["Tcw"], S.K, S.SF, 1.0)
+    ref = LR.run(sc["frames"], table, [mjob])
+    # on the reference's output: the new points are found in the third frame, and a found keypoint is the one that came from the same world point
+    found = np.flatnonzero(ref[0]["match"] >= 0)
+    assert len(found) >= 10
+    owner0, owner3 = sc["owner"][0], sc["owner"][3]
+    assert all(owner3[ref[0]["match"][p]] == owner0[pts["idx1"][p]] for p in found)
+    mfr, mtb, mjb = LS.lib_args(mm, om, {"frames": sc["frames"], "table": table, "jobs": [mjob]})
+    res = mm.match(mfr, mtb, mjb, keep_stages=1)
+    LS.assert_equal(res, ref)
+    res.close()
