@@ -1170,7 +1170,7 @@ iba_status iba_project_gradient(double zn, uint8_t rgb[3]);                     
  * (cv::fastAtan2). O6's tie rule is stated above. The BRIEF test-pair table is an INPUT (256 x 4 int8: x0 y0 x1 y1 per test); the library ships none.
  * Masks, undistortion and ComputeKeyPointsOld are not provided. Windowed matching is iba_orb_match below. Of the two vocabulary matchers,
  * SearchByBoW and SearchForTriangulation, the second is iba_triangulate further below with the DBoW2 node id of every keypoint as an INPUT (it needs
- * the outcome of the vocabulary, not the vocabulary); SearchByBoW remains unprovided, as do Fuse, SearchBySim3, and the SearchByProjection overloads that take a
+ * the outcome of the vocabulary, not the vocabulary); SearchByBoW remains unprovided, as do SearchBySim3 and the SearchByProjection overloads that take a
  * key frame (the overload that takes map points is iba_map_match further below). Two-view initialisation is iba_twoview_init further below; what Tracking::CreateInitialMapMonocular does after a success
  * (global BA, median-depth scaling) and the >= 100-matches gates around the call are the caller's.
  * DEVICE: one chain per chunk over flat tables (one row per image and level, per 64 x 16 tile, per cell, per keypoint): resize level by level, score,
@@ -1685,7 +1685,7 @@ iba_status iba_pose_edges_from_matches(const int32_t* match, const int32_t* quer
  * [0, n_levels - 1]; the table rule gives the same integer except where ratio lies within rounding of a table entry, and keeps transcendentals off
  * the device, as P6 does (profiles/map_match_parity.md counts the differences on the test scene). (2) As in M7 every claim of the call counts,
  * where the reference skips a claimed keypoint only if its map point has Observations() > 0. (3) NOT_FINITE, above.
- * NOT PROVIDED: stereo (mvuRight, mTrackProjXR), the KeyFrame and Sim3 overloads of SearchByProjection, Fuse, the BoW matchers, UpdateLocalMap
+ * NOT PROVIDED: stereo (mvuRight, mTrackProjXR), the KeyFrame and Sim3 overloads of SearchByProjection, the BoW matchers, UpdateLocalMap
  * (choosing the local points and their order is the caller's) and the IncreaseVisible / IncreaseFound bookkeeping (the statuses and matches say
  * which points it applies to).
  * DEVICE (csrc/iba_map_match_kernels.hpp). Before the chunks, over the whole call: the frustum kernel - a flat table of (job, list position)
@@ -1856,7 +1856,7 @@ iba_status iba_map_match_pose_edges(const int32_t* prior_point /* n_kp */, const
  * reprojects between the two. tests/triangulate_scene.py reaches DEGENERATE and REPROJ2 with max_cos_parallax and chi2_line opened, the self-test
  * ZERO_DIST with a hand-made centre.
  * NOT PROVIDED: stereo (mvuRight, bOnlyStereo, UnprojectStereo), mbCheckOrientation = true, the CheckNewKeyFrames() early return, the choice of
- * neighbours, computing the node ids (DBoW2), SearchInNeighbors / Fuse. iba_triangulate_median_depth (host only, pure) is
+ * neighbours, computing the node ids (DBoW2). iba_triangulate_median_depth (host only, pure) is
  * KeyFrame::ComputeSceneMedianDepth: z = (float)dot + zcw with the dot of the pose's third row and the point in double, sorted ascending, element
  * (n - 1) / q.
  * DEVICE (csrc/iba_triangulate_kernels.hpp). The node order of every keyframe - its keypoints with node >= 0 sorted by (node, index) - is a host
@@ -1943,6 +1943,174 @@ iba_status iba_triangulation_points(const iba_triangulation* t, int32_t job, int
 iba_status iba_triangulation_segments(const iba_triangulation* t, int32_t job, int32_t* seg_len);
 /* host only, pure: KeyFrame::ComputeSceneMedianDepth(q) over n world points */
 iba_status iba_triangulate_median_depth(const float* Tcw12, const float* xyz /* n x 3 */, int32_t n, int32_t q, float* out);
+
+/*
+ * ---- Map-point fusion [the camera side's eighth brick: the reference's LocalMapping::SearchInNeighbors (src/orb_slam/src/LocalMapping.cc:453-533)
+ * with ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th) (ORBmatcher.cc:825-975), its Sim3 overload's loop (:977-1100) and
+ * MapPoint::Replace (MapPoint.cc:190-228)] ----
+ * The step that keeps the map from growing duplicates: the points of the current keyframe are projected into the target keyframes and the
+ * targets' points back into the current one; a point that lands on a keypoint which already holds a point is merged with it, one that lands on a
+ * free keypoint becomes an observation. A call takes F frames (iba_orb_frame; xy is mvKeysUn), ONE table of P map points (iba_map_points) and J
+ * jobs; a job is one Fuse call: a keyframe (frame, pose, intrinsics, tables) and a list of points. Frames and the table go up once, however many
+ * jobs name them. TWO FACTS OF THE REFERENCE split the work. (1) Inside one Fuse call the projection, the gates, the predicted level, the window
+ * and the best keypoint (bestIdx, bestDist) of a listed point depend only on the point and the keyframe, never on what earlier points of the list
+ * did: isBad() and IsInKeyFrame(pKF) only skip a point. So every (job, list position) slot is independent: iba_fuse, on the device. (2) What is
+ * done with a pick - AddObservation, or Replace in one of two directions by Observations() - reads and changes the map graph and is sequential:
+ * iba_fuse_apply, a host fold over the caller's map arrays, O(number of picks). JOBS ARE INDEPENDENT and use the point table as given.
+ * Float arithmetic is float32 unless a cast says otherwise, every operation rounded, evaluated left to right, no contraction;
+ * tests/fuse_ref.py restates the device rules in numpy, sequentially as the reference is written, and the fold as MapPoint / KeyFrame objects; the
+ * device and the host restatement (iba_debug_fuse_host) are compared with it byte for byte. The float decisions are ONE text, csrc/iba_fuse_math.hpp,
+ * which reuses csrc/iba_map_match_math.hpp wherever a rule is literally L1's.
+ *
+ *   F1 skip.       Per listed point, in list order. A list entry < 0 (the reference's NULL pointer) or a set skip byte (isBad() ||
+ *                  IsInKeyFrame(pKF) at call time; iba_fuse_skip computes it) gives SKIPPED. The point is not projected.
+ *   F2 projection. Pc as in L1, the same order of sums. PcZ < 0.0f: DEPTH. invz = (float)(1.0 / (double)PcZ). x = PcX * invz, y = PcY * invz,
+ *                  u = fx * x + cx, v = fy * y + cy: Fuse's association, which differs from L1's (fx * PcX) * invz. u or v not finite:
+ *                  NOT_FINITE (the reference skips such a point too, IsInImage is false for NaN and infinity; only the status name is the
+ *                  library's). KeyFrame::IsInImage is HALF OPEN: u >= min_x && u < max_x && v >= min_y && v < max_y, anything else BOUNDS: a
+ *                  centre exactly on max_x is refused here, where L1 keeps it.
+ *   F3 distance and angle. Ow, PO and dist are L1's. dist < 0.8f * min_dist || dist > 1.2f * max_dist: DISTANCE (exactly on a bound is kept).
+ *                  dot = (PO_0 n_0 + PO_1 n_1) + PO_2 n_2 in double; dot < (double)view_cos_limit * (double)dist: ANGLE. No division: this is
+ *                  Fuse's form (PO.dot(Pn) < 0.5 * dist3D), not L1's view_cos.
+ *   F4 level and window. ratio = max_dist / dist (float32, correctly rounded) and the level by L1's table rule. radius = th *
+ *                  scale_factors[level]. The list is M3's with centre (u, v), that radius and levels (level - 1, level), the distances M4's
+ *                  against the point's descriptor. This equals KeyFrame::GetFeaturesInArea(u, v, r) followed by Fuse's kpLevel test, in the same
+ *                  order, because the test only deletes entries of the list. An empty list: NO_CANDIDATE.
+ *   F5 pick.       A candidate is ELIGIBLE iff its distance is below 256 and it passes the gate. The gate applies only where
+ *                  check_reprojection is set: ex = u - kp_x, ey = v - kp_y, e2 = ex * ex + ey * ey; the candidate passes iff NOT
+ *                  (double)(e2 * inv_level_sigma2[octave]) > (double)chi2_mono (the reference's 5.99 is a double literal). The pick is the
+ *                  lexicographic minimum of (distance, list position) over the eligible candidates; the device reduces the key
+ *                  (distance << 32) | position. PICKED iff a pick exists and its distance <= th_low; otherwise NO_MATCH.
+ *                  WHY THE MINIMUM IS THE REFERENCE'S WALK. The reference starts (bestDist, bestIdx) at (256, -1) and walks the list with
+ *                  `if (dist < bestDist) take it`, skipping the candidates the gate refuses. Invariant: after any prefix, (bestDist, bestIdx) is
+ *                  the least (distance, position) pair among the prefix's eligible candidates, or (256, -1). A new eligible candidate has the
+ *                  largest position so far: it is the new least pair iff its distance is strictly below bestDist; at 256 or above it never is.
+ *                  With check_reprojection == 0 this is the loop of the Sim3 overload, which starts bestDist at INT_MAX: that changes no PICKED
+ *                  outcome for th_low < 256, because only a candidate at 256 is treated differently and it is never <= th_low; the caller
+ *                  passes Rcw = sRcw / s, tcw = t / s in Tcw12.
+ *   F6 outputs per job. Per listed point: status (uint8), u, v, level, radius (zeros where F4 was not reached), match (the keypoint, -1 unless
+ *                  PICKED) and dist (the pick's distance, -1 unless PICKED). Counts: one per status, n_candidates (the sum of the list lengths),
+ *                  n_picked. With keep_stages the candidate lists in M3's order as iba_map_matches_lists gives them.
+ *
+ * THE FOLD (iba_fuse_apply, host only, pure). The state is the caller's map (iba_fuse_map), changed IN PLACE.
+ *   U1 state.      IsInKeyFrame(p, k) holds iff some keypoint of keyframe k holds p. Observations(p) = the number of keyframes that hold p (the
+ *                  monocular nObs). THE MAP MUST NAME EVERY KEYFRAME THAT OBSERVES AN INVOLVED POINT: what it does not name does not exist for
+ *                  the fold. Refused at entry with IBA_ERR_INVALID_ARG: a point held twice in one keyframe, a holder entry outside [-1, P), a
+ *                  keyframe whose keypoint count differs from the job's frame. The point -> (keyframe, keypoint) index is built once per call.
+ *   U2 order.      The job's list positions in order; only PICKED entries act (every other op is NONE). A PICKED entry whose point is bad by
+ *                  now: STALE_BAD; one whose point is by now held in the keyframe: STALE_IN_KEYFRAME. Both are the reference's `continue`,
+ *                  reached through an earlier fold or a duplicated list entry; neither counts as fused.
+ *   U3 act.        q = holder[keyframe][match]. q < 0: ADD, holder[keyframe][match] = p. q >= 0 && bad[q]: HELD_BAD, no change. Otherwise in
+ *                  LOCAL mode: Observations(q) > Observations(p): p dies into q (REPLACED_BY_HELD), else q dies into p (REPLACES_HELD; equality
+ *                  takes this branch, as the reference's `>` dictates); in LOOP mode: RECORD, no change (vpReplacePoint[match] = p). other = q in
+ *                  every case but ADD. All of these count in n_fused, as the reference counts them.
+ *   U4 Replace(a dies, b survives). For every (k', i) that holds a: where b is held in k', holder[k'][i] = -1, otherwise holder[k'][i] = b.
+ *                  bad[a] = 1, replaced_by[a] = b, found[b] += found[a], visible[b] += visible[a], descriptor_stale[b] = 1 (the last three where
+ *                  the arrays are given). Each step depends only on (a, b, k'), so the order over the keyframes changes no outcome.
+ *   U5 helpers.    iba_fuse_skip: F1's bytes from the map (entry < 0, bad, or held in the keyframe). iba_fuse_candidates: vpFuseCandidates -
+ *                  the targets in order, their keypoints in ascending index, each held point that is not bad and not already listed.
+ *
+ * UNPINNED, as in L1: the order of the sums of Pc, Ow, the dot product and cv::norm. KNOWN DEVIATIONS: (1) the level by the table rule in place of
+ * libm's ceil(log(ratio) / mfLogScaleFactor), as in L1. (2) NO DESCRIPTOR REFRESH: Replace ends with ComputeDistinctiveDescriptors() on the
+ * survivor, so in the reference a survivor enters the next target keyframe with a new descriptor; every job of a call uses the table as given and
+ * the fold marks the survivors (descriptor_stale) for the caller or a later brick (profiles/fuse_parity.md counts how often the refresh would have
+ * changed a pick). (3) NOT_FINITE, a name only.
+ * NOT PROVIDED: stereo (mvuRight, ur, the 7.8 gate), the choice of target keyframes (covisibility), ComputeDistinctiveDescriptors and
+ * UpdateNormalAndDepth (the "Update points" tail of SearchInNeighbors and the refresh inside Replace), UpdateConnections.
+ * DEVICE (csrc/iba_fuse_kernels.hpp). Before the chunks, over the whole call: the frustum kernel - a flat table of (job, list position) slots, one
+ * lane per slot, blocks that do not straddle a job so that pose, intrinsics, bounds and tables are uniform per block; F1-F4; it writes the status
+ * and the slot's query record and counts the statuses by wave ballot into LDS with one integer atomic per counter and block; then the matcher's
+ * grid kernels and its list kernel, unchanged - the point descriptors lie behind the keypoint descriptors in the one flat descriptor table, as in
+ * iba_map_match. Per chunk of consecutive jobs: scan, the list kernel writing candidates and distances, and the pick kernel: W lanes per slot (W =
+ * 8, 16 or 64; 8 ships, profiles/fuse_bench.md), the lanes stride over the slot's segment of (candidate, distance) entries, gather the candidate's
+ * position and octave for the gate, keep their least key; the group minimum by xor shuffles inside the aligned group; one lane writes match, dist
+ * and status; the NO_CANDIDATE / NO_MATCH / PICKED counts go the way of the frustum's. No floating-point atomics, and no byte depends on the
+ * arrival order of an atomic.
+ * MEMORY: the candidate lists (IBA_FUSE_BYTES_PER_CANDIDATE bytes per entry, sized from the count pass) are cut into chunks of consecutive jobs
+ * under IBA_FUSE_BUDGET_BYTES, or under a quarter of the device memory free at the call where that is less; a chunk holds at least one job and a
+ * chunk boundary changes no byte. A chunk whose lists hold 2^31 entries or more answers IBA_ERR_UNSUPPORTED. The result is host memory and keeps
+ * a copy of every job's list, because the fold needs it.
+ * ERRORS, all IBA_ERR_INVALID_ARG with a message (iba_fuse_last_error, per thread) BEFORE the device is touched: a NULL argument (the table's
+ * arrays may be NULL only where P == 0; skip may always be NULL; points may be NULL only where n_points == P: all P in order) or a wrong
+ * struct_size; J < 1, F < 1, P < 0; a frame that iba_orb_match would refuse; a job's frame out of range or a listed point >= P; n_points < 0; a
+ * pose entry, point, normal, distance, intrinsic or th that is not finite or whose magnitude is above 1e6; n_levels outside [1,
+ * IBA_MAP_MATCH_MAX_LEVELS]; a scale table that is not finite, does not start at 1 or does not ascend strictly; an inv_level_sigma2 that is not
+ * finite, above 1e6 or <= 0; an octave of the job's frame outside [0, n_levels); th_low outside [0, 256]; view_cos_limit or chi2_mono not finite;
+ * a job index outside the result; the stage accessor on a result without keep_stages; the fold's U1 checks, a keyframe outside the map, a mode
+ * that is neither, a listed point >= the map's P. A job with n_points == 0 and a frame with n == 0 are legal.
+ */
+#define IBA_FUSE_BUDGET_BYTES (1ull << 30)
+#define IBA_FUSE_BYTES_PER_CANDIDATE 6ull
+#define IBA_FUSE_N_STATUS 9
+typedef enum iba_fuse_status {
+    IBA_FUSE_PICKED = 0, IBA_FUSE_SKIPPED = 1, IBA_FUSE_DEPTH = 2, IBA_FUSE_NOT_FINITE = 3, IBA_FUSE_BOUNDS = 4, IBA_FUSE_DISTANCE = 5, IBA_FUSE_ANGLE = 6,
+    IBA_FUSE_NO_CANDIDATE = 7, IBA_FUSE_NO_MATCH = 8
+} iba_fuse_status;
+typedef struct iba_fuse_job {                 /* host pointers, read during the call only */
+    int32_t frame;                  /* index into the call's frame array */
+    int32_t n_levels;               /* entries of scale_factors and inv_level_sigma2, 1..IBA_MAP_MATCH_MAX_LEVELS */
+    int32_t n_points;
+    float   th;                     /* 3.0f */
+    float   fx, fy, cx, cy;
+    const float*   Tcw12;           /* 3 x 4 row-major float32: the keyframe's pose */
+    const float*   scale_factors;   /* n_levels: mvScaleFactors, [0] == 1, ascending */
+    const float*   inv_level_sigma2;/* n_levels: mvInvLevelSigma2 */
+    const int32_t* points;          /* n_points table indices in list order; an entry < 0 is the reference's NULL pointer; NULL: all P in order */
+    const uint8_t* skip;            /* n_points, or NULL: none: isBad() || IsInKeyFrame(pKF) at call time */
+} iba_fuse_job;
+typedef struct iba_fuse_options {
+    int32_t struct_size;        /* sizeof(iba_fuse_options) */
+    int32_t th_low;             /* 50 */
+    float   view_cos_limit;     /* 0.5f, widened (F3) */
+    float   chi2_mono;          /* 5.99f, widened (F5) */
+    int32_t check_reprojection; /* 1; 0: the Sim3 overload's loop */
+    int32_t keep_stages;        /* 0; 1 keeps the candidate lists for iba_fusion_lists */
+} iba_fuse_options;
+typedef struct iba_fuse_counts {
+    int32_t n_points;
+    int32_t status[IBA_FUSE_N_STATUS];   /* by iba_fuse_status */
+    int32_t n_candidates, n_picked;      /* n_picked = status[IBA_FUSE_PICKED] */
+} iba_fuse_counts;
+typedef struct iba_fusion iba_fusion;
+iba_status iba_default_fuse_options(iba_fuse_options* opt);
+const char* iba_fuse_last_error(void);                               /* never NULL; of this thread's last iba_fus* call that failed */
+/* *out is NULL on failure; release it with iba_fusion_free */
+iba_status iba_fuse(const iba_orb_frame* frames, int32_t F, const iba_map_points* points, const iba_fuse_job* jobs, int32_t J, const iba_fuse_options* opt, int device,
+                    iba_fusion** out);
+void       iba_fusion_free(iba_fusion* f);
+int32_t    iba_fusion_n_jobs(const iba_fusion* f);                   /* 0 for NULL */
+iba_status iba_fusion_job(const iba_fusion* f, int32_t job, iba_fuse_counts* counts);
+/* F6 per listed point, n_points entries each; any may be NULL */
+iba_status iba_fusion_read(const iba_fusion* f, int32_t job, uint8_t* status, float* u, float* v, int32_t* level, float* radius, int32_t* match, int32_t* dist);
+/* keep_stages only: off[n_points + 1] and, per entry, the keypoint and the distance in M3's order; their length is the job's n_candidates. Every
+ * output may be NULL. */
+iba_status iba_fusion_lists(const iba_fusion* f, int32_t job, int32_t* off, int32_t* index, uint16_t* dist);
+
+/* the fold (U1-U5): host only, pure */
+#define IBA_FUSE_LOCAL 0        /* Fuse(pKF, vpMapPoints, th): Replace by Observations() */
+#define IBA_FUSE_LOOP  1        /* the Sim3 overload: record vpReplacePoint, change nothing */
+typedef enum iba_fuse_op {
+    IBA_FUSE_OP_NONE = 0, IBA_FUSE_OP_ADD = 1, IBA_FUSE_OP_REPLACED_BY_HELD = 2, IBA_FUSE_OP_REPLACES_HELD = 3, IBA_FUSE_OP_HELD_BAD = 4, IBA_FUSE_OP_RECORD = 5,
+    IBA_FUSE_OP_STALE_BAD = 6, IBA_FUSE_OP_STALE_IN_KEYFRAME = 7
+} iba_fuse_op;
+typedef struct iba_fuse_map {
+    int32_t K;                  /* the keyframes of the map */
+    const int32_t* kp_off;      /* K + 1: keyframe k's keypoints are holder[kp_off[k] .. kp_off[k + 1]) */
+    int32_t* holder;            /* kp_off[K]: mvpMapPoints of every keyframe of the map, a table index or -1 */
+    int32_t P;
+    uint8_t* bad;               /* P */
+    int32_t* replaced_by;       /* P, -1: mpReplaced */
+    int32_t* found;             /* P, may be NULL */
+    int32_t* visible;           /* P, may be NULL */
+    uint8_t* descriptor_stale;  /* P, may be NULL: set on every survivor of a Replace */
+} iba_fuse_map;
+/* the fold of one job of f into the map; keyframe = the job's pKF in the map. op and other take n_points entries each (other: the held point, or
+ * -1) and may be NULL, as may n_fused (the reference's return value) */
+iba_status iba_fuse_apply(const iba_fusion* f, int32_t job, int32_t keyframe, iba_fuse_map* map, int32_t mode, int32_t* op, int32_t* other, int32_t* n_fused);
+/* U5: F1's bytes for a list against a keyframe of the map */
+iba_status iba_fuse_skip(const iba_fuse_map* map, int32_t keyframe, const int32_t* points, int32_t n, uint8_t* skip);
+/* U5: vpFuseCandidates over T target keyframes; points takes up to map->P entries, *n is their number */
+iba_status iba_fuse_candidates(const iba_fuse_map* map, const int32_t* targets, int32_t T, int32_t* points, int32_t* n);
 
 /*
  * ---- Bundle adjustment [the camera side's fifth brick: the reference's Optimizer::BundleAdjustment (src/orb_slam/src/Optimizer.cc:215-407: the global

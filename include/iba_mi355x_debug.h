@@ -66,6 +66,10 @@
  *                                                         iba_debug_triangulate_stage_ms; tools/triangulate_bench.py); same results
  *   IBA_TRIANGULATE_PICK_LANES                            8 / 16 / 64: the lanes per query of iba_triangulate's pick kernel in place of the shipped width
  *                                                         (same results; A/B timing and the tests of all three)
+ *   IBA_FUSE_BUDGET, IBA_FUSE_TIMING                      the same two for iba_fuse (6 bytes per candidate-list entry; iba_debug_fuse_chunks,
+ *                                                         iba_debug_fuse_stage_ms; tools/fuse_bench.py); same results
+ *   IBA_FUSE_PICK_LANES                                   8 / 16 / 64: the lanes per slot of iba_fuse's pick kernel in place of the shipped width
+ *                                                         (same results; A/B timing and the tests of all three)
  *   IBA_GROUP_REDUCE_HOST (flag of iba_group_create_ex, not a variable), IBA_DEBUG_FAIL_RANK / IBA_DEBUG_FAIL_PHASE: inject one
  *                                                         failure into a group's evaluation (tests of the fail-not-hang path)
  */
@@ -339,6 +343,17 @@ int32_t iba_debug_triangulate_chunks(const iba_triangulation* t);
 /* debug: with IBA_TRIANGULATE_TIMING set at the call (under IBA_DEBUG_ENV=1), times in ms from HIP events, summed over the chunks: [0] prologue +
  * segments, [1] pick, [2] compaction + triangulation, [3] resolve, counts, scan and gather. Zeros without the variable. Same results. */
 iba_status iba_debug_triangulate_stage_ms(const iba_triangulation* t, float ms[4]);
+
+/* debug: iba_fuse as the host restatement of its rules (csrc/iba_fuse_host.hpp over csrc/iba_fuse_math.hpp, the text the kernels compile), the
+ * whole call without a device; the same checks, the same result object and accessors, iba_fuse_apply included. Byte for byte what the device
+ * gives (tests/test_gpu_fuse.py). */
+iba_status iba_debug_fuse_host(const iba_orb_frame* frames, int32_t F, const iba_map_points* points, const iba_fuse_job* jobs, int32_t J, const iba_fuse_options* opt, iba_fusion** out);
+/* debug: the chunks the jobs of the call behind f were cut into (IBA_FUSE_BUDGET: bytes a chunk's candidate lists may take in place of
+ * IBA_FUSE_BUDGET_BYTES and the free-memory rule, read at every call under IBA_DEBUG_ENV=1; same results); 0 for iba_debug_fuse_host and for NULL */
+int32_t iba_debug_fuse_chunks(const iba_fusion* f);
+/* debug: with IBA_FUSE_TIMING set at the call (under IBA_DEBUG_ENV=1), times in ms from HIP events, summed over the chunks: [0] frustum, [1] grid
+ * (cell, scan, fill) + list count, [2] scan + list write with the distances, [3] pick. Zeros without the variable. Same results. */
+iba_status iba_debug_fuse_stage_ms(const iba_fusion* f, float ms[4]);
 
 #ifdef __cplusplus
 }
