@@ -1849,7 +1849,8 @@ iba_status iba_map_match_pose_edges(const int32_t* prior_point /* n_kp */, const
  * accumulation, cv::SVD against the Jacobi. KNOWN DEVIATIONS: (1) the widened float thresholds, above. (2) The reference's
  * ComputeDistinctiveDescriptors and the order of the normal sum in UpdateNormalAndDepth follow the pointer order of a std::map<KeyFrame*, size_t>;
  * R8 fixes both (with two observations at distance d the median rule picks either descriptor: profiles/triangulate_parity.md counts the points
- * for which the other order would differ). (3) DEGENERATE for a quotient that is not finite.
+ * for which the other order would differ). (3) DEGENERATE for a quotient that is not finite. Once a created point has a third observation, its
+ * descriptor, normal and bounds come from iba_refresh (S1-S7 below), which gives R8's bytes for the two observations listed current keyframe first.
  * GUARDS. Under the default options DEGENERATE and ZERO_DIST are guards, as their tests are in the reference: x[3] == 0 needs parallel rays, which
  * are PARALLAX first, and x3D == Ow_i makes z_i = r_2 . (x3D - Ow_i) zero, which is DEPTH1 / DEPTH2 first. REPROJ2 needs a candidate further than
  * sqrt(chi2_mono) sigma from the reprojection yet nearer than sqrt(chi2_line) sigma, of the same octave, to the line, and the triangulated point
@@ -2015,8 +2016,9 @@ iba_status iba_triangulate_median_depth(const float* Tcw12, const float* xyz /* 
  * survivor, so in the reference a survivor enters the next target keyframe with a new descriptor; every job of a call uses the table as given and
  * the fold marks the survivors (descriptor_stale) for the caller or a later brick (profiles/fuse_parity.md counts how often the refresh would have
  * changed a pick). (3) NOT_FINITE, a name only.
- * NOT PROVIDED: stereo (mvuRight, ur, the 7.8 gate), the choice of target keyframes (covisibility), ComputeDistinctiveDescriptors and
- * UpdateNormalAndDepth (the "Update points" tail of SearchInNeighbors and the refresh inside Replace), UpdateConnections.
+ * NOT PROVIDED: stereo (mvuRight, ur, the 7.8 gate), the choice of target keyframes (covisibility), UpdateConnections. The "Update points" tail
+ * of SearchInNeighbors and the refresh inside Replace are iba_refresh (below): iba_fuse_apply, iba_refresh_observations, iba_refresh of the
+ * descriptor_stale survivors, iba_refresh_store.
  * DEVICE (csrc/iba_fuse_kernels.hpp). Before the chunks, over the whole call: the frustum kernel - a flat table of (job, list position) slots, one
  * lane per slot, blocks that do not straddle a job so that pose, intrinsics, bounds and tables are uniform per block; F1-F4; it writes the status
  * and the slot's query record and counts the statuses by wave ballot into LDS with one integer atomic per counter and block; then the matcher's
@@ -2113,6 +2115,134 @@ iba_status iba_fuse_skip(const iba_fuse_map* map, int32_t keyframe, const int32_
 iba_status iba_fuse_candidates(const iba_fuse_map* map, const int32_t* targets, int32_t T, int32_t* points, int32_t* n);
 
 /*
+ * ---- Map-point refresh [the camera side's ninth brick: the reference's MapPoint::ComputeDistinctiveDescriptors (src/orb_slam/src/MapPoint.cc:255-320)
+ * and MapPoint::UpdateNormalAndDepth (:343-384), the two functions it calls most often on the map: after CreateNewMapPoints, at the end of
+ * MapPoint::Replace, in the "Update points" tail of SearchInNeighbors (LocalMapping.cc:515-530) and after every bundle adjustment] ----
+ * For a batch of map points in ONE call: the representative descriptor (the observed descriptor with the least median Hamming distance to the
+ * others), the mean viewing direction and the two scale-invariance distances, from the points' observations. It closes the loop of one
+ * LocalMapping step inside the C ABI: iba_triangulate / iba_fuse + iba_fuse_apply / iba_bundle_optimize change the map, iba_refresh brings normal,
+ * min_dist, max_dist and desc of the iba_map_points table up to date, iba_refresh_store writes them back, and the next iba_map_match / iba_fuse
+ * reads a table that is not stale. A call takes F frames (iba_orb_frame: ONLY desc, octave and n are read), K keyframes (iba_refresh_keyframe:
+ * the frame, the pose, the scale table, isBad()), ONE table of P points, read as given, point_bad[P] (MapPoint::isBad(); may be NULL: none),
+ * ref_keyframe[P] (mpRefKF as a keyframe index) and the observations of every point as CSR lists: obs_off[P + 1], obs_keyframe[], obs_keypoint[].
+ * THE ORDER INSIDE A POINT'S LIST IS THE CALLER'S AND IS PART OF THE RULE: the reference iterates a std::map<KeyFrame*, size_t>, that is in
+ * pointer order, which nothing can pin (iba_triangulate's deviation (2) says the same). list[n] names the points to refresh in output order
+ * (NULL: all P in order, and n must be P); a duplicated entry is legal and gives equal results. Every point is independent of every other.
+ * Integer work is exact. Float arithmetic is float32 unless a cast says otherwise, every operation rounded, left to right, no contraction, as in
+ * L1 / R8; tests/refresh_ref.py restates the rules in numpy as the reference is written (the full matrix, a sort of every row, the `<` walk); the
+ * device and the host restatement (iba_debug_refresh_host) are compared with it byte for byte. The decisions are ONE text, csrc/iba_refresh_math.hpp.
+ *
+ *   S1 select.     point_bad set: BAD. An empty observation list: EMPTY. Both are the reference's early returns; all four outputs are the table's
+ *                  values as given, desc_state and geo_state NONE, best_obs = best_median = -1, n_desc = 0.
+ *   S2 descriptor set. The observations whose keyframe is not bad, in list order: N of them; entry i is desc row obs_keypoint of the keyframe's
+ *                  frame. N == 0: desc_state KEPT, the descriptor as given, best_obs = best_median = -1; S4 and S5 still run, because
+ *                  UpdateNormalAndDepth never looks at isBad(). Otherwise desc_state PICKED.
+ *   S3 median pick. d(i, j) is the 256-bit Hamming distance, d(i, i) = 0. m = (N - 1) / 2 in integer division: the reference's
+ *                  vDists[0.5 * (N - 1)], truncated. median(i) is the element of rank m of row i in ascending order; equivalently THE LEAST v SUCH
+ *                  THAT AT LEAST m + 1 ENTRIES OF ROW i ARE <= v, which is the form the device and the host restatement evaluate (no sort). The
+ *                  pick is the lexicographic minimum of (median(i), i); the device reduces the key (median << 32) | i.
+ *                  WHY THE MINIMUM IS THE REFERENCE'S WALK. The reference starts BestMedian at INT_MAX and walks the rows in order with
+ *                  `if (median < BestMedian) take it`. Invariant: after any prefix of rows, (BestMedian, BestIdx) is the least (median, row) pair
+ *                  of the prefix. The next row has the largest index so far: it is the new least pair iff its median is strictly below
+ *                  BestMedian; at a tie the earlier row holds. A median is at most 256 < INT_MAX, so row 0 is always taken. And the rank form
+ *                  equals the sorted element: the sorted row's entry m is the least value with at least m + 1 entries at or below it.
+ *                  best_obs is the picked row's position in the point's FULL observation list, best_median its median, n_desc = N.
+ *   S4 normal.     Ow of a keyframe is L1's formula, formed once per keyframe. Per observation k of the FULL list, in order: PO = P - Ow_k
+ *                  (float32), |PO| = L1's dist before its narrowing (squares and sums in double), term_c = (float)((double)PO_c / |PO|): exactly
+ *                  R8's n_i. sum_c starts at 0.0f and adds the terms in float32 IN LIST ORDER. normal_c = (float)((double)sum_c / (double)n), n
+ *                  the length of the full list. For n == 2 this is R8's (n1 + n2) * 0.5f bit for bit.
+ *   S5 distances.  The reference keyframe's entry is the first one of the list whose keyframe equals ref_keyframe. dist = (float)|P - Ow_ref|,
+ *                  level = the octave of that entry's keypoint, max_dist = dist * scale_factors_ref[level], min_dist = max_dist /
+ *                  scale_factors_ref[n_levels_ref - 1], correctly rounded (R8's). geo_state UPDATED.
+ *   S6 guards.     The library's own. ref_keyframe not in the list: geo_state NO_REF, the normal computed, the distances as given. Any |PO| == 0:
+ *                  geo_state DEGENERATE, normal and distances as given.
+ *   S7 outputs per listed point. status (REFRESHED / BAD / EMPTY), desc_state, geo_state (uint8 each), best_obs, best_median, n_desc, normal,
+ *                  min_dist, max_dist, desc. Counts of the call: one per status and state, n_desc_changed (PICKED and the picked 32 bytes differ
+ *                  from the table's), path[3] (the points on each device shape; zeros from the host restatement) and n_rows. With keep_stages:
+ *                  per REFRESHED point the median of every observation's row in the order of the FULL list, -1 for an observation of a bad
+ *                  keyframe (iba_refreshed_medians; n_rows entries).
+ *
+ * HELPERS, host only, pure. iba_refresh_observations builds the CSR lists from an iba_fuse_map: keyframes in ascending index, each (keyframe,
+ * keypoint) that holds p once, so that the output of iba_fuse_apply feeds the refresh; a point held twice in one keyframe is refused as in U1.
+ * iba_refresh_store scatters the REFRESHED entries of a result into the caller's MUTABLE table arrays by listed index and clears
+ * descriptor_stale there where the array is given.
+ * UNPINNED, as in L1: the order of the sums of Ow and cv::norm. KNOWN DEVIATIONS: (1) the list order in place of pointer order, above
+ * (profiles/refresh_parity.md counts what the order can change). (2) NO_REF: the reference's observations[pRefKF] on its local copy would insert
+ * 0 and read keypoint 0. (3) DEGENERATE: the reference divides by zero.
+ * NOT PROVIDED: stereo, UpdateConnections, culling, and the refresh between the jobs of one iba_fuse call (iba_fuse is unchanged).
+ * DEVICE (csrc/iba_refresh_kernels.hpp). The host, which holds obs_off, settles S1 and bins the other listed points by the length of their FULL
+ * list into three work lists; ONE kernel text runs in three shapes, a group of G lanes per point: NARROW (G = 4, 8, 16 or 32 for lists of up to G
+ * entries, 256 / G points per block; 16 ships, profiles/refresh_bench.md), WAVE (G = 64: one wave per point, lane i owns row i) and BLOCK (G = 256:
+ * one block per point, up to IBA_REFRESH_MAX_OBS entries, rows strided over the threads). The group gathers descriptor (32 bytes), S4's term and
+ * keyframe of every observation into LDS once (32 KiB of descriptors at the cap); a lane holds its own row's descriptor in four 64-bit registers
+ * and reads descriptor j at an address uniform across the group, an LDS broadcast; d(i, j) is four xor + popcount. NO N x N TABLE GOES TO GLOBAL
+ * MEMORY: the call allocates inputs and outputs only, so there is no budget and no chunking. The median of a row is S3's counting form, either a
+ * 9-step binary search on v that recomputes the row's distances at every step, or one pass that keeps the row - in LDS for the narrow and wave
+ * shapes, in the registers of a wave that takes the row for the block shape - and searches there (ships; profiles/refresh_bench.md records both). The
+ * pick is the group minimum of the key by xor shuffles (and 4 LDS words for the block). S4 / S5 run in the same kernel: the lanes stride over the
+ * full list for the terms, then lane 0 adds them in list order, because the order is the rule. No floating-point atomics, and no byte depends on
+ * the arrival order of an atomic: the counts go by ballot into LDS and one integer atomic per counter and block.
+ * ERRORS, all IBA_ERR_INVALID_ARG with a message (iba_refresh_last_error, per thread) BEFORE the device is touched: a NULL argument (point_bad and
+ * list may be NULL; the table's arrays and ref_keyframe only where P == 0; obs_keyframe and obs_keypoint only where obs_off[P] == 0) or a wrong
+ * struct_size; F < 1, K < 1, P < 0, n < 0; list NULL and n != P; a frame that iba_orb_match would refuse; a keyframe's frame out of range; a pose
+ * entry, point, normal or distance that is not finite or whose magnitude is above 1e6; n_levels outside [1, IBA_REFRESH_MAX_LEVELS]; a scale table
+ * that is not finite, does not start at 1 or does not ascend strictly; obs_off not ascending from 0; an observation's keyframe or keypoint out of
+ * range; one keyframe twice in a point's list (a std::map cannot hold that); an octave of an observed keypoint outside [0, n_levels) of its
+ * keyframe; a listed point, or the ref_keyframe of a listed point, outside its range; the stage accessor on a result without keep_stages. A listed
+ * point with more than IBA_REFRESH_MAX_OBS observations, or 2^31 observations or keypoints in a call, answer IBA_ERR_UNSUPPORTED.
+ */
+/* 1024: a block's LDS holds the descriptors (32 KiB), terms and keyframes of one point. The reference's own `int Distances[N][N]` on the stack is
+ * 4 MiB there and passes the default 8 MiB stack at N = 1449. */
+#define IBA_REFRESH_MAX_OBS 1024
+#define IBA_REFRESH_MAX_LEVELS 64
+typedef enum iba_refresh_status { IBA_REFRESH_REFRESHED = 0, IBA_REFRESH_BAD = 1, IBA_REFRESH_EMPTY = 2 } iba_refresh_status;
+typedef enum iba_refresh_desc_state { IBA_REFRESH_DESC_NONE = 0, IBA_REFRESH_DESC_PICKED = 1, IBA_REFRESH_DESC_KEPT = 2 } iba_refresh_desc_state;
+typedef enum iba_refresh_geo_state {
+    IBA_REFRESH_GEO_NONE = 0, IBA_REFRESH_GEO_UPDATED = 1, IBA_REFRESH_GEO_NO_REF = 2, IBA_REFRESH_GEO_DEGENERATE = 3
+} iba_refresh_geo_state;
+typedef enum iba_refresh_path { IBA_REFRESH_PATH_NARROW = 0, IBA_REFRESH_PATH_WAVE = 1, IBA_REFRESH_PATH_BLOCK = 2 } iba_refresh_path;
+typedef struct iba_refresh_keyframe {         /* host pointers, read during the call only */
+    int32_t frame;                  /* index into the call's frame array */
+    int32_t n_levels;               /* entries of scale_factors, 1..IBA_REFRESH_MAX_LEVELS */
+    const float* Tcw12;             /* 3 x 4 row-major float32: the keyframe's pose */
+    const float* scale_factors;     /* n_levels: mvScaleFactors, [0] == 1, ascending */
+    int32_t bad;                    /* KeyFrame::isBad() */
+    int32_t reserved;               /* 0 */
+} iba_refresh_keyframe;
+typedef struct iba_refresh_options {
+    int32_t struct_size;        /* sizeof(iba_refresh_options) */
+    int32_t keep_stages;        /* 0; 1 keeps the median of every row for iba_refreshed_medians */
+} iba_refresh_options;
+typedef struct iba_refresh_counts {
+    int32_t n_points;
+    int32_t status[3];          /* by iba_refresh_status */
+    int32_t desc_state[3];      /* by iba_refresh_desc_state */
+    int32_t geo_state[4];       /* by iba_refresh_geo_state */
+    int32_t n_desc_changed;
+    int32_t path[3];            /* by iba_refresh_path: the points each device shape took */
+    int32_t n_rows;             /* keep_stages: the entries of iba_refreshed_medians */
+} iba_refresh_counts;
+typedef struct iba_refreshed iba_refreshed;
+iba_status iba_default_refresh_options(iba_refresh_options* opt);
+const char* iba_refresh_last_error(void);                            /* never NULL; of this thread's last iba_refresh* call that failed */
+/* *out is NULL on failure; release it with iba_refreshed_free */
+iba_status iba_refresh(const iba_orb_frame* frames, int32_t F, const iba_refresh_keyframe* keyframes, int32_t K, const iba_map_points* points, const uint8_t* point_bad,
+                       const int32_t* ref_keyframe, const int32_t* obs_off, const int32_t* obs_keyframe, const int32_t* obs_keypoint, const int32_t* list, int32_t n,
+                       const iba_refresh_options* opt, int device, iba_refreshed** out);
+void       iba_refreshed_free(iba_refreshed* r);
+int32_t    iba_refreshed_n(const iba_refreshed* r);                  /* the listed points; 0 for NULL */
+iba_status iba_refreshed_counts(const iba_refreshed* r, iba_refresh_counts* counts);
+/* S7 per listed point, n entries each (normal n x 3, desc n x 32); any may be NULL */
+iba_status iba_refreshed_read(const iba_refreshed* r, uint8_t* status, uint8_t* desc_state, uint8_t* geo_state, int32_t* best_obs, int32_t* best_median, int32_t* n_desc, float* normal,
+                              float* min_dist, float* max_dist, uint8_t* desc);
+/* keep_stages only: off[n + 1] and the medians (n_rows entries); either may be NULL */
+iba_status iba_refreshed_medians(const iba_refreshed* r, int32_t* off, int32_t* median);
+/* host only, pure: obs_off takes map->P + 1 entries, obs_keyframe and obs_keypoint up to map->kp_off[map->K] each (obs_off[P] are written) */
+iba_status iba_refresh_observations(const iba_fuse_map* map, int32_t* obs_off, int32_t* obs_keyframe, int32_t* obs_keypoint);
+/* host only, pure: the REFRESHED entries of r into the table's arrays of P points (normal P x 3, desc P x 32); descriptor_stale may be NULL */
+iba_status iba_refresh_store(const iba_refreshed* r, int32_t P, float* normal, float* min_dist, float* max_dist, uint8_t* desc, uint8_t* descriptor_stale);
+
+/*
  * ---- Bundle adjustment [the camera side's fifth brick: the reference's Optimizer::BundleAdjustment (src/orb_slam/src/Optimizer.cc:215-407: the global
  * BA of Tracking::CreateInitialMapMonocular, Tracking.cc:686, and of LoopClosing.cc:651) and Optimizer::LocalBundleAdjustment from its "Setup
  * optimizer" on (:671-937, LocalMapping.cc:80)] ----
@@ -2187,6 +2317,8 @@ iba_status iba_fuse_candidates(const iba_fuse_map* map, const int32_t* targets, 
  * more than IBA_BUNDLE_MAX_FREE_CAMERAS free cameras; 2^31 pair items or more; rounds outside 1..4, iterations[r] outside 1..100, robust_rounds
  * outside 0..4, a threshold or delta that is not finite, chi2_threshold < 0, huber_delta <= 0; a job or round index outside the result; the stage
  * accessor on a result without keep_stages.
+ * AFTER A CALL the reference runs UpdateNormalAndDepth() on every point it moved (Optimizer.cc:397, :936, :1200): write the optimised poses and
+ * points into the keyframe and point tables and call iba_refresh (S4 / S5 of the map-point refresh, above) on the moved points.
  */
 #define IBA_BUNDLE_MAX_FREE_CAMERAS 64
 #define IBA_BUNDLE_MAX_ROUNDS 4

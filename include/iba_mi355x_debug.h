@@ -70,6 +70,14 @@
  *                                                         iba_debug_fuse_stage_ms; tools/fuse_bench.py); same results
  *   IBA_FUSE_PICK_LANES                                   8 / 16 / 64: the lanes per slot of iba_fuse's pick kernel in place of the shipped width
  *                                                         (same results; A/B timing and the tests of all three)
+ *   IBA_REFRESH_TIMING                                    iba_refresh records HIP events around its three launches (iba_debug_refresh_stage_ms;
+ *                                                         tools/refresh_bench.py); same results
+ *   IBA_REFRESH_NARROW_LANES                              4 / 8 / 16 / 32: the lanes per point of iba_refresh's narrow shape in place of the shipped
+ *                                                         width (same results; A/B timing and the tests of all four)
+ *   IBA_REFRESH_MEDIAN                                    0: the binary search that recomputes a row's distances; 1: one pass that keeps the row (same
+ *                                                         results; A/B timing and the tests of both)
+ *   IBA_REFRESH_MIN_PATH                                  1 / 2: no listed point of iba_refresh takes a shape below the wave / the block shape (same
+ *                                                         results; the tests that run a whole scene on each wider shape)
  *   IBA_GROUP_REDUCE_HOST (flag of iba_group_create_ex, not a variable), IBA_DEBUG_FAIL_RANK / IBA_DEBUG_FAIL_PHASE: inject one
  *                                                         failure into a group's evaluation (tests of the fail-not-hang path)
  */
@@ -354,6 +362,16 @@ int32_t iba_debug_fuse_chunks(const iba_fusion* f);
 /* debug: with IBA_FUSE_TIMING set at the call (under IBA_DEBUG_ENV=1), times in ms from HIP events, summed over the chunks: [0] frustum, [1] grid
  * (cell, scan, fill) + list count, [2] scan + list write with the distances, [3] pick. Zeros without the variable. Same results. */
 iba_status iba_debug_fuse_stage_ms(const iba_fusion* f, float ms[4]);
+
+/* debug: iba_refresh as the host restatement of its rules (csrc/iba_refresh_host.hpp over csrc/iba_refresh_math.hpp, the text the kernels compile;
+ * S3's rank form through a histogram of every row), the whole call without a device; the same checks, the same result object and accessors,
+ * iba_refresh_store included; counts.path is zero. Byte for byte what the device gives (tests/test_gpu_refresh.py). */
+iba_status iba_debug_refresh_host(const iba_orb_frame* frames, int32_t F, const iba_refresh_keyframe* keyframes, int32_t K, const iba_map_points* points, const uint8_t* point_bad,
+                                  const int32_t* ref_keyframe, const int32_t* obs_off, const int32_t* obs_keyframe, const int32_t* obs_keypoint, const int32_t* list, int32_t n,
+                                  const iba_refresh_options* opt, iba_refreshed** out);
+/* debug: with IBA_REFRESH_TIMING set at the call (under IBA_DEBUG_ENV=1), times in ms from HIP events: [0] the narrow, [1] the wave, [2] the block
+ * launch. Zeros without the variable. Same results. */
+iba_status iba_debug_refresh_stage_ms(const iba_refreshed* r, float ms[3]);
 
 #ifdef __cplusplus
 }
