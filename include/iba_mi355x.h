@@ -2243,6 +2243,155 @@ iba_status iba_refresh_observations(const iba_fuse_map* map, int32_t* obs_off, i
 iba_status iba_refresh_store(const iba_refreshed* r, int32_t P, float* normal, float* min_dist, float* max_dist, uint8_t* desc, uint8_t* descriptor_stale);
 
 /*
+ * ---- Sim3 RANSAC between two keyframes [the camera side's tenth brick and the first of LoopClosing: the reference's Sim3Solver
+ * (src/orb_slam/src/Sim3Solver.cc), driven from LoopClosing::ComputeSim3 (LoopClosing.cc:231-342)] ----
+ * For J keyframe pairs in ONE call: a RANSAC over 3-point sets of matched map points. Horn's closed-form absolute orientation gives each
+ * hypothesis, every hypothesis is scored by reprojecting every correspondence both ways, and a sequential best / early-return rule picks the result.
+ * It is the only monocular step that recovers the scale drift around a loop. A call takes ONE table of P map points (iba_map_points: ONLY xyz and n
+ * are read) and J jobs; a job is the two keyframes' poses and intrinsics, n correspondences as table indices (point1 seen from keyframe 1, point2
+ * from keyframe 2), their thresholds and the 3-point sets. The iterations of a job are Z6's budget, computed by the call from n and the options; the
+ * job's sets hold max_iterations rows, of which the first `iterations` are read. Every iteration of every job is computed, whatever the events: the
+ * host has nothing to do between upload and download, and iba_sim3_iterate replays the reference's iterate(n) calls over the finished result.
+ * ARITHMETIC as in the two-view unit: float32 wherever the reference holds a float; every cv::Mat operation in float64 on the widened entries with
+ * ONE rounding per result element, sums left to right; no contraction. tests/sim3_ref.py restates every rule in numpy, sequentially as the reference
+ * runs; the device and the host restatement (iba_debug_sim3_host) are compared with it byte for byte. The float decisions are ONE text,
+ * csrc/iba_sim3_math.hpp.
+ *
+ *   Z1 thresholds. mvnMaxError is a vector<size_t>: the bound is (size_t)(9.210 * (double)sigma2), TRUNCATED (13 for 1.44f, not 13.26), and is
+ *                  compared as a float32 with err < bound. iba_sim3_correspondences writes that truncated value into max_err1 / max_err2; the device
+ *                  compares with max_err as given.
+ *   Z2 preparation. Per correspondence and camera: Xc_i = ((R_i0 X + R_i1 Y) + R_i2 Z) + t_i in float32, L1's order of sums. The image point
+ *                  (FromCameraToImage): invz = 1 / z in float32, correctly rounded, formed as (float)(1.0 / (double)z); u = fx * (x * invz) + cx,
+ *                  v = fy * (y * invz) + cy. There is NO test on z: a point at or behind the camera gives inf or NaN, which flow through as in the
+ *                  reference.
+ *   Z3 Horn.       (:226-337) P1, P2: the set's three points in camera 1 / 2 as columns. Per row the sum ((a + b) + c) in double, rounded; the
+ *                  centroid O = that sum / 3 in double, rounded; Pr = P - O. M = Pr2 Pr1^T, entry (i, j) = (float)(sum over k of Pr2_ik Pr1_jk).
+ *                  The ten entries of N in double from M's float32 entries, left to right as the reference writes them (N11 = (M00 + M11) + M22,
+ *                  N33 = (-M00 + M11) - M22, ...), stored as float32. The eigenvector of the greatest eigenvalue: a cyclic two-sided Jacobi in
+ *                  float64 on the widened 4 x 4, V = I; the pairs (p, q) in the order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); a pair with |a_pq| <=
+ *                  2^-53 (|a_pp| + |a_qq|) is left alone; else theta = (a_qq - a_pp) / (2 a_pq), t = sign(theta) / (|theta| + sqrt(1 + theta^2))
+ *                  with sign(0) = +1, c = 1 / sqrt(1 + t^2), s = c t; columns p, q of A and V become (c x_p - s x_q, s x_p + c x_q), then rows
+ *                  p, q of A likewise, then a_pq = a_qp = 0 exactly. A sweep without a rotation ends it; the cap is 30 sweeps. The eigenvalue
+ *                  is the greatest diagonal entry, the FIRST on a tie; its column of V narrowed to float32 is the quaternion (w, x, y, z).
+ *                  R is Z4's. P3 = R Pr2 (float32 entries of double sums); nom = the double sum over (i, j) in row-major order of Pr1_ij P3_ij;
+ *                  den = the double sum in the same order of the float32 squares P3_ij * P3_ij; s = (float)(nom / den), or 1.0f with fix_scale.
+ *                  sR = s R (float32); t = O1 - sR O2; T12 = [sR | t]; T21 = [Ri | -(Ri t)] with Ri_ij = (float)((1.0 / (double)s) * R_ji).
+ *   Z4 rotation.   R from the quaternion directly, in float64 with one rounding per entry: n = ((w^2 + x^2) + y^2) + z^2, R00 = 1 - 2 (y^2 + z^2) / n,
+ *                  R01 = 2 (x y - w z) / n, R02 = 2 (x z + w y) / n, R10 = 2 (x y + w z) / n, R11 = 1 - 2 (x^2 + z^2) / n, R12 = 2 (y z - w x) / n,
+ *                  R20 = 2 (x z - w y) / n, R21 = 2 (y z + w x) / n, R22 = 1 - 2 (x^2 + y^2) / n. Where sqrt((x^2 + y^2) + z^2) is 0 or not finite
+ *                  the reference divides by it: every entry of s, R, t, T12, T21 is then NaN and the hypothesis has 0 inliers.
+ *   Z5 score.      (:340-364) Project: p = T X as a matrix product (one rounding) plus the translation (float32), then the image point as in
+ *                  Z2. err1 from camera 2's point through T12 and K1 against camera 1's image point, err2 the other way: d = the float32
+ *                  differences, err = (float)(d_0^2 + d_1^2) in double. Inlier iff err1 < max_err1 && err2 < max_err2; a NaN never passes.
+ *   Z6 budget.     (:114-138, host only) eps = (float)min_inliers / N in float32. N == min_inliers: 1 iteration. Else
+ *                  ceil(log(1 - probability) / log(1 - pow((double)eps, 3))) clamped to [1, max_iterations]; where the quotient is not finite the
+ *                  library's own rule is max_iterations. log and pow are the host's libm.
+ *   Z7 the sequential rule. (:158-206) best = 0; the iterations in order; iteration `it` with n inliers REPLACES THE BEST iff n >= best: ties go to
+ *                  the LATER iteration, and an iteration with 0 inliers replaces a best of 0. It is an EVENT iff it also has n > min_inliers:
+ *                  an event is where the reference's iterate returns. The scan does not stop at an event: a caller whose optimiser refuses the
+ *                  result calls iterate again with the best retained. Hence events are numbered; the first max_events of a job are listed with
+ *                  their inlier bytes.
+ *   Z8 status.     OK: at least one event; the reference's find() is event 0. NO_MORE: no event within the budget. TOO_FEW: N < min_inliers
+ *                  (bNoMore at :146), decided on the host; such a job has 0 iterations. n_events counts ALL events, including those past max_events.
+ *
+ * HELPERS, host only, pure. iba_sim3_correspondences is the constructor's walk (:62-103) over an iba_fuse_map: the keypoints i1 of keyframe kf1 in
+ * ascending order; matches12[i1] < 0, holder(kf1, i1) < 0, either point bad, or either point held by no keypoint of its keyframe: skipped.
+ * WHERE A POINT IS HELD TWICE IN A KEYFRAME THE LOWEST KEYPOINT INDEX IS ITS GetIndexInKeyFrame. The thresholds are Z1's from the octave of that
+ * keypoint. iba_sim3_sets is the reference's swap-with-back draw (:163-177) over splitmix64. iba_sim3_budget is Z6. iba_sim3_iterate is ONE
+ * iterate(n) call as a fold over a finished result: from iteration from_it it walks at most n iterations; the first event among them ends it
+ * (*event = its number, *next_it = the iteration after it, *no_more = 0); else *event = -1 and *no_more = (*next_it >= iterations). A TOO_FEW job
+ * answers *event = -1, *no_more = 1. iba_sim3_compose is gScm * gSmw of LoopClosing.cc:333-335 in float64: R = Rcm Rmw, t = s (Rcm tmw) + tcm, s.
+ * UNPINNED, together: OpenCV's gemm, reduce, dot, cv::eigen and Rodrigues are not vendored and nothing here is compared with recorded OpenCV output;
+ * the eigenvector's sign (the rotation does not depend on it); the sets (the reference draws from DUtils::Random; sets is an INPUT so a caller can
+ * hand in the reference's own); libm in Z6. KNOWN DEVIATIONS: (1) Z4: the reference goes quaternion -> atan2 -> angle-axis -> cv::Rodrigues; the
+ * library forms the same rotation from the quaternion, which keeps libm transcendentals off the device and lets every byte be compared with numpy
+ * (profiles/sim3_parity.md measures the difference). (2) Z6's non-finite quotient.
+ * NOT PROVIDED: SearchByBoW (it needs the vocabulary), SearchBySim3, OptimizeSim3, the covisibility consistency check, CorrectLoop.
+ * DEVICE (csrc/iba_sim3_kernels.hpp), one launch chain per chunk of jobs: preparation (one lane per correspondence, Z2); hypotheses (one lane per
+ * (job, iteration), the Jacobi in registers; s, R, t and the two 3 x 4 transforms); the count kernel (Z5, the hot one: J x iterations x N two-way
+ * reprojections) in two forms - (a) a lane per hypothesis with the transforms in registers, the correspondences tiled through LDS
+ * (IBA_SIM3_TILE per tile) and read at a wave-uniform address, the count in a register; (b) a lane per correspondence, the hypothesis wave-uniform,
+ * coalesced loads, the count the popcount of a ballot; profiles/sim3_bench.md records both and names the shipped one -; selection (one wave per
+ * job: the best before an iteration is the running maximum of the counts before it, so every lane walks a run of consecutive iterations from a
+ * maximum scan's value as Z7 does, and a sum scan numbers the events); flags (the inlier bytes of the listed events and of the best only; per-iteration flags reach global memory
+ * only with keep_stages). Counts are integers and nothing is combined by an atomic: no result depends on an arrival order.
+ * MEMORY: a call is cut into chunks of consecutive jobs that stay under IBA_SIM3_BUDGET_BYTES, or under a quarter of the device memory free at the
+ * call where that is less; a chunk holds at least one job and a chunk boundary changes no byte. The result is host memory.
+ * ERRORS, all IBA_ERR_INVALID_ARG with a message (iba_sim3_last_error, per thread) BEFORE the device is touched: a NULL argument (a job's arrays
+ * may be NULL only where n == 0; sets only where n < min_inliers) or a wrong struct_size; J < 1; n < 0; a point index outside the table; a pose
+ * entry, table point, intrinsic or threshold that is not finite; fx or fy <= 0; probability outside (0, 1); min_inliers < 3; max_iterations outside
+ * 1..IBA_SIM3_MAX_ITERATIONS; max_events outside 1..IBA_SIM3_MAX_EVENTS; a set index outside [0, n) or repeated in its set; a job index outside
+ * the result; an event index at or above max_events ("raise max_events") or at or above the listed events; a stage accessor on a result without
+ * keep_stages. A job with N < min_inliers is legal and gets a status.
+ */
+#define IBA_SIM3_MAX_ITERATIONS 4096
+#define IBA_SIM3_MAX_EVENTS 16
+#define IBA_SIM3_TILE 256
+#define IBA_SIM3_BUDGET_BYTES (1ull << 30)
+typedef enum iba_sim3_status { IBA_SIM3_OK = 0, IBA_SIM3_NO_MORE = 1, IBA_SIM3_TOO_FEW = 2 } iba_sim3_status;
+typedef struct iba_sim3_job {                 /* host pointers, read during the call only */
+    const float*   Tcw12_1;        /* 3 x 4 row-major float32: keyframe 1's pose */
+    const float*   Tcw12_2;        /* keyframe 2's */
+    const int32_t* point1;         /* n table indices: mvpMapPoints1 */
+    const int32_t* point2;         /* n table indices: mvpMapPoints2 */
+    const float*   max_err1;       /* n: Z1 */
+    const float*   max_err2;       /* n */
+    const int32_t* sets;           /* max_iterations x 3 indices into the correspondence list, distinct inside a set; NULL only where n < min_inliers */
+    int32_t n;
+    int32_t reserved;              /* 0 */
+    float fx1, fy1, cx1, cy1;      /* mK1 */
+    float fx2, fy2, cx2, cy2;      /* mK2 */
+} iba_sim3_job;
+typedef struct iba_sim3_options {
+    int32_t struct_size;        /* sizeof(iba_sim3_options) */
+    int32_t min_inliers;        /* 20, >= 3 */
+    double  probability;        /* 0.99, inside (0, 1) */
+    int32_t max_iterations;     /* 300, 1..IBA_SIM3_MAX_ITERATIONS */
+    int32_t fix_scale;          /* 0; 1: s = 1.0f */
+    int32_t max_events;         /* 1, 1..IBA_SIM3_MAX_EVENTS */
+    int32_t keep_stages;        /* 0; 1 keeps every iteration's inlier bytes for iba_sim3_iterations */
+} iba_sim3_options;
+typedef struct iba_sim3_result {
+    int32_t status;             /* iba_sim3_status */
+    int32_t n;                  /* N */
+    int32_t iterations;         /* Z6; 0 for TOO_FEW */
+    int32_t n_events;           /* all of them */
+    int32_t n_listed;           /* min(n_events, max_events) */
+    int32_t best_it;            /* the iteration of the best after the last one; -1 for TOO_FEW */
+    int32_t best_inliers;
+    int32_t sweep_cap_hits;     /* iterations whose Jacobi ran to the cap */
+} iba_sim3_result;
+typedef struct iba_sim3_batch iba_sim3_batch;
+iba_status iba_default_sim3_options(iba_sim3_options* opt);
+const char* iba_sim3_last_error(void);                               /* never NULL; of this thread's last iba_sim3* call that failed */
+/* *out is NULL on failure; release it with iba_sim3_free */
+iba_status iba_sim3_solve(const iba_map_points* points, const iba_sim3_job* jobs, int32_t J, const iba_sim3_options* opt, int device, iba_sim3_batch** out);
+void       iba_sim3_free(iba_sim3_batch* r);
+int32_t    iba_sim3_n_jobs(const iba_sim3_batch* r);                 /* 0 for NULL */
+iba_status iba_sim3_read(const iba_sim3_batch* r, int32_t job, iba_sim3_result* result);
+/* the inliers of every iteration (`iterations` entries); always available */
+iba_status iba_sim3_counts(const iba_sim3_batch* r, int32_t job, int32_t* n_inliers_per_iteration);
+/* the k-th event, k < n_listed: its iteration, n_inliers, s, R, t and N inlier bytes; every output may be NULL */
+iba_status iba_sim3_event(const iba_sim3_batch* r, int32_t job, int32_t k, int32_t* iteration, int32_t* n_inliers, float* s, float R[9], float t[3], uint8_t* inlier);
+/* the same for the best after the last iteration (GetEstimated*); zeros and iteration -1 for a TOO_FEW job */
+iba_status iba_sim3_best(const iba_sim3_batch* r, int32_t job, int32_t* iteration, int32_t* n_inliers, float* s, float R[9], float t[3], uint8_t* inlier);
+/* keep_stages only: per iteration s (iterations), R (x 9), t (x 3) and the inlier bytes (iterations x N); every output may be NULL */
+iba_status iba_sim3_iterations(const iba_sim3_batch* r, int32_t job, float* s, float* R, float* t, uint8_t* inlier);
+/* host only, pure: the walk over keyframe kf1's n1 = kp_off[kf1 + 1] - kp_off[kf1] keypoints; matches12[n1] table indices or < 0; the octaves per keypoint
+ * of either keyframe, the level tables with n_levels entries; every output takes up to n1 entries (index1: mvnIndices1) and may be NULL; *n their number */
+iba_status iba_sim3_correspondences(const iba_fuse_map* map, int32_t kf1, int32_t kf2, const int32_t* matches12, const int32_t* octave1, const int32_t* octave2,
+                                    const float* level_sigma2_1, const float* level_sigma2_2, int32_t n_levels1, int32_t n_levels2, int32_t* index1, int32_t* point1,
+                                    int32_t* point2, float* max_err1, float* max_err2, int32_t* n);
+/* host only, pure: iterations x 3 indices, distinct inside a set; N >= 3 */
+iba_status iba_sim3_sets(int32_t N, int32_t iterations, uint64_t seed, int32_t* out);
+/* host only, pure: Z6; N >= 1 */
+iba_status iba_sim3_budget(int32_t N, const iba_sim3_options* opt, int32_t* iterations);
+/* host only, pure: one iterate(n) of the reference over a finished result; 0 <= from_it <= iterations, n >= 0 */
+iba_status iba_sim3_iterate(const iba_sim3_batch* r, int32_t job, int32_t from_it, int32_t n, int32_t* next_it, int32_t* event, int32_t* no_more);
+/* host only, pure: Scw = Scm * Smw in float64; Tmw12 is the matched keyframe's pose (3 x 4 float32) */
+iba_status iba_sim3_compose(float s, const float R[9], const float t[3], const float* Tmw12, double* s_out, double R_out[9], double t_out[3]);
+
+/*
  * ---- Bundle adjustment [the camera side's fifth brick: the reference's Optimizer::BundleAdjustment (src/orb_slam/src/Optimizer.cc:215-407: the global
  * BA of Tracking::CreateInitialMapMonocular, Tracking.cc:686, and of LoopClosing.cc:651) and Optimizer::LocalBundleAdjustment from its "Setup
  * optimizer" on (:671-937, LocalMapping.cc:80)] ----

@@ -78,6 +78,13 @@
  *                                                         results; A/B timing and the tests of both)
  *   IBA_REFRESH_MIN_PATH                                  1 / 2: no listed point of iba_refresh takes a shape below the wave / the block shape (same
  *                                                         results; the tests that run a whole scene on each wider shape)
+ *   IBA_SIM3_TIMING                                       iba_sim3_solve records HIP events around its five stages (iba_debug_sim3_stage_ms;
+ *                                                         tools/sim3_bench.py); same results
+ *   IBA_SIM3_COUNT_FORM                                   0 / 1: form (a), a lane per hypothesis, or form (b), a lane per correspondence, of
+ *                                                         iba_sim3_solve's count kernel in place of the shipped one (same results; A/B timing and
+ *                                                         the tests of both)
+ *   IBA_SIM3_BUDGET                                       the chunk budget of iba_sim3_solve in bytes in place of IBA_SIM3_BUDGET_BYTES (same results;
+ *                                                         the tests that cut a call into several chunks)
  *   IBA_GROUP_REDUCE_HOST (flag of iba_group_create_ex, not a variable), IBA_DEBUG_FAIL_RANK / IBA_DEBUG_FAIL_PHASE: inject one
  *                                                         failure into a group's evaluation (tests of the fail-not-hang path)
  */
@@ -372,6 +379,16 @@ iba_status iba_debug_refresh_host(const iba_orb_frame* frames, int32_t F, const 
 /* debug: with IBA_REFRESH_TIMING set at the call (under IBA_DEBUG_ENV=1), times in ms from HIP events: [0] the narrow, [1] the wave, [2] the block
  * launch. Zeros without the variable. Same results. */
 iba_status iba_debug_refresh_stage_ms(const iba_refreshed* r, float ms[3]);
+
+/* debug: iba_sim3_solve as the host restatement of its rules (csrc/iba_sim3_host.hpp over csrc/iba_sim3_math.hpp, the text the kernels compile),
+ * the whole call without a device; the same checks, the same result object and accessors. Byte for byte what the device gives
+ * (tests/test_gpu_sim3.py). */
+iba_status iba_debug_sim3_host(const iba_map_points* points, const iba_sim3_job* jobs, int32_t J, const iba_sim3_options* opt, iba_sim3_batch** out);
+/* debug: the chunks the call was cut into (0 from the host restatement) */
+int32_t    iba_debug_sim3_chunks(const iba_sim3_batch* r);
+/* debug: with IBA_SIM3_TIMING set at the call (under IBA_DEBUG_ENV=1), times in ms from HIP events, summed over the chunks: [0] preparation,
+ * [1] hypotheses, [2] the count kernel, [3] selection, [4] flags. Zeros without the variable. Same results. */
+iba_status iba_debug_sim3_stage_ms(const iba_sim3_batch* r, float ms[5]);
 
 #ifdef __cplusplus
 }
