@@ -18,6 +18,9 @@ STALE_IN_KEYFRAME in the keyframe that just received the survivor), `chain` (c i
 point). clean = True leaves the last two out: after the recipe every keypoint that sees a landmark then holds its survivor, which neither an erased
 twin nor a bad holder can. bit_noise flips up to that many descriptor bits per keypoint (profiles/fuse_parity.md: the descriptor deviation).
 
+large_scene(), limit_scene(), many_jobs_scene(): real frame sizes, a frame at the declared limit of keypoints, 139 jobs in a call; SIZES names each
+with the conditions that are asserted on the reference's results (profiles/local_mapping_shapes.md).
+
 e2e_scene(): the chain from iba_triangulate; see there."""
 import numpy as np
 
@@ -101,6 +104,78 @@ def random_scene(seed=9, n_families=100, n_kp=300):
             R.make_job(1, near1, K, SF, LV, TH, np.concatenate([sub[1:130], sub[1:130]])),             # 6: 258 with every entry twice
             R.make_job(2, poses[0], K, SF, LV, TH)]                                                    # 7: the empty frame
     return {"frames": frames, "table": table, "jobs": jobs}
+
+
+def large_scene(seed=9):
+    """random_scene() at the caller's frame size: P = 2100 points (9 frustum and pick blocks in job 0) over frames of 2100 keypoints. Random depths
+    give no NOT_FINITE, so the last job looks along z from exactly point 0's depth: PcZ == 0 for it"""
+    sc = random_scene(seed, 700, 2100)
+    T = IDENTITY.copy()
+    T[2, 3] = -sc["table"]["xyz"][0, 2]
+    sc["jobs"].append(R.make_job(0, T, K, SF, LV, TH, np.arange(300, dtype=np.int32)))
+    return sc
+
+
+def limit_scene():
+    """the frame of exactly IBA_ORB_MATCH_MAX_KEYPOINTS keypoints and the table of map_match_scene.limit_scene(): every planted keypoint lies within
+    a pixel of its point's projection and within 24 bits of its descriptor, so its point picks it; job 1 is the list reversed with a wider window"""
+    base = MS.limit_scene()
+    P = len(base["table"]["min_dist"])
+    jobs = [R.make_job(0, IDENTITY, K, SF, LV, TH), R.make_job(0, IDENTITY, K, SF, LV, 5.0, np.arange(P, dtype=np.int32)[::-1].copy())]
+    return {"frames": base["frames"], "table": base["table"], "jobs": jobs, "where": base["where"], "point_of_kp": base["point_of_kp"]}
+
+
+def many_jobs_scene(seed=27, n_jobs=139):
+    """n_jobs jobs over the table and the three frames of random_scene() (frame 2 is empty): the frame cycles with j, the list length through
+    map_match_scene.MANY_LENGTHS every three jobs, three poses, th from three values, NULL entries and skip bytes on every fourth job. The
+    first, the middle and the last job have 257, 256 and 255 points in frame 0"""
+    base = random_scene()
+    rng = np.random.default_rng(seed)
+    P = len(base["table"]["min_dist"])
+    poses = [pose(0.01, -0.02, 0.015, (0.05, -0.03, 0.1)), pose(-0.02, 0.03, -0.01, (-0.2, 0.05, 0.3)), pose(-0.02, 0.03, -0.01, (-0.21, 0.05, 0.3))]
+    jobs = []
+    for j in range(n_jobs):
+        frame, L = j % 3, MS.MANY_LENGTHS[(j // 3 + 4) % 6]
+        T = poses[frame if (j // 18) % 3 != 2 else (j + 1) % 3]          # its frame's own pose, or the next frame's
+        pts = None if L is None else rng.permutation(P)[:L].astype(np.int32)
+        skip = None
+        if j % 4 == 1:
+            skip = rng.uniform(size=P if L is None else L) < 0.1
+            if pts is not None:
+                pts[rng.uniform(size=L) < 0.1] = -1
+        jobs.append(R.make_job(frame, T, K, SF, LV, (3.0, 4.0, 5.0)[(j // 2) % 3], pts, skip))
+    return {"frames": base["frames"], "table": base["table"], "jobs": jobs}
+
+
+# ---- the conditions of the three scenes above, asserted on the REFERENCE's results before anything is compared with them ----
+
+def check_large(sc, refs):
+    total = np.sum([r["counts"] for r in refs], 0)
+    assert refs[0]["n_points"] == 2100 == len(sc["frames"][0]["octave"]) and -(-refs[0]["n_points"] // 256) == 9
+    assert np.all(total > 0) and sum(r["n_gated_winner"] for r in refs) > 0, total
+    assert max(int(r["match"].max()) for r in refs if r["n_points"]) >= 2080 and refs[-1]["status"][0] == R.NOT_FINITE
+
+
+def check_limit(sc, refs):
+    n = MS.N_LIMIT
+    pk = sc["point_of_kp"]
+    assert len(sc["frames"][0]["octave"]) == n and refs[0]["n_candidates"] > 0
+    for c, p in pk.items():
+        assert refs[0]["status"][p] == R.PICKED and refs[0]["match"][p] == c, (c, p)
+    assert int(np.sum((refs[0]["status"] == R.PICKED) & (refs[0]["match"] >= n - 32))) >= 32 and refs[0]["match"][pk[n - 1]] == n - 1
+    P = refs[0]["n_points"]
+    assert refs[1]["match"][P - 1 - pk[n - 1]] == n - 1 and refs[1]["match"][P - 1 - pk[8192]] == 8192
+
+
+def check_many(sc, refs):
+    n = len(refs)
+    assert n >= 130 and {r["n_points"] for r in refs} == {0, 1, 255, 256, 257, 300} and {j["frame"] for j in sc["jobs"]} == {0, 1, 2}
+    assert len(sc["frames"][2]["octave"]) == 0 and len({j["Tcw"].tobytes() for j in sc["jobs"]}) >= 3 and sum(j["skip"] is not None for j in sc["jobs"]) > 10
+    assert sum(r["n_picked"] > 0 for r in refs) > 40 and sum(r["n_gated_winner"] for r in refs) > 0
+    assert [(sc["jobs"][j]["frame"], refs[j]["n_points"]) for j in (0, n // 2, n - 1)] == [(0, 257), (0, 256), (0, 255)] and all(refs[j]["n_picked"] > 0 for j in (0, n // 2, n - 1))
+
+
+SIZES = {"large": (large_scene, check_large), "limit": (limit_scene, check_limit), "many": (many_jobs_scene, check_many)}      # scene -> (builder, conditions on the reference)
 
 
 # ---- the map scene ----

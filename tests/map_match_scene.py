@@ -7,7 +7,10 @@ lie at chosen distances from the point's. `where` names the table index of every
 occurs before they compare anything with it.
 
 random_scene(): two posed frames over one table with families of near-identical points (ratio refusals, claim chains), the job shapes of the issue
-and an empty frame.  e2e_scene(): noise-free, distinct descriptors."""
+and an empty frame.  e2e_scene(): noise-free, distinct descriptors.
+
+large_scene(), limit_scene(), many_jobs_scene(): real frame sizes, a frame at the declared limit of keypoints, 139 jobs in a call; SIZES names each
+with the conditions that are asserted on the reference's results (profiles/local_mapping_shapes.md)."""
 import numpy as np
 
 import map_match_ref as R
@@ -210,6 +213,115 @@ def random_scene(seed=5, n_families=100, n_kp=450):
             R.make_job(1, near1, K, SF[:3], 1.0, sub[1:257]),                                                           # 7: 256, another pose and a short scale table
             R.make_job(2, poses[0], K, SF, 1.0)]                                                                        # 8: the empty frame
     return {"frames": frames, "table": table, "jobs": jobs}
+
+
+def large_scene(seed=5):
+    """random_scene() at the caller's frame size: P = 2100 points (9 frustum blocks in job 0) over frames of 2100 = 65 * 32 + 20 keypoints, so that the
+    last word of the claimed bitmap is partly in range. The last job is job 0 again with three keypoints in ten occupied (the subset jobs' occupied
+    bytes happen to miss the last word)"""
+    sc = random_scene(seed, 700, 2100)
+    j0 = sc["jobs"][0]
+    occ = np.random.default_rng(seed + 1).uniform(size=2100) < 0.3
+    sc["jobs"].append(R.make_job(j0["frame"], j0["Tcw"], j0["K"], j0["scale_factors"], j0["th"], None, None, occ))
+    return sc
+
+
+N_LIMIT = 32768                              # IBA_ORB_MATCH_MAX_KEYPOINTS
+LIMIT_PLANTED = (0, 8191, 8192) + tuple(range(N_LIMIT - 32, N_LIMIT))
+
+
+def limit_scene(seed=3):
+    """one frame of exactly N_LIMIT keypoints under the identity pose. Random positions and descriptors alone give no match (distances near 128), so
+    the cases are planted: every keypoint of LIMIT_PLANTED (index 0, the two sides of 8192 and the whole last bitmap word) sits half a pixel from
+    its own site (40 pixels apart) with its point's predicted level as octave and a descriptor 5 to 24 bits from its point's. `point_of_kp` names
+    the table index of every planted keypoint's point. Two more points: `second` projects onto the site of keypoint N_LIMIT - 1 after that
+    keypoint's own point (the claim is read back from the last word: nothing is left for it); keypoint `occupied_kp`, in the last word, is occupied
+    in job 0 and free in job 1, and so is keypoint 8191."""
+    b = _Builder(seed)
+    rng = b.rng
+    n = N_LIMIT
+    kxy = np.stack([rng.uniform(5, 635, n), rng.uniform(5, 475, n)], 1)
+    koct = rng.integers(0, 8, n)
+    kdesc = rng.integers(0, 256, (n, 32)).astype(np.uint8)
+    point_of_kp = {}
+    for s, c in enumerate(LIMIT_PLANTED):
+        level = s % 8
+        p, (px, py) = b.site_point("kp%d" % c, s, level)
+        kxy[c], koct[c], kdesc[c] = (px + 0.5, py + 0.25), level, at_distance(b.desc[p], 5 + s % 20, rng)
+        point_of_kp[c] = p
+    last = LIMIT_PLANTED.index(n - 1)
+    b.site_point("second", last, last % 8, flip(b.desc[point_of_kp[n - 1]], range(3)))
+    frame = M.make_frame(kxy, koct, np.zeros(n), kdesc, BOUNDS)
+    table = R.make_table(b.xyz, b.normal, b.min_d, b.max_d, b.desc)
+    occupied_kp = n - 18
+    occ = np.zeros(n, np.uint8); occ[[8191, occupied_kp]] = 1
+    occ[rng.choice(np.setdiff1d(np.arange(n), LIMIT_PLANTED), 500, replace=False)] = 1
+    jobs = [R.make_job(0, IDENTITY, K, SF, 1.0, None, None, occ), R.make_job(0, IDENTITY, K, SF, 1.0)]
+    return {"frames": [frame], "table": table, "jobs": jobs, "where": b.where, "point_of_kp": point_of_kp, "occupied_kp": occupied_kp}
+
+
+MANY_LENGTHS = (0, 1, 255, 256, 257, None)     # None: points == NULL, the whole table
+
+
+def many_jobs_scene(seed=21, n_jobs=139):
+    """n_jobs jobs over the table and the three frames of random_scene() (frame 2 is empty): the frame cycles with j, the list length through
+    MANY_LENGTHS every three jobs, three poses, th from three values, skip bytes on every fourth job and occupied bytes on every fifth. The first, the middle and the
+    last job have 257, 256 and 255 points in frame 0"""
+    base = random_scene()
+    rng = np.random.default_rng(seed)
+    P = len(base["table"]["min_dist"])
+    poses = [pose(0.01, -0.02, 0.015, (0.05, -0.03, 0.1)), pose(-0.02, 0.03, -0.01, (-0.2, 0.05, 0.3)), pose(-0.02, 0.03, -0.01, (-0.21, 0.05, 0.3))]
+    jobs = []
+    for j in range(n_jobs):
+        frame, L = j % 3, MANY_LENGTHS[(j // 3 + 4) % 6]
+        T = poses[frame if (j // 18) % 3 != 2 else (j + 1) % 3]          # its frame's own pose, or the next frame's
+        pts = None if L is None else rng.permutation(P)[:L].astype(np.int32)
+        n, nk = P if L is None else L, len(base["frames"][frame]["octave"])
+        skip = rng.uniform(size=n) < 0.1 if j % 4 == 1 else None
+        occ = rng.uniform(size=nk) < 0.1 if j % 5 == 2 else None
+        jobs.append(R.make_job(frame, T, K, SF, (1.0, 3.0, 5.0)[(j // 2) % 3], pts, skip, occ))
+    return {"frames": base["frames"], "table": base["table"], "jobs": jobs}
+
+
+# ---- the conditions of the three scenes above, asserted on the REFERENCE's results before anything is compared with them ----
+
+def check_large(sc, refs):
+    """2100 points and keypoints: 9 blocks of 256 slots in job 0, a partial last bitmap word that is claimed and that is seeded from `occupied`"""
+    free, taken = refs[0], refs[9]
+    assert free["n_points"] == 2100 == len(sc["frames"][0]["octave"]) and 2100 % 32 == 20 and -(-free["n_points"] // 256) == 9
+    assert max(int(r["match"].max()) for r in refs if r["n_points"]) >= 2080 and free["match"].max() == 2099
+    occ = sc["jobs"][9]["occupied"]
+    assert sc["jobs"][0]["occupied"] is None and all(same_bytes(sc["jobs"][0][k], sc["jobs"][9][k]) for k in ("Tcw", "scale_factors")) and same_bytes(free["off"], taken["off"])
+    # an occupied keypoint of the last word is the nearest candidate of a point: free, the point takes it; occupied, it does not
+    high = [k for k in range(2100) if free["match"][k] >= 2080 and occ[free["match"][k]]]
+    assert high and all(taken["match"][k] != free["match"][k] for k in high) and np.all(taken["point_of"][occ != 0] == -1)
+    assert int(np.sum(taken["match"] >= 2080)) > 0 and taken["n_second_choice"] > 0
+
+
+def check_limit(sc, refs):
+    n = N_LIMIT
+    w, pk, taken, free = sc["where"], sc["point_of_kp"], refs[0], refs[1]
+    assert len(sc["frames"][0]["octave"]) == n and taken["n_candidates"] > 0
+    assert taken["match"][pk[n - 1]] == n - 1 and taken["match"][pk[0]] == 0 and taken["match"][pk[8192]] == 8192 and taken["point_of"][n - 1] == pk[n - 1]
+    # the claim of keypoint n - 1 is read back: the second point on its site finds it among its candidates and is refused
+    a, b = taken["off"][w["second"]], taken["off"][w["second"] + 1]
+    assert n - 1 in taken["index"][a:b] and taken["match"][w["second"]] == -1 and pk[n - 1] < w["second"]
+    # occupied keypoints in the last word and below 8192 are refused to their points
+    for c in (sc["occupied_kp"], 8191):
+        assert sc["jobs"][0]["occupied"][c] and taken["match"][pk[c]] == -1 and free["match"][pk[c]] == c, c
+    assert sc["occupied_kp"] >= n - 32 and all(free["match"][p] == c for c, p in pk.items()) and free["n_matches"] == len(pk) == taken["n_matches"] + 2
+
+
+def check_many(sc, refs):
+    assert len(refs) >= 130 and {r["n_points"] for r in refs} == {0, 1, 255, 256, 257, 300} and {j["frame"] for j in sc["jobs"]} == {0, 1, 2}
+    assert len(sc["frames"][2]["octave"]) == 0 and len({j["Tcw"].tobytes() for j in sc["jobs"]}) >= 3
+    assert sum(j["skip"] is not None for j in sc["jobs"]) > 10 and sum(j["occupied"] is not None for j in sc["jobs"]) > 10
+    assert sum(r["n_matches"] > 0 for r in refs) > 40 and sum(r["n_second_choice"] for r in refs) > 0
+    n = len(refs)
+    assert [(sc["jobs"][j]["frame"], refs[j]["n_points"]) for j in (0, n // 2, n - 1)] == [(0, 257), (0, 256), (0, 255)] and all(refs[j]["n_matches"] > 0 for j in (0, n // 2, n - 1))
+
+
+SIZES = {"large": (large_scene, check_large), "limit": (limit_scene, check_limit), "many": (many_jobs_scene, check_many)}      # scene -> (builder, conditions on the reference)
 
 
 def e2e_scene(seed=11, P=200):

@@ -71,3 +71,48 @@ def claim_job(frames, a, b, th=15.0, n_queries=None, seed=0):
     q = R.motion_queries(f, has, outl, X, np.eye(3, 4, dtype=F), fx, fy, cx, cy, frames[b]["bounds"], SCALE_FACTORS, th)
     k = n if n_queries is None else n_queries
     return dict({key: v[:k] for key, v in q.items()}, query_frame=a, train_frame=b, rule=R.CLAIM)
+
+
+N_LIMIT = 32768                              # IBA_ORB_MATCH_MAX_KEYPOINTS
+FILL_FIRST, FILL_N, FILL_CELL = 16384, 150, (20, 10)
+LIMIT_TARGETS = (0, 8191, 8192) + tuple(range(N_LIMIT - 32, N_LIMIT)) + tuple(range(FILL_FIRST + 60, FILL_FIRST + 70))
+
+
+def limit_scene(seed=17, n_queries=300):
+    """frame 0: exactly N_LIMIT keypoints at random places, about ten per cell. The FILL_N keypoints from index FILL_FIRST (a multiple of 64) on lie
+    in the one cell FILL_CELL and nothing else does: two whole trips of the ordered fill have all 64 lanes in that cell and a third has 22. Frame 1:
+    n_queries keypoints, each half a pixel from a keypoint of frame 0 with its angle and its descriptor within 6 bits: LIMIT_TARGETS first (index 0,
+    the two sides of 8192, the last 32, ten of the filled cell), then random ones; every eighth repeats its predecessor's target. One CLAIM job from
+    frame 1 into frame 0, whose state is in global memory at this size"""
+    rng = np.random.default_rng(seed)
+    n = N_LIMIT
+    xy = np.stack([rng.uniform(5, 635, n), rng.uniform(5, 475, n)], 1).astype(F)
+    fill = np.arange(FILL_FIRST, FILL_FIRST + FILL_N)
+    cx, cy = 10.0 * FILL_CELL[0], 10.0 * FILL_CELL[1]                        # ten pixels per cell: the cell's centre
+    inside = (np.abs(xy[:, 0] - F(cx)) <= 5) & (np.abs(xy[:, 1] - F(cy)) <= 5)
+    xy[inside, 0] += F(20.0)
+    xy[fill] = np.stack([rng.uniform(cx - 4, cx + 4, FILL_N), rng.uniform(cy - 4, cy + 4, FILL_N)], 1)
+    train = R.make_frame(xy, rng.integers(0, 3, n), rng.uniform(0, 360, n).astype(F), rng.integers(0, 256, (n, 32)), BOUNDS)
+    target = np.concatenate([LIMIT_TARGETS, rng.choice(n, n_queries - len(LIMIT_TARGETS), replace=False)]).astype(np.int64)
+    target[7::8] = target[6::8][:len(target[7::8])]
+    qdesc = np.array([flip(train["desc"][t], rng.choice(256, k % 7, replace=False)) for k, t in enumerate(target)], np.uint8)
+    query = R.make_frame(train["xy"][target] + F(0.5), train["octave"][target], train["angle"][target], qdesc, BOUNDS)
+    k = n_queries
+    job = {"query_frame": 1, "train_frame": 0, "rule": R.CLAIM, "centre_xy": query["xy"].copy(), "radius": np.full(k, 12.0, F), "level_range": np.tile(np.array([-1, -1], np.int32), (k, 1)),
+           "query_index": np.arange(k, dtype=np.int32), "valid": None}
+    return {"frames": [train, query], "jobs": [job], "target": target}
+
+
+def check_limit(sc, grids, refs):
+    """the conditions of limit_scene(), on the REFERENCE's grid and results"""
+    n, r, target = N_LIMIT, refs[0], sc["target"]
+    off, lst = grids[0]
+    assert len(sc["frames"][0]["octave"]) == n and off[-1] == n and FILL_FIRST % 64 == 0 and FILL_N >= 130 and FILL_N % 64
+    cell = FILL_CELL[0] * R.ROWS + FILL_CELL[1]
+    assert lst[off[cell]:off[cell + 1]].tolist() == list(range(FILL_FIRST, FILL_FIRST + FILL_N))
+    assert int(np.max(np.diff(off))) == FILL_N and int(np.sum(np.diff(off) > 0)) > 2500
+    # the window job reads the filled cell, and claims up to the last keypoint
+    assert r["max_segment"] >= FILL_N and all(r["match"][k] == target[k] for k in range(len(LIMIT_TARGETS)) if k % 8 != 7)
+    assert n - 1 in r["match"] and int(np.sum(r["match"] >= n - 32)) >= 28 and r["n_matches"] > 250
+    again = [k for k in range(7, len(target), 8)]                            # a repeated target is taken: the query gets another keypoint or none
+    assert all(r["match"][k] != target[k] for k in again) and all(r["match"][k - 1] == target[k] for k in again)

@@ -132,6 +132,8 @@ def test_argument_checks(fz, mm, om, err, hand):
     # frames: what iba_orb_match refuses
     f0 = sc["frames"][0]
     _expect(err, lambda: call(frames=[om.frame(f0["xy"], f0["octave"], f0["angle"], f0["desc"], (0, 0, 0, 480))]), "max <= min")
+    big = S.MS.N_LIMIT + 1
+    _expect(err, lambda: call(frames=[om.frame(np.zeros((big, 2), F), np.zeros(big, np.int32), np.zeros(big, F), np.zeros((big, 32), np.uint8), S.BOUNDS)]), "frame 0: n outside [0, %d]" % S.MS.N_LIMIT)
     # jobs
     _expect(err, lambda: call(jobs=[job(frame=1)]), "a frame index outside")
     _expect(err, lambda: call(jobs=[job(frame=-1)]), "a frame index outside")
@@ -281,6 +283,20 @@ def test_random_scene(fz, mm, om, rand):
     assert sum(r["n_gated_winner"] for r in refs) > 0 and sum(r["n_picked"] for r in refs) > 30 and len(set(refs[0]["level"][refs[0]["status"] == R.PICKED].tolist())) >= 4
     assert refs[7]["counts"][R.NO_CANDIDATE] > 0 and refs[7]["n_candidates"] == 0 and refs[7]["n_picked"] == 0
     assert S.same_bytes(refs[6]["match"][:129], refs[6]["match"][129:])               # a duplicated entry gets the same pick: slots are independent
+    fr, tb, jb = S.lib_args(fz, mm, om, sc)
+    m = fz.fuse_host(fr, tb, jb, keep_stages=1)
+    S.assert_equal(m, refs)
+    m.close()
+
+
+# ---- real frame sizes, the declared limit and many jobs: the conditions on the reference, then the host restatement ----
+
+@pytest.mark.parametrize("name", sorted(S.SIZES))
+def test_sizes_on_the_host(fz, mm, om, name):
+    make, check = S.SIZES[name]
+    sc = make()
+    refs = R.run(sc["frames"], sc["table"], sc["jobs"])
+    check(sc, refs)
     fr, tb, jb = S.lib_args(fz, mm, om, sc)
     m = fz.fuse_host(fr, tb, jb, keep_stages=1)
     S.assert_equal(m, refs)

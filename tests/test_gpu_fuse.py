@@ -97,6 +97,76 @@ def test_chunking_changes_no_byte(fz, mm, om, scenes, monkeypatch):
         cut.close()
 
 
+# ---- real frame sizes, the declared limit, many jobs (the scenes and their conditions: tests/fuse_scene.py, SIZES) ----
+
+@pytest.fixture(scope="module")
+def sizes():
+    made = {}
+
+    def get(name):
+        if name not in made:
+            make, check = S.SIZES[name]
+            sc = make()
+            refs = R.run(sc["frames"], sc["table"], sc["jobs"])
+            check(sc, refs)
+            made[name] = (sc, refs)
+        return made[name]
+    return get
+
+
+@pytest.mark.parametrize("name", ["large", "limit"])
+def test_real_sizes_and_the_limit(fz, mm, om, sizes, name):
+    """2100 points over 2100 keypoints (9 frustum and pick blocks per job, every status); one frame of IBA_ORB_MATCH_MAX_KEYPOINTS keypoints with
+    picks in its last 32"""
+    sc, refs = sizes(name)
+    fr, tb, jb = S.lib_args(fz, mm, om, sc)
+    dev = fz.fuse(fr, tb, jb, keep_stages=1)
+    assert dev.n_chunks == 1
+    S.assert_equal(dev, refs)
+    host = fz.fuse_host(fr, tb, jb, keep_stages=1)
+    S.same_results(dev, host, len(jb))
+    host.close()
+    dev.close()
+
+
+@pytest.mark.parametrize("lanes", [8, 16, 64])
+def test_pick_widths_at_real_sizes(fz, mm, om, sizes, monkeypatch, lanes):
+    sc, refs = sizes("large")
+    fr, tb, jb = S.lib_args(fz, mm, om, sc)
+    monkeypatch.setenv("IBA_DEBUG_ENV", "1")
+    monkeypatch.setenv("IBA_FUSE_PICK_LANES", str(lanes))
+    dev = fz.fuse(fr, tb, jb, keep_stages=1)
+    S.assert_equal(dev, refs)
+    dev.close()
+
+
+def test_many_jobs_in_one_call_and_in_chunks(fz, mm, om, sizes, monkeypatch):
+    """139 jobs: one chunk by default; a budget that cuts them into a few chunks and a budget of 1 (a chunk per job that has candidates) change no byte; a job alone
+    gives the bytes of its slice"""
+    sc, refs = sizes("many")
+    cand = [r["n_candidates"] for r in refs]
+    n = len(refs)
+    fr, tb, jb = S.lib_args(fz, mm, om, sc)
+    dev = fz.fuse(fr, tb, jb, keep_stages=1)
+    assert dev.n_chunks == 1
+    S.assert_equal(dev, refs)
+    dev.close()
+    monkeypatch.setenv("IBA_DEBUG_ENV", "1")
+    for budget in (6 * sum(cand) // 7, 1):
+        want = planned_chunks(cand, budget)
+        assert (3 <= want < n) if budget > 1 else n // 2 < want <= n, (budget, want)          # (a job without candidates starts no chunk)
+        monkeypatch.setenv("IBA_FUSE_BUDGET", str(budget))
+        cut = fz.fuse(fr, tb, jb, keep_stages=1)
+        monkeypatch.delenv("IBA_FUSE_BUDGET")
+        assert cut.n_chunks == want, (budget, cut.n_chunks, want)
+        S.assert_equal(cut, refs)
+        cut.close()
+    for j in (0, n // 2, n - 1):
+        alone = fz.fuse(fr, tb, [jb[j]], keep_stages=1)
+        S.assert_equal(alone, [refs[j]])
+        alone.close()
+
+
 def test_options_flip_the_recorded_cases(fz, mm, om, scenes):
     sc, refs = scenes["hand"]
     w, kp = sc["where"], sc["kp"]

@@ -100,6 +100,64 @@ def test_chunking_changes_no_byte(mm, om, scenes, monkeypatch):
         cut.close()
 
 
+# ---- real frame sizes, the declared limit, many jobs (the scenes and their conditions: tests/map_match_scene.py, SIZES) ----
+
+@pytest.fixture(scope="module")
+def sizes():
+    made = {}
+
+    def get(name):
+        if name not in made:
+            make, check = S.SIZES[name]
+            sc = make()
+            refs = R.run(sc["frames"], sc["table"], sc["jobs"])
+            check(sc, refs)
+            made[name] = (sc, refs)
+        return made[name]
+    return get
+
+
+@pytest.mark.parametrize("name", ["large", "limit"])
+def test_real_sizes_and_the_limit(mm, om, sizes, name):
+    """2100 points over 2100 keypoints (9 blocks per job, a partial last bitmap word, claimed and occupied); one frame of IBA_ORB_MATCH_MAX_KEYPOINTS
+    keypoints (the bitmap's last word, claimed and occupied)"""
+    sc, refs = sizes(name)
+    fr, tb, jb = S.lib_args(mm, om, sc)
+    dev = mm.match(fr, tb, jb, keep_stages=1)
+    assert dev.n_chunks == 1
+    S.assert_equal(dev, refs)
+    host = mm.match_host(fr, tb, jb, keep_stages=1)
+    same_results(dev, host, len(jb))
+    host.close()
+    dev.close()
+
+
+def test_many_jobs_in_one_call_and_in_chunks(mm, om, sizes, monkeypatch):
+    """139 jobs: one chunk by default; a budget that cuts them into a few chunks and a budget of 1 (a chunk per job that has candidates) change no byte; a job alone
+    gives the bytes of its slice"""
+    sc, refs = sizes("many")
+    cand = [r["n_candidates"] for r in refs]
+    n = len(refs)
+    fr, tb, jb = S.lib_args(mm, om, sc)
+    dev = mm.match(fr, tb, jb, keep_stages=1)
+    assert dev.n_chunks == 1
+    S.assert_equal(dev, refs)
+    dev.close()
+    for budget in (6 * sum(cand) // 7, 1):
+        want = planned_chunks(cand, budget)
+        assert (3 <= want < n) if budget > 1 else n // 2 < want <= n, (budget, want)          # (a job without candidates starts no chunk)
+        monkeypatch.setenv("IBA_MAP_MATCH_BUDGET", str(budget))
+        cut = mm.match(fr, tb, jb, keep_stages=1)
+        monkeypatch.delenv("IBA_MAP_MATCH_BUDGET")
+        assert cut.n_chunks == want, (budget, cut.n_chunks, want)
+        S.assert_equal(cut, refs)
+        cut.close()
+    for j in (0, n // 2, n - 1):
+        alone = mm.match(fr, tb, [jb[j]], keep_stages=1)
+        S.assert_equal(alone, [refs[j]])
+        alone.close()
+
+
 def test_end_to_end(mm, om):
     """iba_map_match -> iba_map_match_pose_edges -> iba_pose_optimize on the noise-free scene"""
     S.check_end_to_end(mm, om, importlib.import_module(PKG + ".pose"), host=False)

@@ -239,6 +239,18 @@ def test_train_state_in_global_memory(om):
     m.close()
 
 
+def test_a_frame_at_the_declared_limit(om):
+    """one CLAIM job into a frame of exactly IBA_ORB_MATCH_MAX_KEYPOINTS keypoints: the grid cell for cell (a cell that the ordered fill fills with
+    two whole trips of 64 consecutive keypoints and a part of a third), claims up to the last index with the state in global memory"""
+    sc = S.limit_scene()
+    grids, refs = R.run(sc["frames"], sc["jobs"])
+    S.check_limit(sc, grids, refs)
+    m = om.match(lib_frames(om, sc["frames"]), lib_jobs(om, sc["jobs"]), keep_stages=1)
+    compare(m, grids, refs)
+    assert m.n_chunks == 1
+    m.close()
+
+
 NQ = (300, 257, 129, 64, 300)
 
 

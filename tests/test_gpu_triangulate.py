@@ -96,6 +96,91 @@ def test_chunking_changes_no_byte(tr, om, scenes, monkeypatch):
         cut.close()
 
 
+# ---- real frame sizes, many neighbours, more than 1024 blocks (the scenes and their conditions: tests/triangulate_scene.py, SIZES) ----
+
+@pytest.fixture(scope="module")
+def sizes():
+    made = {}
+
+    def get(name):
+        if name not in made:
+            make, check = S.SIZES[name]
+            sc = make()
+            refs = R.run(sc["frames"], sc["keyframes"], sc["jobs"])
+            check(sc, refs)
+            made[name] = (sc, refs)
+        return made[name]
+    return get
+
+
+@pytest.mark.parametrize("name", ["large", "neighbours"])
+def test_real_sizes_and_many_neighbours(tr, om, sizes, name):
+    """frames of 1500 to 2100 keypoints over 200 nodes (32 blocks in job 0, more than 1024 keys per neighbour, segments above 64); one job with
+    eleven neighbours (points created and superseded at positions 5 to 10). Each call twice: every byte the same, the creation order included"""
+    sc, refs = sizes(name)
+    fr, kf, jb = S.lib_args(tr, om, sc)
+    dev = tr.triangulate(fr, kf, jb, keep_stages=1)
+    assert dev.n_chunks == 1
+    S.assert_equal(dev, refs)
+    host = tr.triangulate_host(fr, kf, jb, keep_stages=1)
+    S.same_results(dev, host, len(jb))
+    host.close()
+    again = tr.triangulate(fr, kf, jb, keep_stages=1)
+    S.same_results(dev, again, len(jb))
+    again.close()
+    dev.close()
+
+
+@pytest.mark.parametrize("lanes", [8, 16, 64])
+def test_pick_widths_at_real_sizes(tr, om, sizes, monkeypatch, lanes):
+    sc, refs = sizes("large")
+    fr, kf, jb = S.lib_args(tr, om, sc)
+    monkeypatch.setenv("IBA_DEBUG_ENV", "1")
+    monkeypatch.setenv("IBA_TRIANGULATE_PICK_LANES", str(lanes))
+    dev = tr.triangulate(fr, kf, jb, keep_stages=1)
+    S.assert_equal(dev, refs)
+    dev.close()
+
+
+def test_more_than_1024_blocks_in_one_call(tr, om, sizes):
+    """700 jobs, 1120 blocks in one chunk: the scan of the per-block created counts runs more than one count per thread, and trg_gather_kernel places
+    the points of the jobs past block 1024 with it. With the kept stages and without; twice; and one job from past block 1024 alone"""
+    sc, refs = sizes("tiny")
+    fr, kf, jb = S.lib_args(tr, om, sc)
+    dev = tr.triangulate(fr, kf, jb, keep_stages=1)
+    assert dev.n_chunks == 1
+    S.assert_equal(dev, refs)
+    again = tr.triangulate(fr, kf, jb, keep_stages=1)
+    S.same_results(dev, again, len(jb))
+    again.close()
+    dev.close()
+    plain = tr.triangulate(fr, kf, jb)
+    assert plain.n_chunks == 1
+    S.assert_equal(plain, refs, keep_stages=False)
+    plain.close()
+    first = np.cumsum([0] + [S.blocks_of(r) for r in refs])
+    j = next(j for j, r in enumerate(refs) if first[j] >= 1024 and r["n_created"] > 0)
+    alone = tr.triangulate(fr, kf, [jb[j]], keep_stages=1)
+    S.assert_equal(alone, [refs[j]])
+    alone.close()
+
+
+def test_more_than_1024_blocks_in_chunks(tr, om, sizes, monkeypatch):
+    sc, refs = sizes("tiny")
+    slots = [r["n_keypoints"] * r["n_neighbours"] for r in refs]
+    fr, kf, jb = S.lib_args(tr, om, sc)
+    monkeypatch.setenv("IBA_DEBUG_ENV", "1")
+    for budget in (120 * sum(slots) // 3, 120 * sum(slots) // 40):
+        want = planned_chunks(slots, budget)
+        assert 3 <= want < len(jb), (budget, want)
+        monkeypatch.setenv("IBA_TRIANGULATE_BUDGET", str(budget))
+        cut = tr.triangulate(fr, kf, jb, keep_stages=1)
+        monkeypatch.delenv("IBA_TRIANGULATE_BUDGET")
+        assert cut.n_chunks == want, (budget, cut.n_chunks, want)
+        S.assert_equal(cut, refs)
+        cut.close()
+
+
 def test_options_flip_the_recorded_cases(tr, om, scenes):
     sc, refs = scenes["hand"]
     w = sc["where"]

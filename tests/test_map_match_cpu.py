@@ -122,6 +122,8 @@ def test_argument_checks(mm, om, err, hand):
     # frames: what iba_orb_match refuses
     f0 = sc["frames"][0]
     _expect(err, lambda: call(frames=[om.frame(f0["xy"], f0["octave"], f0["angle"], f0["desc"], (0, 0, 0, 480))]), "max <= min")
+    big = S.N_LIMIT + 1
+    _expect(err, lambda: call(frames=[om.frame(np.zeros((big, 2), F), np.zeros(big, np.int32), np.zeros(big, F), np.zeros((big, 32), np.uint8), S.BOUNDS)]), "frame 0: n outside [0, %d]" % S.N_LIMIT)
     # jobs
     _expect(err, lambda: call(jobs=[job(frame=1)]), "a frame index outside")
     _expect(err, lambda: call(jobs=[job(frame=-1)]), "a frame index outside")
@@ -271,6 +273,20 @@ def test_random_scene(mm, om, rand):
     assert a != b and np.array_equal(np.sort(refs[2]["u"]), np.sort(refs[3]["u"]))
     # occupied keypoints are never claimed
     assert np.all(refs[1]["point_of"][sc["jobs"][1]["occupied"] != 0] == -1) and refs[1]["n_matches"] > 0
+    fr, tb, jb = S.lib_args(mm, om, sc)
+    m = mm.match_host(fr, tb, jb, keep_stages=1)
+    S.assert_equal(m, refs)
+    m.close()
+
+
+# ---- real frame sizes, the declared limit and many jobs: the conditions on the reference, then the host restatement ----
+
+@pytest.mark.parametrize("name", sorted(S.SIZES))
+def test_sizes_on_the_host(mm, om, name):
+    make, check = S.SIZES[name]
+    sc = make()
+    refs = R.run(sc["frames"], sc["table"], sc["jobs"])
+    check(sc, refs)
     fr, tb, jb = S.lib_args(mm, om, sc)
     m = mm.match_host(fr, tb, jb, keep_stages=1)
     S.assert_equal(m, refs)

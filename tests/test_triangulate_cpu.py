@@ -120,6 +120,8 @@ def test_argument_checks(tr, om, err, hand):
     # frames: what iba_orb_match refuses
     f0 = sc["frames"][0]
     _expect(err, lambda: call(frames=[om.frame(f0["xy"], f0["octave"], f0["angle"], f0["desc"], (0, 0, 0, 480))] + fr[1:]), "max <= min")
+    big = 32768 + 1                                                    # IBA_ORB_MATCH_MAX_KEYPOINTS + 1
+    _expect(err, lambda: call(frames=fr[:1] + [om.frame(np.zeros((big, 2), F), np.zeros(big, np.int32), np.zeros(big, F), np.zeros((big, 32), np.uint8), S.BOUNDS)] + fr[2:]), "frame 1: n outside [0, 32768]")
     # keyframes
     with_kf = lambda k: [k] + kf[1:]
     _expect(err, lambda: call(keyframes=with_kf(keyframe(frame=len(fr)))), "keyframe 0: a frame index outside")
@@ -328,6 +330,20 @@ def test_random_scene(tr, om, rand):
     assert np.all(refs[0]["n_created_of"] > 0) and refs[2]["n_matches"].tolist()[1] == 0 and np.isin(refs[2]["status"][1], (R.HAS_POINT, R.NO_NODE, R.SUPERSEDED)).all()
     assert 1 in sc["jobs"][0]["neighbours"] and 1 in sc["jobs"][2]["neighbours"]            # one keyframe is a neighbour in two jobs
     assert sum(r["n_equal_replaced"] for r in refs) >= 0 and sum(r["n_line_refused"] for r in refs) > 0 and sum(r["n_has_point_walked"] for r in refs) > 0
+    fr, kf, jb = S.lib_args(tr, om, sc)
+    t = tr.triangulate_host(fr, kf, jb, keep_stages=1)
+    S.assert_equal(t, refs)
+    t.close()
+
+
+# ---- real frame sizes, many neighbours and more than 1024 blocks: the conditions on the reference, then the host restatement ----
+
+@pytest.mark.parametrize("name", sorted(S.SIZES))
+def test_sizes_on_the_host(tr, om, name):
+    make, check = S.SIZES[name]
+    sc = make()
+    refs = R.run(sc["frames"], sc["keyframes"], sc["jobs"])
+    check(sc, refs)
     fr, kf, jb = S.lib_args(tr, om, sc)
     t = tr.triangulate_host(fr, kf, jb, keep_stages=1)
     S.assert_equal(t, refs)

@@ -18,7 +18,10 @@ bit for bit, and then z_i = r_2 . (x3D - Ow_i) is zero and DEPTH1 / DEPTH2 come 
 stand-alone self-test reaches that line of the shared text with a hand-made centre.
 
 random_scene(): seeded; points in front of a camera that moves, keypoints with pixel noise, descriptors with bit noise, nodes shared by families of
-points, the job shapes of the issue. noise_free_scene(): the same with exact projections and exact descriptors, and the true point of every keypoint."""
+points, the job shapes of the issue. noise_free_scene(): the same with exact projections and exact descriptors, and the true point of every keypoint.
+
+large_scene(), neighbours_scene(), tiny_scene(): frames of 1500 to 2100 keypoints, a job with eleven neighbours, 700 jobs of 1120 blocks; SIZES names
+each with the conditions that are asserted on the reference's results (profiles/local_mapping_shapes.md)."""
 import numpy as np
 
 import orb_match_ref as M
@@ -184,14 +187,28 @@ def hand_scene(seed=7):
     return {"frames": frames, "keyframes": keyframes, "jobs": jobs, "where": where, "cand": cand}
 
 
-def _moving_scene(seed, n_points, n_kp, pixel_noise, max_bit_noise, n_nodes, family_bits=None):
+JOB_FORMS = ((4, [3, 2, 1, 0]),         # 0
+             (2, []),                   # 1: no neighbours
+             (3, [1, 5, 0]),            # 2: the empty frame as a neighbour; keyframe 1 is a neighbour here and in job 0
+             (5, [0, 1]),               # 3: the empty frame as the current keyframe
+             (0, [1]))                  # 4: one neighbour
+
+
+def _moving_scene(seed, n_points, n_kp, pixel_noise, max_bit_noise, n_nodes, family_bits=None, crowd=None, jobs=None):
+    """one keyframe per entry of n_kp along a path, then an empty one. A point's node is its index modulo n_nodes; crowd = (c, m) gives the first m
+    points the nodes 0 .. c - 1 instead, so that those nodes hold long segments. jobs: (current, neighbours) pairs, by default the five job forms
+    over the first five keyframes and the empty one"""
     rng = np.random.default_rng(seed)
+    n_poses = len(n_kp)
     X = np.stack([rng.uniform(-4, 4, n_points), rng.uniform(-3, 3, n_points), rng.uniform(4, 12, n_points)], 1)
     base = rng.integers(0, 256, (n_points, 32)).astype(np.uint8)
+    node_of = np.arange(n_points) % n_nodes
+    if crowd is not None:
+        node_of[:crowd[1]] = np.arange(crowd[1]) % crowd[0]
     if family_bits is not None:                            # the points of a node look alike: wrong candidates come below th_low and meet the gates
         family = rng.integers(0, 256, (n_nodes, 32)).astype(np.uint8)
-        base = np.array([at_distance(family[p % n_nodes], int(rng.integers(0, family_bits + 1)), rng) for p in range(n_points)], np.uint8)
-    poses = [pose(0.004 * i, -0.01 * i, 0.003 * i, (-0.25 * i, 0.02 * i, -0.05 * i)).astype(F) for i in range(5)]
+        base = np.array([at_distance(family[node_of[p]], int(rng.integers(0, family_bits + 1)), rng) for p in range(n_points)], np.uint8)
+    poses = [pose(0.004 * i, -0.01 * i, 0.003 * i, (-0.25 * i, 0.02 * i, -0.05 * i)).astype(F) for i in range(n_poses)]
     frames, keyframes, owner = [], [], []
     for i, T in enumerate(poses):
         pc = X @ T[:, :3].astype(float).T + T[:, 3].astype(float)
@@ -202,7 +219,7 @@ def _moving_scene(seed, n_points, n_kp, pixel_noise, max_bit_noise, n_nodes, fam
         octave = np.clip(np.round(np.log(pc[pick, 2] / 4.0) / np.log(1.2)), 0, 7).astype(int)
         octave = np.clip(octave + (rng.integers(-1, 2, len(pick)) if pixel_noise else 0), 0, 7)
         desc = np.array([at_distance(base[p], int(rng.integers(0, max_bit_noise + 1)), rng) for p in pick], np.uint8).reshape(-1, 32)
-        node = (pick % n_nodes).astype(np.int32)
+        node = node_of[pick].astype(np.int32)
         node[rng.uniform(size=len(pick)) < 0.03] = -1
         has = (rng.uniform(size=len(pick)) < 0.3).astype(np.uint8)
         frames.append(M.make_frame(xy, octave, np.zeros(len(pick)), desc, BOUNDS))
@@ -210,12 +227,10 @@ def _moving_scene(seed, n_points, n_kp, pixel_noise, max_bit_noise, n_nodes, fam
         keyframes.append(R.make_keyframe(i, T, K, node, has, depth))
         owner.append(pick)
     frames.append(M.make_frame(np.zeros((0, 2)), [], [], np.zeros((0, 32)), BOUNDS))                 # a frame with n == 0
-    keyframes.append(R.make_keyframe(5, poses[2], K, [], None, 8.0))
-    jobs = [R.make_job(4, [3, 2, 1, 0], SF, SIGMA2, 1.2),          # 0
-            R.make_job(2, [], SF, SIGMA2, 1.2),                    # 1: no neighbours
-            R.make_job(3, [1, 5, 0], SF, SIGMA2, 1.2),             # 2: the empty frame as a neighbour; keyframe 1 is a neighbour here and in job 0
-            R.make_job(5, [0, 1], SF, SIGMA2, 1.2),                # 3: the empty frame as the current keyframe
-            R.make_job(0, [1], SF, SIGMA2, 1.2)]                   # 4: one neighbour
+    keyframes.append(R.make_keyframe(n_poses, poses[2], K, [], None, 8.0))
+    if jobs is None:
+        jobs = JOB_FORMS
+    jobs = [R.make_job(cur, nbs, SF, SIGMA2, 1.2) for cur, nbs in jobs]
     return {"frames": frames, "keyframes": keyframes, "jobs": jobs, "points": X.astype(F), "owner": owner}
 
 
@@ -225,6 +240,57 @@ def random_scene(seed=5):
 
 def noise_free_scene(seed=9):
     return _moving_scene(seed, 400, (200, 190, 210, 180, 205), 0.0, 0, 25)
+
+
+def large_scene(seed=5):
+    """random_scene() at the caller's frame sizes: 4000 points over 200 nodes. Spread evenly, a node would hold 20 points and no segment could pass
+    20, so 320 of the points crowd into nodes 0 and 1: segments above 64, more than one trip at every pick width"""
+    return _moving_scene(seed, 4000, (2001, 1500, 2100, 1999, 2048), 0.6, 30, 200, family_bits=24, crowd=(2, 320))
+
+
+MANY_NEIGHBOURS = (6, [5, 7, 4, 8, 3, 9, 2, 10, 1, 11, 0])
+
+
+def neighbours_scene(seed=13):
+    """twelve keyframes of 500 keypoints, each a random part of 1200 points; one job: keyframe 6 against the other eleven, nearest first"""
+    return _moving_scene(seed, 1200, (500,) * 12, 0.6, 30, 60, family_bits=24, jobs=[MANY_NEIGHBOURS])
+
+
+def tiny_scene(seed=5, n_jobs=700):
+    """n_jobs jobs cycling through the five job forms over keyframes of at most 11 keypoints: 8 blocks per cycle, so 700 jobs are 1120 blocks and
+    trg_gather_kernel's scan of the per-block counts goes past its 1024 threads"""
+    return _moving_scene(seed, 60, (9, 7, 11, 5, 8), 0.6, 30, 3, family_bits=24, jobs=[JOB_FORMS[j % 5] for j in range(n_jobs)])
+
+
+def blocks_of(ref):
+    """the blocks of a job: one per 256 keypoints of the current keyframe and neighbour"""
+    return ref["n_neighbours"] * (-(-ref["n_keypoints"] // 256))
+
+
+# ---- the conditions of the scenes above, asserted on the REFERENCE's results before anything is compared with them ----
+
+def check_large(sc, refs):
+    assert [r["n_keypoints"] for r in refs] == [2048, 2100, 1999, 0, 2001] and refs[0]["n_created"] > 300 and refs[2]["n_created"] > 300
+    assert refs[0]["counts"][R.SUPERSEDED] > 0 and refs[2]["counts"][R.SUPERSEDED] > 0
+    assert max(int(r["seg_len"].max()) for r in refs if r["seg_len"].size) > 64
+    assert all(int(np.sum(sc["keyframes"][k]["node"] >= 0)) > 1024 for k in range(5)) and len(set(np.concatenate([k["node"] for k in sc["keyframes"]]).tolist())) == 201
+    assert blocks_of(refs[0]) == 32 and sum(blocks_of(r) for r in refs) == 32 + 24 + 8
+
+
+def check_neighbours(sc, refs):
+    r = refs[0]
+    assert len(refs) == 1 and r["n_keypoints"] == 500 and r["n_neighbours"] == 11
+    assert (r["status"][5:] == R.SUPERSEDED).any() and (r["status"][5:] == R.CREATED).any() and r["n_created_of"][5:].sum() > 0 and not r["skipped"].any()
+
+
+def check_tiny(sc, refs):
+    first, total = np.cumsum([0] + [blocks_of(r) for r in refs]), sum(r["n_created"] for r in refs)
+    assert len(refs) == 700 and first[-1] == 1120 and total == 280
+    assert any(r["n_created"] > 0 for j, r in enumerate(refs) if first[j] >= 1024 and blocks_of(r))
+    assert len({r["n_created"] for r in refs[:5]}) >= 2 and len({tuple(r["n_created_of"].tolist()) for r in refs[:5]}) == 5 and all(same_bytes(refs[j]["status"], refs[j % 5]["status"]) for j in range(5, 700))
+
+
+SIZES = {"large": (large_scene, check_large), "neighbours": (neighbours_scene, check_neighbours), "tiny": (tiny_scene, check_tiny)}      # scene -> (builder, conditions on the reference)
 
 
 # ---- a scene through the library, and the byte-for-byte comparison with the reference's results ----
